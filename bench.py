@@ -18,15 +18,26 @@ as an N-GPU result.
 Workloads (--workload; default detector_train):
   detector_train     backbone + IA-SSD head (target assignment, all losses) + backward + grad clip + adam_onecycle:
                      the reference's whole training iteration (train_utils.py:34-64) on synthetic scenes and boxes.
-  backbone           backbone forward+backward with a synthetic loss (round 1's headline; now under `extra`).
+  backbone           backbone forward+backward with a synthetic loss (round 1's headline; now under `extra` of --full).
   backbone_infer     backbone forward, eval BN, fused SA kernel (BASELINE configs[1]).
   kitti_detector_train_bf16   detector_train on the KITTI yaml in dense-bf16 mode (BASELINE configs[2]; --batch 4).
   kitti_detector_train        the same iteration in the default mode (f32 tensors, split-bf16 contractions, unique tokens).
   train_step, kitti_train_bf16, backbone_bf16, backbone_infer_bf16   see benchmarks/workloads.py.
   sampling_grouping  only the sampling/grouping operators at the ONCE-16k layer shapes.
 
-The default run (N = 1) also times `backbone`, `backbone_infer`, `kitti_detector_train_bf16 --batch 4` and
-`kitti_detector_train --batch 4` for a few steps each and reports them under "extra" (--no-extra skips that).
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the outputs (--dump-outputs) and the line.
+--full adds the secondary legs: the rooflines (HIP-event kernel timers inside the timed steps, the ball query re-timed alone
+after them), the CPU baselines (--no-cpu-baseline skips them) and, for the default workload at N = 1, a few steps each of
+`backbone`, `backbone_infer`, `kitti_detector_train_bf16 --batch 4` and `kitti_detector_train --batch 4` under "extra"
+(--no-extra skips those).
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB; see
+dump_outputs).  Inputs and initial weights depend on the arguments only, and every step of a training workload starts from
+the weights and optimizer state of construction (TrainStepWorkload.restore): a step is the same training iteration every
+time, only the one-cycle schedule position moves.  Over a real trajectory the float-atomic gradient sums (last-bit order
+effects, as in the reference) flip centre-aware top-k picks within a few iterations (DESIGN.md section 7 "(d)"); from a
+fixed state the forward pass is deterministic and the gradients and Adam moments of two runs differ by the rounding
+of one backward pass (the updated parameters are not dumped; see dump_outputs).
 """
 import argparse
 import json
@@ -49,9 +60,16 @@ def parse_args(argv=None):
     ap.add_argument("--workload", default="auto")
     ap.add_argument("--batch", type=int, default=None, help="scenes per GPU (default: the yaml's 2 for ONCE, 4 for KITTI)")
     ap.add_argument("--points", type=int, default=16384)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary timings under 'extra'")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also the rooflines, the CPU baselines and (default workload) the secondary timings under 'extra'")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary timings under 'extra'")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_ranks(args, argv):
@@ -69,10 +87,14 @@ def spawn_ranks(args, argv):
     return subprocess.call(cmd, env=env)
 
 
-def time_workload(wl, steps, warmup, device, parallel):
+def time_workload(wl, steps, warmup, device, parallel, timers=True):
     """W (+2 priming) untimed steps, then exactly K steps between barrier + synchronize on both sides; MAX over
     ranks.  The two priming steps keep first-use costs (code-object loading of every library GEMM, allocator
-    growth, TunableOp table lookups) out of a run with a small W."""
+    growth, TunableOp table lookups) out of a run with a small W.
+
+    A workload with `restore` (the training ones) is put back to its state of construction before every step.
+    `timers`: the workload's HIP-event kernel timers (the rooflines' data) record during the timed steps.
+    Returns (seconds, what the last timed step returned)."""
     trace = [] if os.environ.get("PDA_BENCH_STEP_TIMES") else None     # host-side enqueue time of every step -> stderr
     if trace is not None:
         import gc
@@ -85,9 +107,12 @@ def time_workload(wl, steps, warmup, device, parallel):
                 gcs.append((len(trace), info["generation"], 1e3 * (time.perf_counter() - _t[0]), info["collected"]))
         gc.callbacks.append(on_gc)
     wl.begin()
+    restore = getattr(wl, "restore", None)      # training workloads: every step starts from the weights of construction
     for _ in range(2 + warmup):
         ts = time.perf_counter()
-        wl.step()
+        if restore is not None:
+            restore()
+        out = wl.step()         # held like the timed steps' (the last one's is returned): the same memory in use
         if trace is not None:
             trace.append(time.perf_counter() - ts)
     # What is alive after the warm-up (modules, captured graphs, cached plans and packed weights: ~10^6 objects by the fourth
@@ -101,11 +126,13 @@ def time_workload(wl, steps, warmup, device, parallel):
         gc.collect()
         gc.freeze()
     parallel.barrier(device)
-    wl.record = True
+    wl.record = timers
     t0 = time.perf_counter()
     for _ in range(steps):
         ts = time.perf_counter()
-        wl.step()
+        if restore is not None:
+            restore()
+        out = wl.step()
         if trace is not None:
             trace.append(time.perf_counter() - ts)
     parallel.barrier(device)
@@ -118,7 +145,67 @@ def time_workload(wl, steps, warmup, device, parallel):
         print("bench.py: %s collections (step, generation, ms, objects): %s" % (wl.name, [g for g in gcs if g[2] > 1.0]), file=sys.stderr)
         print("bench.py: %s host ms per step (warm-up %d): %s" % (wl.name, 2 + warmup, " ".join("%.1f" % (1e3 * t) for t in trace)),
               file=sys.stderr)
-    return parallel.max_over_ranks(dt, device)
+    return parallel.max_over_ranks(dt, device), out
+
+
+DUMP_BUDGET = 64 << 20     # bytes, all files of --dump-outputs together
+DUMP_SAMPLE = 4 << 20      # elements: a larger array is written as this many of its elements (fixed seeded choice, in order)
+
+
+def dump_outputs(wl, out, out_dir):
+    """What the last timed step computed, as <out_dir>/<name>.npy:
+      loss (or output)   the step's return value: the loss of the training workloads, `centers_features` of the inference
+                         ones; for --workload sampling_grouping only a count of grouped elements (its indices and grouped
+                         features are not kept), so that workload's dump is a smoke check, not a comparison of results
+      tb_<key>           the logged loss terms of the detector
+      gradients          training workloads: the step's gradients, flattened in model.parameters() order
+      adam_exp_avg,      workloads with the flat-buffer optimizer: its first and second moments after the step (its flat
+      adam_exp_avg_sq    layout, 16-byte aligned slots with zero padding) -- written by csrc/optim.hip from the clipped
+                         gradient (pda_grad_norm's norm), so they cover the gradient-norm and Adam kernels
+    NOT covered: the parameter update itself.  The updated parameters are not written: every step is Adam's first step
+    from the weights of construction (TrainStepWorkload.restore), which moves a parameter by about lr * sign(gradient), so a
+    gradient at the rounding level of the float-atomic sums becomes a full step of either sign (1.9e-3 apart between two
+    runs), while gradients and moments differ between runs by that rounding only.
+    Tensors are written in float32 (float64 for float64 and Python scalars); an array of more than DUMP_SAMPLE elements
+    keeps the elements at np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False), sorted -- the same positions
+    in every run."""
+    import numpy as np
+    import torch
+
+    arrays = {}
+
+    def add(name, v):
+        if torch.is_tensor(v):
+            v = v.detach()
+            v = v.double() if v.dtype == torch.float64 else v.float()
+            a = v.cpu().numpy()
+        else:
+            a = np.asarray(v, dtype=np.float64)
+        if a.size > DUMP_SAMPLE:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        arrays["".join(c if c.isalnum() or c in "_-." else "_" for c in name)] = a
+
+    is_loss = torch.is_tensor(out) and out.dim() == 0
+    add("loss" if is_loss else "output", out if out is not None else float("nan"))
+    for k, v in sorted((getattr(wl, "tb", None) or {}).items()):
+        if torch.is_tensor(v) or isinstance(v, (int, float)):
+            add("tb_" + k, v)
+    model = getattr(wl, "model", None)
+    if model is not None and model.training:
+        params = [p for p in model.parameters() if p.requires_grad]
+        add("gradients", torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1)
+                                    for p in params]))
+    opt = getattr(wl, "opt", None)
+    if opt is not None and hasattr(opt, "exp_avg"):
+        add("adam_exp_avg", opt.exp_avg)
+        add("adam_exp_avg_sq", opt.exp_avg_sq)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_BUDGET))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print("bench.py: wrote %d arrays (%.1f MB) to %s" % (len(arrays), total / 1e6, out_dir), file=sys.stderr)
 
 
 def safe(fn, default, *a):
@@ -247,8 +334,11 @@ def main():
     wl = workloads.create(name, batch, args.points, device, rank, world)
     if args.warmup < 5 and getattr(wl, "_tail_auto", False):
         wl._tail_auto = False        # the probe (iteration 4) and the capture behind it (iteration 5) must stay out of the timed steps
-    dt = time_workload(wl, args.steps, args.warmup, device, parallel)
-    roofs = safe(wl.rooflines, {})
+    dt, out = time_workload(wl, args.steps, args.warmup, device, parallel, timers=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, out, args.dump_outputs)
+    del out
+    roofs = safe(wl.rooflines, {}) if args.full else {}
 
     line = {
         "metric": metric_name(wl.name, args.points),
@@ -275,6 +365,7 @@ def main():
         line["config"]["hipblaslt_tunableop_results_loaded"] = bool(wl.tuned)
     line["config"]["peak_mem_GiB"] = round(torch.cuda.max_memory_allocated(device) / 2**30, 2)
     line["config"]["cpu_affinity"] = cpu_affinity
+    line["config"]["full"] = bool(args.full)
     if hasattr(getattr(wl, "model", None), "graph_tail"):
         # layers 3-5 + head + losses replayed as hipGraphs: chosen by the workload when the host was the limit (workloads.py)
         line["config"]["graph_tail"] = bool(wl.model.graph_tail)
@@ -285,7 +376,7 @@ def main():
         line["config"]["graph_tail_infer"] = bool(wl.model.graph_tail_infer)     # inference: layers 3-5 replayed as one hipGraph
 
     single = world == 1 and rank == 0
-    if single and not args.no_cpu_baseline:
+    if single and args.full and not args.no_cpu_baseline:
         unpin()          # (the timed GPU part of this workload is over; the extra workloads below pin again)
         line["cpu_baseline"] = safe(wl.cpu_baseline, {"value": None, "unit": "scenes/s", "cores": None, "kind": "port", "sample": "failed"})
         # the operator baseline "at 1 thread and at all cores"
@@ -295,7 +386,7 @@ def main():
         line["cpu_baseline_ops"] = {"threads_1": safe(workloads.sampling_grouping_cpu, {}, xyz_np, 1),
                                     "threads_all": safe(workloads.sampling_grouping_cpu, {}, xyz_np, None)}
 
-    if single and not args.no_extra and args.workload == "auto":
+    if single and args.full and not args.no_extra and args.workload == "auto":
         pin_to_gpu_node(torch, local_rank)
         # secondary timings (few steps each): round 1's headline and BASELINE configs[1] / configs[2]
         del wl
@@ -308,7 +399,7 @@ def main():
                 torch.cuda.empty_cache()
                 xw = workloads.create(xname, xbatch, args.points, device, rank, world)
                 xsteps = max(5, min(args.steps, 10))
-                xdt = time_workload(xw, xsteps, 6, device, parallel)     # two warm-up steps left first-use costs (allocator growth, library heuristics) in the timed ones
+                xdt = time_workload(xw, xsteps, 6, device, parallel)[0]     # two warm-up steps left first-use costs (allocator growth, library heuristics) in the timed ones
                 xr = safe(xw.rooflines, {})
                 extra[xname] = {"workload": xw.name, "step": step_text(xw.name), "scenes_per_gpu": xbatch,
                                 "steps": xsteps, "ms_per_step": xdt / xsteps * 1e3, "scenes_per_s": xbatch * xsteps / xdt,

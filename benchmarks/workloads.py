@@ -660,6 +660,32 @@ class TrainStepWorkload(BackboneWorkload):
             self.exchange = "one all-reduce (%s) of the flat fp32 gradient buffer (%.1f MB) between backward and the clipping " \
                             "norm, outside autograd" % ("AVG" if self.opt._dp_avg else "SUM + scale", self.opt.flat_g.numel() * 4 / 1e6)
 
+    def restore(self):
+        """Put the trained parameters and the optimizer state back to where construction left them (the first call takes
+        that snapshot).  bench.py calls it before every step, so each step is the same training iteration from the same
+        weights and the last step's outputs do not depend on the run: over a real trajectory the float-atomic gradient sums
+        (order-dependent in the last bits, as in the reference) grow into different centre-aware top-k picks within a few
+        iterations (DESIGN.md section 7 "(d)").  In place: captured graphs and `.data` views keep their addresses.  The
+        schedule position (`it`, which also places the host-bound probe) still advances; BatchNorm running statistics are
+        not reset (training-mode forward does not read them)."""
+        from pdanet_amd import _lib
+        opt = self.opt
+        if getattr(self, "_flat_p0", None) is None:
+            self._flat_p0 = opt.flat_p.detach().clone()
+            self._step_count0 = opt.step_count
+            self._moments0 = None if opt.step_count == 0 else (opt.exp_avg.clone(), opt.exp_avg_sq.clone())
+        with torch.no_grad():
+            opt.flat_p.copy_(self._flat_p0)
+            if self._moments0 is None:
+                opt.exp_avg.zero_()
+                opt.exp_avg_sq.zero_()
+            else:
+                opt.exp_avg.copy_(self._moments0[0])
+                opt.exp_avg_sq.copy_(self._moments0[1])
+        opt.step_count = self._step_count0
+        _lib.PARAM_EPOCH[0] += 1          # written behind autograd's back: derived caches (packed weights) rebuild
+        _lib.WEIGHT_EPOCH[0] += 1
+
     def step(self):
         model = self.ddp if self.ddp is not None else self.model
         self.sched.step(self.it)
