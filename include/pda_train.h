@@ -415,6 +415,35 @@ int pda_sa_xyz_grad(const float *grad_z1, const float *xyz, const float *new_xyz
                     float *dw, int lddw, float *grad_new_xyz, void *scratch, int b, int n, int m, int nsample, int c1,
                     pda_stream_t stream);
 
+/* ---- the input stage of the data loader (csrc/input_stage.hip; the reference's DataProcessor
+ * mask_points_and_boxes_outside_range -> sample_points -> shuffle_points chain and collate_batch, on the device) ----------
+ * points (n_total, C >= 3) [x, y, z, features...] holds `batch` scenes back to back; offsets (batch + 1) int64 on the
+ * device, scene b = rows [offsets[b], offsets[b+1]), at most n_cap rows each.  range6 (HOST) = [xmin, ymin, zmin, xmax,
+ * ymax, zmax].  out_points (batch * num_points, 1 + C) = [b, x, y, z, features...]; per scene: the points with
+ * xmin <= x <= xmax and ymin <= y <= ymax (z not tested), near = sqrt((x*x + y*y) + z*z) < 40, and with n masked,
+ * n_far far points, k = num_points:
+ *   (A) n > k, n_far < k: choice = near[pick[0 .. k-n_far)] ++ far;  (B) n > k, n_far >= k: choice = masked[pick[0 .. k)];
+ *   (C) n <= k: choice = masked ++ masked[pick[0 .. k-n)];
+ *   out[b][j] = choice[perm1[perm2[j]]]  (perm2 omitted when shuffle == 0).
+ * Explicit mode: pick, perm1 (and perm2 exactly when shuffle == 1) are int32 (batch, num_points) on the device; ranks
+ *   out of range yield a zero row and status bit 8.  Seeded mode (pick == perm1 == perm2 == NULL): the draws are generated
+ *   from `seed` (keyed bijections for the samples without replacement and the shuffles, a counter hash for case C).
+ * info (batch, 4) int32 = [n, n_far, kept boxes, status]: this entry writes columns 0, 1, 3; status bits: 1 no point in
+ *   range (the reference raises), 2 offsets outside [0, n_total], 4 more than n_cap raw points (2 and 4: the scene is
+ *   treated as empty), 8 a draw out of range.  Rows of a scene with a status are [b, 0...].
+ * workspace: pda_input_stage_workspace_bytes(batch, n_cap) bytes, 4-byte aligned (-1: bad sizes).  Four launches, no
+ * host synchronisation; the grids depend on batch, n_cap and num_points only (graph-capturable). */
+int64_t pda_input_stage_workspace_bytes(int batch, int64_t n_cap);
+int pda_input_stage(const float *points, const int64_t *offsets, int64_t n_total, int batch, int c, int64_t n_cap,
+                    const float *range6, int num_points, const int32_t *pick, const int32_t *perm1, const int32_t *perm2,
+                    uint64_t seed, int shuffle, float *out_points, int32_t *info, void *workspace, pda_stream_t stream);
+/* Boxes (m_total, box_dim >= 7) [x, y, z, dx, dy, dz, heading, ...], box_offsets (batch + 1) int64 on the device: a box is
+ * kept when at least min_num_corners of its 8 corners lie inside all six limits of range6 (inclusive; 0 keeps every box),
+ * the kept boxes of scene b are compacted in order into gt_boxes (batch, max_gt, box_dim), zero-padded; info[b][2] = the
+ * kept count (may exceed max_gt: the excess is dropped), -1 when the scene's box offsets are unusable.  One launch. */
+int pda_input_boxes(const float *boxes, const int64_t *box_offsets, int64_t m_total, int batch, int box_dim, int max_gt,
+                    const float *range6, int min_num_corners, float *gt_boxes, int32_t *info, pda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,292 @@
+"""The input stage of the data loader on the device: ragged raw scenes -> the collated batch detector.IASSD takes.
+
+The reference prepares every scene on the host in numpy (pcdet/datasets/processor/data_processor.py:
+mask_points_and_boxes_outside_range -> sample_points -> shuffle_points) and collates the batch afterwards
+(pcdet/datasets/dataset.py DatasetTemplate.collate_batch).  DataProcessor reads the same DATA_PROCESSOR list and runs the
+whole chain for all scenes of a batch in five launches (csrc/input_stage.hip, include/pda_train.h pda_input_stage /
+pda_input_boxes).
+
+Randomness: with `draws` the caller passes the draws the reference would make (explicit mode, index-exact); otherwise
+they are generated on the device from a 64-bit `seed` (seeded mode), which is drawn from torch's CPU generator when not
+given, so torch.manual_seed makes a run reproducible.  Seeded mode approximates the reference's distribution (uniform
+samples without replacement, uniform shuffles, uniform draws with replacement) with keyed Feistel bijections and a counter
+hash -- tested statistically, not exactly uniform -- and does not reproduce numpy's stream.
+
+Boxes are padded to a fixed capacity `max_gt`: the head's graphs (detector.IASSD graph_head / graph_tail) key on argument
+shapes, and the reference's "largest count in the batch" would change the shape, and capture a new graph, from batch to
+batch.  With max_gt given and check=False the call reads nothing back and can be captured into a graph; scenes the
+reference would reject are then only flagged in batch_dict['input_info'] (see DataProcessor.__call__).
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from .pointnet2_batch_cuda import F32, _call, _chk
+
+# input_info[:, 3] status bits (include/pda_train.h pda_input_stage)
+STATUS_EMPTY, STATUS_BAD_OFFSETS, STATUS_OVER_CAP, STATUS_BAD_DRAW = 1, 2, 4, 8
+_STEPS = ("mask_points_and_boxes_outside_range", "sample_points", "shuffle_points")
+
+
+def _get(cfg, key, default=None):
+    return cfg[key] if key in cfg else default
+
+
+class DataProcessor:
+    """DATA_PROCESSOR of a reference-shaped yaml: mask_points_and_boxes_outside_range, sample_points and shuffle_points,
+    in this order (each optional except sample_points).  Anything else raises NotImplementedError."""
+
+    def __init__(self, processor_cfg, point_cloud_range, training, num_point_features):
+        self.point_cloud_range = np.asarray(point_cloud_range, dtype=np.float32)
+        if self.point_cloud_range.shape != (6,):
+            raise ValueError("point_cloud_range must hold 6 values")
+        self.training = bool(training)
+        self.mode = 'train' if self.training else 'test'
+        self.num_point_features = int(num_point_features)
+        self.mask_points, self.remove_outside_boxes, self.min_num_corners = False, False, 1
+        self.num_points, self.shuffle = None, False
+        last = -1
+        for cfg in processor_cfg:
+            name = cfg['NAME']
+            if name not in _STEPS:
+                raise NotImplementedError("DATA_PROCESSOR step %r has no device implementation" % name)
+            if _STEPS.index(name) <= last:
+                raise NotImplementedError("DATA_PROCESSOR steps must come in the order %s" % (_STEPS,))
+            last = _STEPS.index(name)
+            if name == 'mask_points_and_boxes_outside_range':
+                self.mask_points = True
+                self.remove_outside_boxes = bool(_get(cfg, 'REMOVE_OUTSIDE_BOXES', False)) and self.training
+                self.min_num_corners = int(_get(cfg, 'min_num_corners', 1))
+            elif name == 'sample_points':
+                self.num_points = int(cfg['NUM_POINTS'][self.mode])
+                if self.num_points == -1:
+                    raise ValueError("sample_points NUM_POINTS == -1 keeps ragged scenes: the backbone needs the same "
+                                     "number of points in every scene")
+                if self.num_points < 1:
+                    raise ValueError("sample_points NUM_POINTS must be positive")
+            else:
+                self.shuffle = bool(cfg['SHUFFLE_ENABLED'][self.mode])
+        if self.num_points is None:
+            raise ValueError("DATA_PROCESSOR needs a sample_points step (the backbone needs equal scene sizes)")
+        inf = np.float32(np.inf)
+        self._point_range = (self.point_cloud_range if self.mask_points
+                             else np.array([-inf, -inf, -inf, inf, inf, inf], np.float32))
+        self._range_c = (ctypes.c_float * 6)(*self._point_range.tolist())
+
+    # ------------------------------------------------------------------------------------------------------------------
+    def __call__(self, points, gt_boxes=None, max_gt=None, seed=None, draws=None, check=True, device=None):
+        """points: a list of B (n_i, C) arrays (numpy / torch, host or device), or a tuple (packed (n_total, C) float32,
+        offsets (B + 1) int64, n_cap) of device tensors with n_cap >= every n_i.
+        gt_boxes: None, a list of B (m_i, box_dim) arrays, or a tuple (packed (m_total, box_dim), box_offsets (B + 1)
+        int64) of device tensors.
+        max_gt: the box capacity of batch_dict['gt_boxes'] (B, max_gt, box_dim); None pads to the largest kept count of
+        the batch, as collate_batch does (that needs a host read).
+        seed / draws: see the module docstring; draws = dict(pick=, perm1=, perm2=) with one int array per scene (or a
+        (B, k) array): pick = the ranks sample_points draws (into the near list in case A, the masked list in case B,
+        the extra draws in case C), perm1 = its shuffle, perm2 = shuffle_points' permutation (when it is enabled).
+        check: read batch_dict['input_info'] once and raise ValueError on a scene with no point in range (the reference
+        raises there), on more kept boxes than max_gt, or on a malformed input.  With max_gt given and check=False
+        nothing is read back; such scenes are then only flagged: input_info[b] = [n_masked, n_far, n_kept_boxes,
+        status], status bit 1 = empty scene (its rows are [b, 0, ...]), kept > max_gt = boxes dropped beyond the
+        capacity, -1 kept / status bits 2, 4, 8 = bad offsets, more than n_cap points, a draw out of range.
+        Returns {'batch_size', 'points' (B * NUM_POINTS, 1 + C), 'gt_boxes' (when boxes were given), 'input_info'}."""
+        dev = torch.device(device) if device is not None else None
+        pts, offs, n_cap, bxs, boffs, bmax = self._inputs(points, gt_boxes, dev)
+        dev = pts.device
+        B, C, k = offs.numel() - 1, pts.shape[1], self.num_points
+        if C < 3:
+            raise ValueError("points need at least x, y, z")
+        lib = _lib.load()
+        ws_bytes = lib.pda_input_stage_workspace_bytes(B, n_cap)
+        if ws_bytes < 0:
+            raise ValueError("batch %d / n_cap %d out of range" % (B, n_cap))
+        ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+        out = torch.empty((B * k, 1 + C), dtype=torch.float32, device=dev)
+        info = (torch.empty if bxs is not None else torch.zeros)((B, 4), dtype=torch.int32, device=dev)
+        pick = perm1 = perm2 = None
+        if draws is not None:
+            pick = self._draw_rows(draws.get('pick'), B, k, dev, 'pick')
+            perm1 = self._draw_rows(draws.get('perm1'), B, k, dev, 'perm1')
+            if self.shuffle:
+                perm2 = self._draw_rows(draws.get('perm2'), B, k, dev, 'perm2')
+            seed = 0
+        elif seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())   # CPU generator: no device read
+        _call("pda_input_stage", pts, _chk(pts, "points", F32), _chk(offs, "offsets", torch.int64), pts.shape[0], B, C, n_cap,
+              self._range_c, k, pick.data_ptr() if pick is not None else None, perm1.data_ptr() if perm1 is not None else None,
+              perm2.data_ptr() if perm2 is not None else None, ctypes.c_uint64(seed & (2 ** 64 - 1)), int(self.shuffle),
+              out.data_ptr(), info.data_ptr(), ws.data_ptr())
+        ret = {'batch_size': B, 'points': out, 'input_info': info}
+        host_info = None
+        if bxs is not None:
+            cap = max_gt if max_gt is not None else bmax
+            gt = torch.empty((B, cap, bxs.shape[1]), dtype=torch.float32, device=dev)
+            _call("pda_input_boxes", bxs, _chk(bxs, "gt_boxes", F32), _chk(boffs, "box_offsets", torch.int64), bxs.shape[0], B,
+                  bxs.shape[1], cap, self._range_c_boxes(), self.min_num_corners if self.remove_outside_boxes else 0,
+                  gt.data_ptr() if cap > 0 else None, info.data_ptr())
+            if max_gt is None:
+                host_info = info.cpu()
+                kept = host_info[:, 2]
+                cap = int(kept.max()) if B > 0 else 0
+                gt = gt[:, :max(cap, 0)].contiguous()
+            ret['gt_boxes'] = gt
+        if check:
+            self._check(info.cpu() if host_info is None else host_info, max_gt if bxs is not None else None)
+        return ret
+
+    def _range_c_boxes(self):
+        return (ctypes.c_float * 6)(*self.point_cloud_range.tolist())
+
+    @staticmethod
+    def _check(info, max_gt):
+        for b, (n, _, kept, status) in enumerate(info.tolist()):
+            if status & STATUS_BAD_OFFSETS or status & STATUS_OVER_CAP:
+                raise ValueError("scene %d: offsets outside the packed points or more than n_cap points" % b)
+            if status & STATUS_EMPTY:
+                raise ValueError("scene %d has no point inside POINT_CLOUD_RANGE" % b)
+            if status & STATUS_BAD_DRAW:
+                raise ValueError("scene %d: a draw is out of range" % b)
+            if kept < 0:
+                raise ValueError("scene %d: box offsets outside the packed boxes" % b)
+            if max_gt is not None and kept > max_gt:
+                raise ValueError("scene %d keeps %d boxes, more than max_gt=%d" % (b, kept, max_gt))
+
+    @staticmethod
+    def _draw_rows(rows, B, k, dev, name):
+        if rows is None:
+            raise ValueError("draws needs %r" % name)
+        if isinstance(rows, torch.Tensor) and rows.is_cuda:
+            t = rows.to(torch.int32).contiguous()
+            if t.shape != (B, k):
+                raise ValueError("draws[%r] must be (B, NUM_POINTS)" % name)
+            return t
+        a = np.zeros((B, k), np.int32)
+        if len(rows) != B:
+            raise ValueError("draws[%r] needs one row per scene" % name)
+        for b, r in enumerate(rows):
+            r = np.asarray(r.cpu() if isinstance(r, torch.Tensor) else r).reshape(-1)
+            if r.size > k:
+                raise ValueError("draws[%r][%d] holds more than NUM_POINTS entries" % (name, b))
+            a[b, :r.size] = r
+        return torch.from_numpy(a).to(dev)
+
+    def _inputs(self, points, gt_boxes, dev):
+        """-> packed points, offsets, n_cap, packed boxes, box offsets, largest raw box count (all on one device)."""
+        if isinstance(points, tuple):
+            pts, offs, n_cap = points
+            if not (pts.is_cuda and offs.is_cuda):
+                raise ValueError("the (packed, offsets, n_cap) form takes device tensors")
+            bxs = boffs = None
+            bmax = 0
+            if gt_boxes is not None:
+                if not isinstance(gt_boxes, tuple):
+                    raise ValueError("device points take gt_boxes as (packed, box_offsets)")
+                bxs, boffs = gt_boxes
+                bmax = bxs.shape[0]
+            return pts, offs, int(n_cap), bxs, boffs, bmax
+        B = len(points)
+        if B == 0:
+            raise ValueError("empty batch")
+        if gt_boxes is not None and len(gt_boxes) != B:
+            raise ValueError("gt_boxes needs one array per scene")
+        on_dev = [isinstance(p, torch.Tensor) and p.is_cuda for p in points]
+        if all(on_dev):
+            dev = points[0].device
+        elif dev is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        arrs = [p if on_dev[i] else np.asarray(p.numpy() if isinstance(p, torch.Tensor) else p, np.float32)
+                for i, p in enumerate(points)]
+        C = arrs[0].shape[1]
+        if any(a.ndim != 2 or a.shape[1] != C for a in arrs):
+            raise ValueError("every scene must be (n_i, C) with the same C")
+        sizes = [a.shape[0] for a in arrs]
+        n_cap = max(max(sizes), 1)
+        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        boxes = None
+        if gt_boxes is not None:
+            boxes = [np.asarray(g.cpu().numpy() if isinstance(g, torch.Tensor) else g, np.float32) for g in gt_boxes]
+            D = max((g.shape[1] for g in boxes if g.ndim == 2 and g.size), default=7)
+            boxes = [g.reshape(-1, D) for g in boxes]
+            msz = [g.shape[0] for g in boxes]
+            boffs = np.concatenate([[0], np.cumsum(msz)]).astype(np.int64)
+        # one host buffer, one transfer: offsets | box offsets | points (when on the host) | boxes, 8-byte aligned sections
+        parts = [offs.view(np.uint8)]
+        if boxes is not None:
+            parts.append(boffs.view(np.uint8))
+        host_pts = not any(on_dev)
+        if host_pts:
+            parts.append(np.concatenate(arrs, axis=0).astype(np.float32, copy=False).reshape(-1).view(np.uint8))
+        if boxes is not None:
+            parts.append(np.concatenate(boxes, axis=0).reshape(-1).view(np.uint8))
+        pads = [(-p.size) % 8 for p in parts]
+        buf = np.concatenate([x for p, pad in zip(parts, pads) for x in (p, np.zeros(pad, np.uint8))])
+        dbuf = torch.from_numpy(buf).to(dev)
+        views, at = [], 0
+        for p, pad in zip(parts, pads):
+            views.append(dbuf[at:at + p.size])
+            at += p.size + pad
+        it = iter(views)
+        d_offs = next(it).view(torch.int64)
+        d_boffs = next(it).view(torch.int64) if boxes is not None else None
+        if host_pts:
+            pts = next(it).view(torch.float32).view(-1, C)
+        else:
+            pts = torch.cat([torch.as_tensor(a).to(dev, torch.float32) for a in arrs], dim=0).contiguous()
+        bxs = next(it).view(torch.float32).view(-1, D) if boxes is not None else None
+        bmax = max(msz) if boxes is not None else 0
+        return pts, d_offs, n_cap, bxs, d_boffs, bmax
+
+
+def from_config(cfg, training):
+    """DataProcessor of a loaded yaml (pdanet_amd.config.load_yaml): DATA_CONFIG.DATA_PROCESSOR / POINT_CLOUD_RANGE /
+    NUM_POINT_FEATURES."""
+    dc = cfg['DATA_CONFIG']
+    return DataProcessor(dc['DATA_PROCESSOR'], dc['POINT_CLOUD_RANGE'], training, dc['NUM_POINT_FEATURES'])
+
+
+def collate_batch(batch_list, max_gt=None, device=None):
+    """DatasetTemplate.collate_batch for scenes that are already processed (pcdet/datasets/dataset.py), on the GPU:
+    'points' (n_i, C) get the batch column in front and are concatenated, 'gt_boxes' (m_i, D) are zero-padded to max_gt
+    (None: the largest count, as the reference does) by the same kernel DataProcessor uses (pda_input_boxes, every box
+    kept).  Host inputs (numpy, CPU tensors) are moved to `device` (default: the device of the first scene's points when
+    they are a GPU tensor, else the current GPU).  Every other key is stacked as the reference does (np.stack; torch.stack
+    when every value is a tensor), so non-numeric keys such as frame_id pass through."""
+    B = len(batch_list)
+    if B == 0:
+        raise ValueError("empty batch")
+    keys = list(batch_list[0].keys())
+    if device is None:
+        first = batch_list[0].get('points')
+        device = first.device if isinstance(first, torch.Tensor) and first.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    dev = torch.device(device)
+    ret = {}
+    for key in keys:
+        val = [d[key] for d in batch_list]
+        if key == 'points':
+            pts = [torch.as_tensor(v).to(dev, torch.float32) for v in val]
+            ret[key] = torch.cat([torch.cat([torch.full((v.shape[0], 1), float(i), dtype=torch.float32, device=dev), v], dim=1)
+                                  for i, v in enumerate(pts)], dim=0)
+        elif key == 'gt_boxes':
+            boxes = [torch.as_tensor(v).to(dev, torch.float32) for v in val]
+            D = boxes[0].shape[-1]
+            boxes = [b.reshape(-1, D) for b in boxes]
+            counts = [b.shape[0] for b in boxes]
+            cap = max(counts) if max_gt is None else int(max_gt)
+            if max(counts) > cap:
+                raise ValueError("a scene holds more than max_gt=%d boxes" % cap)
+            packed = torch.cat(boxes, dim=0).contiguous()
+            offs = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int64).to(dev)
+            gt = torch.empty((B, cap, D), dtype=torch.float32, device=dev)
+            info = torch.empty((B, 4), dtype=torch.int32, device=dev)
+            rng = (ctypes.c_float * 6)(*([0.0] * 6))        # min_num_corners 0: every box is kept, the range is not read
+            _call("pda_input_boxes", packed, _chk(packed, "gt_boxes", F32), _chk(offs, "box_offsets", torch.int64), packed.shape[0],
+                  B, D, cap, rng, 0, gt.data_ptr() if cap > 0 else None, info.data_ptr())
+            ret[key] = gt
+        elif all(isinstance(v, torch.Tensor) for v in val):
+            ret[key] = torch.stack(val, dim=0)
+        else:
+            ret[key] = np.stack(val, axis=0)
+    ret['batch_size'] = B
+    return ret
