@@ -444,6 +444,42 @@ int pda_input_stage(const float *points, const int64_t *offsets, int64_t n_total
 int pda_input_boxes(const float *boxes, const int64_t *box_offsets, int64_t m_total, int batch, int box_dim, int max_gt,
                     const float *range6, int min_num_corners, float *gt_boxes, int32_t *info, pda_stream_t stream);
 
+/* ---- the training-time augmentor (csrc/augment.hip; the reference's DataAugmentor gt_sampling -> random_world_flip ->
+ * random_world_rotation -> random_world_scaling -> limit_period, then prepare_data's class filter, on the device) ------
+ * Scenes: points (n_total, C) + offsets (batch + 1) int64 as for pda_input_stage (at most n_cap rows a scene); boxes
+ * (m_total, 8) [x, y, z, dx, dy, dz, heading, class] + box_offsets (batch + 1) int64, class 0 = a name outside
+ * CLASS_NAMES (counts for collisions, dropped from the output).
+ * Database: db_points (db_n_points, C) float32 object points relative to their box centre, db_offsets (n_obj + 1) int64,
+ * db_boxes (n_obj, 7) float32, db_centre (n_obj, 3) float64 (box3d_lidar[:3] as stored), db_class (n_obj) int32 >= 1.
+ * Plan (device): cand (batch, k) database ids grouped by class group in SAMPLE_GROUPS order, -1 = no candidate;
+ * cand_group (batch, k) the group of each slot (ascending along a row); cand_dz (batch, k) float64 the road-plane shift
+ * mv_height (0 without road plane); flip (batch, 2) int32 [flip_x, flip_y]; angle (batch) float64 (0: no rotation);
+ * scale (batch) float32 (1: no scaling).  remove_extra_width (HOST) float[3].  k <= 256.
+ * A candidate is accepted iff its BEV IoU is 0 with every existing box, with every other candidate of its group and with
+ * every accepted candidate of an earlier group.  Scene points inside an accepted box enlarged by remove_extra_width
+ * (the CPU test points_in_boxes_cpu: margin 1e-2) are removed.  Output scene b = out_points rows
+ * [out_offsets[b], out_offsets[b+1]): the accepted objects' points (the centre added in double, then - dz), in
+ * acceptance order, then the kept scene points in their order; out_boxes (.., 8) rows [out_box_offsets[b], ..[b+1]):
+ * the existing boxes of class >= 1 in order, then the accepted ones.  Both go through flip_x (y = -y, h = -h), flip_y
+ * (x = -x, h = -(h + pi)), the rotation ([x, y] times [[c, s], [-s, c]], h += angle), the scaling (xyz and box dims
+ * times scale) and, for the heading, limit_period(h, 0.5, 2 pi), each a separately rounded float32 operation.
+ * paste_cap >= the largest total of object points of one scene's candidates (the write grid); out_cap / out_box_cap =
+ * the rows of out_points / out_boxes (n_total + batch * paste_cap / m_total + the candidates always suffice).
+ * info (batch, 4) int32 = [points out, boxes out, accepted candidates, status]; status bits: 1 no box left (the reference
+ * draws another scene), 2 offsets outside the packed points or boxes, 4 more than n_cap points or an output capacity
+ * exceeded, 8 a candidate id outside the database or candidate groups out of order (the candidate is ignored).  A scene
+ * with bit 2 or 4 is written empty.
+ * workspace: pda_augment_workspace_bytes(batch, n_cap, k) bytes, 256-byte aligned (-1: bad sizes).  Four launches, no
+ * host synchronisation. */
+int64_t pda_augment_workspace_bytes(int batch, int64_t n_cap, int k);
+int pda_augment(const float *points, const int64_t *offsets, int64_t n_total, int batch, int c, int64_t n_cap,
+                const float *boxes, const int64_t *box_offsets, int64_t m_total, const float *db_points,
+                const int64_t *db_offsets, int64_t db_n_points, const float *db_boxes, const double *db_centre,
+                const int32_t *db_class, int n_obj, const int32_t *cand, const int32_t *cand_group, const double *cand_dz,
+                int k, const int32_t *flip, const double *angle, const float *scale, const float *remove_extra_width,
+                int64_t paste_cap, float *out_points, int64_t out_cap, int64_t *out_offsets, float *out_boxes,
+                int64_t out_box_cap, int64_t *out_box_offsets, int32_t *info, void *workspace, pda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,10 @@ SIGNATURES = {
     "pda_input_stage": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, ctypes.POINTER(_f), _i, _vp, _vp, _vp,
                         ctypes.c_uint64, _i, _vp, _vp, _vp, _vp],
     "pda_input_boxes": [_vp, _vp, ctypes.c_int64, _i, _i, _i, ctypes.POINTER(_f), _i, _vp, _vp, _vp],
+    "pda_augment_workspace_bytes": [_i, ctypes.c_int64, _i],
+    "pda_augment": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp,
+                    _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, ctypes.POINTER(_f), ctypes.c_int64, _vp, ctypes.c_int64,
+                    _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp],
     # include/pda_pointnet2_stack.h
     "pda_stack_ball_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     "pda_stack_group_points": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -197,6 +201,7 @@ def load():
     lib.pda_sa_small_train_workspace_bytes.restype = ctypes.c_int64
     lib.pda_sa_xyz_grad_scratch_bytes.restype = ctypes.c_int64
     lib.pda_input_stage_workspace_bytes.restype = ctypes.c_int64
+    lib.pda_augment_workspace_bytes.restype = ctypes.c_int64
     lib.pda_abi_version.restype = _i
     lib.pda_last_error.restype = ctypes.c_char_p
     lib.pda_fp_contract_mode.restype = _i

@@ -8,13 +8,9 @@
 // lane tests its point against the records in ascending box order; LDS reads are wave-uniform
 // (broadcast).  HBM traffic is the compulsory pts + boxes + idx; the kernel is latency/VALU-trivial.
 #include "pda_common.h"
+#include "box_rec.h"
 
 namespace pda {
-
-struct BoxRec {
-    float cx, cy, cz, cosa, sina, hz;  // hz = dz/2 (exact in float)
-    double lim_x, lim_y;               // dx/2.0 + MARGIN, dy/2.0 + MARGIN as the reference's double expression
-};
 
 __global__ __launch_bounds__(256) void points_in_boxes_kernel(const float* __restrict__ boxes, const float* __restrict__ pts,
                                                               int* __restrict__ out, int t, int m) {
@@ -33,30 +29,13 @@ __global__ __launch_bounds__(256) void points_in_boxes_kernel(const float* __res
         __syncthreads();
         if ((int)threadIdx.x < nk) {
             const float* b = boxes + ((size_t)bs * t + k0 + threadIdx.x) * 7;
-            BoxRec r;
-            r.cx = b[0]; r.cy = b[1]; r.cz = b[2];
-            r.hz = b[5] * 0.5f;
-            const double a = (double)(-b[6]);
-            r.cosa = (float)cos(a);
-            r.sina = (float)sin(a);
-            r.lim_x = (double)b[3] / 2.0 + (double)1e-5f;
-            r.lim_y = (double)b[4] / 2.0 + (double)1e-5f;
+            const BoxRec r = make_box_rec(b[0], b[1], b[2], b[3], b[4], b[5], b[6], (double)1e-5f);
             rec[threadIdx.x] = r;
         }
         __syncthreads();
         if (live && found < 0) {
             for (int k = 0; k < nk; ++k) {
-                const BoxRec& r = rec[k];
-                if (fabsf(z - r.cz) > r.hz) continue;
-                const float sx = x - r.cx, sy = y - r.cy;
-#if PDA_FP_CONTRACT
-                const float lx = __builtin_fmaf(sx, r.cosa, sy * (-r.sina));
-                const float ly = __builtin_fmaf(sx, r.sina, sy * r.cosa);
-#else
-                const float lx = sx * r.cosa + sy * (-r.sina);
-                const float ly = sx * r.sina + sy * r.cosa;
-#endif
-                if ((int)((double)fabsf(lx) < r.lim_x) & (int)((double)fabsf(ly) < r.lim_y)) {
+                if (in_box_rec<PDA_FP_CONTRACT != 0>(rec[k], x, y, z)) {
                     found = k0 + k;
                     break;
                 }

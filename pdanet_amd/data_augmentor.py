@@ -1,0 +1,421 @@
+"""The training-time augmentor on the device: ragged raw scenes -> ragged augmented scenes, ready for DataProcessor.
+
+The reference augments every scene on the host (pcdet/datasets/augmentor/data_augmentor.py DataAugmentor.forward and
+database_sampler.py DataBaseSampler, called from pcdet/datasets/dataset.py prepare_data).  DataAugmentor reads the same
+DATA_AUGMENTOR block and runs gt_sampling -> random_world_flip -> random_world_rotation -> random_world_scaling ->
+limit_period and prepare_data's class filter for all scenes of a batch in four launches (csrc/augment.hip,
+include/pda_train.h pda_augment).
+
+What stays on the host is what decides, per batch, which objects are tried and how each scene is transformed -- the
+plan: the sampler's pointer / permutation bookkeeping (kept across calls, as the reference keeps it), the flip / rotation
+/ scaling draws and, with USE_ROAD_PLANE, the road-plane shift of every candidate.  It is built from host class ids
+only and uploaded with one copy.  Everything that touches points or boxes -- the BEV collision test, the removal of
+scene points inside the pasted boxes, the paste and the world transforms -- runs on the device.
+
+Randomness: `plan=` takes the draws the reference made (exact reproduction); otherwise they come from a numpy Generator
+seeded from torch's CPU generator, so torch.manual_seed makes a run reproducible.  The Generator's stream is not the
+reference's legacy np.random stream.
+
+A scene the augmentor leaves without a box is only flagged (info[:, 3] bit 1): the reference's prepare_data draws
+another scene there, which a batch-level loader has to decide for itself.
+"""
+import ctypes
+import os
+import pickle
+
+import numpy as np
+import torch
+
+from . import _lib
+from .pointnet2_batch_cuda import F32, _call, _chk
+
+# info[:, 3] status bits (include/pda_train.h pda_augment)
+STATUS_NO_BOX, STATUS_BAD_OFFSETS, STATUS_OVER_CAP, STATUS_BAD_CAND = 1, 2, 4, 8
+MAX_CANDIDATES = 256
+_STEPS = ("gt_sampling", "random_world_flip", "random_world_rotation", "random_world_scaling")
+
+
+def _get(cfg, key, default=None):
+    return cfg[key] if key in cfg else default
+
+
+def class_ids(gt_names, class_names):
+    """prepare_data's class column: CLASS_NAMES.index(name) + 1, and 0 for a name outside CLASS_NAMES."""
+    names = list(class_names)
+    return np.array([names.index(n) + 1 if n in names else 0 for n in gt_names], np.int32)
+
+
+class GtDatabase:
+    """The gt_sampling database on the device: every object of CLASS_NAMES in class order, its points relative to its
+    box centre (as the reference stores them), its box (float32), its centre box3d_lidar[:3] (float64) and class id.
+    Host copies of the boxes and sizes stay for the plan."""
+
+    def __init__(self, class_names, boxes, points, device=None):
+        self.class_names = list(class_names)
+        dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self.start, self.count = {}, {}
+        box_rows, pts, cls = [], [], []
+        for ci, name in enumerate(self.class_names):
+            b = np.asarray(boxes.get(name, np.zeros((0, 7))), np.float64)
+            b = b.reshape(-1, b.shape[-1]) if b.size else np.zeros((0, 7))
+            p = list(points.get(name, []))
+            if b.shape[1] != 7:
+                raise NotImplementedError("database boxes with %d values: boxes with velocities are not supported" % b.shape[1])
+            if len(p) != b.shape[0]:
+                raise ValueError("class %s: %d boxes but %d point sets" % (name, b.shape[0], len(p)))
+            self.start[name] = sum(len(x) for x in box_rows)
+            self.count[name] = b.shape[0]
+            box_rows.append(b)
+            pts.extend(np.asarray(x, np.float32) for x in p)
+            cls.extend([ci + 1] * b.shape[0])
+        centre = np.concatenate(box_rows, 0) if box_rows else np.zeros((0, 7))
+        self.n_obj = centre.shape[0]
+        C = pts[0].shape[1] if pts else 4
+        if any(x.ndim != 2 or x.shape[1] != C for x in pts):
+            raise ValueError("every object needs (n, C) points with the same C")
+        self.num_point_features = C
+        self.sizes = np.array([x.shape[0] for x in pts], np.int64)
+        self.host_boxes = centre.astype(np.float32)                # sampled_boxes = box3d_lidar.astype(np.float32)
+        offs = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)
+        allp = np.concatenate(pts, 0) if pts else np.zeros((0, C), np.float32)
+        self.device = dev
+        self.points = torch.from_numpy(np.ascontiguousarray(allp)).to(dev)
+        self.offsets = torch.from_numpy(offs).to(dev)
+        self.boxes = torch.from_numpy(np.ascontiguousarray(self.host_boxes)).to(dev)
+        self.centre = torch.from_numpy(np.ascontiguousarray(centre[:, :3])).to(dev)
+        self.classes = torch.from_numpy(np.array(cls, np.int32)).to(dev)
+
+    @classmethod
+    def from_arrays(cls, class_names, boxes, points, device=None):
+        """boxes: {class name: (n, 7) box3d_lidar (float64 as the dbinfos hold them)}; points: {class name: [n arrays
+        (n_i, C) of object points relative to the box centre]}."""
+        return cls(class_names, boxes, points, device)
+
+    @classmethod
+    def from_dbinfos(cls, root_path, sampler_cfg, class_names, device=None):
+        """The database DataBaseSampler.__init__ builds: the DB_INFO_PATH pickles under root_path, PREPARE applied
+        (filter_by_min_points, filter_by_difficulty), points from the per-object .bin files or, with
+        USE_SHARED_MEMORY, from DB_DATA_PATH[0] sliced by global_data_offset."""
+        db_infos = {name: [] for name in class_names}
+        for rel in sampler_cfg['DB_INFO_PATH']:
+            with open(os.path.join(str(root_path), rel), 'rb') as f:
+                infos = pickle.load(f)
+            for name in class_names:
+                db_infos[name].extend(infos[name])
+        for func, val in _get(sampler_cfg, 'PREPARE', {}).items():
+            if func == 'filter_by_min_points':
+                db_infos = _filter_by_min_points(db_infos, val)
+            elif func == 'filter_by_difficulty':
+                db_infos = {k: [i for i in v if i['difficulty'] not in val] for k, v in db_infos.items()}
+            else:
+                raise NotImplementedError("PREPARE step %r" % func)
+        C = int(sampler_cfg['NUM_POINT_FEATURES'])
+        data = None
+        if _get(sampler_cfg, 'USE_SHARED_MEMORY', False):
+            data = np.load(os.path.join(str(root_path), sampler_cfg['DB_DATA_PATH'][0]))
+        boxes, points = {}, {}
+        for name in class_names:
+            infos = db_infos[name]
+            boxes[name] = (np.stack([np.asarray(i['box3d_lidar'], np.float64) for i in infos]) if infos
+                           else np.zeros((0, 7)))
+            pl = []
+            for i in infos:
+                if data is not None:
+                    s, e = i['global_data_offset']
+                    pl.append(np.array(data[s:e], np.float32).reshape(-1, C))
+                else:
+                    pl.append(np.fromfile(os.path.join(str(root_path), i['path']), dtype=np.float32).reshape(-1, C))
+            points[name] = pl
+        return cls(class_names, boxes, points, device)
+
+
+def _filter_by_min_points(db_infos, min_gt_points_list):
+    for name_num in min_gt_points_list:
+        name, min_num = name_num.split(':')
+        min_num = int(min_num)
+        if min_num > 0 and name in db_infos:
+            db_infos[name] = [i for i in db_infos[name] if i['num_points_in_gt'] >= min_num]
+    return db_infos
+
+
+class _Group:
+    def __init__(self, name, num, class_id, length):
+        self.name, self.num, self.class_id = name, num, class_id
+        self.pointer, self.indices = length, np.arange(length)
+
+
+class DataAugmentor:
+    """DATA_AUGMENTOR of a reference-shaped yaml (AUG_CONFIG_LIST minus DISABLE_AUG_LIST): gt_sampling,
+    random_world_flip, random_world_rotation and random_world_scaling, in the order the list gives.  Any other step
+    raises NotImplementedError; gt_sampling must come first (the kernel applies the transforms after the paste)."""
+
+    def __init__(self, aug_cfg, class_names, database=None):
+        self.class_names = list(class_names)
+        cfg_list = aug_cfg if isinstance(aug_cfg, list) else aug_cfg['AUG_CONFIG_LIST']
+        disabled = [] if isinstance(aug_cfg, list) else list(_get(aug_cfg, 'DISABLE_AUG_LIST', []))
+        self.sampler_cfg = None
+        self.flip_axes, self.flip_prob = [], 0.5
+        self.rot_range, self.rot_prob = None, 1.0
+        self.scale_range, self.scale_prob = None, 1.0
+        seen = []
+        for cfg in cfg_list:
+            name = cfg['NAME']
+            if name in disabled:
+                continue
+            if name not in _STEPS:
+                raise NotImplementedError("DATA_AUGMENTOR step %r has no device implementation" % name)
+            if name in seen:
+                raise NotImplementedError("DATA_AUGMENTOR step %r appears twice" % name)
+            if name == 'gt_sampling' and seen:
+                raise NotImplementedError("gt_sampling must be the first DATA_AUGMENTOR step")
+            seen.append(name)
+            if name == 'gt_sampling':
+                self.sampler_cfg = cfg
+            elif name == 'random_world_flip':
+                self.flip_axes = list(cfg['ALONG_AXIS_LIST'])
+                if any(a not in ('x', 'y') for a in self.flip_axes):
+                    raise ValueError("random_world_flip takes the axes 'x' and 'y'")
+                self.flip_prob = float(_get(cfg, 'ENABLE_PROB', 0.5))
+            elif name == 'random_world_rotation':
+                r = cfg['WORLD_ROT_ANGLE']
+                self.rot_range = [float(r[0]), float(r[1])] if isinstance(r, (list, tuple)) else [-float(r), float(r)]
+                self.rot_prob = float(_get(cfg, 'ENABLE_PROB', 1.0))
+            else:
+                self.scale_range = [float(x) for x in cfg['WORLD_SCALE_RANGE']]
+                self.scale_prob = float(_get(cfg, 'ENABLE_PROB', 1.0))
+        self.database = database
+        self.groups, self.limit_whole_scene, self.use_road_plane = [], False, False
+        self.remove_extra_width = np.zeros(3, np.float32)
+        if self.sampler_cfg is not None:
+            if database is None:
+                raise ValueError("gt_sampling needs a GtDatabase")
+            if database.class_names != self.class_names:
+                raise ValueError("the database was built for other CLASS_NAMES")
+            if _get(self.sampler_cfg, 'DATABASE_WITH_FAKELIDAR', False):
+                raise NotImplementedError("DATABASE_WITH_FAKELIDAR")
+            self.limit_whole_scene = bool(_get(self.sampler_cfg, 'LIMIT_WHOLE_SCENE', False))
+            self.use_road_plane = bool(_get(self.sampler_cfg, 'USE_ROAD_PLANE', False))
+            self.remove_extra_width = np.asarray(self.sampler_cfg['REMOVE_EXTRA_WIDTH'], np.float32).reshape(3)
+            names = {}
+            for x in self.sampler_cfg['SAMPLE_GROUPS']:
+                name, num = x.split(':')
+                if name not in self.class_names:
+                    continue
+                names[name] = int(num)          # the reference keeps one group per class (a dict), the last count wins
+            for name, num in names.items():
+                self.groups.append(_Group(name, num, self.class_names.index(name) + 1, database.count[name]))
+        self._rew_c = (ctypes.c_float * 3)(*self.remove_extra_width.tolist())
+
+    # ---- the plan ----------------------------------------------------------------------------------------------------
+    def sample_candidates(self, gt_classes, permutation):
+        """DataBaseSampler's bookkeeping for a batch: per scene, the database ids tried by each class group in
+        SAMPLE_GROUPS order, and their groups.  permutation(n) draws the new order when a class's pointer wraps.
+        Advances the sampler state, as the reference does."""
+        cand, group = [], []
+        for cls in gt_classes:
+            cls = np.asarray(cls).reshape(-1)
+            ids, grp = [], []
+            for g, st in enumerate(self.groups):
+                num = st.num - int((cls == st.class_id).sum()) if self.limit_whole_scene else st.num
+                if num <= 0:
+                    continue
+                length = self.database.count[st.name]
+                if st.pointer >= length:
+                    st.indices = np.asarray(permutation(length))
+                    st.pointer = 0
+                sel = st.indices[st.pointer:st.pointer + num]
+                st.pointer += num
+                ids.extend((self.database.start[st.name] + sel).tolist())
+                grp.extend([g] * len(sel))
+            cand.append(np.array(ids, np.int32))
+            group.append(np.array(grp, np.int32))
+        return cand, group
+
+    def make_plan(self, gt_classes, rng=None):
+        """The draws of one batch from a numpy Generator (default: seeded from torch's CPU generator): gt_sampling's
+        permutations, then per scene flip x / flip y, rotation, scaling, each behind its ENABLE_PROB."""
+        if rng is None:
+            rng = np.random.default_rng(int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
+        B = len(gt_classes)
+        plan = {}
+        if self.groups:
+            plan['cand'], plan['cand_group'] = self.sample_candidates(gt_classes, rng.permutation)
+        fx, fy, ang, scl = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B), np.ones(B, np.float32)
+        for b in range(B):
+            for ax in self.flip_axes:
+                on = rng.random() < self.flip_prob
+                if ax == 'x':
+                    fx[b] = on
+                else:
+                    fy[b] = on
+            if self.rot_range is not None and rng.random() < self.rot_prob:
+                ang[b] = rng.uniform(self.rot_range[0], self.rot_range[1])
+            if self.scale_range is not None and self.scale_range[1] - self.scale_range[0] >= 1e-3 and rng.random() < self.scale_prob:
+                scl[b] = np.float32(rng.uniform(self.scale_range[0], self.scale_range[1]))
+        plan.update(flip_x=fx, flip_y=fy, angle=ang, scale=scl)
+        return plan
+
+    def _mv_height(self, ids, road_plane, calib):
+        """put_boxes_on_road_planes for the candidate boxes (each row on its own, so every candidate gets the shift
+        it would get if accepted)."""
+        boxes = self.database.host_boxes[ids].copy()
+        a, b, c, d = road_plane
+        center_cam = calib.lidar_to_rect(boxes[:, 0:3])
+        cur_height_cam = (-d - a * center_cam[:, 0] - c * center_cam[:, 2]) / b
+        center_cam[:, 1] = cur_height_cam
+        cur_lidar_height = calib.rect_to_lidar(center_cam)[:, 2]
+        return np.asarray(boxes[:, 2] - boxes[:, 5] / 2 - cur_lidar_height, np.float64)
+
+    # ------------------------------------------------------------------------------------------------------------------
+    def __call__(self, points, gt_boxes, gt_classes, plan=None, rng=None, road_planes=None, calib=None, check=True):
+        """points: a list of B (n_i, C) arrays (host), or a tuple (packed (n_total, C) float32, offsets (B + 1) int64,
+        n_cap) of device tensors.  gt_boxes: a list of B (m_i, 7) arrays, or a tuple (packed (m_total, 7) float32,
+        box_offsets (B + 1) int64) of device tensors.  gt_classes: per scene, the host class ids of its boxes
+        (class_ids(gt_names, CLASS_NAMES): 0 = a name outside CLASS_NAMES).
+        plan: dict(cand=, cand_group=, flip_x=, flip_y=, angle=, scale=) -- cand / cand_group per scene (database ids
+        in the order the sampler tried them, their group index); flip_x / flip_y 0/1, angle (0 = no rotation), scale
+        (1 = no scaling) per scene.  None: drawn by make_plan(gt_classes, rng), which advances the sampler.
+        road_planes / calib: per scene, required by USE_ROAD_PLANE (the reference's road_plane [a, b, c, d] and a
+        calibration with lidar_to_rect / rect_to_lidar).
+        check: read info once and raise ValueError on malformed input (bad offsets, over capacity, a bad candidate).
+        With check=False and device inputs nothing is read back.
+        Returns ((points (rows, C), offsets (B + 1), n_cap), (boxes (rows, 8) [x, y, z, dx, dy, dz, heading, class],
+        box_offsets (B + 1)), info (B, 4) int32 [points out, boxes out, accepted samples, status]); the first two feed
+        DataProcessor.__call__ as they are."""
+        B = len(gt_classes)
+        if plan is None:
+            plan = self.make_plan(gt_classes, rng)
+        dev_in = isinstance(points, tuple)
+        if dev_in:
+            pts, offs, n_cap = points
+            if not (isinstance(gt_boxes, tuple) and pts.is_cuda and offs.is_cuda):
+                raise ValueError("device points take gt_boxes as a (packed, box_offsets) tuple of device tensors")
+            bxs7, boffs = gt_boxes
+            dev = pts.device
+            if offs.numel() != B + 1 or boffs.numel() != B + 1:
+                raise ValueError("offsets need B + 1 entries")
+            if bxs7.dim() != 2 or bxs7.shape[1] != 7:
+                raise NotImplementedError("boxes with more than 7 values (velocities) are not supported")
+            n_total, C, n_cap, m_total = pts.shape[0], pts.shape[1], int(n_cap), bxs7.shape[0]
+        else:
+            if len(points) != B or len(gt_boxes) != B:
+                raise ValueError("points, gt_boxes and gt_classes need one entry per scene")
+            arrs = [np.asarray(p, np.float32) for p in points]
+            C = arrs[0].shape[1]
+            if any(a.ndim != 2 or a.shape[1] != C for a in arrs):
+                raise ValueError("every scene must be (n_i, C) with the same C")
+            bl = [np.asarray(g, np.float32).reshape(len(g), -1) if len(g) else np.zeros((0, 7), np.float32) for g in gt_boxes]
+            if any(g.shape[1] != 7 for g in bl):
+                raise NotImplementedError("boxes with more than 7 values (velocities) are not supported")
+            sizes = [a.shape[0] for a in arrs]
+            n_total, n_cap, m_total = sum(sizes), max(max(sizes), 1), sum(len(g) for g in bl)
+            dev = self.database.device if self.database is not None else torch.device('cuda', torch.cuda.current_device())
+        cls_rows = [np.asarray(c, np.int32).reshape(-1) for c in gt_classes]
+        if sum(len(c) for c in cls_rows) != m_total:
+            raise ValueError("gt_classes needs one class id per box")
+        db = self.database
+        if db is not None and db.num_point_features != C:
+            raise ValueError("the database holds %d point features, the scenes %d" % (db.num_point_features, C))
+
+        # ---- the plan as arrays --------------------------------------------------------------------------------------
+        cand_rows = plan.get('cand') if self.groups else None
+        cand_rows = cand_rows if cand_rows is not None else [np.zeros(0, np.int32)] * B
+        grp_rows = plan.get('cand_group') if self.groups else None
+        grp_rows = grp_rows if grp_rows is not None else [np.zeros(0, np.int32)] * B
+        if len(cand_rows) != B or len(grp_rows) != B:
+            raise ValueError("plan['cand'] / plan['cand_group'] need one row per scene")
+        K = max([len(r) for r in cand_rows] + [0])
+        if K > MAX_CANDIDATES:
+            raise ValueError("more than %d candidates in one scene" % MAX_CANDIDATES)
+        cand = np.full((B, K), -1, np.int32)
+        grp = np.full((B, K), -1, np.int32)
+        dz = np.zeros((B, K), np.float64)
+        paste = np.zeros(B, np.int64)
+        if self.use_road_plane and any(len(r) for r in cand_rows) and (road_planes is None or calib is None):
+            raise ValueError("USE_ROAD_PLANE needs road_planes and calib")
+        for b in range(B):
+            r = np.asarray(cand_rows[b], np.int64).reshape(-1)
+            g = np.asarray(grp_rows[b], np.int32).reshape(-1)
+            if len(g) != len(r):
+                raise ValueError("plan['cand_group'][%d] does not match plan['cand'][%d]" % (b, b))
+            cand[b, :len(r)] = r
+            grp[b, :len(r)] = g
+            ok = (r >= 0) & (r < (db.n_obj if db is not None else 0))
+            if len(r) and db is not None:
+                paste[b] = int(db.sizes[r[ok]].sum())
+                if self.use_road_plane:
+                    dz[b, :len(r)][ok] = self._mv_height(r[ok], road_planes[b], calib[b])
+        paste_cap = int(paste.max()) if B else 0
+        n_cand = int((cand >= 0).sum())
+        fx = np.asarray(plan.get('flip_x', np.zeros(B)), np.int32).reshape(B)
+        fy = np.asarray(plan.get('flip_y', np.zeros(B)), np.int32).reshape(B)
+        flip = np.ascontiguousarray(np.stack([fx, fy], 1).astype(np.int32))
+        angle = np.asarray(plan.get('angle', np.zeros(B)), np.float64).reshape(B)
+        scale = np.asarray(plan.get('scale', np.ones(B)), np.float32).reshape(B)
+
+        # ---- one upload: plan | class column | host scenes --------------------------------------------------------------
+        parts = [cand, grp, dz, flip, angle, scale, np.concatenate(cls_rows).astype(np.float32) if m_total else np.zeros(0, np.float32)]
+        if not dev_in:
+            parts += [np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64),
+                      np.concatenate([[0], np.cumsum([len(g) for g in bl])]).astype(np.int64),
+                      np.concatenate(arrs, 0) if n_total else np.zeros((0, C), np.float32),
+                      np.concatenate(bl, 0) if m_total else np.zeros((0, 7), np.float32)]
+        sizes_b = [p.nbytes for p in parts]
+        starts = np.concatenate([[0], np.cumsum([(s + 7) // 8 * 8 for s in sizes_b])]).astype(np.int64)
+        host = torch.empty((max(int(starts[-1]), 8),), dtype=torch.uint8, pin_memory=True)
+        hn = host.numpy()
+        for p, s, n in zip(parts, starts[:-1], sizes_b):
+            hn[s:s + n] = np.ascontiguousarray(p).reshape(-1).view(np.uint8)
+        dbuf = host.to(dev, non_blocking=True)
+        views = [dbuf[s:s + n] for s, n in zip(starts[:-1].tolist(), sizes_b)]
+        d_cand, d_grp = views[0].view(torch.int32), views[1].view(torch.int32)
+        d_dz, d_flip = views[2].view(torch.float64), views[3].view(torch.int32)
+        d_angle, d_scale, d_cls = views[4].view(torch.float64), views[5].view(torch.float32), views[6].view(torch.float32)
+        if not dev_in:
+            offs, boffs = views[7].view(torch.int64), views[8].view(torch.int64)
+            pts = views[9].view(torch.float32).view(-1, C)
+            bxs7 = views[10].view(torch.float32).view(-1, 7)
+        bxs = torch.cat([bxs7.to(torch.float32), d_cls.view(-1, 1)], dim=1).contiguous()
+
+        # ---- the launch ------------------------------------------------------------------------------------------------
+        lib = _lib.load()
+        ws_bytes = lib.pda_augment_workspace_bytes(B, n_cap, K)
+        if ws_bytes < 0:
+            raise ValueError("batch %d / n_cap %d / %d candidates out of range" % (B, n_cap, K))
+        ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+        out_cap = n_total + int(paste.sum())
+        box_cap = m_total + n_cand
+        out = torch.empty((max(out_cap, 1), C), dtype=torch.float32, device=dev)
+        out_boxes = torch.empty((max(box_cap, 1), 8), dtype=torch.float32, device=dev)
+        out_offs = torch.empty((B + 1,), dtype=torch.int64, device=dev)
+        out_boffs = torch.empty((B + 1,), dtype=torch.int64, device=dev)
+        info = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        if db is not None:
+            dbp = (db.points.data_ptr() if db.points.numel() else None, db.offsets.data_ptr(), db.points.shape[0],
+                   db.boxes.data_ptr() if db.n_obj else None, db.centre.data_ptr() if db.n_obj else None,
+                   db.classes.data_ptr() if db.n_obj else None, db.n_obj)
+        else:
+            dbp = (None, None, 0, None, None, None, 0)
+        _call("pda_augment", pts, _chk(pts, "points", F32) if n_total else None, _chk(offs, "offsets", torch.int64), n_total, B, C,
+              n_cap, bxs.data_ptr() if m_total else None, _chk(boffs, "box_offsets", torch.int64), m_total, *dbp,
+              d_cand.data_ptr() if K else None, d_grp.data_ptr() if K else None, d_dz.data_ptr() if K else None, K,
+              d_flip.data_ptr(), d_angle.data_ptr(), d_scale.data_ptr(), self._rew_c, paste_cap, out.data_ptr(), out_cap,
+              out_offs.data_ptr(), out_boxes.data_ptr(), box_cap, out_boffs.data_ptr(), info.data_ptr(), ws.data_ptr())
+        if check:
+            self._check(info.cpu())
+        return (out, out_offs, n_cap + paste_cap), (out_boxes, out_boffs), info
+
+    @staticmethod
+    def _check(info):
+        for b, (_, _, _, status) in enumerate(info.tolist()):
+            if status & STATUS_BAD_OFFSETS:
+                raise ValueError("scene %d: offsets outside the packed points or boxes" % b)
+            if status & STATUS_OVER_CAP:
+                raise ValueError("scene %d: more than n_cap points or an output capacity exceeded" % b)
+            if status & STATUS_BAD_CAND:
+                raise ValueError("scene %d: a candidate id outside the database or candidate groups out of order" % b)
+
+
+def from_config(cfg, database=None):
+    """DataAugmentor of a loaded yaml (pdanet_amd.config.load_yaml): DATA_CONFIG.DATA_AUGMENTOR and CLASS_NAMES."""
+    return DataAugmentor(cfg['DATA_CONFIG']['DATA_AUGMENTOR'], cfg['CLASS_NAMES'], database)
