@@ -480,6 +480,52 @@ int pda_augment(const float *points, const int64_t *offsets, int64_t n_total, in
                 int64_t paste_cap, float *out_points, int64_t out_cap, int64_t *out_offsets, float *out_boxes,
                 int64_t out_box_cap, int64_t *out_box_offsets, int32_t *info, void *workspace, pda_stream_t stream);
 
+/* ---- ONCE evaluation (csrc/once_eval.hip; the reference's once_eval get_evaluation_results on the device) ------------
+ * Frames: GT boxes (n_gt_total, 7) float64 [x, y, z, dx, dy, dz, heading] with gt_name (n_gt_total) int32 name ids and
+ * gt_offsets (n_frames + 1) int64; predictions of frame f are rows [pred_start[f], pred_start[f] + pred_count[f]) of
+ * pred_boxes (pred_cap, 7) float32, pred_score (pred_cap) float32 and pred_name (pred_cap) int32 (packed or padded
+ * storage alike).  The IoU block of frame f is n_gt x pred_count row-major at iou[iou_start[f]], iou_start[f] plus
+ * n_gt * pred_count at most iou_cap.  All arrays are on the device; max_gt / max_pred bound every frame (max_pred <= 4096).
+ * A frame outside these bounds sets status bit 1 and counts as empty.  A name id outside [0, n_names) sets bit 2 and is
+ * rejected by every class. */
+typedef struct pda_once_frames {
+    const double *gt_boxes;
+    const int32_t *gt_name;
+    const int64_t *gt_offsets;
+    const float *pred_boxes, *pred_score;
+    const int32_t *pred_name;
+    const int64_t *pred_start;
+    const int32_t *pred_count;
+    const int64_t *iou_start;
+    int64_t n_gt_total, pred_cap, iou_cap;
+    int n_frames, max_gt, max_pred;
+} pda_once_frames_t;
+
+/* workspace of pda_once_eval_accumulate / pda_once_eval_match for n_tasks = classes x difficulties, 256-byte aligned:
+ * the TP-score segments (n_tasks, n_gt_total) float32 at offset 0, then n_tasks int64 TP counts (-1: bad sizes). */
+int64_t pda_once_eval_workspace_bytes(int n_frames, int64_t n_gt_total, int n_tasks);
+/* 3D IoU of every (GT, prediction) pair of a frame, as the reference's iou3d_kernel(_with_heading): the rotated BEV
+ * intersection in float32 (iou_utils.devRotateIoUEval(pred, gt, 2)), the rest in float64; with_heading zeroes pairs whose
+ * heading difference folded to [0, pi] exceeds pi / 2.  One launch. */
+int pda_once_eval_iou(const pda_once_frames_t *frames, int with_heading, double *iou, int32_t *status,
+                      pda_stream_t stream);
+/* accumulate_scores for every (frame, class, difficulty): accept (HOST) n_classes x n_names bytes (1: the class takes
+ * the name), iou_thr (HOST) n_classes, difficulty_mode 0 'Overall&Distance' (4 levels), 1 'Overall' (1), 2 'Distance'
+ * (3); n_classes <= 16, n_names <= 64.  Writes the TP scores of task t = class * n_difficulties + level to workspace
+ * segment t at the frame's GT rows, -inf in the rest, the TP counts, and num_valid_gt (n_tasks) int64.  The caller sorts
+ * each segment in descending order before pda_once_eval_match. */
+int pda_once_eval_accumulate(const pda_once_frames_t *frames, const double *iou, const uint8_t *accept, int n_classes,
+                             int n_names, const double *iou_thr, int difficulty_mode, int64_t *num_valid_gt,
+                             int32_t *status, void *workspace, pda_stream_t stream);
+/* get_thresholds and compute_statistics: sorted_scores (n_tasks, n_gt_total) float32, each row in descending order (the
+ * workspace segments sorted); thresholds (n_tasks, num_pr_points + 1) float64, n_thresholds (n_tasks) int64 (more than
+ * num_pr_points + 1 sets status bit 4), counts (n_tasks, num_pr_points + 1, 3) int64 tp / fp / fn summed over frames.
+ * Same frames, table and mode as pda_once_eval_accumulate.  Two launches. */
+int pda_once_eval_match(const pda_once_frames_t *frames, const double *iou, const uint8_t *accept, int n_classes,
+                        int n_names, const double *iou_thr, int difficulty_mode, int num_pr_points,
+                        const float *sorted_scores, const int64_t *num_valid_gt, double *thresholds,
+                        int64_t *n_thresholds, int64_t *counts, int32_t *status, void *workspace, pda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

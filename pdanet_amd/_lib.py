@@ -21,6 +21,15 @@ class DensityNetScale(ctypes.Structure):
                 ("eps", ctypes.c_float), ("momentum", ctypes.c_float)]
 
 
+class OnceFrames(ctypes.Structure):
+    """pda_once_frames_t (include/pda_train.h)."""
+    _fields_ = [("gt_boxes", ctypes.c_void_p), ("gt_name", ctypes.c_void_p), ("gt_offsets", ctypes.c_void_p),
+                ("pred_boxes", ctypes.c_void_p), ("pred_score", ctypes.c_void_p), ("pred_name", ctypes.c_void_p),
+                ("pred_start", ctypes.c_void_p), ("pred_count", ctypes.c_void_p), ("iou_start", ctypes.c_void_p),
+                ("n_gt_total", ctypes.c_int64), ("pred_cap", ctypes.c_int64), ("iou_cap", ctypes.c_int64),
+                ("n_frames", ctypes.c_int), ("max_gt", ctypes.c_int), ("max_pred", ctypes.c_int)]
+
+
 # Bumped by anything that writes parameters behind autograd's back (optimization.FlatAdamOneCycle.step updates the flat
 # parameter buffer through a raw pointer, so tensor version counters do not move): caches of derived tensors (bf16 weight
 # copies, BatchNorm folded into convolutions) key on it next to the version counters.
@@ -155,6 +164,12 @@ SIGNATURES = {
     "pda_augment": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp,
                     _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, ctypes.POINTER(_f), ctypes.c_int64, _vp, ctypes.c_int64,
                     _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp],
+    "pda_once_eval_workspace_bytes": [_i, ctypes.c_int64, _i],
+    "pda_once_eval_iou": [ctypes.POINTER(OnceFrames), _i, _vp, _vp, _vp],
+    "pda_once_eval_accumulate": [ctypes.POINTER(OnceFrames), _vp, _vp, _i, _i, ctypes.POINTER(ctypes.c_double), _i, _vp, _vp,
+                                 _vp, _vp],
+    "pda_once_eval_match": [ctypes.POINTER(OnceFrames), _vp, _vp, _i, _i, ctypes.POINTER(ctypes.c_double), _i, _i, _vp, _vp,
+                            _vp, _vp, _vp, _vp, _vp, _vp],
     # include/pda_pointnet2_stack.h
     "pda_stack_ball_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     "pda_stack_group_points": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -202,6 +217,7 @@ def load():
     lib.pda_sa_xyz_grad_scratch_bytes.restype = ctypes.c_int64
     lib.pda_input_stage_workspace_bytes.restype = ctypes.c_int64
     lib.pda_augment_workspace_bytes.restype = ctypes.c_int64
+    lib.pda_once_eval_workspace_bytes.restype = ctypes.c_int64
     lib.pda_abi_version.restype = _i
     lib.pda_last_error.restype = ctypes.c_char_p
     lib.pda_fp_contract_mode.restype = _i

@@ -1,0 +1,534 @@
+// once_eval.hip -- ONCE detection evaluation on the device: the reference's once_eval get_evaluation_results
+// (evaluation.py, eval_utils.py, iou_utils.py) minus the final float64 AP composition, which the caller does on the
+// (tasks, thresholds, 3) counts.
+//
+//   once_iou_kernel     one thread per (frame, GT, prediction) pair: iou3d_kernel(_with_heading) of the frame's block.
+//   once_accum_kernel   one wave per (frame, class, level): accumulate_scores; TP scores into the task's segment.
+//   once_thresh_kernel  one wave per (class, level): get_thresholds over the descending TP scores.
+//   once_stats_kernel   four waves per (frame, class, level), one threshold each in turn: compute_statistics, summed
+//                       with integer atomics (order-independent, so deterministic).
+//
+// Predictions j of a frame are owned by lane j % 64 at bit j / 64 of 64-bit lane masks (accepted, ignored, assigned),
+// hence max_pred <= 4096.  The greedy GT loops stay serial over GTs, as in the reference; the scan over predictions is a
+// wave arg-max.
+#include "pda_common.h"
+
+#include <math.h>
+
+namespace pda {
+namespace {
+
+constexpr int OE_MAX_CLASSES = 16;
+constexpr int OE_MAX_NAMES = 64;
+constexpr int OE_MAX_PRED = 64 * 64;
+constexpr int OE_MAX_POLY = 24;  // 8 corners inside the other box + 16 edge crossings (the reference keeps 8)
+
+struct EvalArgs {
+    uint64_t accept[OE_MAX_CLASSES];  // bit n: the class takes name id n
+    double thr[OE_MAX_CLASSES];
+    int n_classes, n_names, n_levels, mode;
+};
+
+// ---- rotated BEV intersection, iou_utils.py (numba.cuda) -------------------------------------------------------------
+// All of it is float32 in the reference's operation order except where numba promotes: a float32 meeting an int or
+// float literal becomes float64.  That is exact for the halvings (x_d / 2, the centroid division rounds once either
+// way, triangle / 2.0) and matters in one place: area() accumulates the triangle areas in float64 (area_val = 0.0),
+// and the result is rounded to float32 when rotate_iou_kernel_eval stores it.  cos / sin are taken in double and
+// rounded, i.e. correctly rounded float32 values.
+
+__device__ __forceinline__ void rbox_corners(float* c, float x, float y, float xd, float yd, float ang) {
+    const float ac = (float)cos((double)ang), as = (float)sin((double)ang);
+    const float cx[4] = {-xd / 2, -xd / 2, xd / 2, xd / 2};
+    const float cy[4] = {-yd / 2, yd / 2, yd / 2, -yd / 2};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        c[2 * i] = (ac * cx[i] + as * cy[i]) + x;
+        c[2 * i + 1] = (-as * cx[i] + ac * cy[i]) + y;
+    }
+}
+
+__device__ __forceinline__ bool point_in_quad(float px, float py, const float* c) {
+    const float pa0 = c[0] - px, pa1 = c[1] - py, pb0 = c[2] - px, pb1 = c[3] - py;
+    const float pc0 = c[4] - px, pc1 = c[5] - py, pd0 = c[6] - px, pd1 = c[7] - py;
+    const float pab = pa0 * pb1 - pb0 * pa1, pbc = pb0 * pc1 - pc0 * pb1;
+    const float pcd = pc0 * pd1 - pd0 * pc1, pda = pd0 * pa1 - pa0 * pd1;
+    return (pab >= 0 && pbc >= 0 && pcd >= 0 && pda >= 0) || (pab <= 0 && pbc <= 0 && pcd <= 0 && pda <= 0);
+}
+
+__device__ __forceinline__ bool segment_cross(const float* p1, const float* p2, int i, int j, float* out) {
+    const float a0 = p1[2 * i], a1 = p1[2 * i + 1], b0 = p1[2 * ((i + 1) & 3)], b1 = p1[2 * ((i + 1) & 3) + 1];
+    const float c0 = p2[2 * j], c1 = p2[2 * j + 1], d0 = p2[2 * ((j + 1) & 3)], d1 = p2[2 * ((j + 1) & 3) + 1];
+    const float ba0 = b0 - a0, ba1 = b1 - a1, da0 = d0 - a0, ca0 = c0 - a0, da1 = d1 - a1, ca1 = c1 - a1;
+    const bool acd = da1 * ca0 > ca1 * da0;
+    const bool bcd = (d1 - b1) * (c0 - b0) > (c1 - b1) * (d0 - b0);
+    if (acd == bcd) return false;
+    const bool abc = ca1 * ba0 > ba1 * ca0;
+    const bool abd = da1 * ba0 > ba1 * da0;
+    if (abc == abd) return false;
+    const float dc0 = d0 - c0, dc1 = d1 - c1;
+    const float abba = a0 * b1 - b0 * a1, cddc = c0 * d1 - d0 * c1;
+    const float dh = ba1 * dc0 - ba0 * dc1;
+    const float dx = abba * dc0 - ba0 * cddc, dy = abba * dc1 - ba1 * cddc;
+    out[0] = dx / dh;
+    out[1] = dy / dh;
+    return true;
+}
+
+// devRotateIoUEval(rbox1 = pred, rbox2 = gt, criterion = 2): the intersection area, rounded to float32.
+__device__ float rotated_intersection(const float* q, const float* g) {
+    float c1[8], c2[8], pts[2 * OE_MAX_POLY], vs[OE_MAX_POLY];
+    rbox_corners(c1, q[0], q[1], q[2], q[3], q[4]);
+    rbox_corners(c2, g[0], g[1], g[2], g[3], g[4]);
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (point_in_quad(c1[2 * i], c1[2 * i + 1], c2)) { pts[2 * n] = c1[2 * i]; pts[2 * n + 1] = c1[2 * i + 1]; ++n; }
+        if (point_in_quad(c2[2 * i], c2[2 * i + 1], c1)) { pts[2 * n] = c2[2 * i]; pts[2 * n + 1] = c2[2 * i + 1]; ++n; }
+    }
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            float t[2];
+            if (segment_cross(c1, c2, i, j, t)) { pts[2 * n] = t[0]; pts[2 * n + 1] = t[1]; ++n; }
+        }
+    if (n == 0) return 0.0f;
+    // sort_vertex_in_convex_polygon: pseudo-angle insertion sort around the centroid
+    float cx = 0.0f, cy = 0.0f;
+    for (int i = 0; i < n; ++i) { cx += pts[2 * i]; cy += pts[2 * i + 1]; }
+    cx /= (float)n;
+    cy /= (float)n;
+    for (int i = 0; i < n; ++i) {
+        float v0 = pts[2 * i] - cx, v1 = pts[2 * i + 1] - cy;
+        const float d = __builtin_sqrtf(v0 * v0 + v1 * v1);
+        v0 = v0 / d;
+        v1 = v1 / d;
+        if (v1 < 0) v0 = -2.0f - v0;
+        vs[i] = v0;
+    }
+    for (int i = 1; i < n; ++i) {
+        if (vs[i - 1] > vs[i]) {
+            const float tv = vs[i], tx = pts[2 * i], ty = pts[2 * i + 1];
+            int j = i;
+            while (j > 0 && vs[j - 1] > tv) {
+                vs[j] = vs[j - 1];
+                pts[2 * j] = pts[2 * j - 2];
+                pts[2 * j + 1] = pts[2 * j - 1];
+                --j;
+            }
+            vs[j] = tv;
+            pts[2 * j] = tx;
+            pts[2 * j + 1] = ty;
+        }
+    }
+    // area(): fan triangulation, |triangle| each, accumulated in float64 (numba: area_val = 0.0, x / 2.0)
+    double a = 0.0;
+    for (int i = 0; i + 2 < n; ++i) {
+        const float* b = pts + 2 * i + 2;
+        const float* c = pts + 2 * i + 4;
+        const float t = (pts[0] - c[0]) * (b[1] - c[1]) - (pts[1] - c[1]) * (b[0] - c[0]);
+        a += fabs((double)t / 2.0);
+    }
+    return (float)a;
+}
+
+// ---- frame bookkeeping --------------------------------------------------------------------------------------------
+struct Frame {
+    int64_t g0, p0, i0;  // first GT row, first prediction row, first IoU element
+    int ng, np;
+};
+
+// The frame's ranges, or an empty frame (status bit 1) when they leave the declared bounds.
+__device__ __forceinline__ Frame load_frame(const pda_once_frames_t& fr, int f, int32_t* status) {
+    Frame F;
+    F.g0 = fr.gt_offsets[f];
+    const int64_t ng = fr.gt_offsets[f + 1] - F.g0;
+    F.p0 = fr.pred_start[f];
+    const int64_t np = fr.pred_count[f];
+    F.i0 = fr.iou_start[f];
+    const bool ok = F.g0 >= 0 && ng >= 0 && ng <= fr.max_gt && F.g0 + ng <= fr.n_gt_total && np >= 0 &&
+                    np <= fr.max_pred && F.p0 >= 0 && F.p0 + np <= fr.pred_cap && F.i0 >= 0 &&
+                    F.i0 + ng * np <= fr.iou_cap;
+    if (!ok) {
+        if (threadIdx.x == 0 && status) atomicOr(status, 1);
+        F.g0 = F.p0 = F.i0 = 0;
+        F.ng = F.np = 0;
+        return F;
+    }
+    F.ng = (int)ng;
+    F.np = (int)np;
+    return F;
+}
+
+// overall_distance_filter / distance_filter / overall_filter: true = the box is in the level (flag not 1).  The norm
+// follows np.sqrt(np.sum(b[:, 0:3] * b[:, 0:3], axis=1)) in the boxes' dtype: float64 for GT, float32 for predictions.
+template <typename T> __device__ __forceinline__ bool in_level(T x, T y, T z, int mode, int level) {
+    if (mode == 1) return true;
+    if (mode == 0) {
+        if (level == 0) return true;
+        --level;
+    }
+    const T d = sqrt((x * x + y * y) + z * z);
+    if (level == 0) return d < T(30);
+    if (level == 1) return d >= T(30) && d < T(50);
+    return d >= T(50);
+}
+
+// filter_data: the class rejection (-1) is written first and the level's ignore (1) over it, so a box of another class
+// outside the level is flagged 1, as in the reference.
+__device__ __forceinline__ int name_ok(const EvalArgs& a, int cls, int name, int32_t* status) {
+    if (name < 0 || name >= a.n_names) {
+        if (status) atomicOr(status, 2);
+        return 0;
+    }
+    return (int)((a.accept[cls] >> name) & 1ull);
+}
+
+__device__ __forceinline__ int gt_flag(const pda_once_frames_t& fr, const EvalArgs& a, int64_t row, int cls, int level) {
+    const double* b = fr.gt_boxes + row * 7;
+    if (!in_level<double>(b[0], b[1], b[2], a.mode, level)) return 1;
+    return name_ok(a, cls, fr.gt_name[row], nullptr) ? 0 : -1;
+}
+
+// The lane's prediction masks for (cls, level): bit k <-> prediction lane + 64 k.  acc: flag != -1, ign: flag == 1.
+__device__ __forceinline__ void pred_masks(const pda_once_frames_t& fr, const EvalArgs& a, const Frame& F, int cls,
+                                           int level, int32_t* status, uint64_t& acc, uint64_t& ign) {
+    acc = ign = 0;
+    const int lane = lane_id();
+    for (int j = lane, k = 0; j < F.np; j += 64, ++k) {
+        const int64_t row = F.p0 + j;
+        const float* b = fr.pred_boxes + row * 7;
+        const bool lev = in_level<float>(b[0], b[1], b[2], a.mode, level);
+        const int ok = name_ok(a, cls, fr.pred_name[row], status);
+        if (!lev) { acc |= 1ull << k; ign |= 1ull << k; }
+        else if (ok) acc |= 1ull << k;
+    }
+}
+
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint64_t w = __shfl_xor(v, o, 64);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+
+__device__ __forceinline__ uint32_t wave_min_u32s(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t w = __shfl_xor(v, o, 64);
+        v = w < v ? w : v;
+    }
+    return v;
+}
+
+// float32 -> unsigned key with the order of the floats
+__device__ __forceinline__ uint32_t ordered(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ bool lane_bit(uint64_t mask, int j) {
+    return (__ballot((mask >> (j >> 6)) & 1ull) >> (j & 63)) & 1ull;
+}
+
+// ---- kernels ----------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) once_iou_kernel(pda_once_frames_t fr, int with_heading, double* __restrict__ iou,
+                                                       int32_t* status) {
+    const int f = blockIdx.x;
+    const Frame F = load_frame(fr, f, status);
+    const int64_t pair = (int64_t)blockIdx.y * blockDim.x + threadIdx.x;
+    if (pair >= (int64_t)F.ng * F.np) return;
+    const int i = (int)(pair / F.np), j = (int)(pair % F.np);
+    const double* g = fr.gt_boxes + (F.g0 + i) * 7;
+    const float* p = fr.pred_boxes + (F.p0 + j) * 7;
+    // rotate_iou_gpu_eval casts both box sets to float32 and returns the float32 areas in the GT dtype
+    const float g5[5] = {(float)g[0], (float)g[1], (float)g[3], (float)g[4], (float)g[6]};
+    const float p5[5] = {p[0], p[1], p[3], p[4], p[6]};
+    const double inter2d = (double)rotated_intersection(p5, g5);
+    // heights and volumes: numpy arithmetic in each side's dtype, float64 once the two meet
+    const double g_max = g[2] + g[5] * 0.5, g_min = g[2] - g[5] * 0.5;
+    const float p_max = p[2] + p[5] * 0.5f, p_min = p[2] - p[5] * 0.5f;
+    const double max_of_min = fmax(g_min, (double)p_min), min_of_max = fmin(g_max, (double)p_max);
+    double inter_h = min_of_max - max_of_min;
+    if (inter_h <= 0) inter_h = 0;
+    const double inter3d = inter2d * inter_h;
+    const double g_vol = g[3] * g[4] * g[5];
+    const float p_vol = p[3] * p[4] * p[5];
+    const double uni = (g_vol + (double)p_vol) - inter3d;
+    double v = inter3d / uni;
+    if (with_heading) {
+        double dr = fabs(g[6] - (double)p[6]);
+        if (dr >= M_PI) dr = 2 * M_PI - dr;
+        if (dr > M_PI / 2) v = 0;
+    }
+    iou[F.i0 + pair] = v;
+}
+
+// accumulate_scores of one (frame, class, level); blockIdx.y = task = class * n_levels + level.
+__global__ void __launch_bounds__(64) once_accum_kernel(pda_once_frames_t fr, const double* __restrict__ iou, EvalArgs a,
+                                                        float* __restrict__ seg, int64_t* ntp, int64_t* nvalid,
+                                                        int32_t* status) {
+    const int f = blockIdx.x, task = blockIdx.y, cls = task / a.n_levels, level = task % a.n_levels;
+    const int lane = lane_id();
+    const Frame F = load_frame(fr, f, status);
+    uint64_t acc, ign;
+    pred_masks(fr, a, F, cls, level, status, acc, ign);
+    const double thr = a.thr[cls];
+    uint64_t assigned = 0;
+    float* out = seg + (int64_t)task * fr.n_gt_total + F.g0;
+    int n_tp = 0, n_valid = 0;
+    for (int i = 0; i < F.ng; ++i) {
+        const int gf = gt_flag(fr, a, F.g0 + i, cls, level);
+        if (gf == -1) continue;
+        n_valid += gf == 0;
+        // the first prediction with the highest score (> -1) among the unassigned accepted ones with iou > thr
+        const double* row = iou + F.i0 + (int64_t)i * F.np;
+        uint64_t best = 0;
+        for (uint64_t m = acc & ~assigned; m; m &= m - 1) {
+            const int j = lane + 64 * (int)__builtin_ctzll(m);
+            const float s = fr.pred_score[F.p0 + j];
+            if (row[j] > thr && s > -1.0f) {
+                const uint64_t key = ((uint64_t)ordered(s) << 32) | (uint32_t)(0xffffffffu - (uint32_t)j);
+                best = key > best ? key : best;
+            }
+        }
+        best = wave_max_u64(best);
+        if (best == 0) continue;
+        const int jd = (int)(0xffffffffu - (uint32_t)best);
+        if (lane == (jd & 63)) assigned |= 1ull << (jd >> 6);
+        if (gf == 1 || lane_bit(ign, jd)) continue;
+        if (lane == 0) out[n_tp] = fr.pred_score[F.p0 + jd];
+        ++n_tp;
+    }
+    for (int s = n_tp + lane; s < F.ng; s += 64) out[s] = -INFINITY;
+    if (lane == 0) {
+        atomicAdd((unsigned long long*)&ntp[task], (unsigned long long)n_tp);
+        atomicAdd((unsigned long long*)&nvalid[task], (unsigned long long)n_valid);
+    }
+}
+
+// get_thresholds of one task over its n TP scores, sorted descending; float64 throughout, recall_level advanced by
+// repeated += 1 / num_pr_points.  r + l is non-decreasing in i, so a wave evaluates 64 ranks at a time and the serial
+// walk only visits the ranks that append.
+__global__ void __launch_bounds__(64) once_thresh_kernel(const float* __restrict__ sorted, int64_t n_gt_total,
+                                                         const int64_t* ntp, const int64_t* nvalid, int num_pr_points,
+                                                         double* thresholds, int64_t* n_thr, int32_t* status) {
+    const int task = blockIdx.x, lane = lane_id();
+    const int64_t n = ntp[task];
+    const double g = (double)nvalid[task];
+    const float* sc = sorted + (int64_t)task * n_gt_total;
+    double* out = thresholds + (int64_t)task * (num_pr_points + 1);
+    const double eps = 1e-6, inc = 1.0 / (double)num_pr_points;
+    double level = 0.0;
+    int64_t nt = 0;
+    for (int64_t base = 0; base < n; base += 64) {
+        const int64_t i = base + lane;
+        const double l = (double)(i + 1) / g;
+        const double r = i < n - 1 ? (double)(i + 2) / g : l;
+        const double s = r + l;
+        int64_t cursor = base;
+        while (true) {
+            const uint64_t take = __ballot(i < n && i >= cursor && !(s < 2 * level && i < n - 1));
+            if (!take) break;
+            const int p = (int)__builtin_ctzll(take);
+            const double sp = __shfl(s, p, 64);
+            const double v = (double)sc[base + p];
+            do {
+                if (lane == 0 && nt <= num_pr_points) out[nt] = v;
+                ++nt;
+                level += inc;
+            } while (sp + eps > 2 * level);
+            cursor = base + p + 1;
+        }
+    }
+    if (lane == 0) {
+        n_thr[task] = nt;
+        if (nt > num_pr_points + 1) atomicOr(status, 4);
+    }
+}
+
+// compute_statistics of one (frame, task) for thresholds t = wave, wave + 4, ...  With iou_thr >= 0 the reference's
+// per-GT state machine picks the first prediction of the highest IoU among the level's predictions (flag 0), else the
+// first ignored one (flag 1).
+__global__ void __launch_bounds__(256) once_stats_kernel(pda_once_frames_t fr, const double* __restrict__ iou, EvalArgs a,
+                                                         int num_pr_points, const double* __restrict__ thresholds,
+                                                         const int64_t* __restrict__ n_thr, int64_t* counts,
+                                                         int32_t* status) {
+    const int f = blockIdx.x, task = blockIdx.y, cls = task / a.n_levels, level = task % a.n_levels;
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const Frame F = load_frame(fr, f, status);
+    uint64_t acc, ign;
+    pred_masks(fr, a, F, cls, level, nullptr, acc, ign);
+    const double thr = a.thr[cls];
+    int64_t nt = n_thr[task];
+    if (nt > num_pr_points + 1) nt = num_pr_points + 1;
+    for (int t = wave; t < nt; t += 4) {
+        const double th = thresholds[(int64_t)task * (num_pr_points + 1) + t];
+        uint64_t above = 0;
+        for (uint64_t m = acc; m; m &= m - 1) {
+            const int k = (int)__builtin_ctzll(m);
+            if (!((double)fr.pred_score[F.p0 + lane + 64 * k] < th)) above |= 1ull << k;
+        }
+        uint64_t assigned = 0;
+        int tp = 0, fn = 0;
+        for (int i = 0; i < F.ng; ++i) {
+            const int gf = gt_flag(fr, a, F.g0 + i, cls, level);
+            if (gf == -1) continue;
+            const double* row = iou + F.i0 + (int64_t)i * F.np;
+            uint64_t best0 = 0;            // IoU bits (positive doubles order as integers)
+            uint32_t j0 = 0xffffffffu, j1 = 0xffffffffu;
+            for (uint64_t m = acc & above & ~assigned; m; m &= m - 1) {
+                const int k = (int)__builtin_ctzll(m);
+                const int j = lane + 64 * k;
+                const double v = row[j];
+                if (!(v > thr)) continue;
+                if ((ign >> k) & 1ull) {
+                    if ((uint32_t)j < j1) j1 = (uint32_t)j;
+                } else {
+                    const uint64_t bits = (uint64_t)__double_as_longlong(v);
+                    if (bits > best0) { best0 = bits; j0 = (uint32_t)j; }
+                }
+            }
+            const uint64_t m0 = wave_max_u64(best0);
+            int jd;
+            bool det_ign;
+            if (m0 != 0) {
+                jd = (int)wave_min_u32s(best0 == m0 ? j0 : 0xffffffffu);
+                det_ign = false;
+            } else {
+                const uint32_t w1 = wave_min_u32s(j1);
+                if (w1 == 0xffffffffu) {
+                    fn += gf == 0;
+                    continue;
+                }
+                jd = (int)w1;
+                det_ign = true;
+            }
+            if (lane == (jd & 63)) assigned |= 1ull << (jd >> 6);
+            if (gf == 0 && !det_ign) ++tp;
+        }
+        const int fp_lane = __builtin_popcountll(acc & ~ign & above & ~assigned);
+        int fp = fp_lane;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) fp += __shfl_xor(fp, o, 64);
+        if (lane == 0) {
+            int64_t* c = counts + ((int64_t)task * (num_pr_points + 1) + t) * 3;
+            if (tp) atomicAdd((unsigned long long*)&c[0], (unsigned long long)tp);
+            if (fp) atomicAdd((unsigned long long*)&c[1], (unsigned long long)fp);
+            if (fn) atomicAdd((unsigned long long*)&c[2], (unsigned long long)fn);
+        }
+    }
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------
+int64_t seg_bytes(int64_t n_gt_total, int n_tasks) { return (n_tasks * n_gt_total * 4 + 255) / 256 * 256; }
+
+int check_frames(const pda_once_frames_t* fr, const char* what) {
+    PDA_REQUIRE(fr, "%s: null frames", what);
+    PDA_REQUIRE(fr->n_frames >= 0 && fr->n_frames <= (1 << 24), "%s: n_frames %d outside [0, 2^24]", what, fr->n_frames);
+    PDA_REQUIRE(fr->max_gt >= 0 && fr->max_pred >= 0 && fr->max_pred <= OE_MAX_PRED,
+                "%s: max_gt %d / max_pred %d (max_pred <= %d)", what, fr->max_gt, fr->max_pred, OE_MAX_PRED);
+    PDA_REQUIRE(fr->n_gt_total >= 0 && fr->pred_cap >= 0 && fr->iou_cap >= 0, "%s: negative sizes", what);
+    PDA_REQUIRE((int64_t)fr->max_gt * fr->max_pred <= ((int64_t)65535 * 256), "%s: max_gt x max_pred too large", what);
+    if (fr->n_frames == 0) return PDA_OK;
+    PDA_REQUIRE(fr->gt_offsets && fr->pred_start && fr->pred_count && fr->iou_start, "%s: null frame arrays", what);
+    PDA_REQUIRE((fr->gt_boxes && fr->gt_name) || fr->n_gt_total == 0, "%s: null GT arrays", what);
+    PDA_REQUIRE((fr->pred_boxes && fr->pred_score && fr->pred_name) || fr->pred_cap == 0, "%s: null prediction arrays",
+                what);
+    return PDA_OK;
+}
+
+int make_args(EvalArgs& a, const uint8_t* accept, int n_classes, int n_names, const double* iou_thr, int mode,
+              const char* what) {
+    PDA_REQUIRE(n_classes >= 1 && n_classes <= OE_MAX_CLASSES, "%s: n_classes %d outside [1, %d]", what, n_classes,
+                OE_MAX_CLASSES);
+    PDA_REQUIRE(n_names >= 1 && n_names <= OE_MAX_NAMES, "%s: n_names %d outside [1, %d]", what, n_names, OE_MAX_NAMES);
+    PDA_REQUIRE(mode >= 0 && mode <= 2, "%s: difficulty_mode %d outside [0, 2]", what, mode);
+    PDA_REQUIRE(accept && iou_thr, "%s: null accept table or thresholds", what);
+    a = EvalArgs{};
+    for (int c = 0; c < n_classes; ++c) {
+        PDA_REQUIRE(iou_thr[c] >= 0.0, "%s: iou threshold %g of class %d < 0", what, iou_thr[c], c);
+        a.thr[c] = iou_thr[c];
+        for (int n = 0; n < n_names; ++n)
+            if (accept[c * n_names + n]) a.accept[c] |= 1ull << n;
+    }
+    a.n_classes = n_classes;
+    a.n_names = n_names;
+    a.mode = mode;
+    a.n_levels = mode == 0 ? 4 : mode == 1 ? 1 : 3;
+    return PDA_OK;
+}
+
+}  // namespace
+}  // namespace pda
+
+PDA_API int64_t pda_once_eval_workspace_bytes(int n_frames, int64_t n_gt_total, int n_tasks) {
+    if (n_frames < 0 || n_gt_total < 0 || n_gt_total > ((int64_t)1 << 31) || n_tasks < 1 ||
+        n_tasks > pda::OE_MAX_CLASSES * 4)
+        return -1;
+    return pda::seg_bytes(n_gt_total, n_tasks) + (int64_t)n_tasks * 8;
+}
+
+PDA_API int pda_once_eval_iou(const pda_once_frames_t* fr, int with_heading, double* iou, int32_t* status,
+                              pda_stream_t stream) {
+    if (int st = pda::check_frames(fr, "pda_once_eval_iou")) return st;
+    PDA_REQUIRE(status, "pda_once_eval_iou: null status");
+    if (fr->n_frames == 0) return PDA_OK;
+    PDA_REQUIRE(iou || fr->iou_cap == 0, "pda_once_eval_iou: null iou");
+    const int64_t pairs = (int64_t)fr->max_gt * fr->max_pred;
+    if (pairs == 0) return PDA_OK;
+    hipLaunchKernelGGL(pda::once_iou_kernel, dim3((unsigned)fr->n_frames, (unsigned)pda::divup64(pairs, 256)), dim3(256), 0,
+                       (hipStream_t)stream, *fr, with_heading ? 1 : 0, iou, status);
+    return pda::check_launch("pda_once_eval_iou");
+}
+
+PDA_API int pda_once_eval_accumulate(const pda_once_frames_t* fr, const double* iou, const uint8_t* accept, int n_classes,
+                                     int n_names, const double* iou_thr, int difficulty_mode, int64_t* num_valid_gt,
+                                     int32_t* status, void* workspace, pda_stream_t stream) {
+    const char* what = "pda_once_eval_accumulate";
+    if (int st = pda::check_frames(fr, what)) return st;
+    pda::EvalArgs a;
+    if (int st = pda::make_args(a, accept, n_classes, n_names, iou_thr, difficulty_mode, what)) return st;
+    const int n_tasks = n_classes * a.n_levels;
+    PDA_REQUIRE(pda_once_eval_workspace_bytes(fr->n_frames, fr->n_gt_total, n_tasks) >= 0, "%s: bad sizes", what);
+    PDA_REQUIRE(workspace && num_valid_gt && status, "%s: null workspace, num_valid_gt or status", what);
+    PDA_REQUIRE(iou || fr->iou_cap == 0, "%s: null iou", what);
+    hipStream_t st = (hipStream_t)stream;
+    float* seg = (float*)workspace;
+    int64_t* ntp = (int64_t*)((char*)workspace + pda::seg_bytes(fr->n_gt_total, n_tasks));
+    if (hipMemsetAsync(ntp, 0, n_tasks * 8, st) != hipSuccess || hipMemsetAsync(num_valid_gt, 0, n_tasks * 8, st) != hipSuccess)
+        return pda::check_launch(what);
+    if (fr->n_frames == 0) return PDA_OK;
+    hipLaunchKernelGGL(pda::once_accum_kernel, dim3((unsigned)fr->n_frames, (unsigned)n_tasks), dim3(64), 0, st, *fr, iou, a,
+                       seg, ntp, num_valid_gt, status);
+    return pda::check_launch(what);
+}
+
+PDA_API int pda_once_eval_match(const pda_once_frames_t* fr, const double* iou, const uint8_t* accept, int n_classes,
+                                int n_names, const double* iou_thr, int difficulty_mode, int num_pr_points,
+                                const float* sorted_scores, const int64_t* num_valid_gt, double* thresholds,
+                                int64_t* n_thresholds, int64_t* counts, int32_t* status, void* workspace,
+                                pda_stream_t stream) {
+    const char* what = "pda_once_eval_match";
+    if (int st = pda::check_frames(fr, what)) return st;
+    pda::EvalArgs a;
+    if (int st = pda::make_args(a, accept, n_classes, n_names, iou_thr, difficulty_mode, what)) return st;
+    PDA_REQUIRE(num_pr_points >= 1 && num_pr_points <= 100000, "%s: num_pr_points %d outside [1, 100000]", what,
+                num_pr_points);
+    const int n_tasks = n_classes * a.n_levels;
+    PDA_REQUIRE(pda_once_eval_workspace_bytes(fr->n_frames, fr->n_gt_total, n_tasks) >= 0, "%s: bad sizes", what);
+    PDA_REQUIRE(workspace && num_valid_gt && thresholds && n_thresholds && counts && status,
+                "%s: null workspace or output", what);
+    PDA_REQUIRE(sorted_scores || fr->n_gt_total == 0, "%s: null sorted_scores", what);
+    PDA_REQUIRE(iou || fr->iou_cap == 0, "%s: null iou", what);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t* ntp = (const int64_t*)((const char*)workspace + pda::seg_bytes(fr->n_gt_total, n_tasks));
+    const int64_t n_counts = (int64_t)n_tasks * (num_pr_points + 1) * 3;
+    if (hipMemsetAsync(counts, 0, n_counts * 8, st) != hipSuccess) return pda::check_launch(what);
+    hipLaunchKernelGGL(pda::once_thresh_kernel, dim3((unsigned)n_tasks), dim3(64), 0, st, sorted_scores, fr->n_gt_total, ntp,
+                       num_valid_gt, num_pr_points, thresholds, n_thresholds, status);
+    if (fr->n_frames > 0)
+        hipLaunchKernelGGL(pda::once_stats_kernel, dim3((unsigned)fr->n_frames, (unsigned)n_tasks), dim3(256), 0, st, *fr,
+                           iou, a, num_pr_points, thresholds, n_thresholds, counts, status);
+    return pda::check_launch(what);
+}
