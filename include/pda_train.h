@@ -526,6 +526,74 @@ int pda_once_eval_match(const pda_once_frames_t *frames, const double *iou, cons
                         const float *sorted_scores, const int64_t *num_valid_gt, double *thresholds,
                         int64_t *n_thresholds, int64_t *counts, int32_t *status, void *workspace, pda_stream_t stream);
 
+
+/* ---- KITTI evaluation (csrc/kitti_eval.hip; the reference's kitti_object_eval_python get_official_eval_result) -------
+ * Frames, in the dtypes of KITTI infos and of generate_prediction_dicts: GT rows gt_bbox (n_gt_total, 4) float32 image
+ * box, gt_loc (n_gt_total, 3) float32 camera location, gt_dims (n_gt_total, 3) float64 (l, h, w), gt_ry, gt_alpha,
+ * gt_trunc, gt_occ (n_gt_total) float64, gt_name int32 name ids (DontCare rows included), gt_offsets (n_frames + 1)
+ * int64.  Detections of frame f are rows [dt_start[f], dt_start[f] + dt_count[f]) of dt_bbox (det_cap, 4), dt_box
+ * (det_cap, 7) camera (x, y, z, l, h, w, ry), dt_alpha, dt_score (det_cap) float32 and dt_name (det_cap) int32 (packed
+ * or padded storage alike).  The overlap block of frame f is n_gt x dt_count row-major (GT rows, detection columns) at
+ * element ov_start[f] of each metric plane; ov_start[f] + n_gt * dt_count at most ov_cap.  frame_mode (n_frames) int32,
+ * may be null: bit 1 detection bboxes of the frame's part are float64, 2 GT bboxes float64, 4 detection location /
+ * dimensions / rotation_y float64, 8 detection bbox / alpha / score float64 (the part of get_split_parts(n_frames, 100)
+ * decides the dtype numpy computes in).  All arrays are on the device; max_det <= 4096.  A frame outside these bounds
+ * sets status bit 1 and counts as empty; a name id outside [0, n_names) sets bit 2 and matches no class. */
+typedef struct pda_kitti_frames {
+    const float *gt_bbox, *gt_loc;
+    const double *gt_dims, *gt_ry, *gt_alpha, *gt_trunc, *gt_occ;
+    const int32_t *gt_name;
+    const int64_t *gt_offsets;
+    const float *dt_bbox, *dt_box, *dt_alpha, *dt_score;
+    const int32_t *dt_name;
+    const int64_t *dt_start;
+    const int32_t *dt_count;
+    const int64_t *ov_start;
+    const int32_t *frame_mode;
+    int64_t n_gt_total, det_cap, ov_cap;
+    int n_frames, max_gt, max_det;
+} pda_kitti_frames_t;
+
+/* Tasks: t = ((metric * n_classes + class) * 3 + difficulty) * 2 + overlap setting, n_tasks = 18 n_classes, metric 0
+ * image, 1 BEV, 2 3D; (class, difficulty) cd = class * 3 + difficulty.  Class tables (HOST), n_classes <= 6 and
+ * n_names <= 64: gt_class (n_classes, n_names) int8 1 the class, 0 ignored (Van for Car, Person_sitting for Pedestrian),
+ * -1 other; dt_class (n_classes, n_names) uint8 1 a detection of the class; dontcare (n_names) uint8; min_overlaps
+ * (2, 3, n_classes) float64 [setting][metric][class].
+ * workspace: pda_kitti_eval_workspace_bytes(n_frames, n_gt_total, det_cap, n_classes) bytes, 256-byte aligned: the
+ * TP-score segments (n_tasks, n_gt_total) float32 at offset 0, then scratch (-1: bad sizes). */
+int64_t pda_kitti_eval_workspace_bytes(int n_frames, int64_t n_gt_total, int64_t det_cap, int n_classes);
+/* The three overlap planes (3, ov_cap) float64 of every frame's (GT, detection) block: image_box_overlap (criterion -1,
+ * in the detection bbox dtype), the BEV rotate_iou of (x, z, l, w, ry) rounded to float32, and d3_box_overlap, the BEV
+ * intersection times the height overlap along camera -y, rounded to float32.  One launch. */
+int pda_kitti_eval_overlaps(const pda_kitti_frames_t *frames, double *overlaps, int32_t *status, pda_stream_t stream);
+/* clean_data and compute_statistics_jit(compute_fp=False): gt_flags (3 n_classes, n_gt_total) and dt_flags
+ * (3 n_classes, det_cap) int8 ignored_gt / ignored_det per cd, num_valid_gt (3 n_classes) int64; the TP scores of task t
+ * into workspace segment t at the frame's GT rows, -inf in the rest.  The caller sorts each segment in descending order
+ * before pda_kitti_eval_match.  Two launches. */
+int pda_kitti_eval_first_pass(const pda_kitti_frames_t *frames, const double *overlaps, int n_classes, int n_names,
+                              const int8_t *gt_class, const uint8_t *dt_class, const uint8_t *dontcare,
+                              const double *min_overlaps, int8_t *gt_flags, int8_t *dt_flags, int64_t *num_valid_gt,
+                              int32_t *status, void *workspace, pda_stream_t stream);
+/* get_thresholds (41 sample points) and compute_statistics_jit(compute_fp=True): sorted_scores (n_tasks, n_gt_total)
+ * float32 rows in descending order; thresholds (n_tasks, 41) float64, n_thresholds (n_tasks) int64 (more than 41 sets
+ * status bit 4), counts (n_tasks, 41, 3) int64 tp / fp / fn summed over frames with DontCare suppression on metric 0,
+ * similarity (6 n_classes, 41) float64 the AOS sums of the metric-0 tasks in frame order (zero unless compute_aos).  Same
+ * frames and tables as pda_kitti_eval_first_pass.  Up to three launches. */
+int pda_kitti_eval_match(const pda_kitti_frames_t *frames, const double *overlaps, int n_classes, int n_names,
+                         const int8_t *gt_class, const uint8_t *dt_class, const uint8_t *dontcare,
+                         const double *min_overlaps, int compute_aos, const int8_t *gt_flags, const int8_t *dt_flags,
+                         const float *sorted_scores, const int64_t *num_valid_gt, double *thresholds,
+                         int64_t *n_thresholds, int64_t *counts, double *similarity, int32_t *status, void *workspace,
+                         pda_stream_t stream);
+/* generate_prediction_dicts' geometry, float32: boxes (n, stride) lidar (x, y, z, dx, dy, dz, heading) of frame
+ * frame_idx[r], or r / rows_per_frame when frame_idx is null; calib (n_frames, 33) P2 (3 x 4), R0 (3 x 3), V2C (3 x 4)
+ * row-major; image_shape (n_frames, 2) int32 (H, W).  Writes cam (n, 7) camera (x, y, z, l, h, w, ry), bbox (n, 4) the
+ * projected corners' box clipped to the image, alpha (n).  A frame index outside [0, n_frames) sets status bit 1 and
+ * leaves the row unwritten.  One launch. */
+int pda_kitti_eval_predictions(const float *boxes, int64_t n, int stride, int rows_per_frame, const int32_t *frame_idx,
+                               const float *calib, const int32_t *image_shape, int n_frames, float *cam, float *bbox,
+                               float *alpha, int32_t *status, pda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,15 @@ class OnceFrames(ctypes.Structure):
                 ("n_frames", ctypes.c_int), ("max_gt", ctypes.c_int), ("max_pred", ctypes.c_int)]
 
 
+class KittiFrames(ctypes.Structure):
+    """pda_kitti_frames_t (include/pda_train.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("gt_bbox", "gt_loc", "gt_dims", "gt_ry", "gt_alpha", "gt_trunc", "gt_occ",
+                                               "gt_name", "gt_offsets", "dt_bbox", "dt_box", "dt_alpha", "dt_score",
+                                               "dt_name", "dt_start", "dt_count", "ov_start", "frame_mode")] + \
+               [("n_gt_total", ctypes.c_int64), ("det_cap", ctypes.c_int64), ("ov_cap", ctypes.c_int64),
+                ("n_frames", ctypes.c_int), ("max_gt", ctypes.c_int), ("max_det", ctypes.c_int)]
+
+
 # Bumped by anything that writes parameters behind autograd's back (optimization.FlatAdamOneCycle.step updates the flat
 # parameter buffer through a raw pointer, so tensor version counters do not move): caches of derived tensors (bf16 weight
 # copies, BatchNorm folded into convolutions) key on it next to the version counters.
@@ -170,6 +179,13 @@ SIGNATURES = {
                                  _vp, _vp],
     "pda_once_eval_match": [ctypes.POINTER(OnceFrames), _vp, _vp, _i, _i, ctypes.POINTER(ctypes.c_double), _i, _i, _vp, _vp,
                             _vp, _vp, _vp, _vp, _vp, _vp],
+    "pda_kitti_eval_workspace_bytes": [_i, ctypes.c_int64, ctypes.c_int64, _i],
+    "pda_kitti_eval_overlaps": [ctypes.POINTER(KittiFrames), _vp, _vp, _vp],
+    "pda_kitti_eval_first_pass": [ctypes.POINTER(KittiFrames), _vp, _i, _i, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_double),
+                                  _vp, _vp, _vp, _vp, _vp, _vp],
+    "pda_kitti_eval_match": [ctypes.POINTER(KittiFrames), _vp, _i, _i, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_double), _i,
+                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pda_kitti_eval_predictions": [_vp, ctypes.c_int64, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp],
     # include/pda_pointnet2_stack.h
     "pda_stack_ball_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     "pda_stack_group_points": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -218,6 +234,7 @@ def load():
     lib.pda_input_stage_workspace_bytes.restype = ctypes.c_int64
     lib.pda_augment_workspace_bytes.restype = ctypes.c_int64
     lib.pda_once_eval_workspace_bytes.restype = ctypes.c_int64
+    lib.pda_kitti_eval_workspace_bytes.restype = ctypes.c_int64
     lib.pda_abi_version.restype = _i
     lib.pda_last_error.restype = ctypes.c_char_p
     lib.pda_fp_contract_mode.restype = _i

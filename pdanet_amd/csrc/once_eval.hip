@@ -12,6 +12,7 @@
 // hence max_pred <= 4096.  The greedy GT loops stay serial over GTs, as in the reference; the scan over predictions is a
 // wave arg-max.
 #include "pda_common.h"
+#include "rotated_inter.h"
 
 #include <math.h>
 
@@ -21,7 +22,6 @@ namespace {
 constexpr int OE_MAX_CLASSES = 16;
 constexpr int OE_MAX_NAMES = 64;
 constexpr int OE_MAX_PRED = 64 * 64;
-constexpr int OE_MAX_POLY = 24;  // 8 corners inside the other box + 16 edge crossings (the reference keeps 8)
 
 struct EvalArgs {
     uint64_t accept[OE_MAX_CLASSES];  // bit n: the class takes name id n
@@ -30,104 +30,12 @@ struct EvalArgs {
 };
 
 // ---- rotated BEV intersection, iou_utils.py (numba.cuda) -------------------------------------------------------------
-// All of it is float32 in the reference's operation order except where numba promotes: a float32 meeting an int or
-// float literal becomes float64.  That is exact for the halvings (x_d / 2, the centroid division rounds once either
-// way, triangle / 2.0) and matters in one place: area() accumulates the triangle areas in float64 (area_val = 0.0),
-// and the result is rounded to float32 when rotate_iou_kernel_eval stores it.  cos / sin are taken in double and
-// rounded, i.e. correctly rounded float32 values.
-
-__device__ __forceinline__ void rbox_corners(float* c, float x, float y, float xd, float yd, float ang) {
-    const float ac = (float)cos((double)ang), as = (float)sin((double)ang);
-    const float cx[4] = {-xd / 2, -xd / 2, xd / 2, xd / 2};
-    const float cy[4] = {-yd / 2, yd / 2, yd / 2, -yd / 2};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        c[2 * i] = (ac * cx[i] + as * cy[i]) + x;
-        c[2 * i + 1] = (-as * cx[i] + ac * cy[i]) + y;
-    }
-}
-
-__device__ __forceinline__ bool point_in_quad(float px, float py, const float* c) {
-    const float pa0 = c[0] - px, pa1 = c[1] - py, pb0 = c[2] - px, pb1 = c[3] - py;
-    const float pc0 = c[4] - px, pc1 = c[5] - py, pd0 = c[6] - px, pd1 = c[7] - py;
-    const float pab = pa0 * pb1 - pb0 * pa1, pbc = pb0 * pc1 - pc0 * pb1;
-    const float pcd = pc0 * pd1 - pd0 * pc1, pda = pd0 * pa1 - pa0 * pd1;
-    return (pab >= 0 && pbc >= 0 && pcd >= 0 && pda >= 0) || (pab <= 0 && pbc <= 0 && pcd <= 0 && pda <= 0);
-}
-
-__device__ __forceinline__ bool segment_cross(const float* p1, const float* p2, int i, int j, float* out) {
-    const float a0 = p1[2 * i], a1 = p1[2 * i + 1], b0 = p1[2 * ((i + 1) & 3)], b1 = p1[2 * ((i + 1) & 3) + 1];
-    const float c0 = p2[2 * j], c1 = p2[2 * j + 1], d0 = p2[2 * ((j + 1) & 3)], d1 = p2[2 * ((j + 1) & 3) + 1];
-    const float ba0 = b0 - a0, ba1 = b1 - a1, da0 = d0 - a0, ca0 = c0 - a0, da1 = d1 - a1, ca1 = c1 - a1;
-    const bool acd = da1 * ca0 > ca1 * da0;
-    const bool bcd = (d1 - b1) * (c0 - b0) > (c1 - b1) * (d0 - b0);
-    if (acd == bcd) return false;
-    const bool abc = ca1 * ba0 > ba1 * ca0;
-    const bool abd = da1 * ba0 > ba1 * da0;
-    if (abc == abd) return false;
-    const float dc0 = d0 - c0, dc1 = d1 - c1;
-    const float abba = a0 * b1 - b0 * a1, cddc = c0 * d1 - d0 * c1;
-    const float dh = ba1 * dc0 - ba0 * dc1;
-    const float dx = abba * dc0 - ba0 * cddc, dy = abba * dc1 - ba1 * cddc;
-    out[0] = dx / dh;
-    out[1] = dy / dh;
-    return true;
-}
+// rotated_inter.h with ONCE's point test (the edge cross-product signs); rotate_iou_kernel_eval stores the float64 area
+// as float32.
 
 // devRotateIoUEval(rbox1 = pred, rbox2 = gt, criterion = 2): the intersection area, rounded to float32.
 __device__ float rotated_intersection(const float* q, const float* g) {
-    float c1[8], c2[8], pts[2 * OE_MAX_POLY], vs[OE_MAX_POLY];
-    rbox_corners(c1, q[0], q[1], q[2], q[3], q[4]);
-    rbox_corners(c2, g[0], g[1], g[2], g[3], g[4]);
-    int n = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (point_in_quad(c1[2 * i], c1[2 * i + 1], c2)) { pts[2 * n] = c1[2 * i]; pts[2 * n + 1] = c1[2 * i + 1]; ++n; }
-        if (point_in_quad(c2[2 * i], c2[2 * i + 1], c1)) { pts[2 * n] = c2[2 * i]; pts[2 * n + 1] = c2[2 * i + 1]; ++n; }
-    }
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            float t[2];
-            if (segment_cross(c1, c2, i, j, t)) { pts[2 * n] = t[0]; pts[2 * n + 1] = t[1]; ++n; }
-        }
-    if (n == 0) return 0.0f;
-    // sort_vertex_in_convex_polygon: pseudo-angle insertion sort around the centroid
-    float cx = 0.0f, cy = 0.0f;
-    for (int i = 0; i < n; ++i) { cx += pts[2 * i]; cy += pts[2 * i + 1]; }
-    cx /= (float)n;
-    cy /= (float)n;
-    for (int i = 0; i < n; ++i) {
-        float v0 = pts[2 * i] - cx, v1 = pts[2 * i + 1] - cy;
-        const float d = __builtin_sqrtf(v0 * v0 + v1 * v1);
-        v0 = v0 / d;
-        v1 = v1 / d;
-        if (v1 < 0) v0 = -2.0f - v0;
-        vs[i] = v0;
-    }
-    for (int i = 1; i < n; ++i) {
-        if (vs[i - 1] > vs[i]) {
-            const float tv = vs[i], tx = pts[2 * i], ty = pts[2 * i + 1];
-            int j = i;
-            while (j > 0 && vs[j - 1] > tv) {
-                vs[j] = vs[j - 1];
-                pts[2 * j] = pts[2 * j - 2];
-                pts[2 * j + 1] = pts[2 * j - 1];
-                --j;
-            }
-            vs[j] = tv;
-            pts[2 * j] = tx;
-            pts[2 * j + 1] = ty;
-        }
-    }
-    // area(): fan triangulation, |triangle| each, accumulated in float64 (numba: area_val = 0.0, x / 2.0)
-    double a = 0.0;
-    for (int i = 0; i + 2 < n; ++i) {
-        const float* b = pts + 2 * i + 2;
-        const float* c = pts + 2 * i + 4;
-        const float t = (pts[0] - c[0]) * (b[1] - c[1]) - (pts[1] - c[1]) * (b[0] - c[0]);
-        a += fabs((double)t / 2.0);
-    }
-    return (float)a;
+    return (float)rotated_intersection_area<InQuadCross>(q, g);
 }
 
 // ---- frame bookkeeping --------------------------------------------------------------------------------------------
