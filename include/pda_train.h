@@ -594,6 +594,19 @@ int pda_kitti_eval_predictions(const float *boxes, int64_t n, int stride, int ro
                                const float *calib, const int32_t *image_shape, int n_frames, float *cam, float *bbox,
                                float *alpha, int32_t *status, pda_stream_t stream);
 
+/* ---- 3-D recall of the eval loop (csrc/recall.hip) -------------------------------------------------------------------------
+ * generate_recall_record (detector3d_template.py:288-329) for b scenes: pred_boxes (b, k, 7) the final boxes after NMS, of
+ * which the first num_pred[s] (b int32, clamped to [0, k]) count; gt_boxes (b, t, gt_cols) float32, gt_cols >= 7, each
+ * scene trimmed as the reference does (rows 0..j, j the last row in 1..t-1 whose float32 sum != 0, else 0).  A kept GT
+ * row's IoU is boxes_iou3d_gpu(pred, gt)'s (iou3d_nms_utils.py:48-84, float32, box_overlap(pred, gt)); it is recalled at
+ * threshold i when its max over the predictions > thresh[i].  thresh: HOST float32, 0 <= n_thresh <= 16.  counters
+ * (1 + n_thresh) int64 [gt, rcnn_0, ...]: the kernel ADDS the kept rows and the recalled rows, so one buffer can sum an
+ * epoch.  max_iou (b, t) or NULL: each kept row's max over the predictions, 0 without predictions; trimmed rows are not
+ * written.  One launch, no host read; integer atomics, so runs are bit-identical. */
+int pda_recall_record(const float *pred_boxes, const int32_t *num_pred, const float *gt_boxes, int gt_cols,
+                      const float *thresh, int n_thresh, int64_t *counters, float *max_iou, int b, int k, int t,
+                      pda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

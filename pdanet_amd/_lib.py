@@ -186,6 +186,7 @@ SIGNATURES = {
     "pda_kitti_eval_match": [ctypes.POINTER(KittiFrames), _vp, _i, _i, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_double), _i,
                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pda_kitti_eval_predictions": [_vp, ctypes.c_int64, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp],
+    "pda_recall_record": [_vp, _vp, _vp, _i, ctypes.POINTER(_f), _i, _vp, _vp, _i, _i, _i, _vp],
     # include/pda_pointnet2_stack.h
     "pda_stack_ball_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     "pda_stack_group_points": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],

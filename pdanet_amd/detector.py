@@ -1,6 +1,7 @@
 """IASSD detector = IASSD_Backbone + IASSD_Head (pcdet/models/detectors/IASSD.py:3-27,
 detector3d_template.py:45-49 module names `backbone_3d` / `point_head`): training forward (loss) and
-inference forward (batched NMS post-processing; recall bookkeeping is eval tooling and not built)."""
+inference forward (batched NMS post-processing, and with RECALL_MODE 'normal' and gt_boxes in the batch the reference's 3-D
+recall dict, counted on the device and read back with the predictions)."""
 import torch
 import torch.nn as nn
 
@@ -192,9 +193,11 @@ class IASSD(nn.Module):
         if self.training:
             loss, tb_dict = self.point_head.get_loss()
             return {'loss': loss}, tb_dict, {}
-        padded = model_nms_utils.post_processing(batch_dict, self.model_cfg["POST_PROCESSING"], self.num_class)
+        post_cfg = self.model_cfg["POST_PROCESSING"]
+        padded = model_nms_utils.post_processing(batch_dict, post_cfg, self.num_class)
         batch_dict['final_padded'] = padded            # device tensors, no synchronisation so far
-        return model_nms_utils.to_pred_dicts(padded), {}   # (pred_dicts, recall_dicts): detectors/IASSD.py:20-22
+        # (pred_dicts, recall_dicts): detectors/IASSD.py:20-22; one host read for both
+        return model_nms_utils.to_pred_and_recall_dicts(padded, post_cfg.get('RECALL_THRESH_LIST', ()))
 
 
 def build_detector(cfg_path="once_pda_ssd.yaml"):

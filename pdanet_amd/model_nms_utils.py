@@ -5,10 +5,21 @@ of a batch at once and without host synchronisation until the final compaction.
 Reference, per scene: sigmoid -> max over classes -> `scores >= SCORE_THRESH` compaction -> topk
 (NMS_PRE_MAXSIZE) -> nms_gpu (sort, mask kernel, device->host copy, host scan) -> first
 NMS_POST_MAXSIZE -> index back.  Here: one masked sort for the batch, one gather, `nms_batched`
-(csrc/iou3d_nms.hip) with per-scene valid counts, one gather."""
+(csrc/iou3d_nms.hip) with per-scene valid counts, one gather.
+
+Recall (detector3d_template.py:271-276, 288-329, with RECALL_MODE 'normal' and a batch that carries gt_boxes): the
+reference trims each scene's GT, runs boxes_iou3d_gpu and reads one count per threshold back to the host.  Here
+`recall_record` (csrc/recall.hip) adds the whole batch's counts to device counters in one launch; post_processing keeps
+them under padded['recall'], `to_pred_and_recall_dicts` reads them with the counts it reads anyway, and `RecallRecorder`
+sums them over an eval loop."""
+import ctypes
+
 import torch
 
 from . import iou3d_nms_utils
+from .pointnet2_batch_cuda import F32, I32, _call, _chk
+
+MAX_RECALL_THRESH = 16
 
 
 def class_agnostic_nms_batched(box_scores, box_preds, nms_config, score_thresh=None):
@@ -36,7 +47,8 @@ def class_agnostic_nms_batched(box_scores, box_preds, nms_config, score_thresh=N
 def post_processing(batch_dict, post_process_cfg, num_class):
     """detector3d_template.py:179-290 for point heads (`batch_index` layout, equal points per scene).
     Returns padded device tensors: pred_boxes (B, K, 7+C), pred_scores (B, K), pred_labels (B, K) int64
-    (0 = padding) and num_pred (B) int32."""
+    (0 = padding) and num_pred (B) int32; with RECALL_MODE 'normal' (the default) and gt_boxes in batch_dict also
+    recall (1 + len(RECALL_THRESH_LIST)) int64 [gt, rcnn_<t>...], this batch's recall counts."""
     if post_process_cfg["NMS_CONFIG"]["MULTI_CLASSES_NMS"]:
         raise NotImplementedError("MULTI_CLASSES_NMS (not used by PDA-SSD.yaml)")
     B = batch_dict['batch_size']
@@ -57,11 +69,121 @@ def post_processing(batch_dict, post_process_cfg, num_class):
         sel_scores = torch.where(ok, torch.gather(raw, 1, safe), torch.zeros_like(sel_scores))
     pred_labels = torch.where(ok, torch.gather(labels, 1, safe), torch.zeros_like(safe))
     pred_boxes = torch.gather(box_preds, 1, safe.unsqueeze(-1).expand(-1, -1, box_preds.shape[-1])) * ok.unsqueeze(-1)
-    return {'pred_boxes': pred_boxes, 'pred_scores': sel_scores, 'pred_labels': pred_labels, 'num_pred': num}
+    padded = {'pred_boxes': pred_boxes, 'pred_scores': sel_scores, 'pred_labels': pred_labels, 'num_pred': num}
+    if post_process_cfg.get('RECALL_MODE', 'normal') == 'normal' and 'gt_boxes' in batch_dict:
+        # (1 + n) int64 [gt, rcnn_<t>...] of this batch, on the device
+        padded['recall'] = recall_record(pred_boxes, num, batch_dict['gt_boxes'], post_process_cfg['RECALL_THRESH_LIST'])
+    return padded
 
 
 def to_pred_dicts(padded):
     """The reference's return value: a list (one per scene) of {'pred_boxes','pred_scores','pred_labels'}
     with variable-length tensors.  One host synchronisation for the whole batch."""
-    counts = padded['num_pred'].tolist()
+    return _split(padded, padded['num_pred'].tolist())
+
+
+def _split(padded, counts):
     return [{k: padded[k][s, :n] for k in ('pred_boxes', 'pred_scores', 'pred_labels')} for s, n in enumerate(counts)]
+
+
+def to_pred_and_recall_dicts(padded, thresh_list):
+    """Detector3DTemplate.post_processing's return value (pred_dicts, recall_dict): the recall dict holds 'gt' and
+    'roi_<t>' / 'rcnn_<t>' for every t of thresh_list (the RECALL_THRESH_LIST post_processing used) when padded carries
+    the batch's recall counters, and is {} otherwise.  The counters come back in the one host read of to_pred_dicts."""
+    if 'recall' not in padded:
+        return to_pred_dicts(padded), {}
+    B = padded['num_pred'].shape[0]
+    h = torch.cat([padded['num_pred'].to(torch.int64), padded['recall']]).tolist()
+    return _split(padded, h[:B]), (recall_dict(h[B:], thresh_list) if B > 0 else {})
+
+
+def recall_dict(counts, thresh_list):
+    """Host counters [gt, rcnn_<t>...] -> generate_recall_record's dict, in its key order (roi_* is 0: no rois)."""
+    ret = {'gt': int(counts[0])}
+    for i, t in enumerate(thresh_list):
+        ret['roi_%s' % str(t)] = 0
+        ret['rcnn_%s' % str(t)] = int(counts[1 + i])
+    return ret
+
+
+def _thresh_array(thresh_list):
+    thresh_list = list(thresh_list)
+    if len(thresh_list) > MAX_RECALL_THRESH:
+        raise ValueError("at most %d recall thresholds, got %d" % (MAX_RECALL_THRESH, len(thresh_list)))
+    return (ctypes.c_float * max(len(thresh_list), 1))(*[float(t) for t in thresh_list]), len(thresh_list)
+
+
+def recall_record(pred_boxes, num_pred, gt_boxes, thresh_list, counters=None, max_iou=None):
+    """generate_recall_record for every scene of a batch, in one launch and without a host read.
+    pred_boxes (B, K, >= 7) float32 post_processing's padded boxes, num_pred (B) int the valid rows of each scene,
+    gt_boxes (B, T, >= 7) float32 batch_dict['gt_boxes'], thresh_list RECALL_THRESH_LIST.  ADDS the kept GT rows and the
+    rows recalled at each threshold to counters ((1 + len(thresh_list)) int64 [gt, rcnn_<t>...], zeros when None) and
+    returns them; max_iou (B, T) float32, optional, receives each kept row's best IoU (0 without predictions)."""
+    for name, x in (("pred_boxes", pred_boxes), ("gt_boxes", gt_boxes)):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != F32 or x.dim() != 3 or x.shape[-1] < 7:
+            raise TypeError("%s must be a (B, N, >= 7) float32 device tensor" % name)
+    B, K = pred_boxes.shape[0], pred_boxes.shape[1]
+    T, C = gt_boxes.shape[1], gt_boxes.shape[2]
+    if gt_boxes.shape[0] != B or not isinstance(num_pred, torch.Tensor) or num_pred.numel() != B:
+        raise ValueError("pred_boxes, num_pred and gt_boxes disagree on the batch size")
+    if not num_pred.is_cuda or num_pred.dtype not in (torch.int32, torch.int64):
+        raise TypeError("num_pred must be an int32 / int64 device tensor")
+    thr, n = _thresh_array(thresh_list)
+    dev = pred_boxes.device
+    if counters is None:
+        counters = torch.zeros(1 + n, dtype=torch.int64, device=dev)
+    elif counters.numel() != 1 + n:
+        raise ValueError("counters need %d elements" % (1 + n))
+    boxes = pred_boxes[..., :7].contiguous()
+    num = num_pred.reshape(B).to(I32).contiguous()
+    gt = gt_boxes.contiguous()
+    mi = None
+    if max_iou is not None:
+        if max_iou.numel() != B * T:
+            raise ValueError("max_iou needs %d elements" % (B * T))
+        mi = _chk(max_iou, "max_iou", F32)
+    _call("pda_recall_record", boxes, _chk(boxes, "pred_boxes", F32), _chk(num, "num_pred", I32), _chk(gt, "gt_boxes", F32), C,
+          thr, n, _chk(counters, "counters", torch.int64), mi, B, K, T)
+    return counters
+
+
+class RecallRecorder:
+    """eval_one_epoch's recall over a whole eval loop, on the device (eval_utils.py:12-20, 111-118).  add() launches one
+    kernel per batch and reads nothing back, so a loop that feeds OnceEvaluator / KittiEvaluator stays free of host
+    reads and add() can be captured in a graph; compute() reads the counters once."""
+
+    def __init__(self, thresh_list, device='cuda', enabled=True):
+        self.thresh_list = list(thresh_list)
+        _thresh_array(self.thresh_list)
+        self.enabled = bool(enabled)
+        self.counters = torch.zeros(1 + len(self.thresh_list), dtype=torch.int64, device=device)
+
+    @classmethod
+    def from_config(cls, post_process_cfg, device='cuda'):
+        """MODEL.POST_PROCESSING: RECALL_THRESH_LIST, and RECALL_MODE (default 'normal'); with any other mode the
+        reference records no recall, and neither does the recorder (its sums stay 0)."""
+        return cls(post_process_cfg['RECALL_THRESH_LIST'], device,
+                   enabled=post_process_cfg.get('RECALL_MODE', 'normal') == 'normal')
+
+    def reset(self):
+        self.counters.zero_()
+
+    def add(self, padded, gt_boxes):
+        """post_processing's padded tensors (pred_boxes, num_pred) and the batch's gt_boxes (B, max_gt, >= 7), or None
+        for a batch without GT (adds nothing, as in the reference)."""
+        if self.enabled and gt_boxes is not None:
+            recall_record(padded['pred_boxes'], padded['num_pred'], gt_boxes, self.thresh_list, self.counters)
+
+    def compute(self):
+        """(metric, ret_dict): statistics_info's sums gt_num, recall_roi_<t>, recall_rcnn_<t>, and eval_one_epoch's
+        recall/roi_<t>, recall/rcnn_<t> = sum / max(gt_num, 1)."""
+        h = self.counters.tolist()                      # the one read
+        metric = {'gt_num': int(h[0])}
+        ret = {}
+        for i, t in enumerate(self.thresh_list):
+            metric['recall_roi_%s' % str(t)] = 0
+            metric['recall_rcnn_%s' % str(t)] = int(h[1 + i])
+        for t in self.thresh_list:
+            ret['recall/roi_%s' % str(t)] = metric['recall_roi_%s' % str(t)] / max(metric['gt_num'], 1)
+            ret['recall/rcnn_%s' % str(t)] = metric['recall_rcnn_%s' % str(t)] / max(metric['gt_num'], 1)
+        return metric, ret
