@@ -17,10 +17,11 @@
 //   kitti_pred_kernel      one thread per prediction: boxes3d_lidar_to_kitti_camera, the image box, alpha.
 //
 // The pass kernels keep the frame's overlap block of their metric in LDS across every task and threshold when it fits
-// (KE_LDS_DOUBLES); otherwise they read it from global memory.  Detections j of a frame are owned by lane j % 64 at bit
-// j / 64 of 64-bit lane masks, hence max_det <= 4096.  The greedy GT loops stay serial over GTs, as in the reference.
+// (KE_LDS_DOUBLES); otherwise they read it from global memory.  The frame record, the lane masks over detections (hence
+// max_det <= 4096) and the two greedy walks over a frame's GT rows are eval_match.h, shared with once_eval.hip.
 #include "pda_common.h"
 #include "rotated_inter.h"
+#include "eval_match.h"
 
 #include <math.h>
 
@@ -29,7 +30,6 @@ namespace {
 
 constexpr int KE_MAX_CLASSES = 6;
 constexpr int KE_MAX_NAMES = 64;
-constexpr int KE_MAX_DET = 64 * 64;
 constexpr int KE_NS = 41;              // N_SAMPLE_PTS
 constexpr int KE_LDS_DOUBLES = 6144;   // 48 KiB
 constexpr int KE_CALIB = 33;           // P2 (3 x 4), R0 (3 x 3), V2C (3 x 4)
@@ -53,31 +53,9 @@ struct KittiArgs {
     int n_classes, n_names, compute_aos;
 };
 
-struct KFrame {
-    int64_t g0, d0, o0;  // first GT row, first detection row, first overlap element
-    int ng, nd, mode;
-};
-
-__device__ __forceinline__ KFrame load_kframe(const pda_kitti_frames_t& fr, int f, int32_t* status) {
-    KFrame F;
-    F.g0 = fr.gt_offsets[f];
-    const int64_t ng = fr.gt_offsets[f + 1] - F.g0;
-    F.d0 = fr.dt_start[f];
-    const int64_t nd = fr.dt_count[f];
-    F.o0 = fr.ov_start[f];
-    F.mode = fr.frame_mode ? fr.frame_mode[f] : 0;
-    const bool ok = F.g0 >= 0 && ng >= 0 && ng <= fr.max_gt && F.g0 + ng <= fr.n_gt_total && nd >= 0 &&
-                    nd <= fr.max_det && F.d0 >= 0 && F.d0 + nd <= fr.det_cap && F.o0 >= 0 &&
-                    F.o0 + ng * nd <= fr.ov_cap;
-    if (!ok) {
-        if (threadIdx.x == 0 && status) atomicOr(status, 1);
-        F.g0 = F.d0 = F.o0 = 0;
-        F.ng = F.nd = 0;
-        return F;
-    }
-    F.ng = (int)ng;
-    F.nd = (int)nd;
-    return F;
+__device__ __forceinline__ EvalFrame load_kframe(const pda_kitti_frames_t& fr, int f, int32_t* status) {
+    return load_eval_frame(fr.gt_offsets, fr.dt_start, fr.dt_count, fr.ov_start, fr.frame_mode, fr.max_gt, fr.max_det,
+                           fr.n_gt_total, fr.det_cap, fr.ov_cap, f, status);
 }
 
 // numba's min / max of a float32 and a float64 unify to float64
@@ -100,43 +78,9 @@ __device__ __forceinline__ double image_overlap(const float* bf, const TQ* q, in
     return (double)(TB)(iw * ih / ua);
 }
 
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t w = __shfl_xor(v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t w = __shfl_xor(v, o, 64);
-        v = w < v ? w : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// float32 -> unsigned key with the order of the floats
-__device__ __forceinline__ uint32_t ordered(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ bool lane_bit(uint64_t mask, int j) {
-    return (__ballot((mask >> (j >> 6)) & 1ull) >> (j & 63)) & 1ull;
-}
-
 // The lane's detection masks for (class, difficulty) cd: bit k <-> detection lane + 64 k.  acc: ignored_det != -1,
 // ign: ignored_det == 1.
-__device__ __forceinline__ void det_masks(const int8_t* __restrict__ dt_flags, const KFrame& F, uint64_t& acc,
+__device__ __forceinline__ void det_masks(const int8_t* __restrict__ dt_flags, const EvalFrame& F, uint64_t& acc,
                                           uint64_t& ign) {
     acc = ign = 0;
     for (int j = lane_id(), k = 0; j < F.nd; j += 64, ++k) {
@@ -147,7 +91,7 @@ __device__ __forceinline__ void det_masks(const int8_t* __restrict__ dt_flags, c
 }
 
 // The frame's overlap block of one metric: into LDS when it fits, else the global block itself.
-__device__ __forceinline__ const double* stage_block(const double* __restrict__ ov, const KFrame& F, double* lds) {
+__device__ __forceinline__ const double* stage_block(const double* __restrict__ ov, const EvalFrame& F, double* lds) {
     const double* src = ov + F.o0;
     const int n = F.ng * F.nd;
     if (n > KE_LDS_DOUBLES) return src;
@@ -161,7 +105,7 @@ __device__ __forceinline__ const double* stage_block(const double* __restrict__ 
 __global__ void __launch_bounds__(256) kitti_overlap_kernel(pda_kitti_frames_t fr, double* __restrict__ ov,
                                                             int32_t* status) {
     const int f = blockIdx.x;
-    const KFrame F = load_kframe(fr, f, status);
+    const EvalFrame F = load_kframe(fr, f, status);
     const int64_t pair = (int64_t)blockIdx.y * blockDim.x + threadIdx.x;
     if (pair >= (int64_t)F.ng * F.nd) return;
     const int i = (int)(pair / F.nd), j = (int)(pair % F.nd);
@@ -223,7 +167,7 @@ __global__ void __launch_bounds__(256) kitti_flags_kernel(pda_kitti_frames_t fr,
                                                           int64_t* num_valid_gt, int32_t* status) {
     __shared__ int nvalid[KE_MAX_CLASSES * 3];
     const int f = blockIdx.x, ncd = a.n_classes * 3;
-    const KFrame F = load_kframe(fr, f, status);
+    const EvalFrame F = load_kframe(fr, f, status);
     if (threadIdx.x < ncd) nvalid[threadIdx.x] = 0;
     __syncthreads();
     for (int i = threadIdx.x; i < F.ng; i += blockDim.x) {
@@ -292,7 +236,7 @@ __global__ void __launch_bounds__(256) kitti_pass1_kernel(pda_kitti_frames_t fr,
                                                           int64_t* ntp, int32_t* status) {
     __shared__ double lds[KE_LDS_DOUBLES];
     const int f = blockIdx.x, metric = blockIdx.y, lane = lane_id(), wave = threadIdx.x >> 6;
-    const KFrame F = load_kframe(fr, f, status);
+    const EvalFrame F = load_kframe(fr, f, status);
     const double* blk = stage_block(ov + (int64_t)metric * fr.ov_cap, F, lds);
     for (int local = wave; local < a.n_classes * 6; local += 4) {
         const int cd = local >> 1, k = local & 1, c = cd / 3;
@@ -301,31 +245,9 @@ __global__ void __launch_bounds__(256) kitti_pass1_kernel(pda_kitti_frames_t fr,
         const int8_t* gfl = gt_flags + (int64_t)cd * fr.n_gt_total;
         uint64_t acc, ign;
         det_masks(dt_flags + (int64_t)cd * fr.det_cap, F, acc, ign);
-        uint64_t assigned = 0;
-        float* out = seg + (int64_t)task * fr.n_gt_total + F.g0;
-        int n_tp = 0;
-        for (int i = 0; i < F.ng; ++i) {
-            const int gf = gfl[F.g0 + i];
-            if (gf == -1) continue;
-            const double* row = blk + i * F.nd;
-            uint64_t best = 0;
-            for (uint64_t m = acc & ~assigned; m; m &= m - 1) {
-                const int j = lane + 64 * (int)__builtin_ctzll(m);
-                const float s = fr.dt_score[F.d0 + j];
-                if (row[j] > thr && (double)s > -10000000.0) {
-                    const uint64_t key = ((uint64_t)ordered(s) << 32) | (uint32_t)(0xffffffffu - (uint32_t)j);
-                    best = key > best ? key : best;
-                }
-            }
-            best = wave_max_u64(best);
-            if (best == 0) continue;
-            const int jd = (int)(0xffffffffu - (uint32_t)best);
-            if (lane == (jd & 63)) assigned |= 1ull << (jd >> 6);
-            if (gf == 1 || lane_bit(ign, jd)) continue;
-            if (lane == 0) out[n_tp] = fr.dt_score[F.d0 + jd];
-            ++n_tp;
-        }
-        for (int s = n_tp + lane; s < F.ng; s += 64) out[s] = -INFINITY;
+        const int n_tp = match_first_pass<ScoreFloorKitti>(blk, F.ng, F.nd, fr.dt_score + F.d0, acc, ign, thr,
+                                                           [&](int i) { return (int)gfl[F.g0 + i]; },
+                                                           seg + (int64_t)task * fr.n_gt_total + F.g0);
         if (lane == 0 && n_tp) atomicAdd((unsigned long long*)&ntp[task], (unsigned long long)n_tp);
     }
 }
@@ -378,7 +300,7 @@ __global__ void __launch_bounds__(256) kitti_pass2_kernel(pda_kitti_frames_t fr,
                                                           double* __restrict__ sim_frames, int32_t* status) {
     __shared__ double lds[KE_LDS_DOUBLES];
     const int f = blockIdx.x, metric = blockIdx.y, lane = lane_id(), wave = threadIdx.x >> 6;
-    const KFrame F = load_kframe(fr, f, status);
+    const EvalFrame F = load_kframe(fr, f, status);
     const double* blk = stage_block(ov + (int64_t)metric * fr.ov_cap, F, lds);
     const bool aos = metric == 0 && a.compute_aos;
     const int n_items = a.n_classes * 6 * KE_NS;
@@ -393,60 +315,20 @@ __global__ void __launch_bounds__(256) kitti_pass2_kernel(pda_kitti_frames_t fr,
         const int8_t* gfl = gt_flags + (int64_t)cd * fr.n_gt_total;
         uint64_t acc, ign;
         det_masks(dt_flags + (int64_t)cd * fr.det_cap, F, acc, ign);
-        uint64_t above = 0;
-        for (uint64_t m = acc; m; m &= m - 1) {
-            const int q = (int)__builtin_ctzll(m);
-            if (!((double)fr.dt_score[F.d0 + lane + 64 * q] < th)) above |= 1ull << q;
-        }
-        uint64_t assigned = 0;
-        int tp = 0, fn = 0;
-        double sim = 0.0;
-        for (int i = 0; i < F.ng; ++i) {
-            const int gf = gfl[F.g0 + i];
-            if (gf == -1) continue;
-            const double* row = blk + i * F.nd;
-            uint64_t best0 = 0;  // overlap bits (positive doubles order as integers)
-            uint32_t j0 = 0xffffffffu, j1 = 0xffffffffu;
-            for (uint64_t m = acc & above & ~assigned; m; m &= m - 1) {
-                const int q = (int)__builtin_ctzll(m);
-                const int j = lane + 64 * q;
-                const double v = row[j];
-                if (!(v > thr)) continue;
-                if ((ign >> q) & 1ull) {
-                    if ((uint32_t)j < j1) j1 = (uint32_t)j;
-                } else {
-                    const uint64_t bits = (uint64_t)__double_as_longlong(v);
-                    if (bits > best0) { best0 = bits; j0 = (uint32_t)j; }
+        double sim = 0.0;  // the AOS similarity of the frame's true positives, summed in GT order
+        const MatchStats r = match_second_pass(
+            blk, F.ng, F.nd, fr.dt_score + F.d0, acc, ign, thr, th, [&](int i) { return (int)gfl[F.g0 + i]; },
+            [&](int i, int jd) {
+                if (aos) {
+                    const double delta = fr.gt_alpha[F.g0 + i] - (double)fr.dt_alpha[F.d0 + jd];
+                    sim += (1.0 + cos(delta)) / 2.0;
                 }
-            }
-            const uint64_t m0 = wave_max_u64(best0);
-            int jd;
-            bool det_ign;
-            if (m0 != 0) {
-                jd = (int)wave_min_u32(best0 == m0 ? j0 : 0xffffffffu);
-                det_ign = false;
-            } else {
-                const uint32_t w1 = wave_min_u32(j1);
-                if (w1 == 0xffffffffu) {
-                    fn += gf == 0;
-                    continue;
-                }
-                jd = (int)w1;
-                det_ign = true;
-            }
-            if (lane == (jd & 63)) assigned |= 1ull << (jd >> 6);
-            if (gf == 1 || det_ign) continue;
-            ++tp;
-            if (aos) {
-                const double delta = fr.gt_alpha[F.g0 + i] - (double)fr.dt_alpha[F.d0 + jd];
-                sim += (1.0 + cos(delta)) / 2.0;
-            }
-        }
-        const uint64_t open = acc & ~ign & above & ~assigned;
-        int fp = wave_sum_i32(__builtin_popcountll(open));
+            });
+        const int tp = r.tp, fn = r.fn;
+        int fp = wave_sum_i32(__builtin_popcountll(r.open));
         if (metric == 0) {
             int nstuff = 0;
-            for (uint64_t m = open; m; m &= m - 1) {
+            for (uint64_t m = r.open; m; m &= m - 1) {
                 const int q = (int)__builtin_ctzll(m);
                 nstuff += dc_max[F.d0 + lane + 64 * q] > thr;
             }
@@ -561,13 +443,11 @@ Workspace layout(int n_frames, int64_t n_gt_total, int64_t det_cap, int n_classe
 
 int check_frames(const pda_kitti_frames_t* fr, const char* what) {
     PDA_REQUIRE(fr, "%s: null frames", what);
-    PDA_REQUIRE(fr->n_frames >= 0 && fr->n_frames <= (1 << 24), "%s: n_frames %d outside [0, 2^24]", what, fr->n_frames);
-    PDA_REQUIRE(fr->max_gt >= 0 && fr->max_det >= 0 && fr->max_det <= KE_MAX_DET,
-                "%s: max_gt %d / max_det %d (max_det <= %d)", what, fr->max_gt, fr->max_det, KE_MAX_DET);
-    PDA_REQUIRE(fr->n_gt_total >= 0 && fr->n_gt_total <= ((int64_t)1 << 31) && fr->det_cap >= 0 &&
-                    fr->det_cap <= ((int64_t)1 << 31) && fr->ov_cap >= 0,
-                "%s: sizes outside [0, 2^31]", what);
-    PDA_REQUIRE((int64_t)fr->max_gt * fr->max_det <= ((int64_t)65535 * 256), "%s: max_gt x max_det too large", what);
+    if (int st = check_frame_limits(what, "max_det", fr->n_frames, fr->max_gt, fr->max_det, fr->n_gt_total, fr->det_cap,
+                                    fr->ov_cap))
+        return st;
+    PDA_REQUIRE(fr->n_gt_total <= ((int64_t)1 << 31) && fr->det_cap <= ((int64_t)1 << 31), "%s: sizes outside [0, 2^31]",
+                what);
     if (fr->n_frames == 0) return PDA_OK;
     PDA_REQUIRE(fr->gt_offsets && fr->dt_start && fr->dt_count && fr->ov_start, "%s: null frame arrays", what);
     PDA_REQUIRE((fr->gt_bbox && fr->gt_loc && fr->gt_dims && fr->gt_ry && fr->gt_alpha && fr->gt_trunc && fr->gt_occ &&

@@ -8,11 +8,11 @@
 //   once_stats_kernel   four waves per (frame, class, level), one threshold each in turn: compute_statistics, summed
 //                       with integer atomics (order-independent, so deterministic).
 //
-// Predictions j of a frame are owned by lane j % 64 at bit j / 64 of 64-bit lane masks (accepted, ignored, assigned),
-// hence max_pred <= 4096.  The greedy GT loops stay serial over GTs, as in the reference; the scan over predictions is a
-// wave arg-max.
+// The frame record, the lane masks over predictions (hence max_pred <= 4096) and the two greedy walks over a frame's GT
+// rows are eval_match.h, shared with kitti_eval.hip; here are ONCE's flags, its score floor and its thresholds.
 #include "pda_common.h"
 #include "rotated_inter.h"
+#include "eval_match.h"
 
 #include <math.h>
 
@@ -21,7 +21,6 @@ namespace {
 
 constexpr int OE_MAX_CLASSES = 16;
 constexpr int OE_MAX_NAMES = 64;
-constexpr int OE_MAX_PRED = 64 * 64;
 
 struct EvalArgs {
     uint64_t accept[OE_MAX_CLASSES];  // bit n: the class takes name id n
@@ -39,31 +38,9 @@ __device__ float rotated_intersection(const float* q, const float* g) {
 }
 
 // ---- frame bookkeeping --------------------------------------------------------------------------------------------
-struct Frame {
-    int64_t g0, p0, i0;  // first GT row, first prediction row, first IoU element
-    int ng, np;
-};
-
-// The frame's ranges, or an empty frame (status bit 1) when they leave the declared bounds.
-__device__ __forceinline__ Frame load_frame(const pda_once_frames_t& fr, int f, int32_t* status) {
-    Frame F;
-    F.g0 = fr.gt_offsets[f];
-    const int64_t ng = fr.gt_offsets[f + 1] - F.g0;
-    F.p0 = fr.pred_start[f];
-    const int64_t np = fr.pred_count[f];
-    F.i0 = fr.iou_start[f];
-    const bool ok = F.g0 >= 0 && ng >= 0 && ng <= fr.max_gt && F.g0 + ng <= fr.n_gt_total && np >= 0 &&
-                    np <= fr.max_pred && F.p0 >= 0 && F.p0 + np <= fr.pred_cap && F.i0 >= 0 &&
-                    F.i0 + ng * np <= fr.iou_cap;
-    if (!ok) {
-        if (threadIdx.x == 0 && status) atomicOr(status, 1);
-        F.g0 = F.p0 = F.i0 = 0;
-        F.ng = F.np = 0;
-        return F;
-    }
-    F.ng = (int)ng;
-    F.np = (int)np;
-    return F;
+__device__ __forceinline__ EvalFrame load_frame(const pda_once_frames_t& fr, int f, int32_t* status) {
+    return load_eval_frame(fr.gt_offsets, fr.pred_start, fr.pred_count, fr.iou_start, nullptr, fr.max_gt, fr.max_pred,
+                           fr.n_gt_total, fr.pred_cap, fr.iou_cap, f, status);
 }
 
 // overall_distance_filter / distance_filter / overall_filter: true = the box is in the level (flag not 1).  The norm
@@ -97,12 +74,12 @@ __device__ __forceinline__ int gt_flag(const pda_once_frames_t& fr, const EvalAr
 }
 
 // The lane's prediction masks for (cls, level): bit k <-> prediction lane + 64 k.  acc: flag != -1, ign: flag == 1.
-__device__ __forceinline__ void pred_masks(const pda_once_frames_t& fr, const EvalArgs& a, const Frame& F, int cls,
+__device__ __forceinline__ void pred_masks(const pda_once_frames_t& fr, const EvalArgs& a, const EvalFrame& F, int cls,
                                            int level, int32_t* status, uint64_t& acc, uint64_t& ign) {
     acc = ign = 0;
     const int lane = lane_id();
-    for (int j = lane, k = 0; j < F.np; j += 64, ++k) {
-        const int64_t row = F.p0 + j;
+    for (int j = lane, k = 0; j < F.nd; j += 64, ++k) {
+        const int64_t row = F.d0 + j;
         const float* b = fr.pred_boxes + row * 7;
         const bool lev = in_level<float>(b[0], b[1], b[2], a.mode, level);
         const int ok = name_ok(a, cls, fr.pred_name[row], status);
@@ -111,44 +88,16 @@ __device__ __forceinline__ void pred_masks(const pda_once_frames_t& fr, const Ev
     }
 }
 
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t w = __shfl_xor(v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_min_u32s(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t w = __shfl_xor(v, o, 64);
-        v = w < v ? w : v;
-    }
-    return v;
-}
-
-// float32 -> unsigned key with the order of the floats
-__device__ __forceinline__ uint32_t ordered(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ bool lane_bit(uint64_t mask, int j) {
-    return (__ballot((mask >> (j >> 6)) & 1ull) >> (j & 63)) & 1ull;
-}
-
 // ---- kernels ----------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) once_iou_kernel(pda_once_frames_t fr, int with_heading, double* __restrict__ iou,
                                                        int32_t* status) {
     const int f = blockIdx.x;
-    const Frame F = load_frame(fr, f, status);
+    const EvalFrame F = load_frame(fr, f, status);
     const int64_t pair = (int64_t)blockIdx.y * blockDim.x + threadIdx.x;
-    if (pair >= (int64_t)F.ng * F.np) return;
-    const int i = (int)(pair / F.np), j = (int)(pair % F.np);
+    if (pair >= (int64_t)F.ng * F.nd) return;
+    const int i = (int)(pair / F.nd), j = (int)(pair % F.nd);
     const double* g = fr.gt_boxes + (F.g0 + i) * 7;
-    const float* p = fr.pred_boxes + (F.p0 + j) * 7;
+    const float* p = fr.pred_boxes + (F.d0 + j) * 7;
     // rotate_iou_gpu_eval casts both box sets to float32 and returns the float32 areas in the GT dtype
     const float g5[5] = {(float)g[0], (float)g[1], (float)g[3], (float)g[4], (float)g[6]};
     const float p5[5] = {p[0], p[1], p[3], p[4], p[6]};
@@ -169,7 +118,7 @@ __global__ void __launch_bounds__(256) once_iou_kernel(pda_once_frames_t fr, int
         if (dr >= M_PI) dr = 2 * M_PI - dr;
         if (dr > M_PI / 2) v = 0;
     }
-    iou[F.i0 + pair] = v;
+    iou[F.o0 + pair] = v;
 }
 
 // accumulate_scores of one (frame, class, level); blockIdx.y = task = class * n_levels + level.
@@ -178,37 +127,17 @@ __global__ void __launch_bounds__(64) once_accum_kernel(pda_once_frames_t fr, co
                                                         int32_t* status) {
     const int f = blockIdx.x, task = blockIdx.y, cls = task / a.n_levels, level = task % a.n_levels;
     const int lane = lane_id();
-    const Frame F = load_frame(fr, f, status);
+    const EvalFrame F = load_frame(fr, f, status);
     uint64_t acc, ign;
     pred_masks(fr, a, F, cls, level, status, acc, ign);
-    const double thr = a.thr[cls];
-    uint64_t assigned = 0;
-    float* out = seg + (int64_t)task * fr.n_gt_total + F.g0;
-    int n_tp = 0, n_valid = 0;
-    for (int i = 0; i < F.ng; ++i) {
+    int n_valid = 0;
+    const auto flag = [&](int i) {
         const int gf = gt_flag(fr, a, F.g0 + i, cls, level);
-        if (gf == -1) continue;
         n_valid += gf == 0;
-        // the first prediction with the highest score (> -1) among the unassigned accepted ones with iou > thr
-        const double* row = iou + F.i0 + (int64_t)i * F.np;
-        uint64_t best = 0;
-        for (uint64_t m = acc & ~assigned; m; m &= m - 1) {
-            const int j = lane + 64 * (int)__builtin_ctzll(m);
-            const float s = fr.pred_score[F.p0 + j];
-            if (row[j] > thr && s > -1.0f) {
-                const uint64_t key = ((uint64_t)ordered(s) << 32) | (uint32_t)(0xffffffffu - (uint32_t)j);
-                best = key > best ? key : best;
-            }
-        }
-        best = wave_max_u64(best);
-        if (best == 0) continue;
-        const int jd = (int)(0xffffffffu - (uint32_t)best);
-        if (lane == (jd & 63)) assigned |= 1ull << (jd >> 6);
-        if (gf == 1 || lane_bit(ign, jd)) continue;
-        if (lane == 0) out[n_tp] = fr.pred_score[F.p0 + jd];
-        ++n_tp;
-    }
-    for (int s = n_tp + lane; s < F.ng; s += 64) out[s] = -INFINITY;
+        return gf;
+    };
+    const int n_tp = match_first_pass<ScoreFloorOnce>(iou + F.o0, F.ng, F.nd, fr.pred_score + F.d0, acc, ign, a.thr[cls],
+                                                      flag, seg + (int64_t)task * fr.n_gt_total + F.g0);
     if (lane == 0) {
         atomicAdd((unsigned long long*)&ntp[task], (unsigned long long)n_tp);
         atomicAdd((unsigned long long*)&nvalid[task], (unsigned long long)n_valid);
@@ -264,61 +193,18 @@ __global__ void __launch_bounds__(256) once_stats_kernel(pda_once_frames_t fr, c
                                                          int32_t* status) {
     const int f = blockIdx.x, task = blockIdx.y, cls = task / a.n_levels, level = task % a.n_levels;
     const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const Frame F = load_frame(fr, f, status);
+    const EvalFrame F = load_frame(fr, f, status);
     uint64_t acc, ign;
     pred_masks(fr, a, F, cls, level, nullptr, acc, ign);
     const double thr = a.thr[cls];
+    const auto flag = [&](int i) { return gt_flag(fr, a, F.g0 + i, cls, level); };
     int64_t nt = n_thr[task];
     if (nt > num_pr_points + 1) nt = num_pr_points + 1;
     for (int t = wave; t < nt; t += 4) {
         const double th = thresholds[(int64_t)task * (num_pr_points + 1) + t];
-        uint64_t above = 0;
-        for (uint64_t m = acc; m; m &= m - 1) {
-            const int k = (int)__builtin_ctzll(m);
-            if (!((double)fr.pred_score[F.p0 + lane + 64 * k] < th)) above |= 1ull << k;
-        }
-        uint64_t assigned = 0;
-        int tp = 0, fn = 0;
-        for (int i = 0; i < F.ng; ++i) {
-            const int gf = gt_flag(fr, a, F.g0 + i, cls, level);
-            if (gf == -1) continue;
-            const double* row = iou + F.i0 + (int64_t)i * F.np;
-            uint64_t best0 = 0;            // IoU bits (positive doubles order as integers)
-            uint32_t j0 = 0xffffffffu, j1 = 0xffffffffu;
-            for (uint64_t m = acc & above & ~assigned; m; m &= m - 1) {
-                const int k = (int)__builtin_ctzll(m);
-                const int j = lane + 64 * k;
-                const double v = row[j];
-                if (!(v > thr)) continue;
-                if ((ign >> k) & 1ull) {
-                    if ((uint32_t)j < j1) j1 = (uint32_t)j;
-                } else {
-                    const uint64_t bits = (uint64_t)__double_as_longlong(v);
-                    if (bits > best0) { best0 = bits; j0 = (uint32_t)j; }
-                }
-            }
-            const uint64_t m0 = wave_max_u64(best0);
-            int jd;
-            bool det_ign;
-            if (m0 != 0) {
-                jd = (int)wave_min_u32s(best0 == m0 ? j0 : 0xffffffffu);
-                det_ign = false;
-            } else {
-                const uint32_t w1 = wave_min_u32s(j1);
-                if (w1 == 0xffffffffu) {
-                    fn += gf == 0;
-                    continue;
-                }
-                jd = (int)w1;
-                det_ign = true;
-            }
-            if (lane == (jd & 63)) assigned |= 1ull << (jd >> 6);
-            if (gf == 0 && !det_ign) ++tp;
-        }
-        const int fp_lane = __builtin_popcountll(acc & ~ign & above & ~assigned);
-        int fp = fp_lane;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) fp += __shfl_xor(fp, o, 64);
+        const MatchStats r = match_second_pass(iou + F.o0, F.ng, F.nd, fr.pred_score + F.d0, acc, ign, thr, th, flag,
+                                               [](int, int) {});
+        const int tp = r.tp, fn = r.fn, fp = wave_sum_i32(__builtin_popcountll(r.open));
         if (lane == 0) {
             int64_t* c = counts + ((int64_t)task * (num_pr_points + 1) + t) * 3;
             if (tp) atomicAdd((unsigned long long*)&c[0], (unsigned long long)tp);
@@ -333,11 +219,9 @@ int64_t seg_bytes(int64_t n_gt_total, int n_tasks) { return (n_tasks * n_gt_tota
 
 int check_frames(const pda_once_frames_t* fr, const char* what) {
     PDA_REQUIRE(fr, "%s: null frames", what);
-    PDA_REQUIRE(fr->n_frames >= 0 && fr->n_frames <= (1 << 24), "%s: n_frames %d outside [0, 2^24]", what, fr->n_frames);
-    PDA_REQUIRE(fr->max_gt >= 0 && fr->max_pred >= 0 && fr->max_pred <= OE_MAX_PRED,
-                "%s: max_gt %d / max_pred %d (max_pred <= %d)", what, fr->max_gt, fr->max_pred, OE_MAX_PRED);
-    PDA_REQUIRE(fr->n_gt_total >= 0 && fr->pred_cap >= 0 && fr->iou_cap >= 0, "%s: negative sizes", what);
-    PDA_REQUIRE((int64_t)fr->max_gt * fr->max_pred <= ((int64_t)65535 * 256), "%s: max_gt x max_pred too large", what);
+    if (int st = check_frame_limits(what, "max_pred", fr->n_frames, fr->max_gt, fr->max_pred, fr->n_gt_total, fr->pred_cap,
+                                    fr->iou_cap))
+        return st;
     if (fr->n_frames == 0) return PDA_OK;
     PDA_REQUIRE(fr->gt_offsets && fr->pred_start && fr->pred_count && fr->iou_start, "%s: null frame arrays", what);
     PDA_REQUIRE((fr->gt_boxes && fr->gt_name) || fr->n_gt_total == 0, "%s: null GT arrays", what);

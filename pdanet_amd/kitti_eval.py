@@ -20,7 +20,7 @@ import io
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, eval_common as ec
 from .pointnet2_batch_cuda import _call
 
 CLASS_TO_NAME = {0: 'Car', 1: 'Pedestrian', 2: 'Cyclist', 3: 'Van', 4: 'Person_sitting', 5: 'Truck'}
@@ -35,6 +35,7 @@ MAX_DET = 4096
 CALIB_FLOATS = 33
 # frame_mode bits (include/pda_train.h)
 MODE_IMG_DT64, MODE_IMG_GT64, MODE_3D_DT64, MODE_DC_DT64 = 1, 2, 4, 8
+ptr = ec.ptr
 
 
 def class_ids(current_classes):
@@ -99,13 +100,7 @@ def _names(anno):
 
 
 def _vocab(*name_lists):
-    vocab = {}
-    for names in name_lists:
-        for n in names:
-            vocab.setdefault(n, len(vocab))
-    if len(vocab) > MAX_NAMES:
-        raise ValueError("KITTI evaluation supports at most %d distinct names, got %d" % (MAX_NAMES, len(vocab)))
-    return vocab
+    return ec.vocab(name_lists, MAX_NAMES, "KITTI")
 
 
 def _col(annos, key, dtype, width=None):
@@ -116,22 +111,6 @@ def _col(annos, key, dtype, width=None):
     if parts:
         return np.ascontiguousarray(np.concatenate(parts, 0))
     return np.zeros((0, width) if width else 0, dtype)
-
-
-def _upload(arrays, device):
-    """One host-to-device copy of several numpy arrays; returns device views with their dtypes and shapes."""
-    offs, total = [], 0
-    for a in arrays:
-        total = (total + 255) // 256 * 256
-        offs.append(total)
-        total += a.nbytes
-    buf = np.zeros(max(total, 1), np.uint8)
-    for a, o in zip(arrays, offs):
-        buf[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-    dev = torch.from_numpy(buf).to(device, non_blocking=False)
-    tdt = {np.dtype(np.float64): torch.float64, np.dtype(np.float32): torch.float32, np.dtype(np.int64): torch.int64,
-           np.dtype(np.int32): torch.int32}
-    return [dev[o:o + a.nbytes].view(tdt[a.dtype]).reshape(a.shape) for a, o in zip(arrays, offs)]
 
 
 def gt_arrays(gt_annos, vocab):
@@ -156,13 +135,9 @@ class _Frames:
         self.dt = dt                                     # device: bbox (R, 4), box (R, 7), alpha, score, name
         self.dt_rows, self.max_det = dt_rows, max_det    # host: the overlap row length of each frame
         self.dt_start, self.dt_count, self.ov_start, self.mode = dt_start, dt_count, ov_start, mode
-        starts = np.zeros(len(n_gt) + 1, np.int64)
-        np.cumsum(n_gt.astype(np.int64) * dt_rows, out=starts[1:])
-        self.ov_total = int(starts[-1])
-        self.ov_start_host = starts[:-1]
+        self.ov_start_host, self.ov_total = ec.pair_offsets(n_gt, dt_rows)
 
     def struct(self):
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
         return _lib.KittiFrames(*[ptr(t) for t in self.gt], *[ptr(t) for t in self.dt], ptr(self.dt_start),
                                 ptr(self.dt_count), ptr(self.ov_start), ptr(self.mode), int(self.gt[0].shape[0]),
                                 int(self.dt[3].shape[0]), self.ov_total, len(self.n_gt), int(self.n_gt.max(initial=0)),
@@ -180,11 +155,9 @@ def frames_from_annos(gt_annos, dt_annos, vocab, device, num_parts=NUM_PARTS):
     dcols = [_col(dt_annos, 'bbox', np.float32, 4), np.ascontiguousarray(box), _col(dt_annos, 'alpha', np.float32),
              _col(dt_annos, 'score', np.float32),
              np.array([vocab[n] for a in dt_annos for n in _names(a)], np.int32)]
-    start = np.zeros(len(dt_annos), np.int64)
-    np.cumsum(n_dt[:-1], out=start[1:])
     fr = _Frames(None, n_gt, None, n_dt, int(n_dt.max(initial=0)))
-    d = _upload(gcols + dcols + [start, n_dt.astype(np.int32), fr.ov_start_host,
-                                 frame_modes(gt_annos, dt_annos, num_parts)], device)
+    d = ec.upload(gcols + dcols + [ec.row_starts(n_dt), n_dt.astype(np.int32), fr.ov_start_host,
+                                   frame_modes(gt_annos, dt_annos, num_parts)], device)
     fr.gt, fr.dt = d[:9], d[9:14]
     fr.dt_start, fr.dt_count, fr.ov_start, fr.mode = d[14:18]
     return fr
@@ -203,6 +176,12 @@ class _Plan:
             self.gt_class = np.full((self.C, 1), -1, np.int8)
             self.dt_class = np.zeros((self.C, 1), np.uint8)
             self.dontcare = np.zeros(1, np.uint8)
+        C, P = self.C, N_SAMPLE_PTS
+        self.layout = ec.ResultLayout("KITTI", [('counts', np.int64, (3, C, 3, 2, P, 3)),
+                                                ('n_thresholds', np.int64, (3, C, 3, 2)),
+                                                ('num_valid_gt', np.int64, (C, 3)),
+                                                ('thresholds', np.float64, (3, C, 3, 2, P)),
+                                                ('similarity', np.float64, (C, 3, 2, P))])
 
     @property
     def T(self):
@@ -211,22 +190,16 @@ class _Plan:
 
 def _run_stages(fr, plan, compute_aos, overlaps=None):
     """Overlaps (unless given), first pass, sort, match on the current stream.  Returns the device overlaps, the flags and
-    one int64 device result buffer: counts (T, 41, 3) | n_thresholds (T) | num_valid_gt (3C) | thresholds (T, 41) f64 |
-    similarity (6C, 41) f64 | status."""
+    the one int64 device result buffer of plan.layout."""
     lib = _lib.load()
     dev = fr.gt[8].device
-    T, C, P = plan.T, plan.C, N_SAMPLE_PTS
-    sizes = [T * P * 3, T, 3 * C, T * P, 6 * C * P, 1]
-    offs = np.concatenate([[0], np.cumsum(sizes)])
-    res = torch.zeros(int(offs[-1]), dtype=torch.int64, device=dev)
-    counts, n_thr, nvalid = (res[offs[i]:offs[i + 1]] for i in range(3))
-    thresholds = res[offs[3]:offs[4]].view(torch.float64)
-    similarity = res[offs[4]:offs[5]].view(torch.float64)
-    status = res[-1:].view(torch.int32)
+    T, C = plan.T, plan.C
+    res = plan.layout.alloc(dev)
+    out = {k: v.data_ptr() for k, v in plan.layout.device_views(res).items()}
     st = ctypes.byref(fr.struct())
     if overlaps is None:
         overlaps = torch.empty(max(3 * fr.ov_total, 1), dtype=torch.float64, device=dev)
-        _call("pda_kitti_eval_overlaps", res, st, overlaps.data_ptr(), status.data_ptr())
+        _call("pda_kitti_eval_overlaps", res, st, overlaps.data_ptr(), out['status'])
     n_gt_total, det_cap = int(fr.gt[0].shape[0]), int(fr.dt[3].shape[0])
     ws_bytes = lib.pda_kitti_eval_workspace_bytes(len(fr.n_gt), n_gt_total, det_cap, C)
     if ws_bytes < 0:
@@ -236,20 +209,20 @@ def _run_stages(fr, plan, compute_aos, overlaps=None):
     gt_flags, dt_flags = flags[:3 * C * n_gt_total], flags[3 * C * n_gt_total:-1]
     mo = (ctypes.c_double * plan.min_overlaps.size)(*plan.min_overlaps.reshape(-1).tolist())
     tables = (plan.C, plan.n_names, plan.gt_class.ctypes.data, plan.dt_class.ctypes.data, plan.dontcare.ctypes.data, mo)
-    fp = lambda t: t.data_ptr() if t.numel() else None
-    _call("pda_kitti_eval_first_pass", res, st, overlaps.data_ptr(), *tables, fp(gt_flags), fp(dt_flags),
-          nvalid.data_ptr(), status.data_ptr(), ws.data_ptr())
+    _call("pda_kitti_eval_first_pass", res, st, overlaps.data_ptr(), *tables, ptr(gt_flags), ptr(dt_flags),
+          out['num_valid_gt'], out['status'], ws.data_ptr())
     seg = ws[:T * n_gt_total * 4].view(torch.float32).view(T, n_gt_total)
     ordered = torch.sort(seg, dim=1, descending=True).values if n_gt_total else seg
-    _call("pda_kitti_eval_match", res, st, overlaps.data_ptr(), *tables, 1 if compute_aos else 0, fp(gt_flags),
-          fp(dt_flags), ordered.data_ptr() if n_gt_total else None, nvalid.data_ptr(), thresholds.data_ptr(),
-          n_thr.data_ptr(), counts.data_ptr(), similarity.data_ptr(), status.data_ptr(), ws.data_ptr())
+    _call("pda_kitti_eval_match", res, st, overlaps.data_ptr(), *tables, 1 if compute_aos else 0, ptr(gt_flags),
+          ptr(dt_flags), ordered.data_ptr() if n_gt_total else None, out['num_valid_gt'], out['thresholds'],
+          out['n_thresholds'], out['counts'], out['similarity'], out['status'], ws.data_ptr())
     return overlaps, (gt_flags, dt_flags), res
 
 
 def _read(res, plan):
-    """The one device-to-host copy of _run_stages' result buffer (see _read_host)."""
-    return _read_host(res.cpu().numpy(), plan)
+    """The one device-to-host copy of _run_stages' result buffer: counts (3, C, 3, 2, 41, 3), n_thresholds (3, C, 3, 2),
+    num_valid_gt (C, 3), thresholds (3, C, 3, 2, 41) and similarity (C, 3, 2, 41); raises on a status bit."""
+    return plan.layout.host_views(res.cpu().numpy())
 
 
 def _eval_metric(out, metric, compute_aos):
@@ -382,7 +355,6 @@ def convert_predictions(boxes, frame_idx, calib, image_shape, rows_per_frame=0):
     out = torch.empty(n * 12 + 1, dtype=torch.float32, device=dev)
     cam, bbox, alpha = out[:7 * n].view(n, 7), out[7 * n:11 * n].view(n, 4), out[11 * n:12 * n]
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
     _call("pda_kitti_eval_predictions", out, ptr(boxes), n, int(boxes.shape[1]) if n else 7, int(rows_per_frame),
           ptr(frame_idx), ptr(calib), ptr(image_shape), int(calib.shape[0]), ptr(cam), ptr(bbox), ptr(alpha),
           status.data_ptr())
@@ -450,7 +422,7 @@ class KittiEvaluator:
         self.plan = _Plan(self.ids, list(self.vocab))
         self.device = torch.device(device)
         gcols, self.n_gt = gt_arrays(gt_annos, self.vocab)
-        self.gt = _upload(gcols, self.device)
+        self.gt = ec.upload(gcols, self.device)
         self.gt_bbox64 = [np.asarray(a['bbox']).dtype == np.float64 for a in gt_annos]
         self.batches = []
         self.n_frames = 0
@@ -465,11 +437,8 @@ class KittiEvaluator:
         calib = calib_mats.to(self.device, torch.float32).reshape(B, CALIB_FLOATS).contiguous()
         shape = image_shape.to(self.device, torch.int32).reshape(B, 2).contiguous()
         cam, bbox, alpha, status = convert_predictions(boxes.view(B * K, 7), None, calib, shape, rows_per_frame=max(K, 1))
-        nc = len(self.class_names)
-        idx = padded['pred_labels'].to(torch.int64) - 1
-        idx = torch.where(idx < 0, idx + nc, idx)                     # numpy's class_names[label - 1]
-        idx = torch.where((idx >= 0) & (idx < nc), idx, torch.full_like(idx, -1)).to(torch.int32)
-        num = torch.clamp(padded['num_pred'].to(torch.int32), 0, K)
+        idx = ec.label_name_ids(padded['pred_labels'], len(self.class_names))
+        num = ec.clamp_num_pred(padded['num_pred'], K)
         self.batches.append((bbox, cam, alpha, padded['pred_scores'].to(torch.float32).reshape(B * K).contiguous(),
                              idx.reshape(B * K).contiguous(), num.reshape(B), status, B, K))
         self.n_frames += B
@@ -480,9 +449,7 @@ class KittiEvaluator:
         dev = self.device
         empty = lambda dt, *s: torch.zeros(s, dtype=dt, device=dev)
         cat = lambda i, dt, *s: torch.cat([b[i] for b in self.batches]) if self.batches else empty(dt, *s)
-        rows = np.concatenate([np.full(b[7], b[8], np.int64) for b in self.batches]) if self.batches else np.zeros(0, np.int64)
-        start = np.zeros(len(rows), np.int64)
-        np.cumsum(rows[:-1], out=start[1:])
+        rows = ec.padded_rows([b[7:9] for b in self.batches])
         dt = [cat(0, torch.float32, 0, 4), cat(1, torch.float32, 0, 7), cat(2, torch.float32, 0),
               cat(3, torch.float32, 0), cat(4, torch.int32, 0)]
         fr = _Frames(self.gt, self.n_gt, dt, rows, int(rows.max(initial=0)))
@@ -494,7 +461,8 @@ class KittiEvaluator:
         for p in range(len(parts)):
             if any(np.asarray(self.gt_bbox64)[part_of == p]):
                 gt_mode[part_of == p] = MODE_IMG_GT64
-        fr.dt_start, fr.ov_start, gt_mode_d, part_d = _upload([start, fr.ov_start_host, gt_mode, part_of], dev)
+        fr.dt_start, fr.ov_start, gt_mode_d, part_d = ec.upload(
+            [ec.row_starts(rows), fr.ov_start_host, gt_mode, part_of], dev)
         fr.dt_count = cat(5, torch.int32, 0)
         empty_part = torch.zeros(len(parts), dtype=torch.int32, device=dev).scatter_reduce_(
             0, part_d, (fr.dt_count == 0).to(torch.int32), reduce='amax')
@@ -507,21 +475,4 @@ class KittiEvaluator:
         if int(h[-2]):
             raise RuntimeError("KITTI prediction conversion: frame index out of range")
         compute_aos = bool(h[-1] > 0)
-        out = _read_host(h[:-2], self.plan)
-        return compose(out, self.plan, compute_aos, PR_detail_dict)
-
-
-def _read_host(h, plan):
-    """Host int64 result buffer -> counts (3, C, 3, 2, 41, 3), n_thresholds (3, C, 3, 2), num_valid_gt (C, 3),
-    thresholds (3, C, 3, 2, 41) and similarity (C, 3, 2, 41); raises on a status bit."""
-    T, C, P = plan.T, plan.C, N_SAMPLE_PTS
-    sizes = [T * P * 3, T, 3 * C, T * P, 6 * C * P, 1]
-    offs = np.concatenate([[0], np.cumsum(sizes)])
-    seg = lambda i: h[offs[i]:offs[i + 1]]
-    status = int(h[-1:].view(np.int32)[0])
-    if status:
-        raise RuntimeError("KITTI evaluation: inconsistent inputs (status %d: 1 frame bounds, 2 unknown name id, "
-                           "4 too many thresholds)" % status)
-    return dict(counts=seg(0).reshape(3, C, 3, 2, P, 3), n_thresholds=seg(1).reshape(3, C, 3, 2),
-                num_valid_gt=seg(2).reshape(C, 3), thresholds=seg(3).view(np.float64).reshape(3, C, 3, 2, P),
-                similarity=seg(4).view(np.float64).reshape(C, 3, 2, P))
+        return compose(self.plan.layout.host_views(h[:-2]), self.plan, compute_aos, PR_detail_dict)

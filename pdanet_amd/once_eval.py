@@ -16,7 +16,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, eval_common as ec
 from .pointnet2_batch_cuda import _call
 
 IOU_THRESHOLDS = {'Car': 0.7, 'Bus': 0.7, 'Truck': 0.7, 'Pedestrian': 0.3, 'Cyclist': 0.5}
@@ -28,6 +28,7 @@ _VEHICLES = ('Car', 'Bus', 'Truck')
 _NOT_VEHICLE = ('Pedestrian', 'Cyclist')
 MAX_NAMES = 64
 MAX_PRED = 4096
+ptr = ec.ptr
 
 
 def eval_classes(classes, use_superclass):
@@ -61,22 +62,6 @@ def _rows7(boxes, n, dtype):
     return b.reshape(n, b.size // n)[:, :7] if n else np.zeros((0, 7), dtype)
 
 
-def _upload(arrays, device):
-    """One host-to-device copy of several numpy arrays; returns device views with their dtypes and shapes."""
-    offs, total = [], 0
-    for a in arrays:
-        total = (total + 255) // 256 * 256
-        offs.append(total)
-        total += a.nbytes
-    buf = np.zeros(max(total, 1), np.uint8)
-    for a, o in zip(arrays, offs):
-        buf[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-    dev = torch.from_numpy(buf).to(device, non_blocking=False)
-    tdt = {np.dtype(np.float64): torch.float64, np.dtype(np.float32): torch.float32, np.dtype(np.int64): torch.int64,
-           np.dtype(np.int32): torch.int32}
-    return [dev[o:o + a.nbytes].view(tdt[a.dtype]).reshape(a.shape) for a, o in zip(arrays, offs)]
-
-
 class _Frames:
     """Device GT and predictions of a frame set, in the pda_once_frames_t layout."""
 
@@ -86,22 +71,13 @@ class _Frames:
         self.pred_boxes, self.pred_score, self.pred_name = pred_boxes, pred_score, pred_name
         self.pred_start, self.pred_count, self.max_pred = pred_start, pred_count, max_pred
         self.pred_rows = pred_rows                       # host: the IoU row length of each frame (count or capacity)
-        starts = np.zeros(len(n_gt) + 1, np.int64)
-        np.cumsum(n_gt.astype(np.int64) * pred_rows, out=starts[1:])
-        self.iou_total = int(starts[-1])
-        self.iou_start_host = starts[:-1]
+        self.iou_start_host, self.iou_total = ec.pair_offsets(n_gt, pred_rows)
 
     def struct(self, iou_start):
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
         return _lib.OnceFrames(ptr(self.gt_boxes), ptr(self.gt_name), ptr(self.gt_offsets), ptr(self.pred_boxes),
                                ptr(self.pred_score), ptr(self.pred_name), ptr(self.pred_start), ptr(self.pred_count),
                                ptr(iou_start), int(self.gt_boxes.shape[0]), int(self.pred_score.shape[0]),
                                self.iou_total, len(self.n_gt), int(self.n_gt.max(initial=0)), int(self.max_pred))
-
-
-def _check_names(names):
-    if len(names) > MAX_NAMES:
-        raise ValueError("ONCE evaluation supports at most %d distinct names, got %d" % (MAX_NAMES, len(names)))
 
 
 class _Plan:
@@ -120,26 +96,24 @@ class _Plan:
         self.num_pr_points = int(num_pr_points)
         self.accept = np.ascontiguousarray(accept_table(self.classes, names, use_superclass))
         self.n_names = len(names)
+        C, D, P1 = len(self.classes), len(self.diff_types), self.num_pr_points + 1
+        self.layout = ec.ResultLayout("ONCE", [('counts', np.int64, (C, D, P1, 3)), ('n_thresholds', np.int64, (C, D)),
+                                               ('num_valid_gt', np.int64, (C, D)),
+                                               ('thresholds', np.float64, (C, D, P1))])
 
 
 def _run_stages(fr, plan, with_heading, iou=None):
-    """IoU (unless given), accumulate, sort, match on the current stream.  Returns the device iou buffer and one
-    int64 device result buffer: counts (T, P+1, 3) | n_thresholds (T) | num_valid_gt (T) | thresholds (T, P+1) f64 |
-    status."""
+    """IoU (unless given), accumulate, sort, match on the current stream.  Returns the device iou buffer and the one
+    int64 device result buffer of plan.layout."""
     lib = _lib.load()
     dev = fr.gt_offsets.device
-    T, P1 = len(plan.classes) * len(plan.diff_types), plan.num_pr_points + 1
-    n_counts = T * P1 * 3
-    res = torch.zeros(n_counts + 2 * T + T * P1 + 1, dtype=torch.int64, device=dev)
-    counts, n_thr = res[:n_counts], res[n_counts:n_counts + T]
-    nvalid = res[n_counts + T:n_counts + 2 * T]
-    thresholds = res[n_counts + 2 * T:n_counts + 2 * T + T * P1].view(torch.float64)
-    status = res[-1:].view(torch.int32)
-    iou_start = fr.iou_start
-    st = ctypes.byref(fr.struct(iou_start))
+    T = len(plan.classes) * len(plan.diff_types)
+    res = plan.layout.alloc(dev)
+    out = {k: v.data_ptr() for k, v in plan.layout.device_views(res).items()}
+    st = ctypes.byref(fr.struct(fr.iou_start))
     if iou is None:
         iou = torch.empty(max(fr.iou_total, 1), dtype=torch.float64, device=dev)
-        _call("pda_once_eval_iou", res, st, 1 if with_heading else 0, iou.data_ptr(), status.data_ptr())
+        _call("pda_once_eval_iou", res, st, 1 if with_heading else 0, iou.data_ptr(), out['status'])
     n_gt_total = int(fr.gt_boxes.shape[0])
     ws_bytes = lib.pda_once_eval_workspace_bytes(len(fr.n_gt), n_gt_total, T)
     if ws_bytes < 0:
@@ -148,29 +122,19 @@ def _run_stages(fr, plan, with_heading, iou=None):
     thr_c = (ctypes.c_double * len(plan.thr))(*plan.thr.tolist())
     acc = plan.accept.ctypes.data
     args = (acc, len(plan.classes), plan.n_names, thr_c, plan.mode)
-    _call("pda_once_eval_accumulate", res, st, iou.data_ptr(), *args, nvalid.data_ptr(), status.data_ptr(), ws.data_ptr())
+    _call("pda_once_eval_accumulate", res, st, iou.data_ptr(), *args, out['num_valid_gt'], out['status'], ws.data_ptr())
     seg = ws[:T * n_gt_total * 4].view(torch.float32).view(T, n_gt_total)
     ordered = torch.sort(seg, dim=1, descending=True).values if n_gt_total else seg
     _call("pda_once_eval_match", res, st, iou.data_ptr(), *args, plan.num_pr_points,
-          ordered.data_ptr() if n_gt_total else None, nvalid.data_ptr(), thresholds.data_ptr(), n_thr.data_ptr(),
-          counts.data_ptr(), status.data_ptr(), ws.data_ptr())
+          ordered.data_ptr() if n_gt_total else None, out['num_valid_gt'], out['thresholds'], out['n_thresholds'],
+          out['counts'], out['status'], ws.data_ptr())
     return iou, res
 
 
 def _read(res, plan):
     """The one device-to-host copy, split into counts (C, D, P+1, 3), n_thresholds (C, D), num_valid_gt (C, D) and
-    thresholds (C, D, P+1)."""
-    h = res.cpu().numpy()
-    C, D, P1 = len(plan.classes), len(plan.diff_types), plan.num_pr_points + 1
-    T = C * D
-    n_counts = T * P1 * 3
-    status = int(h[-1:].view(np.int32)[0])
-    if status:
-        raise RuntimeError("ONCE evaluation: inconsistent inputs (status %d: 1 frame bounds, 2 unknown name id, "
-                           "4 too many thresholds)" % status)
-    return dict(counts=h[:n_counts].reshape(C, D, P1, 3), n_thresholds=h[n_counts:n_counts + T].reshape(C, D),
-                num_valid_gt=h[n_counts + T:n_counts + 2 * T].reshape(C, D),
-                thresholds=h[n_counts + 2 * T:n_counts + 2 * T + T * P1].view(np.float64).reshape(C, D, P1))
+    thresholds (C, D, P+1); raises on a status bit."""
+    return plan.layout.host_views(res.cpu().numpy())
 
 
 def compose(out, plan, print_ok=False):
@@ -216,12 +180,7 @@ def _gt_arrays(gt_annos, vocab):
 
 
 def _vocab(*name_lists):
-    vocab = {}
-    for names in name_lists:
-        for n in names:
-            vocab.setdefault(n, len(vocab))
-    _check_names(vocab)
-    return vocab
+    return ec.vocab(name_lists, MAX_NAMES, "ONCE")
 
 
 def frames_from_annos(gt_annos, pred_annos, vocab, device):
@@ -237,10 +196,9 @@ def frames_from_annos(gt_annos, pred_annos, vocab, device):
     pn = [_names(a) for a in pred_annos]
     pn = np.concatenate(pn) if pn else np.zeros(0, str)
     pid = np.array([vocab[n] for n in pn.tolist()], np.int32)
-    pstart = np.zeros(len(pred_annos), np.int64)
-    np.cumsum(n_pred[:-1], out=pstart[1:])
     fr = _Frames(None, None, None, n_gt, None, None, None, None, None, n_pred, int(n_pred.max(initial=0)))
-    d = _upload([gb, gid, goffs, pb, ps, pid, pstart, n_pred.astype(np.int32), fr.iou_start_host], device)
+    d = ec.upload([gb, gid, goffs, pb, ps, pid, ec.row_starts(n_pred), n_pred.astype(np.int32), fr.iou_start_host],
+                  device)
     fr.gt_boxes, fr.gt_name, fr.gt_offsets, fr.pred_boxes, fr.pred_score, fr.pred_name = d[:6]
     fr.pred_start, fr.pred_count, fr.iou_start = d[6], d[7], d[8]
     return fr
@@ -291,7 +249,7 @@ class OnceEvaluator:
         self.with_heading = ap_with_heading
         self.device = torch.device(device)
         gb, gid, goffs, self.n_gt = _gt_arrays(gt_annos, self.vocab)
-        self.gt = _upload([gb, gid, goffs], self.device)
+        self.gt = ec.upload([gb, gid, goffs], self.device)
         self.batches = []
         self.n_frames = 0
 
@@ -301,11 +259,8 @@ class OnceEvaluator:
         B, K = boxes.shape[0], boxes.shape[1]
         if K > MAX_PRED:
             raise ValueError("ONCE evaluation supports at most %d predictions a frame" % MAX_PRED)
-        nc = len(self.class_names)
-        idx = padded['pred_labels'].to(torch.int64) - 1
-        idx = torch.where(idx < 0, idx + nc, idx)                     # numpy's class_names[label - 1]
-        idx = torch.where((idx >= 0) & (idx < nc), idx, torch.full_like(idx, -1)).to(torch.int32)
-        num = torch.clamp(padded['num_pred'].to(torch.int32), 0, K)
+        idx = ec.label_name_ids(padded['pred_labels'], len(self.class_names))
+        num = ec.clamp_num_pred(padded['num_pred'], K)
         self.batches.append((boxes.view(B * K, 7), padded['pred_scores'].to(torch.float32).reshape(B * K).contiguous(),
                              idx.reshape(B * K).contiguous(), num.reshape(B), B, K))
         self.n_frames += B
@@ -315,11 +270,9 @@ class OnceEvaluator:
             raise ValueError("%d frames of predictions for %d GT frames" % (self.n_frames, len(self.n_gt)))
         empty = lambda dt, *s: torch.zeros(s, dtype=dt, device=self.device)
         cat = lambda i, dt, *s: torch.cat([b[i] for b in self.batches]) if self.batches else empty(dt, *s)
-        rows = np.concatenate([np.full(b[4], b[5], np.int64) for b in self.batches]) if self.batches else np.zeros(0, np.int64)
-        pstart = np.zeros(len(rows), np.int64)
-        np.cumsum(rows[:-1], out=pstart[1:])
+        rows = ec.padded_rows([b[4:6] for b in self.batches])
         fr = _Frames(self.gt[0], self.gt[1], self.gt[2], self.n_gt, cat(0, torch.float32, 0, 7), cat(1, torch.float32, 0),
                      cat(2, torch.int32, 0), None, cat(3, torch.int32, 0), rows, int(rows.max(initial=0)))
-        fr.pred_start, fr.iou_start = _upload([pstart, fr.iou_start_host], self.device)
+        fr.pred_start, fr.iou_start = ec.upload([ec.row_starts(rows), fr.iou_start_host], self.device)
         _, res = _run_stages(fr, self.plan, self.with_heading)
         return compose(_read(res, self.plan), self.plan, print_ok)
