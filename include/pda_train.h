@@ -607,6 +607,47 @@ int pda_recall_record(const float *pred_boxes, const int32_t *num_pred, const fl
                       const float *thresh, int n_thresh, int64_t *counters, float *max_iou, int b, int k, int t,
                       pda_stream_t stream);
 
+/* ---- preparing frames (csrc/frame_stage.hip) ---------------------------------------------------------------------------------
+ * KittiDataset's FOV_POINTS_ONLY step (kitti_dataset.py get_fov_flag behind calib.lidar_to_rect / calib.rect_to_img) for
+ * `batch` scenes in the layout of pda_input_stage: points (n_total, C >= 3), offsets (batch + 1) int64, at most n_cap rows a
+ * scene.  calib (batch, 24) float32 on the device: M = V2C^T R0^T (4, 3) row-major, formed by the caller in float32 as
+ * Calibration.lidar_to_rect forms it, then P2 (3, 4) row-major.  image_shape (batch, 2) int32 (H, W) on the device.  Per
+ * point, in float32 without FMA:
+ *   rect_k = ((x*M[0][k] + y*M[1][k]) + z*M[2][k]) + M[3][k];  h_j = ((rx*P2[j][0] + ry*P2[j][1]) + rz*P2[j][2]) + P2[j][3];
+ *   u = h_0 / rz, v = h_1 / rz, depth = h_2 - P2[2][3];  kept iff u >= 0 && u < W && v >= 0 && v < H && depth >= 0
+ * (a NaN keeps nothing).  out_points (out_cap, C): the kept rows of every scene in their order, bit-identical, back to back
+ * (out_cap = n_total always suffices for scenes that do not overlap); out_offsets (batch + 1) int64.
+ * info (batch, 4) int32 = [n_in, n_kept, 0, status]; status bits: 2 offsets outside [0, n_total], 4 more than n_cap rows
+ * (both: the scene is written empty), 4 also when out_cap is exceeded (rows beyond it are dropped).
+ * workspace: pda_kitti_fov_filter_workspace_bytes(batch, n_cap) bytes, 4-byte aligned (-1: bad sizes).  Four launches, no
+ * host synchronisation; the grids depend on batch and n_cap only (graph-capturable). */
+int64_t pda_kitti_fov_filter_workspace_bytes(int batch, int64_t n_cap);
+int pda_kitti_fov_filter(const float *points, const int64_t *offsets, int64_t n_total, int batch, int c, int64_t n_cap,
+                         const float *calib, const int32_t *image_shape, float *out_points, int64_t out_cap,
+                         int64_t *out_offsets, int32_t *info, void *workspace, pda_stream_t stream);
+/* The body of create_groundtruth_database (kitti_dataset.py / once_dataset.py) for `batch` frames: the same points and
+ * offsets; boxes (m_total, 7) float32 [x, y, z, dx, dy, dz, heading] with box_offsets (batch + 1) int64, at most 256 boxes a
+ * frame; centre (m_total, 3) float64 = gt_boxes[i, :3] as the infos hold it.  Object g (a row of boxes) holds the points of
+ * its own frame that pass the CPU test points_in_boxes_cpu (margin 1e-2, no FMA), in point order, each row
+ * [(float)((double)x - cx), (float)((double)y - cy), (float)((double)z - cz), features...].  A point may land in several
+ * boxes.
+ *   pda_gt_extract_count: counts (m_total) int32, 0 for the boxes of a frame with a status;
+ *   pda_gt_extract_write: obj_offsets (m_total + 1) int64 = the exclusive scan of counts (made by the caller), obj_points
+ *                         (out_cap, C); same arguments and the workspace as pda_gt_extract_count left it.
+ * info (batch, 4) int32 = [points, boxes, 0, status]; status bits: 2 point or box offsets outside their buffers, 4 more
+ * than n_cap points, 8 more than 256 boxes (all three: the frame is written empty); the write sets 4 when obj_offsets or
+ * out_cap do not hold what was counted (such rows are dropped).
+ * workspace: pda_gt_extract_workspace_bytes(batch, n_cap, m_total) bytes, 4-byte aligned (-1: bad sizes).  Two launches
+ * and one; nothing decides an order but ballots and scans. */
+int64_t pda_gt_extract_workspace_bytes(int batch, int64_t n_cap, int64_t m_total);
+int pda_gt_extract_count(const float *points, const int64_t *offsets, int64_t n_total, int batch, int c, int64_t n_cap,
+                         const float *boxes, const int64_t *box_offsets, int64_t m_total, int32_t *counts, int32_t *info,
+                         void *workspace, pda_stream_t stream);
+int pda_gt_extract_write(const float *points, const int64_t *offsets, int64_t n_total, int batch, int c, int64_t n_cap,
+                         const float *boxes, const int64_t *box_offsets, int64_t m_total, const double *centre,
+                         const int64_t *obj_offsets, float *obj_points, int64_t out_cap, int32_t *info, void *workspace,
+                         pda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

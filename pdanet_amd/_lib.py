@@ -187,6 +187,12 @@ SIGNATURES = {
                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pda_kitti_eval_predictions": [_vp, ctypes.c_int64, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp],
     "pda_recall_record": [_vp, _vp, _vp, _i, ctypes.POINTER(_f), _i, _vp, _vp, _i, _i, _i, _vp],
+    "pda_kitti_fov_filter_workspace_bytes": [_i, ctypes.c_int64],
+    "pda_kitti_fov_filter": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp],
+    "pda_gt_extract_workspace_bytes": [_i, ctypes.c_int64, ctypes.c_int64],
+    "pda_gt_extract_count": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp],
+    "pda_gt_extract_write": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp,
+                             ctypes.c_int64, _vp, _vp, _vp],
     # include/pda_pointnet2_stack.h
     "pda_stack_ball_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     "pda_stack_group_points": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -236,6 +242,8 @@ def load():
     lib.pda_augment_workspace_bytes.restype = ctypes.c_int64
     lib.pda_once_eval_workspace_bytes.restype = ctypes.c_int64
     lib.pda_kitti_eval_workspace_bytes.restype = ctypes.c_int64
+    lib.pda_kitti_fov_filter_workspace_bytes.restype = ctypes.c_int64
+    lib.pda_gt_extract_workspace_bytes.restype = ctypes.c_int64
     lib.pda_abi_version.restype = _i
     lib.pda_last_error.restype = ctypes.c_char_p
     lib.pda_fp_contract_mode.restype = _i

@@ -92,6 +92,49 @@ class GtDatabase:
         return cls(class_names, boxes, points, device)
 
     @classmethod
+    def from_device(cls, class_names, boxes, points, offsets, ids):
+        """A database whose object points are on the device already (frame_stage.GtDatabaseBuilder.finish): boxes as for
+        from_arrays; points (rows, C) float32 device tensor holding object o at rows [offsets[o], offsets[o + 1]), offsets
+        a host int64 array; ids: the objects taken, class by class in CLASS_NAMES order (one per box).  The points are
+        gathered on the device."""
+        self = cls.__new__(cls)
+        self.class_names = list(class_names)
+        self.start, self.count = {}, {}
+        box_rows, cls_ids = [], []
+        for ci, name in enumerate(self.class_names):
+            b = np.asarray(boxes.get(name, np.zeros((0, 7))), np.float64)
+            b = b.reshape(-1, b.shape[-1]) if b.size else np.zeros((0, 7))
+            if b.shape[1] != 7:
+                raise NotImplementedError("database boxes with %d values: boxes with velocities are not supported" % b.shape[1])
+            self.start[name] = sum(len(x) for x in box_rows)
+            self.count[name] = b.shape[0]
+            box_rows.append(b)
+            cls_ids.extend([ci + 1] * b.shape[0])
+        centre = np.concatenate(box_rows, 0) if box_rows else np.zeros((0, 7))
+        ids = np.asarray(ids, np.int64).reshape(-1)
+        offsets = np.asarray(offsets, np.int64).reshape(-1)
+        if ids.size != centre.shape[0]:
+            raise ValueError("%d boxes but %d object ids" % (centre.shape[0], ids.size))
+        if ids.size and (ids.min() < 0 or ids.max() >= offsets.size - 1):
+            raise ValueError("an object id outside the packed points")
+        if not points.is_cuda or points.dim() != 2 or points.dtype != torch.float32:
+            raise ValueError("points must be a (rows, C) float32 device tensor")
+        self.n_obj = centre.shape[0]
+        self.num_point_features = points.shape[1]
+        self.sizes = (offsets[ids + 1] - offsets[ids]).astype(np.int64)
+        self.host_boxes = centre.astype(np.float32)
+        offs = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)
+        # the source row of every database row: object starts repeated, plus the position inside the object
+        rows = np.repeat(offsets[ids] - offs[:-1], self.sizes) + np.arange(offs[-1], dtype=np.int64)
+        dev = self.device = points.device
+        self.points = points.index_select(0, torch.from_numpy(rows).to(dev)).contiguous()
+        self.offsets = torch.from_numpy(offs).to(dev)
+        self.boxes = torch.from_numpy(np.ascontiguousarray(self.host_boxes)).to(dev)
+        self.centre = torch.from_numpy(np.ascontiguousarray(centre[:, :3])).to(dev)
+        self.classes = torch.from_numpy(np.array(cls_ids, np.int32)).to(dev)
+        return self
+
+    @classmethod
     def from_dbinfos(cls, root_path, sampler_cfg, class_names, device=None):
         """The database DataBaseSampler.__init__ builds: the DB_INFO_PATH pickles under root_path, PREPARE applied
         (filter_by_min_points, filter_by_difficulty), points from the per-object .bin files or, with
