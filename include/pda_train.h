@@ -480,6 +480,44 @@ int pda_augment(const float *points, const int64_t *offsets, int64_t n_total, in
                 int64_t paste_cap, float *out_points, int64_t out_cap, int64_t *out_offsets, float *out_boxes,
                 int64_t out_box_cap, int64_t *out_box_offsets, int32_t *info, void *workspace, pda_stream_t stream);
 
+/* The paste-only form of pda_augment, in front of pda_augment_steps: the same collision test, point removal and paste,
+ * but no transform, no limit_period, and boxes of class 0 stay in the output (they take part in the steps that follow).
+ * Arguments, workspace and info as for pda_augment, without flip / angle / scale. */
+int pda_augment_paste(const float *points, const int64_t *offsets, int64_t n_total, int batch, int c, int64_t n_cap,
+                      const float *boxes, const int64_t *box_offsets, int64_t m_total, const float *db_points,
+                      const int64_t *db_offsets, int64_t db_n_points, const float *db_boxes, const double *db_centre,
+                      const int32_t *db_class, int n_obj, const int32_t *cand, const int32_t *cand_group,
+                      const double *cand_dz, int k, const float *remove_extra_width, int64_t paste_cap, float *out_points,
+                      int64_t out_cap, int64_t *out_offsets, float *out_boxes, int64_t out_box_cap,
+                      int64_t *out_box_offsets, int32_t *info, void *workspace, pda_stream_t stream);
+
+/* ---- the augmentor's ordered step program (csrc/augment_steps.hip; the reference's random_world_flip / _rotation /
+ * _scaling / _translation / _frustum_dropout and random_local_translation / _rotation / _scaling / _frustum_dropout of
+ * pcdet/datasets/augmentor/augmentor_utils.py, in any order, then limit_period and prepare_data's class filter) --------
+ * Scenes and boxes as for pda_augment (boxes (m_total, 8), class 0 takes part in every step and is dropped at the end).
+ * ops (HOST) (n_ops, 2) int32 [code, arg], n_ops <= 32, run in order:
+ *   0 flip_x, 1 flip_y, 2 world rotation, 3 world scaling, 4 world translation (arg: axis 0..2), 5 world frustum dropout
+ *   (arg: 0 top, 1 bottom, 2 left, 3 right; at most 4 such ops), 6 local translation (arg: axis), 7 local rotation,
+ *   8 local scaling, 9 local frustum dropout (arg: direction).
+ * scene_draws (batch, n_ops) float64 on the device: the scene's draw of op i (flip 0 / 1, angle with 0 = off, scale with
+ *   1 = off, translation offset, dropout intensity; unused for local ops).  box_draws (batch, n_local, draw_cap) float64:
+ *   row l belongs to the l-th local op (codes 6..9) of the program; draw j of a row belongs to the j-th box alive at
+ *   that op, in order (a world dropout removes boxes).
+ * A local op walks the scene's boxes in order, each box tested against the points as they are then (get_points_in_box:
+ * margin 1e-1 on x and y, <= on all axes); box_slots (<= 256) bounds the boxes of one scene: a scene with more boxes, or
+ * with more alive boxes than draw_cap at a local op, gets status bit 4 and is written empty.
+ * info_in (batch, 4) int32 or NULL: the info of the pda_augment_paste call that made the input; column 2 and the status
+ * bits 2, 4, 8 are carried into info.  Output, out_cap / out_box_cap and info as for pda_augment (points never grow:
+ * n_total / m_total rows suffice); status bit 1: no box or no point left.
+ * workspace: pda_augment_steps_workspace_bytes(batch, n_cap, box_slots, n_ops) bytes, 256-byte aligned (-1: bad sizes).
+ * 2 * (world dropout ops) + 4 launches, no allocation, no host synchronisation. */
+int64_t pda_augment_steps_workspace_bytes(int batch, int64_t n_cap, int box_slots, int n_ops);
+int pda_augment_steps(const float *points, const int64_t *offsets, int64_t n_total, int batch, int c, int64_t n_cap,
+                      const float *boxes, const int64_t *box_offsets, int64_t m_total, const int32_t *ops, int n_ops,
+                      const double *scene_draws, const double *box_draws, int draw_cap, int box_slots,
+                      const int32_t *info_in, float *out_points, int64_t out_cap, int64_t *out_offsets, float *out_boxes,
+                      int64_t out_box_cap, int64_t *out_box_offsets, int32_t *info, void *workspace, pda_stream_t stream);
+
 /* ---- ONCE evaluation (csrc/once_eval.hip; the reference's once_eval get_evaluation_results on the device) ------------
  * Frames: GT boxes (n_gt_total, 7) float64 [x, y, z, dx, dy, dz, heading] with gt_name (n_gt_total) int32 name ids and
  * gt_offsets (n_frames + 1) int64; predictions of frame f are rows [pred_start[f], pred_start[f] + pred_count[f]) of

@@ -173,6 +173,13 @@ SIGNATURES = {
     "pda_augment": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp,
                     _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, ctypes.POINTER(_f), ctypes.c_int64, _vp, ctypes.c_int64,
                     _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp],
+    "pda_augment_paste": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp,
+                          _vp, _vp, _i, _vp, _vp, _vp, _i, ctypes.POINTER(_f), ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp,
+                          ctypes.c_int64, _vp, _vp, _vp, _vp],
+    "pda_augment_steps_workspace_bytes": [_i, ctypes.c_int64, _i, _i],
+    "pda_augment_steps": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp, _vp, ctypes.c_int64,
+                          ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _i, _i, _vp, _vp, ctypes.c_int64, _vp, _vp,
+                          ctypes.c_int64, _vp, _vp, _vp, _vp],
     "pda_once_eval_workspace_bytes": [_i, ctypes.c_int64, _i],
     "pda_once_eval_iou": [ctypes.POINTER(OnceFrames), _i, _vp, _vp, _vp],
     "pda_once_eval_accumulate": [ctypes.POINTER(OnceFrames), _vp, _vp, _i, _i, ctypes.POINTER(ctypes.c_double), _i, _vp, _vp,
@@ -240,6 +247,7 @@ def load():
     lib.pda_sa_xyz_grad_scratch_bytes.restype = ctypes.c_int64
     lib.pda_input_stage_workspace_bytes.restype = ctypes.c_int64
     lib.pda_augment_workspace_bytes.restype = ctypes.c_int64
+    lib.pda_augment_steps_workspace_bytes.restype = ctypes.c_int64
     lib.pda_once_eval_workspace_bytes.restype = ctypes.c_int64
     lib.pda_kitti_eval_workspace_bytes.restype = ctypes.c_int64
     lib.pda_kitti_fov_filter_workspace_bytes.restype = ctypes.c_int64

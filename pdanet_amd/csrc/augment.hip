@@ -15,11 +15,14 @@
 //   ag_scan_kernel   (1)              : tile offsets per scene, the packed output offsets of points and boxes, info.
 //   ag_write_kernel  (tiles + ptiles + 1, B): stable ballot scatter of the kept points, the gather of the pasted object
 //                                       points, and the boxes, all through flip -> rotate -> scale (-> limit_period).
+// pda_augment_paste is the same four launches in front of the ordered step program (augment_steps.hip): the identity
+// transform, the boxes of class 0 kept, no limit_period.
 // The file is built with -ffp-contract=off: every product and sum below is a separately rounded float32 (or double)
 // operation, as in the reference's numpy / torch CPU code.
 #include "pda_common.h"
 #include "bev_overlap.h"
 #include "box_rec.h"
+#include "augment_xf.h"
 
 namespace pda {
 namespace {
@@ -55,6 +58,7 @@ struct Plan {
     const float* scale;       // (B)
     float ew[3];              // REMOVE_EXTRA_WIDTH
     int k;
+    int raw;                  // the paste-only form (pda_augment_paste): boxes of class 0 stay, no transform, no limit_period
 };
 
 struct Ws {
@@ -63,10 +67,6 @@ struct Ws {
     int32_t* pfx;             // (B, k + 1) pasted-point prefix of the accepted objects
     int32_t* tile;            // (B, tiles) kept points per tile, then their exclusive scan
 };
-
-__device__ __forceinline__ int rank_below(uint64_t ballot) {
-    return (int)__mbcnt_hi((uint32_t)(ballot >> 32), __mbcnt_lo((uint32_t)ballot, 0u));
-}
 
 __device__ __forceinline__ bool offsets_ok(const int64_t* off, int b, int64_t total) {
     const int64_t s = off[b], e = off[b + 1];
@@ -79,48 +79,14 @@ __device__ __forceinline__ bool object_ok(const Db& db, int id) {
     return s >= 0 && e >= s && e <= db.n_points && e - s <= (1 << 30);
 }
 
-// ---- the scene transform: flip -> rotate -> scale, each a separately rounded float32 operation ------------------------
-struct Xf {
-    int fx, fy, rot;
-    float c, s, a, sc;
-};
-
+// ---- the scene transform: flip -> rotate -> scale (augment_xf.h); the paste-only form is the identity ----------------
 __device__ __forceinline__ Xf xf_of(const Plan& p, int b) {
-    Xf t;
-    t.fx = p.flip[2 * b];
-    t.fy = p.flip[2 * b + 1];
-    const float a = (float)p.angle[b];       // the reference's rotation angle is a float32 tensor
-    t.rot = a != 0.f;                        // angle 0 = rotation disabled: an exact identity
-    t.a = a;
-    t.c = (float)cos((double)a);
-    t.s = (float)sin((double)a);
-    t.sc = p.scale[b];
-    return t;
+    if (p.raw) return xf_make(0, 0, 0.0, 1.f);
+    return xf_make(p.flip[2 * b], p.flip[2 * b + 1], p.angle[b], p.scale[b]);
 }
 
-// random_flip_along_x / _y, rotate_points_along_z ([x, y, z] times [[c, s, 0], [-s, c, 0], [0, 0, 1]]), global_scaling
-__device__ __forceinline__ void xf_point(const Xf& t, float& x, float& y, float& z) {
-    if (t.fx) y = -y;
-    if (t.fy) x = -x;
-    if (t.rot) {
-        const float nx = x * t.c + y * (-t.s), ny = x * t.s + y * t.c;
-        x = nx;
-        y = ny;
-    }
-    x = x * t.sc;
-    y = y * t.sc;
-    z = z * t.sc;
-}
-
-// the heading through the same steps, then limit_period(h, 0.5, 2 pi) as torch's separate float32 ops
-__device__ __forceinline__ float xf_heading(const Xf& t, float h) {
-    const float pi = 3.14159265358979323846f, two_pi = 6.28318530717958647692f;
-    if (t.fx) h = -h;
-    if (t.fy) h = -(h + pi);
-    if (t.rot) h = h + t.a;
-    const float q = h / two_pi + 0.5f;
-    return h - floorf(q) * two_pi;
-}
+// the heading: through the transform and limit_period, or as it is in the paste-only form
+__device__ __forceinline__ float heading_of(const Plan& p, const Xf& t, float h) { return p.raw ? h : xf_heading(t, h); }
 
 // the enlarged accepted boxes of scene b as CPU point-test records (margin 1e-2, no FMA)
 __device__ int stage_removal_boxes(const Db& db, const Plan& p, const Ws& ws, int b, BoxRec* rec) {
@@ -197,7 +163,7 @@ __global__ __launch_bounds__(256) void ag_select_kernel(const int64_t* __restric
         if (tid < ne) {
             const float* bx = boxes + (bs + e0 + tid) * 8;
             eb[tid] = make_box(bx);
-            keep += bx[7] != 0.f ? 1 : 0;
+            keep += (p.raw || bx[7] != 0.f) ? 1 : 0;
         }
         __syncthreads();
         for (int q = tid; q < K * ne; q += 256) {
@@ -384,7 +350,7 @@ __global__ __launch_bounds__(AG_TILE) void ag_write_kernel(const float* __restri
         for (int e0 = 0; e0 < m; e0 += AG_TILE) {
             const int e = e0 + tid;
             const float* bx = boxes + (bs + e) * 8;
-            const bool keep = e < m && bx[7] != 0.f;
+            const bool keep = e < m && (p.raw || bx[7] != 0.f);
             const uint64_t bk = __ballot(keep);
             const int w = wave_id();
             if (lane_id() == 0) wk[w] = __popcll(bk);
@@ -397,7 +363,7 @@ __global__ __launch_bounds__(AG_TILE) void ag_write_kernel(const float* __restri
                 float* o = ob + (int64_t)pos * 8;
                 o[0] = x; o[1] = y; o[2] = z;
                 o[3] = bx[3] * xf.sc; o[4] = bx[4] * xf.sc; o[5] = bx[5] * xf.sc;
-                o[6] = xf_heading(xf, bx[6]);
+                o[6] = heading_of(p, xf, bx[6]);
                 o[7] = bx[7];
             }
             __syncthreads();
@@ -414,7 +380,7 @@ __global__ __launch_bounds__(AG_TILE) void ag_write_kernel(const float* __restri
             float* o = ob + (int64_t)(n_keep + a) * 8;
             o[0] = x; o[1] = y; o[2] = z;
             o[3] = bx[3] * xf.sc; o[4] = bx[4] * xf.sc; o[5] = bx[5] * xf.sc;
-            o[6] = xf_heading(xf, bx[6]);
+            o[6] = heading_of(p, xf, bx[6]);
             o[7] = (float)db.cls[id];
         }
     }
@@ -435,8 +401,9 @@ PDA_API int64_t pda_augment_workspace_bytes(int batch, int64_t n_cap, int k) {
            pda::al256((int64_t)batch * pda::aug_tiles(n_cap) * 4);
 }
 
-PDA_API int pda_augment(const float* points, const int64_t* offsets, int64_t n_total, int batch, int c, int64_t n_cap,
-                        const float* boxes, const int64_t* box_offsets, int64_t m_total, const float* db_points,
+// pda_augment (raw = 0) and its paste-only form pda_augment_paste (raw = 1: no flip / angle / scale)
+static int augment_launch(const char* what, int raw, const float* points, const int64_t* offsets, int64_t n_total, int batch,
+                        int c, int64_t n_cap, const float* boxes, const int64_t* box_offsets, int64_t m_total, const float* db_points,
                         const int64_t* db_offsets, int64_t db_n_points, const float* db_boxes, const double* db_centre,
                         const int32_t* db_class, int n_obj, const int32_t* cand, const int32_t* cand_group,
                         const double* cand_dz, int k, const int32_t* flip, const double* angle, const float* scale,
@@ -445,16 +412,16 @@ PDA_API int pda_augment(const float* points, const int64_t* offsets, int64_t n_t
                         void* workspace, pda_stream_t stream) {
     PDA_REQUIRE(pda::aug_sizes_ok(batch, n_cap, k) && n_total >= 0 && c >= 3 && c <= 64 && m_total >= 0 && db_n_points >= 0 &&
                     n_obj >= 0 && paste_cap >= 0 && paste_cap <= (1 << 30) && out_cap >= 0 && out_box_cap >= 0,
-                "pda_augment: bad size: batch=%d n_total=%lld C=%d n_cap=%lld m_total=%lld db_points=%lld n_obj=%d K=%d "
+                "%s: bad size: batch=%d n_total=%lld C=%d n_cap=%lld m_total=%lld db_points=%lld n_obj=%d K=%d "
                 "paste_cap=%lld out_cap=%lld out_box_cap=%lld",
-                batch, (long long)n_total, c, (long long)n_cap, (long long)m_total, (long long)db_n_points, n_obj, k,
+                what, batch, (long long)n_total, c, (long long)n_cap, (long long)m_total, (long long)db_n_points, n_obj, k,
                 (long long)paste_cap, (long long)out_cap, (long long)out_box_cap);
     if (batch == 0) return PDA_OK;
-    PDA_REQUIRE(offsets && box_offsets && out_offsets && out_box_offsets && info && workspace && remove_extra_width && flip &&
-                    angle && scale && (points || n_total == 0) && (boxes || m_total == 0) && (out_points || out_cap == 0) &&
-                    (out_boxes || out_box_cap == 0) && (k == 0 || (cand && cand_group && cand_dz)) &&
+    PDA_REQUIRE(offsets && box_offsets && out_offsets && out_box_offsets && info && workspace && remove_extra_width &&
+                    (raw || (flip && angle && scale)) && (points || n_total == 0) && (boxes || m_total == 0) &&
+                    (out_points || out_cap == 0) && (out_boxes || out_box_cap == 0) && (k == 0 || (cand && cand_group && cand_dz)) &&
                     (n_obj == 0 || (db_offsets && db_boxes && db_centre && db_class)) && (db_points || db_n_points == 0),
-                "pda_augment: null pointer");
+                "%s: null pointer", what);
     const int tiles = (int)pda::aug_tiles(n_cap);
     const int ptiles = (int)pda::divup64(paste_cap, pda::AG_TILE);
     char* w = (char*)workspace;
@@ -468,7 +435,7 @@ PDA_API int pda_augment(const float* points, const int64_t* offsets, int64_t n_t
     ws.tile = (int32_t*)w;
     const pda::Db db{db_points, db_offsets, db_boxes, db_centre, db_class, db_n_points, n_obj};
     const pda::Plan p{cand, cand_group, cand_dz, flip, angle, scale,
-                      {remove_extra_width[0], remove_extra_width[1], remove_extra_width[2]}, k};
+                      {remove_extra_width[0], remove_extra_width[1], remove_extra_width[2]}, k, raw};
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(pda::ag_select_kernel, dim3((unsigned)batch), dim3(256), 0, st, offsets, n_total, n_cap, boxes, box_offsets,
                        m_total, db, p, paste_cap, ws);
@@ -479,5 +446,32 @@ PDA_API int pda_augment(const float* points, const int64_t* offsets, int64_t n_t
     hipLaunchKernelGGL(pda::ag_write_kernel, dim3((unsigned)(tiles + ptiles + 1), (unsigned)batch), dim3(pda::AG_TILE), 0, st,
                        points, offsets, c, boxes, box_offsets, db, p, tiles, ws, out_offsets, out_box_offsets, out_points,
                        out_boxes);
-    return pda::check_launch("pda_augment");
+    return pda::check_launch(what);
+}
+
+PDA_API int pda_augment(const float* points, const int64_t* offsets, int64_t n_total, int batch, int c, int64_t n_cap,
+                        const float* boxes, const int64_t* box_offsets, int64_t m_total, const float* db_points,
+                        const int64_t* db_offsets, int64_t db_n_points, const float* db_boxes, const double* db_centre,
+                        const int32_t* db_class, int n_obj, const int32_t* cand, const int32_t* cand_group,
+                        const double* cand_dz, int k, const int32_t* flip, const double* angle, const float* scale,
+                        const float* remove_extra_width, int64_t paste_cap, float* out_points, int64_t out_cap,
+                        int64_t* out_offsets, float* out_boxes, int64_t out_box_cap, int64_t* out_box_offsets, int32_t* info,
+                        void* workspace, pda_stream_t stream) {
+    return augment_launch("pda_augment", 0, points, offsets, n_total, batch, c, n_cap, boxes, box_offsets, m_total, db_points,
+                          db_offsets, db_n_points, db_boxes, db_centre, db_class, n_obj, cand, cand_group, cand_dz, k, flip,
+                          angle, scale, remove_extra_width, paste_cap, out_points, out_cap, out_offsets, out_boxes, out_box_cap,
+                          out_box_offsets, info, workspace, stream);
+}
+
+PDA_API int pda_augment_paste(const float* points, const int64_t* offsets, int64_t n_total, int batch, int c, int64_t n_cap,
+                              const float* boxes, const int64_t* box_offsets, int64_t m_total, const float* db_points,
+                              const int64_t* db_offsets, int64_t db_n_points, const float* db_boxes, const double* db_centre,
+                              const int32_t* db_class, int n_obj, const int32_t* cand, const int32_t* cand_group,
+                              const double* cand_dz, int k, const float* remove_extra_width, int64_t paste_cap,
+                              float* out_points, int64_t out_cap, int64_t* out_offsets, float* out_boxes, int64_t out_box_cap,
+                              int64_t* out_box_offsets, int32_t* info, void* workspace, pda_stream_t stream) {
+    return augment_launch("pda_augment_paste", 1, points, offsets, n_total, batch, c, n_cap, boxes, box_offsets, m_total,
+                          db_points, db_offsets, db_n_points, db_boxes, db_centre, db_class, n_obj, cand, cand_group, cand_dz, k,
+                          nullptr, nullptr, nullptr, remove_extra_width, paste_cap, out_points, out_cap, out_offsets, out_boxes,
+                          out_box_cap, out_box_offsets, info, workspace, stream);
 }

@@ -16,6 +16,11 @@ Randomness: `plan=` takes the draws the reference made (exact reproduction); oth
 seeded from torch's CPU generator, so torch.manual_seed makes a run reproducible.  The Generator's stream is not the
 reference's legacy np.random stream.
 
+A DATA_AUGMENTOR list that holds one of the six further steps -- random_world_translation, random_world_frustum_dropout,
+random_local_translation, random_local_rotation, random_local_scaling, random_local_frustum_dropout -- takes another
+path: the paste alone (pda_augment_paste), then every step in the order the yaml lists it as one ordered program on the
+device (csrc/augment_steps.hip, pda_augment_steps).  A list of only the four steps above takes the path above, unchanged.
+
 A scene the augmentor leaves without a box is only flagged (info[:, 3] bit 1): the reference's prepare_data draws
 another scene there, which a batch-level loader has to decide for itself.
 """
@@ -32,7 +37,19 @@ from .pointnet2_batch_cuda import F32, _call, _chk
 # info[:, 3] status bits (include/pda_train.h pda_augment)
 STATUS_NO_BOX, STATUS_BAD_OFFSETS, STATUS_OVER_CAP, STATUS_BAD_CAND = 1, 2, 4, 8
 MAX_CANDIDATES = 256
+MAX_SCENE_BOXES = 256            # boxes per scene (its own plus the candidates) on the program path
 _STEPS = ("gt_sampling", "random_world_flip", "random_world_rotation", "random_world_scaling")
+# the steps of the program path and the parameters each cannot run without
+_PROGRAM_STEPS = {"random_world_translation": ("NOISE_TRANSLATE_STD", "ALONG_AXIS_LIST"),
+                  "random_world_frustum_dropout": ("INTENSITY_RANGE", "DIRECTION"),
+                  "random_local_translation": ("LOCAL_TRANSLATION_RANGE", "ALONG_AXIS_LIST"),
+                  "random_local_rotation": ("LOCAL_ROT_ANGLE",),
+                  "random_local_scaling": ("LOCAL_SCALE_RANGE",),
+                  "random_local_frustum_dropout": ("INTENSITY_RANGE", "DIRECTION")}
+# op codes of pda_augment_steps (include/pda_train.h)
+OP_FLIP_X, OP_FLIP_Y, OP_ROT, OP_SCALE, OP_TRANS, OP_WDROP, OP_LTRANS, OP_LROT, OP_LSCALE, OP_LDROP = range(10)
+_AXES = {"x": 0, "y": 1, "z": 2}
+_DIRECTIONS = {"top": 0, "bottom": 1, "left": 2, "right": 3}
 
 
 def _get(cfg, key, default=None):
@@ -181,6 +198,11 @@ def _filter_by_min_points(db_infos, min_gt_points_list):
     return db_infos
 
 
+# plan key, op code, one draw per box (else one per scene)
+_PLAN_KEYS = (("translation", OP_TRANS, False), ("world_dropout", OP_WDROP, False), ("local_translation", OP_LTRANS, True),
+              ("local_rotation", OP_LROT, True), ("local_scaling", OP_LSCALE, True), ("local_dropout", OP_LDROP, True))
+
+
 class _Group:
     def __init__(self, name, num, class_id, length):
         self.name, self.num, self.class_id = name, num, class_id
@@ -189,8 +211,22 @@ class _Group:
 
 class DataAugmentor:
     """DATA_AUGMENTOR of a reference-shaped yaml (AUG_CONFIG_LIST minus DISABLE_AUG_LIST): gt_sampling,
-    random_world_flip, random_world_rotation and random_world_scaling, in the order the list gives.  Any other step
-    raises NotImplementedError; gt_sampling must come first (the kernel applies the transforms after the paste)."""
+    random_world_flip, random_world_rotation, random_world_scaling, random_world_translation,
+    random_world_frustum_dropout, random_local_translation, random_local_rotation, random_local_scaling and
+    random_local_frustum_dropout, in the order the list gives, each at most once; gt_sampling must come first (the
+    transforms follow the paste).  Any other step (random_image_flip, random_local_pyramid_aug) raises
+    NotImplementedError.
+
+    An entry of one of the last six steps that lacks a parameter the step needs cannot be run and raises
+    NotImplementedError naming the step and the key: NOISE_TRANSLATE_STD and ALONG_AXIS_LIST (world translation),
+    LOCAL_TRANSLATION_RANGE and ALONG_AXIS_LIST (local translation), LOCAL_ROT_ANGLE, LOCAL_SCALE_RANGE, INTENSITY_RANGE
+    and DIRECTION (both dropouts).
+
+    A list of only the first four steps runs as pda_augment (flip, rotation, scaling in that fixed place); a list with
+    one of the others runs the paste, then `program`: one op per step, axis or direction, in yaml order.
+
+    random_world_frustum_dropout: the reference drops the box rows but not their gt_names, so its own class mask no
+    longer fits once a box is dropped; here a dropped box goes together with its class."""
 
     def __init__(self, aug_cfg, class_names, database=None):
         self.class_names = list(class_names)
@@ -201,12 +237,16 @@ class DataAugmentor:
         self.rot_range, self.rot_prob = None, 1.0
         self.scale_range, self.scale_prob = None, 1.0
         seen = []
+        steps = []                       # (op code, arg, step name, its parameters), in yaml order
         for cfg in cfg_list:
             name = cfg['NAME']
             if name in disabled:
                 continue
-            if name not in _STEPS:
+            if name not in _STEPS and name not in _PROGRAM_STEPS:
                 raise NotImplementedError("DATA_AUGMENTOR step %r has no device implementation" % name)
+            for key in _PROGRAM_STEPS.get(name, ()):
+                if key not in cfg:
+                    raise NotImplementedError("DATA_AUGMENTOR step %r cannot run without %s" % (name, key))
             if name in seen:
                 raise NotImplementedError("DATA_AUGMENTOR step %r appears twice" % name)
             if name == 'gt_sampling' and seen:
@@ -219,13 +259,48 @@ class DataAugmentor:
                 if any(a not in ('x', 'y') for a in self.flip_axes):
                     raise ValueError("random_world_flip takes the axes 'x' and 'y'")
                 self.flip_prob = float(_get(cfg, 'ENABLE_PROB', 0.5))
+                steps += [(OP_FLIP_X if a == 'x' else OP_FLIP_Y, 0, name, None) for a in self.flip_axes]
             elif name == 'random_world_rotation':
                 r = cfg['WORLD_ROT_ANGLE']
                 self.rot_range = [float(r[0]), float(r[1])] if isinstance(r, (list, tuple)) else [-float(r), float(r)]
                 self.rot_prob = float(_get(cfg, 'ENABLE_PROB', 1.0))
-            else:
+                steps.append((OP_ROT, 0, name, None))
+            elif name == 'random_world_scaling':
                 self.scale_range = [float(x) for x in cfg['WORLD_SCALE_RANGE']]
                 self.scale_prob = float(_get(cfg, 'ENABLE_PROB', 1.0))
+                steps.append((OP_SCALE, 0, name, None))
+            elif name in ('random_world_translation', 'random_local_translation'):
+                axes = list(cfg['ALONG_AXIS_LIST'])
+                if any(a not in _AXES for a in axes):
+                    raise ValueError("%s takes the axes 'x', 'y' and 'z'" % name)
+                if name == 'random_world_translation':
+                    std = float(cfg['NOISE_TRANSLATE_STD'])
+                    if std != 0:                 # the reference returns before any draw
+                        steps += [(OP_TRANS, _AXES[a], name, std) for a in axes]
+                else:
+                    r = [float(x) for x in cfg['LOCAL_TRANSLATION_RANGE']]
+                    steps += [(OP_LTRANS, _AXES[a], name, r) for a in axes]
+            elif name == 'random_local_rotation':
+                r = cfg['LOCAL_ROT_ANGLE']
+                r = [float(r[0]), float(r[1])] if isinstance(r, (list, tuple)) else [-float(r), float(r)]
+                steps.append((OP_LROT, 0, name, r))
+            elif name == 'random_local_scaling':
+                r = [float(x) for x in cfg['LOCAL_SCALE_RANGE']]
+                if r[1] - r[0] >= 1e-3:          # the reference skips the step as a whole, without a draw
+                    steps.append((OP_LSCALE, 0, name, r))
+            else:
+                dirs = list(cfg['DIRECTION'])
+                if any(d not in _DIRECTIONS for d in dirs):
+                    raise ValueError("%s takes the directions 'top', 'bottom', 'left' and 'right'" % name)
+                r = [float(x) for x in cfg['INTENSITY_RANGE']]
+                code = OP_WDROP if name == 'random_world_frustum_dropout' else OP_LDROP
+                steps += [(code, _DIRECTIONS[d], name, r) for d in dirs]
+        # the ordered program, or None: a list of the four first steps alone keeps the pda_augment path
+        self.program = steps if any(n in _PROGRAM_STEPS for n in seen) else None
+        if self.program is not None and sum(1 for st in steps if st[0] == OP_WDROP) > 4:
+            raise ValueError("random_world_frustum_dropout takes at most four directions")
+        if self.program is not None and len(steps) > 32:
+            raise ValueError("more than 32 ops in the DATA_AUGMENTOR program")
         self.database = database
         self.groups, self.limit_whole_scene, self.use_road_plane = [], False, False
         self.remove_extra_width = np.zeros(3, np.float32)
@@ -276,7 +351,11 @@ class DataAugmentor:
 
     def make_plan(self, gt_classes, rng=None):
         """The draws of one batch from a numpy Generator (default: seeded from torch's CPU generator): gt_sampling's
-        permutations, then per scene flip x / flip y, rotation, scaling, each behind its ENABLE_PROB."""
+        permutations, then per scene flip x / flip y, rotation, scaling, each behind its ENABLE_PROB.  On the program
+        path also: translation (B, axes) normal(0, NOISE_TRANSLATE_STD), world_dropout (B, directions), and for the local
+        steps one row of D draws per scene and sub-step -- local_translation (B, axes, D), local_rotation (B, D),
+        local_scaling (B, D), local_dropout (B, directions, D) -- with D = the most boxes a scene can hold (its own plus
+        its candidates): how many survive the collision test is known on the device only, and the draws are i.i.d."""
         if rng is None:
             rng = np.random.default_rng(int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
         B = len(gt_classes)
@@ -296,7 +375,67 @@ class DataAugmentor:
             if self.scale_range is not None and self.scale_range[1] - self.scale_range[0] >= 1e-3 and rng.random() < self.scale_prob:
                 scl[b] = np.float32(rng.uniform(self.scale_range[0], self.scale_range[1]))
         plan.update(flip_x=fx, flip_y=fy, angle=ang, scale=scl)
+        if self.program is not None:
+            cand = plan.get('cand') or [()] * B
+            D = max([len(np.asarray(gt_classes[b]).reshape(-1)) + len(cand[b]) for b in range(B)] + [0])
+            for key, code, per_box in _PLAN_KEYS:
+                ops = [st for st in self.program if st[0] == code]
+                if not ops:
+                    continue
+                shape = (B, len(ops), D) if per_box else (B, len(ops))
+                if code == OP_TRANS:
+                    val = rng.normal(0.0, ops[0][3], shape)
+                else:
+                    val = rng.uniform(ops[0][3][0], ops[0][3][1], shape)
+                plan[key] = val[:, 0] if code in (OP_LROT, OP_LSCALE) else val
         return plan
+
+    def _program_draws(self, plan, B, fx, fy, angle, scale):
+        """The plan as pda_augment_steps takes it: ops (n_ops, 2) int32, scene_draws (B, n_ops) float64 and box_draws
+        (B, local ops, D) float64, draw j of a row for the j-th box alive at that op."""
+        n_ops = len(self.program)
+        ops = np.array([[st[0], st[1]] for st in self.program], np.int32).reshape(n_ops, 2)
+        scene = np.zeros((B, n_ops), np.float64)
+        local = [i for i, st in enumerate(self.program) if st[0] >= OP_LTRANS]
+        rows = {}
+        for key, code, per_box in _PLAN_KEYS:
+            at = [i for i, st in enumerate(self.program) if st[0] == code]
+            if not at:
+                continue
+            if key not in plan:
+                raise ValueError("the plan lacks %r" % key)
+            val = plan[key]
+            if len(val) != B:
+                raise ValueError("plan[%r] needs one entry per scene" % key)
+            for b in range(B):
+                row = val[b]
+                if per_box:
+                    sub = [row] if len(at) == 1 and np.ndim(row) == 1 and not isinstance(row, (list, tuple)) else list(row)
+                    if len(sub) != len(at):
+                        raise ValueError("plan[%r][%d] needs %d rows of draws" % (key, b, len(at)))
+                    for i, r in zip(at, sub):
+                        rows[(b, i)] = np.asarray(r, np.float64).reshape(-1)
+                else:
+                    r = np.asarray(row, np.float64).reshape(-1)
+                    if len(r) != len(at):
+                        raise ValueError("plan[%r][%d] needs %d draws" % (key, b, len(at)))
+                    scene[b, at] = r
+        for i, st in enumerate(self.program):
+            if st[0] == OP_FLIP_X:
+                scene[:, i] = fx
+            elif st[0] == OP_FLIP_Y:
+                scene[:, i] = fy
+            elif st[0] == OP_ROT:
+                scene[:, i] = angle
+            elif st[0] == OP_SCALE:
+                scene[:, i] = scale.astype(np.float64)
+        D = max([len(r) for r in rows.values()] + [0])
+        if D > MAX_SCENE_BOXES:
+            raise ValueError("more than %d draws in one row of a local step" % MAX_SCENE_BOXES)
+        box = np.zeros((B, max(len(local), 1), max(D, 1)), np.float64)
+        for (b, i), r in rows.items():
+            box[b, local.index(i), :len(r)] = r
+        return ops, scene, box, D
 
     def _mv_height(self, ids, road_plane, calib):
         """put_boxes_on_road_planes for the candidate boxes (each row on its own, so every candidate gets the shift
@@ -317,7 +456,14 @@ class DataAugmentor:
         (class_ids(gt_names, CLASS_NAMES): 0 = a name outside CLASS_NAMES).
         plan: dict(cand=, cand_group=, flip_x=, flip_y=, angle=, scale=) -- cand / cand_group per scene (database ids
         in the order the sampler tried them, their group index); flip_x / flip_y 0/1, angle (0 = no rotation), scale
-        (1 = no scaling) per scene.  None: drawn by make_plan(gt_classes, rng), which advances the sampler.
+        (1 = no scaling) per scene.  On the program path also, per scene: translation (one offset per axis of
+        random_world_translation's ALONG_AXIS_LIST, in list order), world_dropout (one intensity per DIRECTION), and for
+        the local steps rows of per-box draws -- local_translation (axes, n), local_rotation (n), local_scaling (n),
+        local_dropout (directions, n); rows may differ in length between scenes and sub-steps.  Draw j of a row belongs
+        to the j-th box alive at that sub-step, in order (the scene's own boxes, then the accepted candidates, minus what
+        a world dropout removed): the order in which the reference consumes np.random.uniform.  A scene with more alive
+        boxes than draws in a row, or more than 256 boxes, is flagged (status 4) and written empty.
+        None: drawn by make_plan(gt_classes, rng), which advances the sampler.
         road_planes / calib: per scene, required by USE_ROAD_PLANE (the reference's road_plane [a, b, c, d] and a
         calibration with lidar_to_rect / rect_to_lidar).
         check: read info once and raise ValueError on malformed input (bad offsets, over capacity, a bad candidate).
@@ -403,6 +549,9 @@ class DataAugmentor:
                       np.concatenate([[0], np.cumsum([len(g) for g in bl])]).astype(np.int64),
                       np.concatenate(arrs, 0) if n_total else np.zeros((0, C), np.float32),
                       np.concatenate(bl, 0) if m_total else np.zeros((0, 7), np.float32)]
+        if self.program is not None:
+            ops, scene_draws, box_draws, D = self._program_draws(plan, B, fx, fy, angle, scale)
+            parts += [scene_draws, box_draws]
         sizes_b = [p.nbytes for p in parts]
         starts = np.concatenate([[0], np.cumsum([(s + 7) // 8 * 8 for s in sizes_b])]).astype(np.int64)
         host = torch.empty((max(int(starts[-1]), 8),), dtype=torch.uint8, pin_memory=True)
@@ -439,6 +588,28 @@ class DataAugmentor:
                    db.classes.data_ptr() if db.n_obj else None, db.n_obj)
         else:
             dbp = (None, None, 0, None, None, None, 0)
+        if self.program is not None:
+            _call("pda_augment_paste", pts, _chk(pts, "points", F32) if n_total else None, _chk(offs, "offsets", torch.int64), n_total,
+                  B, C, n_cap, bxs.data_ptr() if m_total else None, _chk(boffs, "box_offsets", torch.int64), m_total, *dbp,
+                  d_cand.data_ptr() if K else None, d_grp.data_ptr() if K else None, d_dz.data_ptr() if K else None, K,
+                  self._rew_c, paste_cap, out.data_ptr(), out_cap, out_offs.data_ptr(), out_boxes.data_ptr(), box_cap,
+                  out_boffs.data_ptr(), info.data_ptr(), ws.data_ptr())
+            # the pasted scenes through the ordered program
+            n_ops = len(self.program)
+            slots = min(MAX_SCENE_BOXES, max([len(c) + int((cand[b] >= 0).sum()) for b, c in enumerate(cls_rows)] + [0]))
+            ws_bytes = lib.pda_augment_steps_workspace_bytes(B, n_cap + paste_cap, slots, n_ops)
+            if ws_bytes < 0:
+                raise ValueError("batch %d / n_cap %d / %d ops out of range" % (B, n_cap + paste_cap, n_ops))
+            ws2 = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+            out2, out_boxes2 = torch.empty_like(out), torch.empty_like(out_boxes)
+            out_offs2, out_boffs2, info2 = torch.empty_like(out_offs), torch.empty_like(out_boffs), torch.empty_like(info)
+            _call("pda_augment_steps", out, out.data_ptr(), out_offs.data_ptr(), out_cap, B, C, n_cap + paste_cap,
+                  out_boxes.data_ptr(), out_boffs.data_ptr(), box_cap, ops.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n_ops,
+                  views[-2].data_ptr(), views[-1].data_ptr(), D, slots, info.data_ptr(), out2.data_ptr(), out_cap,
+                  out_offs2.data_ptr(), out_boxes2.data_ptr(), box_cap, out_boffs2.data_ptr(), info2.data_ptr(), ws2.data_ptr())
+            if check:
+                self._check(info2.cpu())
+            return (out2, out_offs2, n_cap + paste_cap), (out_boxes2, out_boffs2), info2
         _call("pda_augment", pts, _chk(pts, "points", F32) if n_total else None, _chk(offs, "offsets", torch.int64), n_total, B, C,
               n_cap, bxs.data_ptr() if m_total else None, _chk(boffs, "box_offsets", torch.int64), m_total, *dbp,
               d_cand.data_ptr() if K else None, d_grp.data_ptr() if K else None, d_dz.data_ptr() if K else None, K,
@@ -454,7 +625,7 @@ class DataAugmentor:
             if status & STATUS_BAD_OFFSETS:
                 raise ValueError("scene %d: offsets outside the packed points or boxes" % b)
             if status & STATUS_OVER_CAP:
-                raise ValueError("scene %d: more than n_cap points or an output capacity exceeded" % b)
+                raise ValueError("scene %d: more than n_cap points, an output capacity exceeded, or (program path) more boxes than the cap or than draws" % b)
             if status & STATUS_BAD_CAND:
                 raise ValueError("scene %d: a candidate id outside the database or candidate groups out of order" % b)
 
