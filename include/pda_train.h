@@ -686,6 +686,46 @@ int pda_gt_extract_write(const float *points, const int64_t *offsets, int64_t n_
                          const int64_t *obj_offsets, float *obj_points, int64_t out_cap, int32_t *info, void *workspace,
                          pda_stream_t stream);
 
+/* ---- voxel down-sampling (csrc/voxel_stage.hip; the reference's VoxelGeneratorWrapper.generate -- spconv's CPU
+ * point-to-voxel loop -- and DataProcessor.sample_points_by_voxels up to its sample_points call) --------------------------------
+ * Scenes in the layout of pda_input_stage: points (n_total, C >= 3), offsets (batch + 1) int64, at most n_cap rows a scene.
+ * HOST arrays: range6 = [xmin, ymin, zmin, xmax, ymax, zmax], voxel_size3 = [vx, vy, vz], grid3 = the cells along x, y, z
+ * (int32; the caller rounds (range[3:6] - range[0:3]) / voxel_size as the reference does).  Each axis holds 1 .. 2^24 cells
+ * and the grid at most 2^32 - 1 cells (the cell key is 32 bits); a larger grid is refused before any launch.
+ * Per scene, over the points in order: c_j = floor((p_j - lo_j) / vs_j) in float32 with a correctly rounded division; a
+ * point with a c_j outside [0, grid_j) (or NaN) joins nothing; a cell met for the first time becomes the next voxel unless
+ * max_voxels voxels exist already (the point is skipped; later points of existing voxels still join); a voxel keeps its
+ * first max_points points (1 .. 64).  Voxels are numbered in order of first appearance.
+ * workspace: pda_voxel_workspace_bytes(batch, n_cap, max_voxels, max_points) bytes, 8-byte aligned (-1: bad sizes); it holds
+ * a hash table of 2^ceil(log2(2 n_cap)) 64-bit entries a scene.  No host synchronisation, no float atomics: the grids depend on
+ * batch, n_cap and max_voxels only (graph-capturable) and two runs give the same bits.
+ *
+ * pda_voxelize: voxels (batch, max_voxels, max_points, C) zero-padded, coords (batch, max_voxels, 3) int32 (z, y, x),
+ * num_points_per_voxel (batch, max_voxels) int32, num_voxels (batch) int32 (-1: the scene's offsets are unusable or it holds
+ * more than n_cap rows). */
+int64_t pda_voxel_workspace_bytes(int batch, int64_t n_cap, int max_voxels, int max_points);
+int pda_voxelize(const float *points, const int64_t *offsets, int64_t n_total, int batch, int c, int64_t n_cap,
+                 const float *range6, const float *voxel_size3, const int32_t *grid3, int max_voxels, int max_points,
+                 float *voxels, int32_t *coords, int32_t *num_points_per_voxel, int32_t *num_voxels, void *workspace,
+                 pda_stream_t stream);
+/* pda_voxel_sample: [mask_xy: keep xmin <= x <= xmax and ymin <= y <= ymax, z not tested] -> [shuffle: shuffled[s] =
+ * masked[perm0[s]]] -> voxelize -> one row a voxel, in voxel order: its first point bit for bit (mean_vfe == 0), or
+ * (float)((double)sum / (double)count) per column with sum = the float32 sum over the voxel's max_points slots in slot order
+ * (mean_vfe == 1; numpy's voxels.sum(axis=1) / num_points).
+ * The shuffle (shuffle == 1): explicit mode takes perm0, ragged int32 with perm0_offsets (batch + 1) int64 into its
+ * perm0_total entries, scene b's slice a permutation of [0, n_masked_b); seeded mode (perm0 == perm0_offsets == NULL) draws
+ * a keyed bijection of [0, n_masked_b) from `seed`.
+ * out_points (out_cap >= batch * min(n_cap, max_voxels), C): the scenes' rows back to back; out_offsets (batch + 1) int64.
+ * info (batch, 4) int32 = [n_masked, n_in_grid, n_voxels_before_cap, status]; status bits: 1 no voxel, 2 offsets outside
+ * [0, n_total], 4 more than n_cap rows, 8 a bad draw (the perm0 slice has another length than n_masked or an entry outside
+ * [0, n_masked)) -- 2, 4, 8: the scene is written empty --, 16 more than max_voxels cells were occupied (not an error: the
+ * reference caps silently). */
+int pda_voxel_sample(const float *points, const int64_t *offsets, int64_t n_total, int batch, int c, int64_t n_cap,
+                     const float *range6, const float *voxel_size3, const int32_t *grid3, int mask_xy, int max_voxels,
+                     int max_points, int mean_vfe, int shuffle, const int32_t *perm0, const int64_t *perm0_offsets,
+                     int64_t perm0_total, uint64_t seed, float *out_points, int64_t out_cap, int64_t *out_offsets,
+                     int32_t *info, void *workspace, pda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

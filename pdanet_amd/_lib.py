@@ -200,6 +200,12 @@ SIGNATURES = {
     "pda_gt_extract_count": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp],
     "pda_gt_extract_write": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp,
                              ctypes.c_int64, _vp, _vp, _vp],
+    "pda_voxel_workspace_bytes": [_i, ctypes.c_int64, _i, _i],
+    "pda_voxelize": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, ctypes.POINTER(_f), ctypes.POINTER(_f),
+                     ctypes.POINTER(ctypes.c_int32), _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pda_voxel_sample": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, ctypes.POINTER(_f), ctypes.POINTER(_f),
+                         ctypes.POINTER(ctypes.c_int32), _i, _i, _i, _i, _i, _vp, _vp, ctypes.c_int64, ctypes.c_uint64, _vp,
+                         ctypes.c_int64, _vp, _vp, _vp, _vp],
     # include/pda_pointnet2_stack.h
     "pda_stack_ball_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     "pda_stack_group_points": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -252,6 +258,7 @@ def load():
     lib.pda_kitti_eval_workspace_bytes.restype = ctypes.c_int64
     lib.pda_kitti_fov_filter_workspace_bytes.restype = ctypes.c_int64
     lib.pda_gt_extract_workspace_bytes.restype = ctypes.c_int64
+    lib.pda_voxel_workspace_bytes.restype = ctypes.c_int64
     lib.pda_abi_version.restype = _i
     lib.pda_last_error.restype = ctypes.c_char_p
     lib.pda_fp_contract_mode.restype = _i

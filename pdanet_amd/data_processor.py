@@ -24,10 +24,12 @@ import torch
 
 from . import _lib
 from .pointnet2_batch_cuda import F32, _call, _chk
+from .voxel_utils import VoxelSpec
 
-# input_info[:, 3] status bits (include/pda_train.h pda_input_stage)
-STATUS_EMPTY, STATUS_BAD_OFFSETS, STATUS_OVER_CAP, STATUS_BAD_DRAW = 1, 2, 4, 8
+# input_info[:, 3] status bits (include/pda_train.h pda_input_stage); voxel_info[:, 3] adds STATUS_VOXEL_CAP (pda_voxel_sample)
+STATUS_EMPTY, STATUS_BAD_OFFSETS, STATUS_OVER_CAP, STATUS_BAD_DRAW, STATUS_VOXEL_CAP = 1, 2, 4, 8, 16
 _STEPS = ("mask_points_and_boxes_outside_range", "sample_points", "shuffle_points")
+_VOXEL_STEPS = ("mask_points_and_boxes_outside_range", "shuffle_points", "sample_points_by_voxels")
 
 
 def _get(cfg, key, default=None):
@@ -36,7 +38,8 @@ def _get(cfg, key, default=None):
 
 class DataProcessor:
     """DATA_PROCESSOR of a reference-shaped yaml: mask_points_and_boxes_outside_range, sample_points and shuffle_points,
-    in this order (each optional except sample_points).  Anything else raises NotImplementedError."""
+    in this order (each optional except sample_points), or mask_points_and_boxes_outside_range, shuffle_points and
+    sample_points_by_voxels in this order (each optional except the last).  Anything else raises NotImplementedError."""
 
     def __init__(self, processor_cfg, point_cloud_range, training, num_point_features):
         self.point_cloud_range = np.asarray(point_cloud_range, dtype=np.float32)
@@ -47,14 +50,17 @@ class DataProcessor:
         self.num_point_features = int(num_point_features)
         self.mask_points, self.remove_outside_boxes, self.min_num_corners = False, False, 1
         self.num_points, self.shuffle = None, False
+        self.voxel, self.sample_type, self.shuffle_first = None, None, False
+        for cfg in processor_cfg:
+            if cfg['NAME'] not in _STEPS + _VOXEL_STEPS:
+                raise NotImplementedError("DATA_PROCESSOR step %r has no device implementation" % cfg['NAME'])
+        steps = _VOXEL_STEPS if any(cfg['NAME'] == 'sample_points_by_voxels' for cfg in processor_cfg) else _STEPS
         last = -1
         for cfg in processor_cfg:
             name = cfg['NAME']
-            if name not in _STEPS:
-                raise NotImplementedError("DATA_PROCESSOR step %r has no device implementation" % name)
-            if _STEPS.index(name) <= last:
-                raise NotImplementedError("DATA_PROCESSOR steps must come in the order %s" % (_STEPS,))
-            last = _STEPS.index(name)
+            if name not in steps or steps.index(name) <= last:
+                raise NotImplementedError("DATA_PROCESSOR steps must come in the order %s" % (steps,))
+            last = steps.index(name)
             if name == 'mask_points_and_boxes_outside_range':
                 self.mask_points = True
                 self.remove_outside_boxes = bool(_get(cfg, 'REMOVE_OUTSIDE_BOXES', False)) and self.training
@@ -66,12 +72,28 @@ class DataProcessor:
                                      "number of points in every scene")
                 if self.num_points < 1:
                     raise ValueError("sample_points NUM_POINTS must be positive")
+            elif name == 'sample_points_by_voxels':
+                self.num_points = int(cfg['NUM_POINTS'][self.mode])
+                if self.num_points == -1:
+                    raise ValueError("sample_points_by_voxels NUM_POINTS == -1 (dynamic voxelization) keeps ragged scenes: the "
+                                     "backbone needs the same number of points in every scene")
+                if self.num_points < 1:
+                    raise ValueError("sample_points_by_voxels NUM_POINTS must be positive")
+                self.sample_type = str(_get(cfg, 'SAMPLE_TYPE', 'raw'))
+                if self.sample_type not in ('raw', 'mean_vfe'):
+                    # the reference treats every other value as 'raw'; a typo should not pass silently
+                    raise ValueError("sample_points_by_voxels SAMPLE_TYPE must be 'raw' or 'mean_vfe'")
+                self.voxel = VoxelSpec(self.point_cloud_range, cfg['VOXEL_SIZE'], cfg['MAX_POINTS_PER_VOXEL'],
+                                       cfg['MAX_NUMBER_OF_VOXELS'][self.mode])
+            elif steps is _VOXEL_STEPS:
+                self.shuffle_first = bool(cfg['SHUFFLE_ENABLED'][self.mode])
             else:
                 self.shuffle = bool(cfg['SHUFFLE_ENABLED'][self.mode])
         if self.num_points is None:
             raise ValueError("DATA_PROCESSOR needs a sample_points step (the backbone needs equal scene sizes)")
         inf = np.float32(np.inf)
-        self._point_range = (self.point_cloud_range if self.mask_points
+        # in the voxel chain the mask runs in the voxel stage, in front of the shuffle
+        self._point_range = (self.point_cloud_range if self.mask_points and self.voxel is None
                              else np.array([-inf, -inf, -inf, inf, inf, inf], np.float32))
         self._range_c = (ctypes.c_float * 6)(*self._point_range.tolist())
 
@@ -85,13 +107,18 @@ class DataProcessor:
         the batch, as collate_batch does (that needs a host read).
         seed / draws: see the module docstring; draws = dict(pick=, perm1=, perm2=) with one int array per scene (or a
         (B, k) array): pick = the ranks sample_points draws (into the near list in case A, the masked list in case B,
-        the extra draws in case C), perm1 = its shuffle, perm2 = shuffle_points' permutation (when it is enabled).
+        the extra draws in case C), perm1 = its shuffle, perm2 = shuffle_points' permutation (when it is enabled).  In the
+        voxel chain the ranks refer to the voxel rows, and perm0 = the leading shuffle_points' permutation of the masked
+        points (when it is enabled), one int array of that length per scene.
         check: read batch_dict['input_info'] once and raise ValueError on a scene with no point in range (the reference
         raises there), on more kept boxes than max_gt, or on a malformed input.  With max_gt given and check=False
         nothing is read back; such scenes are then only flagged: input_info[b] = [n_masked, n_far, n_kept_boxes,
         status], status bit 1 = empty scene (its rows are [b, 0, ...]), kept > max_gt = boxes dropped beyond the
         capacity, -1 kept / status bits 2, 4, 8 = bad offsets, more than n_cap points, a draw out of range.
-        Returns {'batch_size', 'points' (B * NUM_POINTS, 1 + C), 'gt_boxes' (when boxes were given), 'input_info'}."""
+        Returns {'batch_size', 'points' (B * NUM_POINTS, 1 + C), 'gt_boxes' (when boxes were given), 'input_info'}; the
+        voxel chain adds 'voxel_info' (B, 4) int32 = [n_masked, n_in_grid, n_voxels_before_cap, status] with the same status
+        bits (1 = no voxel) and 16 = MAX_NUMBER_OF_VOXELS was reached, which is not an error (the reference caps silently);
+        input_info then counts voxel rows."""
         dev = torch.device(device) if device is not None else None
         pts, offs, n_cap, bxs, boffs, bmax = self._inputs(points, gt_boxes, dev)
         dev = pts.device
@@ -99,6 +126,11 @@ class DataProcessor:
         if C < 3:
             raise ValueError("points need at least x, y, z")
         lib = _lib.load()
+        if draws is None and seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())   # CPU generator: no device read
+        voxel_info = None
+        if self.voxel is not None:
+            pts, offs, n_cap, voxel_info = self._voxel_stage(pts, offs, n_cap, seed, draws)
         ws_bytes = lib.pda_input_stage_workspace_bytes(B, n_cap)
         if ws_bytes < 0:
             raise ValueError("batch %d / n_cap %d out of range" % (B, n_cap))
@@ -112,13 +144,13 @@ class DataProcessor:
             if self.shuffle:
                 perm2 = self._draw_rows(draws.get('perm2'), B, k, dev, 'perm2')
             seed = 0
-        elif seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())   # CPU generator: no device read
         _call("pda_input_stage", pts, _chk(pts, "points", F32), _chk(offs, "offsets", torch.int64), pts.shape[0], B, C, n_cap,
               self._range_c, k, pick.data_ptr() if pick is not None else None, perm1.data_ptr() if perm1 is not None else None,
               perm2.data_ptr() if perm2 is not None else None, ctypes.c_uint64(seed & (2 ** 64 - 1)), int(self.shuffle),
               out.data_ptr(), info.data_ptr(), ws.data_ptr())
         ret = {'batch_size': B, 'points': out, 'input_info': info}
+        if voxel_info is not None:
+            ret['voxel_info'] = voxel_info
         host_info = None
         if bxs is not None:
             cap = max_gt if max_gt is not None else bmax
@@ -133,8 +165,45 @@ class DataProcessor:
                 gt = gt[:, :max(cap, 0)].contiguous()
             ret['gt_boxes'] = gt
         if check:
+            if voxel_info is not None:
+                self._check_voxels(voxel_info.cpu())
             self._check(info.cpu() if host_info is None else host_info, max_gt if bxs is not None else None)
         return ret
+
+    def _voxel_stage(self, pts, offs, n_cap, seed, draws):
+        """pda_voxel_sample: -> the voxel rows (packed, offsets, their capacity a scene) and voxel_info."""
+        sp = self.voxel
+        dev = pts.device
+        B, C = offs.numel() - 1, pts.shape[1]
+        mean = self.sample_type == 'mean_vfe'
+        v_cap = min(n_cap, sp.max_voxels)
+        ws = sp.workspace(B, n_cap, sp.max_points if mean else 1, dev)
+        rows = torch.empty((B * v_cap, C), dtype=torch.float32, device=dev)
+        row_offs = torch.empty((B + 1,), dtype=torch.int64, device=dev)
+        info = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        perm0 = poffs = None
+        if draws is not None and self.shuffle_first:
+            per_scene = draws.get('perm0')
+            if per_scene is None or len(per_scene) != B:
+                raise ValueError("draws needs 'perm0' with one array per scene")
+            per_scene = [np.asarray(r.cpu() if isinstance(r, torch.Tensor) else r).reshape(-1).astype(np.int32) for r in per_scene]
+            poffs = torch.from_numpy(np.concatenate([[0], np.cumsum([r.size for r in per_scene])]).astype(np.int64)).to(dev)
+            perm0 = torch.from_numpy(np.concatenate(per_scene + [np.zeros(1, np.int32)])).to(dev)     # never empty
+        _call("pda_voxel_sample", pts, _chk(pts, "points", F32), _chk(offs, "offsets", torch.int64), pts.shape[0], B, C, n_cap,
+              sp.range_c, sp.vsize_c, sp.grid_c, int(self.mask_points), sp.max_voxels, sp.max_points if mean else 1, int(mean),
+              int(self.shuffle_first), perm0.data_ptr() if perm0 is not None else None,
+              poffs.data_ptr() if poffs is not None else None, perm0.numel() - 1 if perm0 is not None else 0,
+              ctypes.c_uint64((seed or 0) & (2 ** 64 - 1)), rows.data_ptr(), rows.shape[0], row_offs.data_ptr(), info.data_ptr(),
+              ws.data_ptr())
+        return rows, row_offs, v_cap, info
+
+    @staticmethod
+    def _check_voxels(info):
+        for b, (_, _, _, status) in enumerate(info.tolist()):
+            if status & STATUS_BAD_OFFSETS or status & STATUS_OVER_CAP:
+                raise ValueError("scene %d: offsets outside the packed points or more than n_cap points" % b)
+            if status & STATUS_BAD_DRAW:
+                raise ValueError("scene %d: perm0 is not a permutation of the masked points" % b)
 
     def _range_c_boxes(self):
         return (ctypes.c_float * 6)(*self.point_cloud_range.tolist())

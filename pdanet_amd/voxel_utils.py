@@ -1,0 +1,86 @@
+"""Point-to-voxel on the device (csrc/voxel_stage.hip, include/pda_train.h pda_voxelize): the reference's
+VoxelGeneratorWrapper (pcdet/datasets/processor/data_processor.py), i.e. the CPU path of spconv's point-to-voxel.
+
+The contract is the loop in include/pda_train.h: cells from floor((p - lo) / voxel_size) in float32, voxels numbered in
+order of first appearance, the first max_num_points_per_voxel points of a voxel kept in scene order, at most max_num_voxels
+voxels.  spconv itself was not run against it.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from .pointnet2_batch_cuda import F32, _call, _chk
+
+
+def grid_size(point_cloud_range, voxel_size):
+    """The cells along x, y, z as DataProcessor.sample_points_by_voxels computes them."""
+    pr = np.asarray(point_cloud_range)
+    return np.round((pr[3:6] - pr[0:3]) / np.array(voxel_size)).astype(np.int64)
+
+
+class VoxelSpec:
+    """The host-side arguments of the voxel entries: range, voxel size and grid as C arrays."""
+
+    def __init__(self, point_cloud_range, voxel_size, max_points, max_voxels):
+        self.point_cloud_range = np.asarray(point_cloud_range, dtype=np.float32)
+        self.voxel_size = np.asarray(voxel_size, dtype=np.float32)
+        if self.point_cloud_range.shape != (6,) or self.voxel_size.shape != (3,):
+            raise ValueError("point_cloud_range must hold 6 values and the voxel size 3")
+        self.grid = grid_size(point_cloud_range, voxel_size)
+        self.max_points, self.max_voxels = int(max_points), int(max_voxels)
+        if self.max_points < 1 or self.max_voxels < 1:
+            raise ValueError("MAX_POINTS_PER_VOXEL and MAX_NUMBER_OF_VOXELS must be positive")
+        if (self.grid < 1).any() or (self.grid > 2 ** 31 - 1).any():
+            raise ValueError("the voxel grid %s is empty or beyond int32" % (self.grid.tolist(),))
+        self.range_c = (ctypes.c_float * 6)(*self.point_cloud_range.tolist())
+        self.vsize_c = (ctypes.c_float * 3)(*self.voxel_size.tolist())
+        self.grid_c = (ctypes.c_int32 * 3)(*self.grid.tolist())
+
+    def workspace(self, batch, n_cap, max_points, dev):
+        nbytes = _lib.load().pda_voxel_workspace_bytes(batch, n_cap, self.max_voxels, max_points)
+        if nbytes < 0:
+            raise ValueError("batch %d / n_cap %d / max voxels %d / points per voxel %d out of range"
+                             % (batch, n_cap, self.max_voxels, max_points))
+        return torch.empty((max(nbytes, 8) // 8 + 1,), dtype=torch.int64, device=dev)       # 8-byte aligned
+
+
+class VoxelGenerator:
+    """VoxelGeneratorWrapper's signature.  generate(points) takes one scene; generate_batch takes packed scenes."""
+
+    def __init__(self, vsize_xyz, coors_range_xyz, num_point_features, max_num_points_per_voxel, max_num_voxels):
+        self.spec = VoxelSpec(coors_range_xyz, vsize_xyz, max_num_points_per_voxel, max_num_voxels)
+        self.num_point_features = int(num_point_features)
+
+    def generate_batch(self, points):
+        """points: (packed (n_total, C) float32, offsets (B + 1) int64, n_cap), device tensors.  Returns voxels (B, max_voxels,
+        max_points, C), coordinates (B, max_voxels, 3) int32 (z, y, x), num_points (B, max_voxels) int32 -- all zero beyond a
+        scene's voxel count -- and num_voxels (B) int32 (-1: unusable offsets).  Nothing is read back."""
+        pts, offs, n_cap = points
+        sp = self.spec
+        B, C, n_cap = offs.numel() - 1, pts.shape[1], max(int(n_cap), 1)
+        if C != self.num_point_features:
+            raise ValueError("points have %d columns, the generator was made for %d" % (C, self.num_point_features))
+        dev = pts.device
+        ws = sp.workspace(B, n_cap, sp.max_points, dev)
+        voxels = torch.empty((B, sp.max_voxels, sp.max_points, C), dtype=torch.float32, device=dev)
+        coords = torch.empty((B, sp.max_voxels, 3), dtype=torch.int32, device=dev)
+        num_points = torch.empty((B, sp.max_voxels), dtype=torch.int32, device=dev)
+        num_voxels = torch.empty((B,), dtype=torch.int32, device=dev)
+        _call("pda_voxelize", pts, _chk(pts, "points", F32), _chk(offs, "offsets", torch.int64), pts.shape[0], B, C, n_cap,
+              sp.range_c, sp.vsize_c, sp.grid_c, sp.max_voxels, sp.max_points, voxels.data_ptr(), coords.data_ptr(),
+              num_points.data_ptr(), num_voxels.data_ptr(), ws.data_ptr())
+        return voxels, coords, num_points, num_voxels
+
+    def generate(self, points):
+        """points (n, C), numpy or torch -> (voxels (V, max_points, C), coordinates (V, 3), num_points (V)) trimmed to the
+        voxel count V (one host read): numpy arrays for a numpy input, device tensors otherwise."""
+        as_numpy = not isinstance(points, torch.Tensor)
+        pts = torch.as_tensor(np.asarray(points, np.float32) if as_numpy else points)
+        pts = pts.to("cuda" if not pts.is_cuda else pts.device, torch.float32).contiguous()
+        offs = torch.tensor([0, pts.shape[0]], dtype=torch.int64).to(pts.device)
+        voxels, coords, num_points, num_voxels = self.generate_batch((pts, offs, pts.shape[0]))
+        v = int(num_voxels.item())
+        out = voxels[0, :v], coords[0, :v], num_points[0, :v]
+        return tuple(t.cpu().numpy() for t in out) if as_numpy else out
