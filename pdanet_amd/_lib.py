@@ -214,6 +214,12 @@ SIGNATURES = {
     "pda_stack_three_nn": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "pda_stack_three_interpolate": [_vp, _vp, _vp, _vp, _i, _i, _vp],
     "pda_stack_three_interpolate_grad": [_vp, _vp, _vp, _vp, _i, _i, _vp],
+    "pda_stack_voxel_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp],
+    "pda_stack_query_local_neighbor_idxs": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _i, _i, _i, _vp],
+    "pda_stack_three_nn_by_local_idxs": [_vp, _vp, _vp, _vp, _vp, _vp, _i, ctypes.c_int64, _i, _i, _vp],
+    "pda_stack_vector_pool": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i,
+                              _i, _i, _i, _vp],
+    "pda_stack_vector_pool_grad": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
 }
 INFO_SYMBOLS = ["pda_abi_version", "pda_last_error", "pda_fp_contract_mode", "pda_opt_n_threads",
                 "pda_fps_coop_timeouts", "pda_debug_fps_spin_limit", "pda_debug_fps_exchange_nonzero"]
