@@ -305,6 +305,35 @@ int pda_pda_geometry(const float *xyz, const float *new_xyz, const int32_t *idx,
  * entries of points in no box are NOT written (the caller pre-fills -1, roiaware_pool3d_utils.py:41). */
 int pda_points_in_boxes(const float *boxes, const float *pts, int32_t *box_idx_of_points, int b, int t,
                         int m, pda_stream_t stream);
+/* ---- RoI pooling of the two-stage heads (csrc/roi_pool.hip) ------------------------------------------
+ * roiaware_pool3d (roiaware_pool3d_kernel.cu:39-233): rois (N,7), pts (P,3), pts_feature (P,C) ->
+ * pts_idx_of_voxels (N,ox,oy,oz,K) int32 [slot 0: the voxel's count, capped at K-1; slots 1..count: its first K-1
+ * points in ascending point index], pooled_features (N,ox,oy,oz,C) and, for pool_method 0 (max), argmax
+ * (N,ox,oy,oz,C) int32 (-1 for an empty voxel, whose pooled_features are not written); pool_method 1 (avg) is the
+ * float32 sum in slot order divided once by the count and leaves argmax alone.  The caller zero-fills the three
+ * outputs.  A point is in a box by the test of pda_points_in_boxes; its voxel follows the reference's float32
+ * expressions, unsigned clamp included.  ox, oy, oz in 1..255, K >= 1.  Two runs give the same bits. */
+int pda_roiaware_pool3d_fwd(const float *rois, const float *pts, const float *pts_feature, int32_t *argmax,
+                            int32_t *pts_idx_of_voxels, float *pooled_features, int boxes_num, int pts_num,
+                            int channels, int max_pts_each_voxel, int out_x, int out_y, int out_z, int pool_method,
+                            pda_stream_t stream);
+/* roiaware_pool3d backward (:236-310): grad_in (P,C), zero-filled by the caller, += grad_out at argmax (max, -1
+ * skipped) or grad_out * (1 / max(count, 1)) at every slot's point (avg); float atomics.  Point indices outside
+ * [0, pts_num) are skipped. */
+int pda_roiaware_pool3d_bwd(const int32_t *pts_idx_of_voxels, const int32_t *argmax, const float *grad_out,
+                            float *grad_in, int boxes_num, int pts_num, int channels, int max_pts_each_voxel,
+                            int out_x, int out_y, int out_z, int pool_method, pda_stream_t stream);
+/* roipoint_pool3d (roipoint_pool3d_kernel.cu:38-165): xyz (B,P,3), boxes3d (B,M,7) already enlarged, pts_feature
+ * (B,P,C) -> pooled_features (B,M,S,3+C): the rows [x, y, z, features] of the first S points inside each box in
+ * ascending index, slot k >= cnt repeating slot k % cnt; pooled_empty_flag (B,M) int32 = 1 for a box without points,
+ * whose rows are not written.  The caller zero-fills both.  S <= 15360, B <= 65535. */
+int pda_roipoint_pool3d_fwd(const float *xyz, const float *boxes3d, const float *pts_feature, float *pooled_features,
+                            int32_t *pooled_empty_flag, int batch_size, int pts_num, int boxes_num, int channels,
+                            int sampled_pts_num, pda_stream_t stream);
+/* points_in_boxes_cpu (roiaware_pool3d.cpp:128-168) on the device: boxes (N,7), pts (P,3) -> mask (N,P) int32 of
+ * 0 / 1, every entry written; the host statement of the test: margin 1e-2, no FMA. */
+int pda_points_in_boxes_mask(const float *boxes, const float *pts, int32_t *mask, int boxes_num, int pts_num,
+                             pda_stream_t stream);
 /* The point-wise remainder of the IA-SSD head's target assignment (IASSD_head.py:132-277 after the two points_in_boxes
  * queries), one launch per point set: from in_box / in_ext (B, N) = index of the ground-truth box / enlarged box each point
  * lies in (-1: none) and gt_boxes (B, T, 8) [x y z dx dy dz heading class]:

@@ -145,6 +145,10 @@ SIGNATURES = {
     "pda_densitynet_bwd_unique": [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _i, _f, _vp],
     "pda_pda_geometry": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
     "pda_points_in_boxes": [_vp, _vp, _vp, _i, _i, _i, _vp],
+    "pda_roiaware_pool3d_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "pda_roiaware_pool3d_bwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "pda_roipoint_pool3d_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "pda_points_in_boxes_mask": [_vp, _vp, _vp, _i, _i, _vp],
     "pda_assign_point_targets": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "pda_sa_gaussian_mask": [_vp, _i, _i, _vp, _vp, _vp, ctypes.c_int64, _vp],
     "pda_head_assign_targets": [_vp, _i, _i, _vp, ctypes.POINTER(ctypes.c_float), _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],

@@ -41,4 +41,20 @@ __device__ __forceinline__ bool in_box_rec(const BoxRec& r, float x, float y, fl
     return (int)((double)fabsf(lx) < r.lim_x) & (int)((double)fabsf(ly) < r.lim_y);
 }
 
+// The same test, also handing out the local coordinates the RoI-aware pooling bins by (roiaware_pool3d_kernel.cu:52-66);
+// lx / ly are written only when the z test passes.
+template <bool FMA>
+__device__ __forceinline__ bool in_box_rec_local(const BoxRec& r, float x, float y, float z, float& lx, float& ly) {
+    if (fabsf(z - r.cz) > r.hz) return false;
+    const float sx = x - r.cx, sy = y - r.cy;
+    if (FMA) {
+        lx = __builtin_fmaf(sx, r.cosa, sy * (-r.sina));
+        ly = __builtin_fmaf(sx, r.sina, sy * r.cosa);
+    } else {
+        lx = sx * r.cosa + sy * (-r.sina);
+        ly = sx * r.sina + sy * r.cosa;
+    }
+    return (int)((double)fabsf(lx) < r.lim_x) & (int)((double)fabsf(ly) < r.lim_y);
+}
+
 }  // namespace pda

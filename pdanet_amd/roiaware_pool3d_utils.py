@@ -17,6 +17,42 @@ class roiaware_pool3d_cuda:  # noqa: N801  (the reference's extension module nam
               _chk(box_idx_of_points, "box_idx_of_points", I32), b, t, m)
         return 1
 
+    @staticmethod
+    def forward(rois, pts, pts_feature, argmax, pts_idx_of_voxels, pooled_features, pool_method):
+        """roiaware_pool3d.cpp:29-66: rois (N,7), pts (P,3), pts_feature (P,C); the three outputs zero-filled by the caller,
+        sizes taken from the tensors.  pool_method 0 max, 1 avg -> 1."""
+        n, p, c = rois.shape[0], pts.shape[0], pts_feature.shape[1]
+        ox, oy, oz, k = (int(v) for v in pts_idx_of_voxels.shape[1:5])
+        _numel_ok(rois, n * 7, "rois"); _numel_ok(pts, p * 3, "pts"); _numel_ok(pts_feature, p * c, "pts_feature")
+        _numel_ok(argmax, n * ox * oy * oz * c, "argmax"); _numel_ok(pooled_features, n * ox * oy * oz * c, "pooled_features")
+        _numel_ok(pts_idx_of_voxels, n * ox * oy * oz * k, "pts_idx_of_voxels")
+        _call("pda_roiaware_pool3d_fwd", pts_feature, _chk(rois, "rois", F32), _chk(pts, "pts", F32),
+              _chk(pts_feature, "pts_feature", F32), _chk(argmax, "argmax", I32), _chk(pts_idx_of_voxels, "pts_idx_of_voxels", I32),
+              _chk(pooled_features, "pooled_features", F32), n, p, c, k, ox, oy, oz, int(pool_method))
+        if p == 0 and int(pool_method) == 0:
+            argmax.fill_(-1)                       # the library leaves an empty problem alone; every voxel is empty
+        return 1
+
+    @staticmethod
+    def backward(pts_idx_of_voxels, argmax, grad_out, grad_in, pool_method):
+        """roiaware_pool3d.cpp:68-96: grad_in (P,C), zero-filled by the caller, receives the gradient -> 1."""
+        n, ox, oy, oz, k = (int(v) for v in pts_idx_of_voxels.shape)
+        c, p = int(grad_out.shape[4]), int(grad_in.shape[0])
+        _numel_ok(argmax, n * ox * oy * oz * c, "argmax"); _numel_ok(grad_out, n * ox * oy * oz * c, "grad_out")
+        _numel_ok(pts_idx_of_voxels, n * ox * oy * oz * k, "pts_idx_of_voxels"); _numel_ok(grad_in, p * c, "grad_in")
+        _call("pda_roiaware_pool3d_bwd", grad_out, _chk(pts_idx_of_voxels, "pts_idx_of_voxels", I32), _chk(argmax, "argmax", I32),
+              _chk(grad_out, "grad_out", F32), _chk(grad_in, "grad_in", F32), n, p, c, k, ox, oy, oz, int(pool_method))
+        return 1
+
+    @staticmethod
+    def points_in_boxes_cpu(boxes, pts, pts_indices):
+        """roiaware_pool3d.cpp:143-168 on the device: boxes (N,7), pts (P,3) -> pts_indices (N,P) int32 of 0 / 1 -> 1."""
+        n, p = boxes.shape[0], pts.shape[0]
+        _numel_ok(boxes, n * 7, "boxes"); _numel_ok(pts, p * 3, "pts"); _numel_ok(pts_indices, n * p, "pts_indices")
+        _call("pda_points_in_boxes_mask", pts, _chk(boxes, "boxes", F32), _chk(pts, "pts", F32),
+              _chk(pts_indices, "pts_indices", I32), n, p)
+        return 1
+
 
 def points_in_boxes_gpu(points, boxes):
     """
@@ -171,3 +207,79 @@ def head_corner_loss(box_preds, centers, cls_preds, gt, cls_labels, mean_size, b
               _chk(gb, "grad_box", F32), _chk(gc, "grad_centers", F32))
         return (out[0],), (gb, gc)
     return _ScaledGrad.apply(run, box_preds, centers)[0]
+
+
+# ---- RoI-aware pooling of the Part-A2 head (roiaware_pool3d_utils.py:9-107; csrc/roi_pool.hip) ---------------------------------
+def points_in_boxes_cpu(points, boxes):
+    """
+    Args:
+        points: (num_points, 3)
+        boxes: [x, y, z, dx, dy, dz, heading], (x, y, z) is the box center, each box DO NOT overlaps
+    Returns:
+        point_indices: (N, num_points)
+    The reference computes this on the host; here numpy input (or a CPU tensor) travels to the current device and the
+    result comes back as numpy (or to the input's device).  The test is the host statement: margin 1e-2, no FMA.
+    """
+    import numpy as np
+    assert boxes.shape[1] == 7
+    assert points.shape[1] == 3
+    is_numpy = isinstance(points, np.ndarray)
+    points = torch.from_numpy(points).float() if is_numpy else points
+    boxes = torch.from_numpy(boxes).float() if isinstance(boxes, np.ndarray) else boxes
+    home = points.device
+    dev = home if home.type == "cuda" else (boxes.device if boxes.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    point_indices = torch.zeros((boxes.shape[0], points.shape[0]), dtype=torch.int, device=dev)
+    roiaware_pool3d_cuda.points_in_boxes_cpu(boxes.to(dev).float().contiguous(), points.to(dev).float().contiguous(), point_indices)
+    return point_indices.cpu().numpy() if is_numpy else point_indices.to(home)
+
+
+class RoIAwarePool3d(torch.nn.Module):
+    def __init__(self, out_size, max_pts_each_voxel=128):
+        super().__init__()
+        self.out_size = out_size
+        self.max_pts_each_voxel = max_pts_each_voxel
+
+    def forward(self, rois, pts, pts_feature, pool_method='max'):
+        assert pool_method in ['max', 'avg']
+        return RoIAwarePool3dFunction.apply(rois, pts, pts_feature, self.out_size, self.max_pts_each_voxel, pool_method)
+
+
+class RoIAwarePool3dFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rois, pts, pts_feature, out_size, max_pts_each_voxel, pool_method):
+        """
+        Args:
+            rois: (N, 7) [x, y, z, dx, dy, dz, heading] (x, y, z) is the box center
+            pts: (npoints, 3)
+            pts_feature: (npoints, C)
+            out_size: int or tuple, like 7 or (7, 7, 7)
+            max_pts_each_voxel:
+            pool_method: 'max' or 'avg'
+        Returns:
+            pooled_features: (N, out_x, out_y, out_z, C)
+        """
+        assert rois.shape[1] == 7 and pts.shape[1] == 3
+        if isinstance(out_size, int):
+            out_x = out_y = out_z = out_size
+        else:
+            assert len(out_size) == 3
+            for k in range(3):
+                assert isinstance(out_size[k], int)
+            out_x, out_y, out_z = out_size
+        num_rois, num_channels, num_pts = rois.shape[0], pts_feature.shape[-1], pts.shape[0]
+        pooled_features = pts_feature.new_zeros((num_rois, out_x, out_y, out_z, num_channels))
+        argmax = pts_feature.new_zeros((num_rois, out_x, out_y, out_z, num_channels), dtype=torch.int)
+        pts_idx_of_voxels = pts_feature.new_zeros((num_rois, out_x, out_y, out_z, max_pts_each_voxel), dtype=torch.int)
+        pool_method = {'max': 0, 'avg': 1}[pool_method]
+        roiaware_pool3d_cuda.forward(rois.contiguous(), pts.contiguous(), pts_feature.contiguous(), argmax, pts_idx_of_voxels,
+                                     pooled_features, pool_method)
+        ctx.roiaware_pool3d_for_backward = (pts_idx_of_voxels, argmax, pool_method, num_pts, num_channels)
+        return pooled_features
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        """grad_out (N, out_x, out_y, out_z, C) -> grad_in (npoints, C) for pts_feature, None for the other inputs"""
+        pts_idx_of_voxels, argmax, pool_method, num_pts, num_channels = ctx.roiaware_pool3d_for_backward
+        grad_in = grad_out.new_zeros((num_pts, num_channels))
+        roiaware_pool3d_cuda.backward(pts_idx_of_voxels, argmax, grad_out.contiguous(), grad_in, pool_method)
+        return None, None, grad_in, None, None, None
