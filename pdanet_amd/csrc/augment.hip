@@ -20,6 +20,7 @@
 // The file is built with -ffp-contract=off: every product and sum below is a separately rounded float32 (or double)
 // operation, as in the reference's numpy / torch CPU code.
 #include "pda_common.h"
+#include "ragged_scene.h"
 #include "bev_overlap.h"
 #include "box_rec.h"
 #include "augment_xf.h"
@@ -31,8 +32,8 @@ constexpr int AG_TILE = 256;
 constexpr int AG_WAVES = AG_TILE / PDA_WAVE;
 constexpr int AG_KMAX = 256;                 // candidates per scene
 constexpr int AG_KWORDS = AG_KMAX / 32;
-// info[b][3] status bits (include/pda_train.h)
-constexpr int ST_NO_BOX = 1, ST_BAD_OFFSETS = 2, ST_OVER_CAP = 4, ST_BAD_CAND = 8;
+// info[b][3] status bits of this stage (include/pda_train.h), next to ragged_scene.h's
+constexpr int ST_NO_BOX = 1, ST_BAD_CAND = 8;
 
 // per-scene record the select kernel leaves in the workspace
 struct SceneRec {
@@ -67,11 +68,6 @@ struct Ws {
     int32_t* pfx;             // (B, k + 1) pasted-point prefix of the accepted objects
     int32_t* tile;            // (B, tiles) kept points per tile, then their exclusive scan
 };
-
-__device__ __forceinline__ bool offsets_ok(const int64_t* off, int b, int64_t total) {
-    const int64_t s = off[b], e = off[b + 1];
-    return s >= 0 && e >= s && e <= total;
-}
 
 __device__ __forceinline__ bool object_ok(const Db& db, int id) {
     if (id < 0 || id >= db.n_obj) return false;

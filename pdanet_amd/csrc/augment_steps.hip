@@ -37,6 +37,7 @@
 //   * np.max / np.min of a float32 column are np.float32: the world-dropout threshold max - (float)i * (max - min) is
 //     float32, as is the local one (z + dz / 2) - (float)i * dz.
 #include "pda_common.h"
+#include "ragged_scene.h"
 #include "augment_xf.h"
 
 namespace pda {
@@ -47,7 +48,7 @@ constexpr int SP_WAVES = SP_TILE / PDA_WAVE;
 constexpr int SP_BMAX = 256;                 // boxes per scene
 constexpr int SP_MAX_OPS = 32;
 constexpr int SP_MAX_DROP = 4;
-constexpr int ST_NO_BOX = 1, ST_BAD_OFFSETS = 2, ST_OVER_CAP = 4, ST_BAD_CAND = 8;
+constexpr int ST_NO_BOX = 1, ST_BAD_CAND = 8;    // next to ragged_scene.h's ST_BAD_OFFSETS / ST_OVER_CAP
 enum { OP_FLIP_X = 0, OP_FLIP_Y, OP_ROT, OP_SCALE, OP_TRANS, OP_WDROP, OP_LTRANS, OP_LROT, OP_LSCALE, OP_LDROP, OP_COUNT };
 enum { DIR_TOP = 0, DIR_BOTTOM, DIR_LEFT, DIR_RIGHT };
 
@@ -76,11 +77,6 @@ struct Ws {
     float* fin;                              // (B, slots, 8) the final boxes, compacted
     int32_t* tile;                           // (B, tiles)
 };
-
-__device__ __forceinline__ bool offsets_ok(const int64_t* off, int b, int64_t total) {
-    const int64_t s = off[b], e = off[b + 1];
-    return s >= 0 && e >= s && e <= total;
-}
 
 // float <-> an unsigned key with the same order
 __device__ __forceinline__ uint32_t key_of(float v) {

@@ -62,8 +62,4 @@ __device__ __forceinline__ float xf_heading_raw(const Xf& t, float h) {
 
 __device__ __forceinline__ float xf_heading(const Xf& t, float h) { return limit_heading(xf_heading_raw(t, h)); }
 
-__device__ __forceinline__ int rank_below(uint64_t ballot) {
-    return (int)__mbcnt_hi((uint32_t)(ballot >> 32), __mbcnt_lo((uint32_t)ballot, 0u));
-}
-
 }  // namespace pda

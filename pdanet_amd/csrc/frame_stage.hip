@@ -24,6 +24,7 @@
 //   gx_write_kernel (tile groups, B): the same ballots again; a row's position is the object's offset + the scanned tile
 //                                     offset + the waves before + mbcnt.  No atomics decide an order.
 #include "pda_common.h"
+#include "ragged_scene.h"
 #include "box_rec.h"
 
 namespace pda {
@@ -33,31 +34,8 @@ constexpr int FS_TILE = 256;
 constexpr int FS_WAVES = FS_TILE / PDA_WAVE;
 constexpr int GX_MAX_BOXES = 256;   // boxes of one frame (LDS staging)
 constexpr int GX_GROUP = 4;         // tiles one workgroup walks with the records staged once
-// info[b][3] status bits (include/pda_train.h)
-constexpr int ST_BAD_OFFSETS = 2, ST_OVER_CAP = 4, ST_OVER_BOXES = 8;
-
-struct Scene {
-    int64_t start;
-    int n;       // points this scene holds (0 when its offsets are unusable)
-    int status;  // ST_BAD_OFFSETS / ST_OVER_CAP
-};
-
-__device__ __forceinline__ Scene scene_of(const int64_t* __restrict__ off, int b, int64_t n_total, int64_t n_cap) {
-    const int64_t s = off[b], e = off[b + 1];
-    Scene r{0, 0, 0};
-    if (s < 0 || e < s || e > n_total) r.status = ST_BAD_OFFSETS;
-    else if (e - s > n_cap) r.status = ST_OVER_CAP;
-    else { r.start = s; r.n = (int)(e - s); }
-    return r;
-}
-
-// lanes below mine with the bit set
-__device__ __forceinline__ int rank_below(uint64_t ballot) {
-    return (int)__mbcnt_hi((uint32_t)(ballot >> 32), __mbcnt_lo((uint32_t)ballot, 0u));
-}
-
-// The library is built with -fno-honor-nans; the bit pattern decides, whatever the compiler assumes about comparisons.
-__device__ __forceinline__ bool is_nan_bits(float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
+// info[b][3] status bit of this stage (include/pda_train.h), next to ragged_scene.h's
+constexpr int ST_OVER_BOXES = 8;
 
 // cal: 24 floats, M (4, 3) row-major then P2 (3, 4) row-major, wave-uniform (scalar loads)
 __device__ __forceinline__ bool fov_keep(float x, float y, float z, cfloat_ptr cal, double hh, double ww) {
@@ -392,7 +370,6 @@ __global__ __launch_bounds__(FS_TILE) void gx_write_kernel(const float* __restri
 }
 
 int64_t tiles_of(int64_t n_cap) { return divup64(n_cap, FS_TILE); }
-bool stage_sizes_ok(int batch, int64_t n_cap) { return batch >= 0 && batch <= 65535 && n_cap >= 1 && n_cap <= (1 << 30); }
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 int64_t gx_bytes(int64_t m_total, int64_t n_cap) { return (m_total * tiles_of(n_cap) * 4 + 255) / 256 * 256; }
 bool gx_sizes_ok(int batch, int64_t n_cap, int64_t m_total) {

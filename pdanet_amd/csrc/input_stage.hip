@@ -22,6 +22,7 @@
 // mode): a keyed bijection on [0, m) -- a 6-round Feistel network over 2h bits (4^h >= m) with cycle walking -- gives
 // the samples without replacement (its first r outputs) and the shuffles; a counter-based hash gives case C's draws.
 #include "pda_common.h"
+#include "ragged_scene.h"
 #include "stage_rng.h"
 
 namespace pda {
@@ -29,27 +30,12 @@ namespace {
 
 constexpr int IS_TILE = 256;
 constexpr int IS_WAVES = IS_TILE / PDA_WAVE;
-// info[b][3] status bits (include/pda_train.h)
-constexpr int ST_EMPTY = 1, ST_BAD_OFFSETS = 2, ST_OVER_CAP = 4, ST_BAD_DRAW = 8;
+// info[b][3] status bits of this stage (include/pda_train.h), next to ragged_scene.h's
+constexpr int ST_EMPTY = 1, ST_BAD_DRAW = 8;
 
 struct Range {
     float lo[3], hi[3];
 };
-
-struct Scene {
-    int64_t start;
-    int n;       // raw points this scene holds (0 when its offsets are unusable)
-    int status;  // ST_BAD_OFFSETS / ST_OVER_CAP
-};
-
-__device__ __forceinline__ Scene scene_of(const int64_t* __restrict__ off, int b, int64_t n_total, int64_t n_cap) {
-    const int64_t s = off[b], e = off[b + 1];
-    Scene r{0, 0, 0};
-    if (s < 0 || e < s || e > n_total) r.status = ST_BAD_OFFSETS;
-    else if (e - s > n_cap) r.status = ST_OVER_CAP;
-    else { r.start = s; r.n = (int)(e - s); }
-    return r;
-}
 
 __device__ __forceinline__ bool in_range_xy(float x, float y, const Range& rg) {
     return x >= rg.lo[0] && x <= rg.hi[0] && y >= rg.lo[1] && y <= rg.hi[1];
@@ -70,11 +56,6 @@ __device__ __forceinline__ void point_flags(const float* __restrict__ pts, const
         masked = in_range_xy(x, y, rg);
         near = masked && is_near(x, y, z);
     }
-}
-
-// lanes below mine with the bit set
-__device__ __forceinline__ int rank_below(uint64_t ballot) {
-    return (int)__mbcnt_hi((uint32_t)(ballot >> 32), __mbcnt_lo((uint32_t)ballot, 0u));
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------
@@ -279,7 +260,6 @@ __global__ __launch_bounds__(256) void is_boxes_kernel(const float* __restrict__
 
 int64_t tiles_of(int64_t n_cap) { return divup64(n_cap, IS_TILE); }
 int64_t tile_bytes(int batch, int64_t n_cap) { return (batch * tiles_of(n_cap) * 2 * 4 + 255) / 256 * 256; }
-bool stage_sizes_ok(int batch, int64_t n_cap) { return batch >= 0 && batch <= 65535 && n_cap >= 1 && n_cap <= (1 << 30); }
 
 Range range_of(const float* r6) {
     Range rg;

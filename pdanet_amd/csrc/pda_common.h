@@ -111,6 +111,10 @@ __device__ __forceinline__ int wave_id() {
     return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 }
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
+// lanes below mine with the bit set
+__device__ __forceinline__ int rank_below(uint64_t ballot) {
+    return (int)__mbcnt_hi((uint32_t)(ballot >> 32), __mbcnt_lo((uint32_t)ballot, 0u));
+}
 
 // Read-only, wave-uniform streams (the point cloud every lane tests against) are read
 // through the CONSTANT address space: with a wave-uniform address the backend then emits

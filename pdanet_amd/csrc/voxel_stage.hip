@@ -22,6 +22,7 @@
 //   vx_mean          : SAMPLE_TYPE mean_vfe, one thread per voxel.
 // Integer atomics only; the file is built with -ffp-contract=off.
 #include "pda_common.h"
+#include "ragged_scene.h"
 #include "stage_rng.h"
 
 namespace pda {
@@ -29,8 +30,8 @@ namespace {
 
 constexpr int VX_TILE = 256;
 constexpr int VX_WAVES = VX_TILE / PDA_WAVE;
-// info[b][3] status bits (include/pda_train.h)
-constexpr int ST_EMPTY = 1, ST_BAD_OFFSETS = 2, ST_OVER_CAP = 4, ST_BAD_DRAW = 8, ST_VOXEL_CAP = 16;
+// info[b][3] status bits of this stage (include/pda_train.h), next to ragged_scene.h's
+constexpr int ST_EMPTY = 1, ST_BAD_DRAW = 8, ST_VOXEL_CAP = 16;
 constexpr int ST_UNUSABLE = ST_BAD_OFFSETS | ST_OVER_CAP | ST_BAD_DRAW;
 constexpr uint64_t VX_EMPTY = ~0ull;
 constexpr uint32_t VX_NONE = 0xffffffffu;
@@ -42,29 +43,6 @@ struct Grid {
     int32_t n[3];      // cells along x, y, z
     int mask;          // 1: the x / y range mask of mask_points_and_boxes_outside_range comes first
 };
-
-struct Scene {
-    int64_t start;
-    int n;       // raw points this scene holds (0 when its offsets are unusable)
-    int status;  // ST_BAD_OFFSETS / ST_OVER_CAP
-};
-
-__device__ __forceinline__ Scene scene_of(const int64_t* __restrict__ off, int b, int64_t n_total, int64_t n_cap) {
-    const int64_t s = off[b], e = off[b + 1];
-    Scene r{0, 0, 0};
-    if (s < 0 || e < s || e > n_total) r.status = ST_BAD_OFFSETS;
-    else if (e - s > n_cap) r.status = ST_OVER_CAP;
-    else { r.start = s; r.n = (int)(e - s); }
-    return r;
-}
-
-// lanes below mine with the bit set
-__device__ __forceinline__ int rank_below(uint64_t ballot) {
-    return (int)__mbcnt_hi((uint32_t)(ballot >> 32), __mbcnt_lo((uint32_t)ballot, 0u));
-}
-
-// The library is built with -fno-honor-nans; the bit pattern decides, whatever the compiler assumes about comparisons.
-__device__ __forceinline__ bool is_nan_bits(float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
 
 __device__ __forceinline__ uint64_t perm0_key(uint64_t seed, int b) {
     return splitmix64(~seed ^ splitmix64(0x766f78656c5f7030ull + (uint64_t)b));

@@ -31,11 +31,16 @@ import pickle
 import numpy as np
 import torch
 
-from . import _lib
 from .pointnet2_batch_cuda import F32, _call, _chk
+from .stage_common import (STATUS_BAD_OFFSETS, STATUS_OVER_CAP, cfg_get, current_device, offsets_of, pack_scenes, packed_form,
+                           raise_on_status, upload, workspace)
 
-# info[:, 3] status bits (include/pda_train.h pda_augment)
-STATUS_NO_BOX, STATUS_BAD_OFFSETS, STATUS_OVER_CAP, STATUS_BAD_CAND = 1, 2, 4, 8
+# info[:, 3] status bits (include/pda_train.h pda_augment) next to the two shared ones, and what check=True raises
+STATUS_NO_BOX, STATUS_BAD_CAND = 1, 8
+_RULES = [(STATUS_BAD_OFFSETS, ": offsets outside the packed points or boxes"),
+          (STATUS_OVER_CAP, ": more than n_cap points, an output capacity exceeded, or (program path) more boxes than the cap or "
+                            "than draws"),
+          (STATUS_BAD_CAND, ": a candidate id outside the database or candidate groups out of order")]
 MAX_CANDIDATES = 256
 MAX_SCENE_BOXES = 256            # boxes per scene (its own plus the candidates) on the program path
 _STEPS = ("gt_sampling", "random_world_flip", "random_world_rotation", "random_world_scaling")
@@ -52,10 +57,6 @@ _AXES = {"x": 0, "y": 1, "z": 2}
 _DIRECTIONS = {"top": 0, "bottom": 1, "left": 2, "right": 3}
 
 
-def _get(cfg, key, default=None):
-    return cfg[key] if key in cfg else default
-
-
 def class_ids(gt_names, class_names):
     """prepare_data's class column: CLASS_NAMES.index(name) + 1, and 0 for a name outside CLASS_NAMES."""
     names = list(class_names)
@@ -69,7 +70,7 @@ class GtDatabase:
 
     def __init__(self, class_names, boxes, points, device=None):
         self.class_names = list(class_names)
-        dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        dev = torch.device(device) if device is not None else current_device()
         self.start, self.count = {}, {}
         box_rows, pts, cls = [], [], []
         for ci, name in enumerate(self.class_names):
@@ -93,7 +94,7 @@ class GtDatabase:
         self.num_point_features = C
         self.sizes = np.array([x.shape[0] for x in pts], np.int64)
         self.host_boxes = centre.astype(np.float32)                # sampled_boxes = box3d_lidar.astype(np.float32)
-        offs = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)
+        offs = offsets_of(self.sizes)
         allp = np.concatenate(pts, 0) if pts else np.zeros((0, C), np.float32)
         self.device = dev
         self.points = torch.from_numpy(np.ascontiguousarray(allp)).to(dev)
@@ -140,7 +141,7 @@ class GtDatabase:
         self.num_point_features = points.shape[1]
         self.sizes = (offsets[ids + 1] - offsets[ids]).astype(np.int64)
         self.host_boxes = centre.astype(np.float32)
-        offs = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)
+        offs = offsets_of(self.sizes)
         # the source row of every database row: object starts repeated, plus the position inside the object
         rows = np.repeat(offsets[ids] - offs[:-1], self.sizes) + np.arange(offs[-1], dtype=np.int64)
         dev = self.device = points.device
@@ -162,7 +163,7 @@ class GtDatabase:
                 infos = pickle.load(f)
             for name in class_names:
                 db_infos[name].extend(infos[name])
-        for func, val in _get(sampler_cfg, 'PREPARE', {}).items():
+        for func, val in cfg_get(sampler_cfg, 'PREPARE', {}).items():
             if func == 'filter_by_min_points':
                 db_infos = _filter_by_min_points(db_infos, val)
             elif func == 'filter_by_difficulty':
@@ -171,7 +172,7 @@ class GtDatabase:
                 raise NotImplementedError("PREPARE step %r" % func)
         C = int(sampler_cfg['NUM_POINT_FEATURES'])
         data = None
-        if _get(sampler_cfg, 'USE_SHARED_MEMORY', False):
+        if cfg_get(sampler_cfg, 'USE_SHARED_MEMORY', False):
             data = np.load(os.path.join(str(root_path), sampler_cfg['DB_DATA_PATH'][0]))
         boxes, points = {}, {}
         for name in class_names:
@@ -231,7 +232,7 @@ class DataAugmentor:
     def __init__(self, aug_cfg, class_names, database=None):
         self.class_names = list(class_names)
         cfg_list = aug_cfg if isinstance(aug_cfg, list) else aug_cfg['AUG_CONFIG_LIST']
-        disabled = [] if isinstance(aug_cfg, list) else list(_get(aug_cfg, 'DISABLE_AUG_LIST', []))
+        disabled = [] if isinstance(aug_cfg, list) else list(cfg_get(aug_cfg, 'DISABLE_AUG_LIST', []))
         self.sampler_cfg = None
         self.flip_axes, self.flip_prob = [], 0.5
         self.rot_range, self.rot_prob = None, 1.0
@@ -258,16 +259,16 @@ class DataAugmentor:
                 self.flip_axes = list(cfg['ALONG_AXIS_LIST'])
                 if any(a not in ('x', 'y') for a in self.flip_axes):
                     raise ValueError("random_world_flip takes the axes 'x' and 'y'")
-                self.flip_prob = float(_get(cfg, 'ENABLE_PROB', 0.5))
+                self.flip_prob = float(cfg_get(cfg, 'ENABLE_PROB', 0.5))
                 steps += [(OP_FLIP_X if a == 'x' else OP_FLIP_Y, 0, name, None) for a in self.flip_axes]
             elif name == 'random_world_rotation':
                 r = cfg['WORLD_ROT_ANGLE']
                 self.rot_range = [float(r[0]), float(r[1])] if isinstance(r, (list, tuple)) else [-float(r), float(r)]
-                self.rot_prob = float(_get(cfg, 'ENABLE_PROB', 1.0))
+                self.rot_prob = float(cfg_get(cfg, 'ENABLE_PROB', 1.0))
                 steps.append((OP_ROT, 0, name, None))
             elif name == 'random_world_scaling':
                 self.scale_range = [float(x) for x in cfg['WORLD_SCALE_RANGE']]
-                self.scale_prob = float(_get(cfg, 'ENABLE_PROB', 1.0))
+                self.scale_prob = float(cfg_get(cfg, 'ENABLE_PROB', 1.0))
                 steps.append((OP_SCALE, 0, name, None))
             elif name in ('random_world_translation', 'random_local_translation'):
                 axes = list(cfg['ALONG_AXIS_LIST'])
@@ -309,10 +310,10 @@ class DataAugmentor:
                 raise ValueError("gt_sampling needs a GtDatabase")
             if database.class_names != self.class_names:
                 raise ValueError("the database was built for other CLASS_NAMES")
-            if _get(self.sampler_cfg, 'DATABASE_WITH_FAKELIDAR', False):
+            if cfg_get(self.sampler_cfg, 'DATABASE_WITH_FAKELIDAR', False):
                 raise NotImplementedError("DATABASE_WITH_FAKELIDAR")
-            self.limit_whole_scene = bool(_get(self.sampler_cfg, 'LIMIT_WHOLE_SCENE', False))
-            self.use_road_plane = bool(_get(self.sampler_cfg, 'USE_ROAD_PLANE', False))
+            self.limit_whole_scene = bool(cfg_get(self.sampler_cfg, 'LIMIT_WHOLE_SCENE', False))
+            self.use_road_plane = bool(cfg_get(self.sampler_cfg, 'USE_ROAD_PLANE', False))
             self.remove_extra_width = np.asarray(self.sampler_cfg['REMOVE_EXTRA_WIDTH'], np.float32).reshape(3)
             names = {}
             for x in self.sampler_cfg['SAMPLE_GROUPS']:
@@ -476,29 +477,25 @@ class DataAugmentor:
             plan = self.make_plan(gt_classes, rng)
         dev_in = isinstance(points, tuple)
         if dev_in:
-            pts, offs, n_cap = points
-            if not (isinstance(gt_boxes, tuple) and pts.is_cuda and offs.is_cuda):
+            if not (isinstance(gt_boxes, tuple) and points[0].is_cuda and points[1].is_cuda):
                 raise ValueError("device points take gt_boxes as a (packed, box_offsets) tuple of device tensors")
+            pts, offs, n_cap = packed_form(points)
             bxs7, boffs = gt_boxes
             dev = pts.device
             if offs.numel() != B + 1 or boffs.numel() != B + 1:
                 raise ValueError("offsets need B + 1 entries")
             if bxs7.dim() != 2 or bxs7.shape[1] != 7:
                 raise NotImplementedError("boxes with more than 7 values (velocities) are not supported")
-            n_total, C, n_cap, m_total = pts.shape[0], pts.shape[1], int(n_cap), bxs7.shape[0]
+            n_total, C, m_total = pts.shape[0], pts.shape[1], bxs7.shape[0]
         else:
             if len(points) != B or len(gt_boxes) != B:
                 raise ValueError("points, gt_boxes and gt_classes need one entry per scene")
-            arrs = [np.asarray(p, np.float32) for p in points]
-            C = arrs[0].shape[1]
-            if any(a.ndim != 2 or a.shape[1] != C for a in arrs):
-                raise ValueError("every scene must be (n_i, C) with the same C")
+            packed, offs_h, n_cap, C = pack_scenes(points)
             bl = [np.asarray(g, np.float32).reshape(len(g), -1) if len(g) else np.zeros((0, 7), np.float32) for g in gt_boxes]
             if any(g.shape[1] != 7 for g in bl):
                 raise NotImplementedError("boxes with more than 7 values (velocities) are not supported")
-            sizes = [a.shape[0] for a in arrs]
-            n_total, n_cap, m_total = sum(sizes), max(max(sizes), 1), sum(len(g) for g in bl)
-            dev = self.database.device if self.database is not None else torch.device('cuda', torch.cuda.current_device())
+            n_total, m_total = packed.shape[0], sum(len(g) for g in bl)
+            dev = self.database.device if self.database is not None else current_device()
         cls_rows = [np.asarray(c, np.int32).reshape(-1) for c in gt_classes]
         if sum(len(c) for c in cls_rows) != m_total:
             raise ValueError("gt_classes needs one class id per box")
@@ -545,36 +542,20 @@ class DataAugmentor:
         # ---- one upload: plan | class column | host scenes --------------------------------------------------------------
         parts = [cand, grp, dz, flip, angle, scale, np.concatenate(cls_rows).astype(np.float32) if m_total else np.zeros(0, np.float32)]
         if not dev_in:
-            parts += [np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64),
-                      np.concatenate([[0], np.cumsum([len(g) for g in bl])]).astype(np.int64),
-                      np.concatenate(arrs, 0) if n_total else np.zeros((0, C), np.float32),
+            parts += [offs_h, offsets_of([len(g) for g in bl]), packed,
                       np.concatenate(bl, 0) if m_total else np.zeros((0, 7), np.float32)]
         if self.program is not None:
             ops, scene_draws, box_draws, D = self._program_draws(plan, B, fx, fy, angle, scale)
             parts += [scene_draws, box_draws]
-        sizes_b = [p.nbytes for p in parts]
-        starts = np.concatenate([[0], np.cumsum([(s + 7) // 8 * 8 for s in sizes_b])]).astype(np.int64)
-        host = torch.empty((max(int(starts[-1]), 8),), dtype=torch.uint8, pin_memory=True)
-        hn = host.numpy()
-        for p, s, n in zip(parts, starts[:-1], sizes_b):
-            hn[s:s + n] = np.ascontiguousarray(p).reshape(-1).view(np.uint8)
-        dbuf = host.to(dev, non_blocking=True)
-        views = [dbuf[s:s + n] for s, n in zip(starts[:-1].tolist(), sizes_b)]
-        d_cand, d_grp = views[0].view(torch.int32), views[1].view(torch.int32)
-        d_dz, d_flip = views[2].view(torch.float64), views[3].view(torch.int32)
-        d_angle, d_scale, d_cls = views[4].view(torch.float64), views[5].view(torch.float32), views[6].view(torch.float32)
+        views = upload(parts, dev, pinned=True)
+        d_cand, d_grp, d_dz, d_flip, d_angle, d_scale, d_cls = views[:7]
         if not dev_in:
-            offs, boffs = views[7].view(torch.int64), views[8].view(torch.int64)
-            pts = views[9].view(torch.float32).view(-1, C)
-            bxs7 = views[10].view(torch.float32).view(-1, 7)
+            offs, boffs, pts, bxs7 = views[7:11]
         bxs = torch.cat([bxs7.to(torch.float32), d_cls.view(-1, 1)], dim=1).contiguous()
 
         # ---- the launch ------------------------------------------------------------------------------------------------
-        lib = _lib.load()
-        ws_bytes = lib.pda_augment_workspace_bytes(B, n_cap, K)
-        if ws_bytes < 0:
-            raise ValueError("batch %d / n_cap %d / %d candidates out of range" % (B, n_cap, K))
-        ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+        ws = workspace("pda_augment_workspace_bytes", (B, n_cap, K),
+                       "batch %d / n_cap %d / %d candidates out of range" % (B, n_cap, K), dev)
         out_cap = n_total + int(paste.sum())
         box_cap = m_total + n_cand
         out = torch.empty((max(out_cap, 1), C), dtype=torch.float32, device=dev)
@@ -597,10 +578,8 @@ class DataAugmentor:
             # the pasted scenes through the ordered program
             n_ops = len(self.program)
             slots = min(MAX_SCENE_BOXES, max([len(c) + int((cand[b] >= 0).sum()) for b, c in enumerate(cls_rows)] + [0]))
-            ws_bytes = lib.pda_augment_steps_workspace_bytes(B, n_cap + paste_cap, slots, n_ops)
-            if ws_bytes < 0:
-                raise ValueError("batch %d / n_cap %d / %d ops out of range" % (B, n_cap + paste_cap, n_ops))
-            ws2 = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+            ws2 = workspace("pda_augment_steps_workspace_bytes", (B, n_cap + paste_cap, slots, n_ops),
+                            "batch %d / n_cap %d / %d ops out of range" % (B, n_cap + paste_cap, n_ops), dev)
             out2, out_boxes2 = torch.empty_like(out), torch.empty_like(out_boxes)
             out_offs2, out_boffs2, info2 = torch.empty_like(out_offs), torch.empty_like(out_boffs), torch.empty_like(info)
             _call("pda_augment_steps", out, out.data_ptr(), out_offs.data_ptr(), out_cap, B, C, n_cap + paste_cap,
@@ -608,7 +587,7 @@ class DataAugmentor:
                   views[-2].data_ptr(), views[-1].data_ptr(), D, slots, info.data_ptr(), out2.data_ptr(), out_cap,
                   out_offs2.data_ptr(), out_boxes2.data_ptr(), box_cap, out_boffs2.data_ptr(), info2.data_ptr(), ws2.data_ptr())
             if check:
-                self._check(info2.cpu())
+                raise_on_status(info2.cpu(), _RULES)
             return (out2, out_offs2, n_cap + paste_cap), (out_boxes2, out_boffs2), info2
         _call("pda_augment", pts, _chk(pts, "points", F32) if n_total else None, _chk(offs, "offsets", torch.int64), n_total, B, C,
               n_cap, bxs.data_ptr() if m_total else None, _chk(boffs, "box_offsets", torch.int64), m_total, *dbp,
@@ -616,18 +595,8 @@ class DataAugmentor:
               d_flip.data_ptr(), d_angle.data_ptr(), d_scale.data_ptr(), self._rew_c, paste_cap, out.data_ptr(), out_cap,
               out_offs.data_ptr(), out_boxes.data_ptr(), box_cap, out_boffs.data_ptr(), info.data_ptr(), ws.data_ptr())
         if check:
-            self._check(info.cpu())
+            raise_on_status(info.cpu(), _RULES)
         return (out, out_offs, n_cap + paste_cap), (out_boxes, out_boffs), info
-
-    @staticmethod
-    def _check(info):
-        for b, (_, _, _, status) in enumerate(info.tolist()):
-            if status & STATUS_BAD_OFFSETS:
-                raise ValueError("scene %d: offsets outside the packed points or boxes" % b)
-            if status & STATUS_OVER_CAP:
-                raise ValueError("scene %d: more than n_cap points, an output capacity exceeded, or (program path) more boxes than the cap or than draws" % b)
-            if status & STATUS_BAD_CAND:
-                raise ValueError("scene %d: a candidate id outside the database or candidate groups out of order" % b)
 
 
 def from_config(cfg, database=None):

@@ -22,18 +22,19 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
 from .pointnet2_batch_cuda import F32, _call, _chk
+from .stage_common import (STATUS_BAD_OFFSETS, STATUS_OVER_CAP, cfg_get, current_device, offsets_of, pack_scenes, packed_form,
+                           raise_on_status, upload, workspace)
 from .voxel_utils import VoxelSpec
 
-# input_info[:, 3] status bits (include/pda_train.h pda_input_stage); voxel_info[:, 3] adds STATUS_VOXEL_CAP (pda_voxel_sample)
-STATUS_EMPTY, STATUS_BAD_OFFSETS, STATUS_OVER_CAP, STATUS_BAD_DRAW, STATUS_VOXEL_CAP = 1, 2, 4, 8, 16
+# input_info[:, 3] status bits (include/pda_train.h pda_input_stage) next to the two shared ones; voxel_info[:, 3] adds
+# STATUS_VOXEL_CAP (pda_voxel_sample)
+STATUS_EMPTY, STATUS_BAD_DRAW, STATUS_VOXEL_CAP = 1, 8, 16
+_BAD_SCENE = (STATUS_BAD_OFFSETS | STATUS_OVER_CAP, ": offsets outside the packed points or more than n_cap points")
+_INPUT_RULES = [_BAD_SCENE, (STATUS_EMPTY, " has no point inside POINT_CLOUD_RANGE"), (STATUS_BAD_DRAW, ": a draw is out of range")]
+_VOXEL_RULES = [_BAD_SCENE, (STATUS_BAD_DRAW, ": perm0 is not a permutation of the masked points")]
 _STEPS = ("mask_points_and_boxes_outside_range", "sample_points", "shuffle_points")
 _VOXEL_STEPS = ("mask_points_and_boxes_outside_range", "shuffle_points", "sample_points_by_voxels")
-
-
-def _get(cfg, key, default=None):
-    return cfg[key] if key in cfg else default
 
 
 class DataProcessor:
@@ -63,8 +64,8 @@ class DataProcessor:
             last = steps.index(name)
             if name == 'mask_points_and_boxes_outside_range':
                 self.mask_points = True
-                self.remove_outside_boxes = bool(_get(cfg, 'REMOVE_OUTSIDE_BOXES', False)) and self.training
-                self.min_num_corners = int(_get(cfg, 'min_num_corners', 1))
+                self.remove_outside_boxes = bool(cfg_get(cfg, 'REMOVE_OUTSIDE_BOXES', False)) and self.training
+                self.min_num_corners = int(cfg_get(cfg, 'min_num_corners', 1))
             elif name == 'sample_points':
                 self.num_points = int(cfg['NUM_POINTS'][self.mode])
                 if self.num_points == -1:
@@ -79,7 +80,7 @@ class DataProcessor:
                                      "backbone needs the same number of points in every scene")
                 if self.num_points < 1:
                     raise ValueError("sample_points_by_voxels NUM_POINTS must be positive")
-                self.sample_type = str(_get(cfg, 'SAMPLE_TYPE', 'raw'))
+                self.sample_type = str(cfg_get(cfg, 'SAMPLE_TYPE', 'raw'))
                 if self.sample_type not in ('raw', 'mean_vfe'):
                     # the reference treats every other value as 'raw'; a typo should not pass silently
                     raise ValueError("sample_points_by_voxels SAMPLE_TYPE must be 'raw' or 'mean_vfe'")
@@ -125,16 +126,12 @@ class DataProcessor:
         B, C, k = offs.numel() - 1, pts.shape[1], self.num_points
         if C < 3:
             raise ValueError("points need at least x, y, z")
-        lib = _lib.load()
         if draws is None and seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())   # CPU generator: no device read
         voxel_info = None
         if self.voxel is not None:
             pts, offs, n_cap, voxel_info = self._voxel_stage(pts, offs, n_cap, seed, draws)
-        ws_bytes = lib.pda_input_stage_workspace_bytes(B, n_cap)
-        if ws_bytes < 0:
-            raise ValueError("batch %d / n_cap %d out of range" % (B, n_cap))
-        ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+        ws = workspace("pda_input_stage_workspace_bytes", (B, n_cap), "batch %d / n_cap %d out of range" % (B, n_cap), dev)
         out = torch.empty((B * k, 1 + C), dtype=torch.float32, device=dev)
         info = (torch.empty if bxs is not None else torch.zeros)((B, 4), dtype=torch.int32, device=dev)
         pick = perm1 = perm2 = None
@@ -166,7 +163,7 @@ class DataProcessor:
             ret['gt_boxes'] = gt
         if check:
             if voxel_info is not None:
-                self._check_voxels(voxel_info.cpu())
+                raise_on_status(voxel_info.cpu(), _VOXEL_RULES)
             self._check(info.cpu() if host_info is None else host_info, max_gt if bxs is not None else None)
         return ret
 
@@ -187,7 +184,7 @@ class DataProcessor:
             if per_scene is None or len(per_scene) != B:
                 raise ValueError("draws needs 'perm0' with one array per scene")
             per_scene = [np.asarray(r.cpu() if isinstance(r, torch.Tensor) else r).reshape(-1).astype(np.int32) for r in per_scene]
-            poffs = torch.from_numpy(np.concatenate([[0], np.cumsum([r.size for r in per_scene])]).astype(np.int64)).to(dev)
+            poffs = torch.from_numpy(offsets_of([r.size for r in per_scene])).to(dev)
             perm0 = torch.from_numpy(np.concatenate(per_scene + [np.zeros(1, np.int32)])).to(dev)     # never empty
         _call("pda_voxel_sample", pts, _chk(pts, "points", F32), _chk(offs, "offsets", torch.int64), pts.shape[0], B, C, n_cap,
               sp.range_c, sp.vsize_c, sp.grid_c, int(self.mask_points), sp.max_voxels, sp.max_points if mean else 1, int(mean),
@@ -197,30 +194,19 @@ class DataProcessor:
               ws.data_ptr())
         return rows, row_offs, v_cap, info
 
-    @staticmethod
-    def _check_voxels(info):
-        for b, (_, _, _, status) in enumerate(info.tolist()):
-            if status & STATUS_BAD_OFFSETS or status & STATUS_OVER_CAP:
-                raise ValueError("scene %d: offsets outside the packed points or more than n_cap points" % b)
-            if status & STATUS_BAD_DRAW:
-                raise ValueError("scene %d: perm0 is not a permutation of the masked points" % b)
-
     def _range_c_boxes(self):
         return (ctypes.c_float * 6)(*self.point_cloud_range.tolist())
 
     @staticmethod
     def _check(info, max_gt):
-        for b, (n, _, kept, status) in enumerate(info.tolist()):
-            if status & STATUS_BAD_OFFSETS or status & STATUS_OVER_CAP:
-                raise ValueError("scene %d: offsets outside the packed points or more than n_cap points" % b)
-            if status & STATUS_EMPTY:
-                raise ValueError("scene %d has no point inside POINT_CLOUD_RANGE" % b)
-            if status & STATUS_BAD_DRAW:
-                raise ValueError("scene %d: a draw is out of range" % b)
-            if kept < 0:
-                raise ValueError("scene %d: box offsets outside the packed boxes" % b)
-            if max_gt is not None and kept > max_gt:
-                raise ValueError("scene %d keeps %d boxes, more than max_gt=%d" % (b, kept, max_gt))
+        # the first scene whose kept-box count is an error of its own; a status bit of that scene or an earlier one goes first
+        kept = info[:, 2].tolist()
+        bad = next((b for b, n in enumerate(kept) if n < 0 or (max_gt is not None and n > max_gt)), len(kept))
+        raise_on_status(info[:bad + 1], _INPUT_RULES)
+        if bad < len(kept):
+            if kept[bad] < 0:
+                raise ValueError("scene %d: box offsets outside the packed boxes" % bad)
+            raise ValueError("scene %d keeps %d boxes, more than max_gt=%d" % (bad, kept[bad], max_gt))
 
     @staticmethod
     def _draw_rows(rows, B, k, dev, name):
@@ -244,9 +230,7 @@ class DataProcessor:
     def _inputs(self, points, gt_boxes, dev):
         """-> packed points, offsets, n_cap, packed boxes, box offsets, largest raw box count (all on one device)."""
         if isinstance(points, tuple):
-            pts, offs, n_cap = points
-            if not (pts.is_cuda and offs.is_cuda):
-                raise ValueError("the (packed, offsets, n_cap) form takes device tensors")
+            pts, offs, n_cap = packed_form(points)
             bxs = boffs = None
             bmax = 0
             if gt_boxes is not None:
@@ -254,7 +238,7 @@ class DataProcessor:
                     raise ValueError("device points take gt_boxes as (packed, box_offsets)")
                 bxs, boffs = gt_boxes
                 bmax = bxs.shape[0]
-            return pts, offs, int(n_cap), bxs, boffs, bmax
+            return pts, offs, n_cap, bxs, boffs, bmax
         B = len(points)
         if B == 0:
             raise ValueError("empty batch")
@@ -264,47 +248,32 @@ class DataProcessor:
         if all(on_dev):
             dev = points[0].device
         elif dev is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
-        arrs = [p if on_dev[i] else np.asarray(p.numpy() if isinstance(p, torch.Tensor) else p, np.float32)
-                for i, p in enumerate(points)]
-        C = arrs[0].shape[1]
-        if any(a.ndim != 2 or a.shape[1] != C for a in arrs):
-            raise ValueError("every scene must be (n_i, C) with the same C")
-        sizes = [a.shape[0] for a in arrs]
-        n_cap = max(max(sizes), 1)
-        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        boxes = None
+            dev = current_device()
+        # one transfer: offsets | points (when every scene is on the host) | box offsets | boxes
+        host_pts = not any(on_dev)
+        if host_pts:
+            packed, offs, n_cap, _ = pack_scenes(points)
+            host = [offs, packed]
+        else:
+            pts = [torch.as_tensor(p).to(dev, torch.float32) for p in points]
+            if any(p.dim() != 2 or p.shape[1] != pts[0].shape[-1] for p in pts):
+                raise ValueError("every scene must be (n_i, C) with the same C")
+            sizes = [p.shape[0] for p in pts]
+            n_cap = max(max(sizes), 1)
+            pts = torch.cat(pts, dim=0).contiguous()
+            host = [offsets_of(sizes)]
+        bmax = 0
         if gt_boxes is not None:
             boxes = [np.asarray(g.cpu().numpy() if isinstance(g, torch.Tensor) else g, np.float32) for g in gt_boxes]
             D = max((g.shape[1] for g in boxes if g.ndim == 2 and g.size), default=7)
             boxes = [g.reshape(-1, D) for g in boxes]
-            msz = [g.shape[0] for g in boxes]
-            boffs = np.concatenate([[0], np.cumsum(msz)]).astype(np.int64)
-        # one host buffer, one transfer: offsets | box offsets | points (when on the host) | boxes, 8-byte aligned sections
-        parts = [offs.view(np.uint8)]
-        if boxes is not None:
-            parts.append(boffs.view(np.uint8))
-        host_pts = not any(on_dev)
+            bmax = max(g.shape[0] for g in boxes)
+            host += [offsets_of([g.shape[0] for g in boxes]), np.concatenate(boxes, axis=0)]
+        views = upload(host, dev)
+        d_offs = views[0]
         if host_pts:
-            parts.append(np.concatenate(arrs, axis=0).astype(np.float32, copy=False).reshape(-1).view(np.uint8))
-        if boxes is not None:
-            parts.append(np.concatenate(boxes, axis=0).reshape(-1).view(np.uint8))
-        pads = [(-p.size) % 8 for p in parts]
-        buf = np.concatenate([x for p, pad in zip(parts, pads) for x in (p, np.zeros(pad, np.uint8))])
-        dbuf = torch.from_numpy(buf).to(dev)
-        views, at = [], 0
-        for p, pad in zip(parts, pads):
-            views.append(dbuf[at:at + p.size])
-            at += p.size + pad
-        it = iter(views)
-        d_offs = next(it).view(torch.int64)
-        d_boffs = next(it).view(torch.int64) if boxes is not None else None
-        if host_pts:
-            pts = next(it).view(torch.float32).view(-1, C)
-        else:
-            pts = torch.cat([torch.as_tensor(a).to(dev, torch.float32) for a in arrs], dim=0).contiguous()
-        bxs = next(it).view(torch.float32).view(-1, D) if boxes is not None else None
-        bmax = max(msz) if boxes is not None else 0
+            pts = views[1]
+        d_boffs, bxs = views[-2:] if gt_boxes is not None else (None, None)
         return pts, d_offs, n_cap, bxs, d_boffs, bmax
 
 
@@ -328,7 +297,7 @@ def collate_batch(batch_list, max_gt=None, device=None):
     keys = list(batch_list[0].keys())
     if device is None:
         first = batch_list[0].get('points')
-        device = first.device if isinstance(first, torch.Tensor) and first.is_cuda else torch.device('cuda', torch.cuda.current_device())
+        device = first.device if isinstance(first, torch.Tensor) and first.is_cuda else current_device()
     dev = torch.device(device)
     ret = {}
     for key in keys:
@@ -346,7 +315,7 @@ def collate_batch(batch_list, max_gt=None, device=None):
             if max(counts) > cap:
                 raise ValueError("a scene holds more than max_gt=%d boxes" % cap)
             packed = torch.cat(boxes, dim=0).contiguous()
-            offs = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int64).to(dev)
+            offs = torch.from_numpy(offsets_of(counts)).to(dev)
             gt = torch.empty((B, cap, D), dtype=torch.float32, device=dev)
             info = torch.empty((B, 4), dtype=torch.int32, device=dev)
             rng = (ctypes.c_float * 6)(*([0.0] * 6))        # min_num_corners 0: every box is kept, the range is not read

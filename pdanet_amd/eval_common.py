@@ -1,26 +1,12 @@
-"""Host-side plumbing shared by the device evaluations (once_eval.py, kitti_eval.py): the one-copy upload, the name
-table, post_processing's label-to-name rule, the frame row bookkeeping and the layout of the one int64 result buffer.
+"""Host-side plumbing shared by the device evaluations (once_eval.py, kitti_eval.py): the one-copy upload and the
+workspace (stage_common.py's, shared with the data stages), the name table, post_processing's label-to-name rule, the
+frame row bookkeeping and the layout of the one int64 result buffer.
 What is dataset-specific (class and accept tables, frame modes, the AP composition) stays in the two modules.
 """
 import numpy as np
 import torch
 
-_TORCH_DTYPE = {np.dtype(np.float64): torch.float64, np.dtype(np.float32): torch.float32,
-                np.dtype(np.int64): torch.int64, np.dtype(np.int32): torch.int32}
-
-
-def upload(arrays, device):
-    """One host-to-device copy of several numpy arrays; returns device views with their dtypes and shapes."""
-    offs, total = [], 0
-    for a in arrays:
-        total = (total + 255) // 256 * 256
-        offs.append(total)
-        total += a.nbytes
-    buf = np.zeros(max(total, 1), np.uint8)
-    for a, o in zip(arrays, offs):
-        buf[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-    dev = torch.from_numpy(buf).to(device, non_blocking=False)
-    return [dev[o:o + a.nbytes].view(_TORCH_DTYPE[a.dtype]).reshape(a.shape) for a, o in zip(arrays, offs)]
+from .stage_common import upload, workspace  # noqa: F401  (the evaluations upload pageable: upload(arrays, device))
 
 
 def ptr(t):

@@ -19,13 +19,17 @@ import pickle
 import numpy as np
 import torch
 
-from . import _lib
-from .data_augmentor import GtDatabase, _filter_by_min_points, _get
+from .data_augmentor import GtDatabase, _filter_by_min_points
 from .pointnet2_batch_cuda import F32, _call, _chk
+from .stage_common import (STATUS_BAD_OFFSETS, STATUS_OVER_CAP, cfg_get, current_device, offsets_of, pack_scenes, packed_form,
+                           raise_on_status, upload, workspace)
 
-# info[:, 3] status bits (include/pda_train.h)
-STATUS_BAD_OFFSETS, STATUS_OVER_CAP, STATUS_OVER_BOXES = 2, 4, 8
 MAX_BOXES_PER_FRAME = 256
+# info[:, 3] status bits (include/pda_train.h) next to the two shared ones, and what check=True raises for each
+STATUS_OVER_BOXES = 8
+_RULES = [(STATUS_BAD_OFFSETS, ": offsets outside the packed points or boxes"),
+          (STATUS_OVER_CAP, ": more than n_cap points or an output capacity exceeded"),
+          (STATUS_OVER_BOXES, ": more than %d boxes" % MAX_BOXES_PER_FRAME)]
 CALIB_RECORD_FLOATS = 24
 KITTI_KEYS = ('name', 'path', 'image_idx', 'gt_idx', 'box3d_lidar', 'num_points_in_gt', 'difficulty', 'bbox', 'score')
 ONCE_KEYS = ('name', 'path', 'gt_idx', 'box3d_lidar', 'num_points_in_gt')
@@ -45,36 +49,6 @@ def calib_records(calibs):
     return out
 
 
-def _upload(parts, dev):
-    """Host arrays -> device views through one pinned buffer and one asynchronous copy (16-byte aligned sections)."""
-    parts = [np.ascontiguousarray(p) for p in parts]
-    sizes = [p.nbytes for p in parts]
-    starts = np.concatenate([[0], np.cumsum([(s + 15) // 16 * 16 for s in sizes])]).astype(np.int64)
-    host = torch.empty((max(int(starts[-1]), 8),), dtype=torch.uint8, pin_memory=True)
-    hn = host.numpy()
-    for p, s, n in zip(parts, starts[:-1], sizes):
-        hn[s:s + n] = p.reshape(-1).view(np.uint8)
-    dbuf = host.to(dev, non_blocking=True)
-    return [dbuf[s:s + n] for s, n in zip(starts[:-1].tolist(), sizes)]
-
-
-def _pack_scenes(points):
-    arrs = [np.asarray(p, np.float32) for p in points]
-    if not arrs:
-        raise ValueError("empty batch")
-    C = arrs[0].shape[1] if arrs[0].ndim == 2 else -1
-    if any(a.ndim != 2 or a.shape[1] != C for a in arrs):
-        raise ValueError("every scene must be (n_i, C) with the same C")
-    sizes = [a.shape[0] for a in arrs]
-    offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    packed = np.concatenate(arrs, 0) if sum(sizes) else np.zeros((0, C), np.float32)
-    return packed, offs, max(max(sizes), 1), C
-
-
-def _device():
-    return torch.device('cuda', torch.cuda.current_device())
-
-
 def fov_filter(points, calibs, image_shapes, check=True):
     """points: a list of B (n_i, C) host arrays, or a tuple (packed (n_total, C) float32, offsets (B + 1) int64, n_cap)
     of device tensors.  calibs: per scene a Calibration (or its dict), the (B, 33) rows of kitti_eval.calib_matrix, or a
@@ -84,17 +58,13 @@ def fov_filter(points, calibs, image_shapes, check=True):
     Returns ((packed (rows, C), offsets (B + 1), n_cap), info (B, 4) int32 [n_in, n_kept, 0, status]): the kept rows of
     every scene in their order; the first part feeds DataAugmentor.__call__ / DataProcessor.__call__ unchanged."""
     dev_in = isinstance(points, tuple)
-    host = []
     if dev_in:
-        pts, offs, n_cap = points
-        if not (pts.is_cuda and offs.is_cuda):
-            raise ValueError("the (packed, offsets, n_cap) form takes device tensors")
-        dev = pts.device
+        pts, offs, n_cap = packed_form(points)
+        dev, host = pts.device, []
     else:
-        packed, offs_h, n_cap, _ = _pack_scenes(points)
-        dev = _device()
-        host = [offs_h, packed]
-    B = (offs.numel() if dev_in else offs_h.size) - 1
+        packed, offs, n_cap, _ = pack_scenes(points)
+        dev, host = current_device(), [offs, packed]
+    B = offs.shape[0] - 1
     cal_dev = isinstance(calibs, torch.Tensor)
     if not cal_dev:
         host.append(calib_records(calibs))
@@ -105,22 +75,17 @@ def fov_filter(points, calibs, image_shapes, check=True):
         host.append(np.asarray(image_shapes.cpu() if isinstance(image_shapes, torch.Tensor) else image_shapes).astype(np.int32).reshape(-1, 2))
         if host[-1].shape[0] != B:
             raise ValueError("image_shapes needs one (H, W) per scene")
-    views = iter(_upload(host, dev)) if host else iter(())
+    views = iter(upload(host, dev, pinned=True)) if host else iter(())
     if not dev_in:
-        offs = next(views).view(torch.int64)
-        pts = next(views).view(torch.float32).view(-1, packed.shape[1])
-    cal = calibs if cal_dev else next(views).view(torch.float32).view(B, CALIB_RECORD_FLOATS)
-    shp = image_shapes if shp_dev else next(views).view(torch.int32).view(B, 2)
+        offs, pts = next(views), next(views)
+    cal = calibs if cal_dev else next(views)
+    shp = image_shapes if shp_dev else next(views)
     if cal.shape != (B, CALIB_RECORD_FLOATS) or shp.shape != (B, 2):
         raise ValueError("calibs must be (B, 24) and image_shapes (B, 2)")
-    n_total, C, n_cap = pts.shape[0], pts.shape[1], int(n_cap)
+    n_total, C = pts.shape
     if C < 3:
         raise ValueError("points need at least x, y, z")
-    lib = _lib.load()
-    ws_bytes = lib.pda_kitti_fov_filter_workspace_bytes(B, n_cap)
-    if ws_bytes < 0:
-        raise ValueError("batch %d / n_cap %d out of range" % (B, n_cap))
-    ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+    ws = workspace("pda_kitti_fov_filter_workspace_bytes", (B, n_cap), "batch %d / n_cap %d out of range" % (B, n_cap), dev)
     out = torch.empty((max(n_total, 1), C), dtype=torch.float32, device=dev)
     out_offs = torch.empty((B + 1,), dtype=torch.int64, device=dev)
     info = torch.empty((B, 4), dtype=torch.int32, device=dev)
@@ -128,18 +93,8 @@ def fov_filter(points, calibs, image_shapes, check=True):
           C, n_cap, _chk(cal, "calibs", F32), _chk(shp, "image_shapes", torch.int32), out.data_ptr(), n_total,
           out_offs.data_ptr(), info.data_ptr(), ws.data_ptr())
     if check:
-        _check(info.cpu(), "scene")
+        raise_on_status(info.cpu(), _RULES)
     return (out, out_offs, n_cap), info
-
-
-def _check(info, what):
-    for b, (_, _, _, status) in enumerate(info.tolist()):
-        if status & STATUS_BAD_OFFSETS:
-            raise ValueError("%s %d: offsets outside the packed points or boxes" % (what, b))
-        if status & STATUS_OVER_CAP:
-            raise ValueError("%s %d: more than n_cap points or an output capacity exceeded" % (what, b))
-        if status & STATUS_OVER_BOXES:
-            raise ValueError("%s %d: more than %d boxes" % (what, b, MAX_BOXES_PER_FRAME))
 
 
 def gt_extract(points, boxes, box_offsets, centre, check=True):
@@ -152,11 +107,8 @@ def gt_extract(points, boxes, box_offsets, centre, check=True):
     B, n_total, C, m_total, n_cap = offs.numel() - 1, pts.shape[0], pts.shape[1], boxes.shape[0], int(n_cap)
     if boxes.dim() != 2 or boxes.shape[1] != 7 or tuple(centre.shape) != (m_total, 3):
         raise ValueError("boxes must be (m_total, 7) and centre (m_total, 3)")
-    lib = _lib.load()
-    ws_bytes = lib.pda_gt_extract_workspace_bytes(B, n_cap, m_total)
-    if ws_bytes < 0:
-        raise ValueError("batch %d / n_cap %d / %d boxes out of range" % (B, n_cap, m_total))
-    ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+    ws = workspace("pda_gt_extract_workspace_bytes", (B, n_cap, m_total),
+                   "batch %d / n_cap %d / %d boxes out of range" % (B, n_cap, m_total), dev)
     counts = torch.empty((m_total,), dtype=torch.int32, device=dev)
     info = torch.empty((B, 4), dtype=torch.int32, device=dev)
     head = (_chk(pts, "points", F32) if n_total else None, _chk(offs, "offsets", torch.int64), n_total, B, C, n_cap,
@@ -169,7 +121,7 @@ def gt_extract(points, boxes, box_offsets, centre, check=True):
     _call("pda_gt_extract_write", pts, *head, _chk(centre, "centre", torch.float64) if m_total else None, obj_offs.data_ptr(),
           obj_points.data_ptr(), total, info.data_ptr(), ws.data_ptr())
     if check:
-        _check(info.cpu(), "frame")
+        raise_on_status(info.cpu(), _RULES, "frame")
     return obj_points[:total], obj_offs, counts, info
 
 
@@ -220,8 +172,8 @@ class GtDatabaseBuilder:
         else:
             if len(points) != B:
                 raise ValueError("points needs one entry per frame")
-            packed, offs_h, n_cap, _ = _pack_scenes(points)
-            dev = _device()
+            packed, offs_h, n_cap, _ = pack_scenes(points)
+            dev = current_device()
             pts, offs = torch.from_numpy(packed).to(dev), torch.from_numpy(offs_h).to(dev)
         if pts.shape[1] != self.num_point_features:
             raise ValueError("the builder holds %d point features, the frames %d" % (self.num_point_features, pts.shape[1]))
@@ -229,7 +181,7 @@ class GtDatabaseBuilder:
         if any(r.shape[1] != 7 for r in rows):
             raise NotImplementedError("boxes with more than 7 values (velocities) are not supported")
         allb = np.concatenate(rows, 0) if rows else np.zeros((0, 7))
-        boffs = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+        boffs = offsets_of([len(r) for r in rows])
         d_boxes = torch.from_numpy(np.ascontiguousarray(allb.astype(np.float32))).to(dev)
         d_centre = torch.from_numpy(np.ascontiguousarray(allb[:, :3].astype(np.float64))).to(dev)
         obj_points, obj_offs, counts, _ = gt_extract((pts, offs, n_cap), d_boxes, torch.from_numpy(boffs).to(dev), d_centre)
@@ -279,7 +231,7 @@ class GtDatabaseBuilder:
             offs.append(o[1:] + at)
             at += p.shape[0]
         if not self._batches:
-            return torch.zeros((0, self.num_point_features), dtype=torch.float32, device=_device()), offs[0]
+            return torch.zeros((0, self.num_point_features), dtype=torch.float32, device=current_device()), offs[0]
         return torch.cat([p for p, _, _ in self._batches], 0), np.concatenate(offs)
 
     def finish(self, class_names, sampler_cfg=None):
@@ -289,7 +241,7 @@ class GtDatabaseBuilder:
         for o, obj in enumerate(self.objects):
             if obj['name'] in db_infos and (self.used_classes is None or obj['name'] in self.used_classes):
                 db_infos[obj['name']].append(dict(obj, _id=o, **obj['extra']))
-        for func, val in (_get(sampler_cfg, 'PREPARE', {}) if sampler_cfg is not None else {}).items():
+        for func, val in (cfg_get(sampler_cfg, 'PREPARE', {}) if sampler_cfg is not None else {}).items():
             if func == 'filter_by_min_points':
                 db_infos = _filter_by_min_points(db_infos, val)
             elif func == 'filter_by_difficulty':

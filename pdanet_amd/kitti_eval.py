@@ -191,7 +191,6 @@ class _Plan:
 def _run_stages(fr, plan, compute_aos, overlaps=None):
     """Overlaps (unless given), first pass, sort, match on the current stream.  Returns the device overlaps, the flags and
     the one int64 device result buffer of plan.layout."""
-    lib = _lib.load()
     dev = fr.gt[8].device
     T, C = plan.T, plan.C
     res = plan.layout.alloc(dev)
@@ -201,10 +200,8 @@ def _run_stages(fr, plan, compute_aos, overlaps=None):
         overlaps = torch.empty(max(3 * fr.ov_total, 1), dtype=torch.float64, device=dev)
         _call("pda_kitti_eval_overlaps", res, st, overlaps.data_ptr(), out['status'])
     n_gt_total, det_cap = int(fr.gt[0].shape[0]), int(fr.dt[3].shape[0])
-    ws_bytes = lib.pda_kitti_eval_workspace_bytes(len(fr.n_gt), n_gt_total, det_cap, C)
-    if ws_bytes < 0:
-        raise ValueError("KITTI evaluation: sizes out of range")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = ec.workspace("pda_kitti_eval_workspace_bytes", (len(fr.n_gt), n_gt_total, det_cap, C),
+                      "KITTI evaluation: sizes out of range", dev)
     flags = torch.empty(3 * C * (n_gt_total + det_cap) + 1, dtype=torch.int8, device=dev)
     gt_flags, dt_flags = flags[:3 * C * n_gt_total], flags[3 * C * n_gt_total:-1]
     mo = (ctypes.c_double * plan.min_overlaps.size)(*plan.min_overlaps.reshape(-1).tolist())

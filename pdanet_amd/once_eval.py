@@ -105,7 +105,6 @@ class _Plan:
 def _run_stages(fr, plan, with_heading, iou=None):
     """IoU (unless given), accumulate, sort, match on the current stream.  Returns the device iou buffer and the one
     int64 device result buffer of plan.layout."""
-    lib = _lib.load()
     dev = fr.gt_offsets.device
     T = len(plan.classes) * len(plan.diff_types)
     res = plan.layout.alloc(dev)
@@ -115,10 +114,7 @@ def _run_stages(fr, plan, with_heading, iou=None):
         iou = torch.empty(max(fr.iou_total, 1), dtype=torch.float64, device=dev)
         _call("pda_once_eval_iou", res, st, 1 if with_heading else 0, iou.data_ptr(), out['status'])
     n_gt_total = int(fr.gt_boxes.shape[0])
-    ws_bytes = lib.pda_once_eval_workspace_bytes(len(fr.n_gt), n_gt_total, T)
-    if ws_bytes < 0:
-        raise ValueError("ONCE evaluation: sizes out of range")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws = ec.workspace("pda_once_eval_workspace_bytes", (len(fr.n_gt), n_gt_total, T), "ONCE evaluation: sizes out of range", dev)
     thr_c = (ctypes.c_double * len(plan.thr))(*plan.thr.tolist())
     acc = plan.accept.ctypes.data
     args = (acc, len(plan.classes), plan.n_names, thr_c, plan.mode)

@@ -10,8 +10,8 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
 from .pointnet2_batch_cuda import F32, _call, _chk
+from .stage_common import workspace
 
 
 def grid_size(point_cloud_range, voxel_size):
@@ -39,11 +39,9 @@ class VoxelSpec:
         self.grid_c = (ctypes.c_int32 * 3)(*self.grid.tolist())
 
     def workspace(self, batch, n_cap, max_points, dev):
-        nbytes = _lib.load().pda_voxel_workspace_bytes(batch, n_cap, self.max_voxels, max_points)
-        if nbytes < 0:
-            raise ValueError("batch %d / n_cap %d / max voxels %d / points per voxel %d out of range"
-                             % (batch, n_cap, self.max_voxels, max_points))
-        return torch.empty((max(nbytes, 8) // 8 + 1,), dtype=torch.int64, device=dev)       # 8-byte aligned
+        return workspace("pda_voxel_workspace_bytes", (batch, n_cap, self.max_voxels, max_points),
+                         "batch %d / n_cap %d / max voxels %d / points per voxel %d out of range"
+                         % (batch, n_cap, self.max_voxels, max_points), dev)
 
 
 class VoxelGenerator:

@@ -526,7 +526,8 @@ def test_extraction_of_a_large_random_batch():
         p = scans[b][~_near_face64(scans[b], bx, 1e-5)]
         frames.append(p)
         boxes.append(bx)
-    packed, offs_h, n_cap, _ = fs._pack_scenes(frames)
+    from pdanet_amd import stage_common
+    packed, offs_h, n_cap, _ = stage_common.pack_scenes(frames)
     allb = np.concatenate(boxes)
     dev = "cuda"
     obj_points, obj_offs, counts, info = fs.gt_extract(
