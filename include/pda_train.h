@@ -755,6 +755,54 @@ int pda_voxel_sample(const float *points, const int64_t *offsets, int64_t n_tota
                      int64_t perm0_total, uint64_t seed, float *out_points, int64_t out_cap, int64_t *out_offsets,
                      int32_t *info, void *workspace, pda_stream_t stream);
 
+/* ---- dynamic voxelization (csrc/dyn_voxel.hip; the reference's DynamicMeanVFE / DynamicPillarVFE up to their Linear layers:
+ * torch.unique(merge_coords, return_inverse, return_counts) followed by torch_scatter.scatter_mean / scatter_max) -------------
+ * points (n, columns >= 4) float32 = the collated [batch_idx, x, y, z, ...] rows, scenes in any order.  HOST arrays range6,
+ * voxel_size3, grid3 as pda_voxelize takes them; each axis holds 1 .. 2^24 cells.  pillars == 0: cells in x, y, z;
+ * pillars == 1: cells in x and y, z is not tested.  The cell of a coordinate is floor((p - lo) / vs) in float32 with a
+ * correctly rounded division (the function of pda_voxelize).  A row joins nothing when a cell lies outside the grid, when x, y
+ * or z is NaN, or when its batch index (truncated towards zero) lies outside [0, batch).
+ * key = merge_coords: b * gx*gy*gz + cx * gy*gz + cy * gz + cz, pillars b * gx*gy + cx * gy + cy.  The reference computes it
+ * in int32 and wraps silently; here batch * cells >= 2^31 is refused before any launch.
+ * Outputs, all int32, padded to n rows, zero beyond the live counts:
+ *   counts (2) = [n_kept, n_voxels];
+ *   point_idx (n): the kept rows in ascending order (points[mask]); "kept position" i below means point_idx[i];
+ *   unq_inv (n): for kept position i the rank of its key among the distinct keys in ascending order;
+ *   unq_cnt (n): the points of voxel v;  voxel_coords (n, 4): (b, z, y, x), pillars (b, 0, y, x);
+ *   seg_start (n + 1), seg_points (n): voxel v holds the kept positions seg_points[seg_start[v] .. seg_start[v + 1]), ascending;
+ *   seg_start[n_voxels] = n_kept.
+ * workspace: pda_dyn_voxel_workspace_bytes(n, key_bits) bytes, 4-byte aligned, key_bits = the bits of batch * cells - 1
+ * (1 .. 31); -1 for bad sizes.  A stable radix sort of (key, kept position), 8 bits a pass, ceil(key_bits / 8) passes.
+ * Every grid is sized from n alone; nothing is read back or allocated (graph-capturable); the only atomics are integer adds in
+ * LDS, and two runs give the same bits.  n == 0 returns PDA_OK and touches nothing. */
+int64_t pda_dyn_voxel_workspace_bytes(int64_t n, int key_bits);
+int pda_dyn_voxel_index(const float *points, int64_t n, int columns, const float *range6, const float *voxel_size3,
+                        const int32_t *grid3, int batch, int pillars, int32_t *counts, int32_t *point_idx, int32_t *unq_inv,
+                        int32_t *unq_cnt, int32_t *voxel_coords, int32_t *seg_start, int32_t *seg_points, void *workspace,
+                        pda_stream_t stream);
+/* The reductions walk seg_start / seg_points and read the live counts on the device; `rows` is the number of rows the output
+ * holds (rows beyond n_voxels are written as zeros; seg_start holds at least rows + 1 entries).  One thread per (voxel, column).
+ * pda_dyn_scatter_mean: out[v][f] = (the float32 sum of src[p][f] over the voxel's kept positions p in ascending order) /
+ * float32(count): torch_scatter.scatter_mean's sum / count with the order of the sum fixed.  src (>= n_kept, columns).
+ * pda_dyn_scatter_max_fwd: out[v][f] = the maximum, arg[v][f] = the lowest kept position that attains it (torch_scatter's CPU
+ * rule: an update needs a strictly greater value). */
+int pda_dyn_scatter_mean(const float *src, int columns, const int32_t *seg_start, const int32_t *seg_points,
+                         const int32_t *counts, int64_t rows, float *out, pda_stream_t stream);
+int pda_dyn_scatter_max_fwd(const float *x, int columns, const int32_t *seg_start, const int32_t *seg_points,
+                            const int32_t *counts, int64_t rows, float *out, int32_t *arg, pda_stream_t stream);
+/* grad_x (rows, columns): grad_x[p][f] = grad_out[v][f] when p == arg[v][f] for v = unq_inv[p], else 0 -- rows that are the
+ * argmax of nothing and rows beyond n_kept are written as zeros here.  grad_out, arg (vox_rows, columns).  No atomics. */
+int pda_dyn_scatter_max_bwd(const float *grad_out, const int32_t *arg, const int32_t *unq_inv, const int32_t *counts,
+                            int64_t rows, int64_t vox_rows, int columns, float *grad_x, pda_stream_t stream);
+/* The rows DynamicPillarVFE feeds its first PFN layer, for every kept position i (row r = point_idx[i], voxel v = unq_inv[i]):
+ * [points[r, 1:] (absolute_xyz == 1) or points[r, 4:], xyz - mean[v], x - (float32(cx) * vx + offset_x), y - (float32(cy) * vy
+ * + offset_y), z - offset_z, (sqrt(fma(z, z, fma(y, y, x*x))) when with_distance == 1)]; mean (>= n_voxels, 3) from
+ * pda_dyn_scatter_mean; HOST arrays voxel_size3 and offset3 = float32(v / 2 + lo), computed by the caller in double.
+ * out (n, width), width = columns - 1 or columns - 4, + 6, + with_distance; rows beyond n_kept are written as zeros. */
+int pda_dyn_pillar_features(const float *points, int64_t n, int columns, const int32_t *point_idx, const int32_t *unq_inv,
+                            const int32_t *voxel_coords, const float *mean, const int32_t *counts, const float *voxel_size3,
+                            const float *offset3, int absolute_xyz, int with_distance, float *out, pda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

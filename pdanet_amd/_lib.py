@@ -210,6 +210,14 @@ SIGNATURES = {
     "pda_voxel_sample": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, ctypes.POINTER(_f), ctypes.POINTER(_f),
                          ctypes.POINTER(ctypes.c_int32), _i, _i, _i, _i, _i, _vp, _vp, ctypes.c_int64, ctypes.c_uint64, _vp,
                          ctypes.c_int64, _vp, _vp, _vp, _vp],
+    "pda_dyn_voxel_workspace_bytes": [ctypes.c_int64, _i],
+    "pda_dyn_voxel_index": [_vp, ctypes.c_int64, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), ctypes.POINTER(ctypes.c_int32),
+                            _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pda_dyn_scatter_mean": [_vp, _i, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp],
+    "pda_dyn_scatter_max_fwd": [_vp, _i, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp],
+    "pda_dyn_scatter_max_bwd": [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _vp, _vp],
+    "pda_dyn_pillar_features": [_vp, ctypes.c_int64, _i, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_f), ctypes.POINTER(_f), _i,
+                                _i, _vp, _vp],
     # include/pda_pointnet2_stack.h
     "pda_stack_ball_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     "pda_stack_group_points": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -269,6 +277,7 @@ def load():
     lib.pda_kitti_fov_filter_workspace_bytes.restype = ctypes.c_int64
     lib.pda_gt_extract_workspace_bytes.restype = ctypes.c_int64
     lib.pda_voxel_workspace_bytes.restype = ctypes.c_int64
+    lib.pda_dyn_voxel_workspace_bytes.restype = ctypes.c_int64
     lib.pda_abi_version.restype = _i
     lib.pda_last_error.restype = ctypes.c_char_p
     lib.pda_fp_contract_mode.restype = _i

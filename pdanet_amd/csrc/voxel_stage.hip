@@ -24,6 +24,7 @@
 #include "pda_common.h"
 #include "ragged_scene.h"
 #include "stage_rng.h"
+#include "voxel_cell.h"
 
 namespace pda {
 namespace {
@@ -48,17 +49,12 @@ __device__ __forceinline__ uint64_t perm0_key(uint64_t seed, int b) {
     return splitmix64(~seed ^ splitmix64(0x766f78656c5f7030ull + (uint64_t)b));
 }
 
-// The cell of a point: false when a coordinate is NaN or falls outside the grid.  `/` is the correctly rounded float32
-// division (HIP's default -fhip-fp32-correctly-rounded-divide-sqrt): a reciprocal multiply would move points that lie on a
-// voxel face into the neighbouring cell.
+// The cell of a point (voxel_cell.h): false when a coordinate is NaN or falls outside the grid.
 __device__ __forceinline__ bool cell_of(const float* __restrict__ p, const Grid& g, uint32_t& key) {
     uint32_t c[3];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float f = __builtin_floorf((p[a] - g.lo[a]) / g.vs[a]);
-        if (is_nan_bits(f) || f < 0.f || f >= (float)g.n[a]) return false;
-        c[a] = (uint32_t)(int)f;
-    }
+    for (int a = 0; a < 3; ++a)
+        if (!cell_axis(p[a], g.lo[a], g.vs[a], g.n[a], c[a])) return false;
     key = (c[2] * (uint32_t)g.n[1] + c[1]) * (uint32_t)g.n[0] + c[0];
     return true;
 }

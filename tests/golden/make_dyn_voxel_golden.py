@@ -1,0 +1,361 @@
+#!/usr/bin/env python
+"""Generates tests/golden/dyn_voxel.npz: the REFERENCE's dynamic encoders
+(/root/reference/pcdet/models/backbones_3d/vfe/dynamic_mean_vfe.py DynamicMeanVFE and dynamic_pillar_vfe.py
+DynamicPillarVFE / PFNLayerV2) run on the CPU over one synthetic collated batch, in the two settings of the Waymo recipes
+centerpoint_dyn_pillar_1x.yaml and voxel_rcnn_with_centerhead_dyn_voxel.yaml.
+
+The two files are loaded the way make_input_golden.py loads the processor: stub packages for the absent ones, nothing
+copied.  Tensor.cuda() is a no-op while the constructors run (they move three tensors).  torch_scatter is not installed
+and WAS NOT RUN: sys.modules holds the stand-in defined below, which states the contract of the two functions the
+encoders call:
+  scatter_mean(src, index, dim=0): the sum over the rows of a segment in ascending row order (np.add.at, in src's dtype)
+                                   divided by the count in that dtype;
+  scatter_max(src, index, dim=0):  (out, arg) by the first-strictly-greater rule over the rows in ascending order, the rule
+                                   of torch_scatter's CPU kernel: arg is the lowest row that attains the maximum.  Its
+                                   backward sends grad_out[v, f] to row arg[v, f].
+Everything else -- the cells, the mask, merge_coords, torch.unique, the feature rows, Linear / BatchNorm1d / ReLU, the
+coordinates -- is the reference's own code.  Only inputs, settings and outputs are stored.
+
+DynamicPillarVFE is also run in float64 (module.double(), the same points).  The cells of a float64 quotient differ from
+the float32 ones for points one float32 step from a voxel face, so for that run torch.floor inside the reference module is
+replaced by a lookup of the float32 run's cells: both runs group the same points.  dev_ref_* = the largest absolute
+deviation of the float32 run from the float64 one, per output.  The float64 arrays are stored as the float32 run plus a
+float32 difference (`*_d64`): float64 value = float64(f32) + float64(d64), far below dev_ref.
+
+The feature rows the first PFN layer sees are stored as their computed columns only (`pillar_fcols`: f_cluster, f_center,
+dist); the leading columns are columns of `points`.
+
+Run here only:  python tests/golden/make_dyn_voxel_golden.py
+"""
+import importlib
+import os
+import sys
+import types
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REF = "/root/reference"
+OUT = os.path.join(HERE, "dyn_voxel.npz")
+BATCH, C = 3, 5
+VOXEL = dict(voxel_size=[0.1, 0.1, 0.15], range=[-75.2, -75.2, -2, 75.2, 75.2, 4])
+PILLAR = dict(voxel_size=[0.32, 0.32, 6], range=[-74.88, -74.88, -2, 74.88, 74.88, 4])
+PILLAR_CASES = (("abs_dist", True, True), ("rel", False, False))      # tag, USE_ABSLOTE_XYZ, WITH_DISTANCE
+NUM_FILTERS = [64, 64]
+
+
+class AD(dict):
+    def __getattr__(self, k):
+        try:
+            return self[k]
+        except KeyError:
+            raise AttributeError(k)
+
+
+# ---- the stand-in torch_scatter --------------------------------------------------------------------------------------------
+def scatter_mean_np(src, index, size):
+    total = np.zeros((size,) + src.shape[1:], src.dtype)
+    np.add.at(total, index, src)                      # unbuffered: row after row, in src's dtype
+    count = np.bincount(index, minlength=size).astype(src.dtype)
+    return total / count.reshape((-1,) + (1,) * (src.ndim - 1))
+
+
+def scatter_max_np(src, index, size):
+    out = np.full((size, src.shape[1]), np.finfo(src.dtype).min, src.dtype)
+    arg = np.full((size, src.shape[1]), src.shape[0], np.int64)
+    for i in range(src.shape[0]):
+        v = index[i]
+        upd = src[i] > out[v]                         # strictly greater: the first row that attains the maximum stays
+        out[v][upd] = src[i][upd]
+        arg[v][upd] = i
+    return out, arg
+
+
+class _ScatterMax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, src, index):
+        size = int(index.max()) + 1
+        out, arg = scatter_max_np(src.detach().numpy(), index.numpy(), size)
+        ctx.rows = src.shape[0]
+        arg = torch.from_numpy(arg)
+        ctx.save_for_backward(arg)
+        ctx.mark_non_differentiable(arg)
+        return torch.from_numpy(out), arg
+
+    @staticmethod
+    def backward(ctx, grad_out, _):
+        arg, = ctx.saved_tensors
+        grad = torch.zeros((ctx.rows, grad_out.shape[1]), dtype=grad_out.dtype)
+        cols = torch.arange(grad_out.shape[1]).expand_as(arg)
+        grad[arg.reshape(-1), cols.reshape(-1)] = grad_out.reshape(-1)
+        return grad, None
+
+
+def install_torch_scatter():
+    def scatter_mean(src, index, dim=0):
+        assert dim == 0
+        return torch.from_numpy(scatter_mean_np(src.detach().numpy(), index.numpy(), int(index.max()) + 1))
+
+    def scatter_max(src, index, dim=0):
+        assert dim == 0
+        return _ScatterMax.apply(src, index)
+
+    m = types.ModuleType("torch_scatter")
+    m.scatter_mean, m.scatter_max = scatter_mean, scatter_max
+    sys.modules["torch_scatter"] = m
+    return m
+
+
+def import_reference():
+    install_torch_scatter()
+    for pkg in ("pcdet", "pcdet.models", "pcdet.models.backbones_3d", "pcdet.models.backbones_3d.vfe"):
+        m = types.ModuleType(pkg)
+        m.__path__ = [REF + "/" + pkg.replace(".", "/")]
+        sys.modules[pkg] = m
+    mean = importlib.import_module("pcdet.models.backbones_3d.vfe.dynamic_mean_vfe")
+    pillar = importlib.import_module("pcdet.models.backbones_3d.vfe.dynamic_pillar_vfe")
+    return mean, pillar
+
+
+class no_cuda:
+    """Tensor.cuda() returns the tensor itself while a constructor runs."""
+
+    def __enter__(self):
+        self.cuda = torch.Tensor.cuda
+        torch.Tensor.cuda = lambda t, *a, **k: t
+
+    def __exit__(self, *a):
+        torch.Tensor.cuda = self.cuda
+
+
+class FloorLookup:
+    """Stands for `torch` inside the reference module during the float64 run: floor() answers the float32 run's cells."""
+
+    def __init__(self, cells):
+        self.cells = cells
+
+    def floor(self, x):
+        assert x.shape == self.cells.shape
+        return self.cells.to(x.dtype)
+
+    def __getattr__(self, name):
+        return getattr(torch, name)
+
+
+def grid_of(setting):
+    pr = np.asarray(setting["range"], np.float64)
+    return np.round((pr[3:6] - pr[0:3]) / np.array(setting["voxel_size"])).astype(np.int64)
+
+
+# ---- the scenes ------------------------------------------------------------------------------------------------------------
+def _q(x):
+    return (np.round(np.asarray(x, np.float64) * 256.0) / 256.0).astype(np.float32)      # compressible values
+
+
+def make_points(rng):
+    f = np.float32
+    vlo, vvs = np.array(VOXEL["range"][:3]), np.array(VOXEL["voxel_size"])
+    plo, pvs = np.array(PILLAR["range"][:3]), np.array(PILLAR["voxel_size"])
+    rows = []          # (scene, xyz (m, 3) float32)
+
+    def in_voxel(cell, m):
+        return (vlo + (np.array(cell) + rng.uniform(0.1, 0.9, (m, 3))) * vvs).astype(f)
+
+    rows.append((0, in_voxel((900, 700, 17), 1100)))                    # one voxel with more than 1 024 points
+    rows.append((1, in_voxel((333, 1200, 9), 257)))                     # one with 257
+    # most points: inside 120 pillars, spread over their voxels (mostly one point a voxel)
+    cells = set()
+    while len(cells) < 120:
+        cells.add((int(rng.integers(5, 460)), int(rng.integers(5, 460))))
+    cells = np.array(sorted(cells))
+    pick = cells[rng.integers(0, len(cells), 4300)]
+    xy = plo[:2] + (pick + rng.uniform(0.03, 0.97, (4300, 2))) * pvs[:2]
+    body = np.concatenate([_q(xy), _q(rng.uniform(-1.9, 3.9, (4300, 1)))], 1)
+    scene = rng.integers(0, 2, 4300)
+    rows += [(0, body[scene == 0]), (1, body[scene == 1])]
+    # isolated points: pillars and voxels with exactly one point
+    iso = np.concatenate([_q(rng.uniform(-74, 74, (110, 2))), _q(rng.uniform(-1.9, 3.9, (110, 1)))], 1)
+    rows += [(0, iso[:55]), (1, iso[55:])]
+    # outside the range on each of the six sides (both ranges), 12 points a side
+    for axis, lo, hi in ((0, -75.2, 75.2), (1, -75.2, 75.2), (2, -2.0, 4.0)):
+        for sign in (-1, 1):
+            p = np.concatenate([rng.uniform(-70, 70, (12, 2)), rng.uniform(-1.5, 3.5, (12, 1))], 1)
+            if axis == 2:          # outside in z only: x, y of an occupied pillar; pillars keep them, voxels drop them
+                p[:, :2] = plo[:2] + (cells[rng.integers(0, len(cells), 12)] + rng.uniform(0.1, 0.9, (12, 2))) * pvs[:2]
+            p[:, axis] = (lo - rng.uniform(0.01, 9, 12)) if sign < 0 else (hi + rng.uniform(0.01, 9, 12))
+            rows.append((int(rng.integers(0, 2)), _q(p)))
+    # on voxel faces and one float32 step either side, both grids; the limits themselves
+    mid = [f(3.3), f(-7.1), f(0.8)]
+    face = []
+    for setting, axes, ks in ((VOXEL, (0, 1, 2), ((1, 700, 1503), (2, 801, 1502), (1, 20, 39))),
+                              (PILLAR, (0, 1), ((1, 234, 467), (2, 301, 466)))):
+        lo, vs = np.array(setting["range"][:3]), np.array(setting["voxel_size"])
+        for axis, kk in zip(axes, ks):
+            for k in kk:
+                v0 = f(lo[axis] + k * vs[axis])
+                for v in (v0, np.nextafter(v0, f(-1e9)), np.nextafter(v0, f(1e9))):
+                    p = list(mid)
+                    p[axis] = v
+                    p[(axis + 1) % 2] = f(p[(axis + 1) % 2] + 0.7 * (k % 5))
+                    face.append(p)
+        hi = np.array(setting["range"][3:])
+        for axis in axes:
+            for v in (f(lo[axis]), f(hi[axis]), np.nextafter(f(lo[axis]), f(-1e9)), np.nextafter(f(hi[axis]), f(-1e9))):
+                p = list(mid)
+                p[axis] = v
+                face.append(p)
+    face = np.array(face, f)
+    rows += [(0, face[0::2]), (1, face[1::2])]
+    rows.append((2, np.array([[f(10.25), f(-20.5), f(1.0)]], f)))      # a scene with a single point
+    b = np.concatenate([np.full(len(x), s) for s, x in rows])
+    xyz = np.concatenate([x for _, x in rows])
+    pts = np.zeros((len(xyz), 1 + C), f)
+    pts[:, 0], pts[:, 1:4] = b, xyz
+    pts[:, 4:] = _q(rng.uniform(0, 1, (len(xyz), C - 3)))
+    dup = pts[rng.integers(1100 + 257, len(pts) - 1, 30)]               # exact duplicates, none of the two counted voxels
+    pts = np.concatenate([pts, dup])
+    return pts[rng.permutation(len(pts))]                               # the scenes' rows interleaved
+
+
+# ---- the runs --------------------------------------------------------------------------------------------------------------
+def index_outputs(points, setting, pillars):
+    """The reference's own index expressions (forward's first lines), for storing what torch.unique gives."""
+    t = torch.from_numpy(points)
+    pr, vs = torch.tensor(setting["range"]), torch.tensor(setting["voxel_size"])
+    grid = torch.tensor(grid_of(setting))
+    if pillars:
+        pc = torch.floor((t[:, [1, 2]] - pr[[0, 1]]) / vs[[0, 1]]).int()
+        mask = ((pc >= 0) & (pc < grid[[0, 1]])).all(dim=1)
+    else:
+        pc = torch.floor((t[:, 1:4] - pr[0:3]) / vs).int()
+        mask = ((pc >= 0) & (pc < grid)).all(dim=1)
+    return mask.numpy(), torch.floor((t[:, 1:4] - pr[0:3]) / vs)
+
+
+def capture_unique():
+    """Wraps torch.unique to keep what the reference's forward got from it."""
+    seen = {}
+    real = torch.unique
+
+    def unique(*a, **k):
+        out = real(*a, **k)
+        seen["unq"], seen["inv"], seen["cnt"] = (o.numpy().copy() for o in out)
+        return out
+    torch.unique = unique
+    return seen, real
+
+
+def projection(rows, cols):
+    v, f = np.meshgrid(np.arange(rows), np.arange(cols), indexing="ij")
+    return np.sin(0.37 * v + 1.3 * f + 0.5)
+
+
+def run_pillar(pillar_mod, points, use_abs, with_dist, dtype, state, cells):
+    cfg = AD(USE_NORM=True, WITH_DISTANCE=with_dist, USE_ABSLOTE_XYZ=use_abs, NUM_FILTERS=NUM_FILTERS)
+    with no_cuda():
+        vfe = pillar_mod.DynamicPillarVFE(cfg, C, PILLAR["voxel_size"], grid_of(PILLAR).tolist(), PILLAR["range"])
+    if state is None:
+        torch.manual_seed(20261018)
+        for p in vfe.parameters():                      # seeded weights; BatchNorm away from its identity start
+            p.data.copy_(torch.randn(p.shape) * (0.5 if p.dim() > 1 else 0.3) + (1.0 if p.dim() == 1 else 0.0))
+        state = {k: v.clone() for k, v in vfe.state_dict().items()}
+    vfe.load_state_dict(state, strict=True)
+    vfe = vfe.to(dtype).train()
+    head = torch.from_numpy(points[:, :4]).to(dtype)
+    extra = torch.from_numpy(points[:, 4:]).to(dtype).requires_grad_(True)
+    feats_seen = {}
+    layer0 = vfe.pfn_layers[0]
+    layer0.register_forward_pre_hook(lambda m, inp: feats_seen.__setitem__("features", inp[0].detach().numpy().copy()))
+    if cells is not None:
+        pillar_mod.torch = FloorLookup(cells)
+    try:
+        out = vfe({"points": torch.cat([head, extra], 1), "batch_size": BATCH})
+    finally:
+        pillar_mod.torch = torch
+    pf = out["pillar_features"]
+    loss = pf.sum() + (pf * torch.from_numpy(projection(*pf.shape)).to(dtype)).sum()
+    loss.backward()
+    res = {"pillar_features": pf.detach().numpy(), "grad_extra": extra.grad.numpy(),
+           "voxel_coords": out["voxel_coords"].numpy(), "features": feats_seen["features"]}
+    for k, p in vfe.named_parameters():
+        res["grad." + k] = p.grad.numpy()
+    return res, state
+
+
+def main():
+    mean_mod, pillar_mod = import_reference()
+    rng = np.random.default_rng(20261018)
+    points = make_points(rng)
+    n = len(points)
+    data = {"points": points, "batch": np.array(BATCH), "num_filters": np.array(NUM_FILTERS)}
+    seen, real_unique = capture_unique()
+    try:
+        # ---- DynamicMeanVFE, the voxel setting -------------------------------------------------------------------------
+        with no_cuda():
+            vfe = mean_mod.DynamicMeanVFE(AD(), C, VOXEL["voxel_size"], grid_of(VOXEL).tolist(), VOXEL["range"])
+        out = vfe({"points": torch.from_numpy(points), "batch_size": BATCH})
+        mask, _ = index_outputs(points, VOXEL, False)
+        data.update(voxel_range=np.array(VOXEL["range"], np.float64), voxel_size=np.array(VOXEL["voxel_size"], np.float64),
+                    voxel_grid=grid_of(VOXEL), voxel_point_idx=np.nonzero(mask)[0].astype(np.int32),
+                    voxel_unq_inv=seen["inv"].astype(np.int32), voxel_unq_cnt=seen["cnt"].astype(np.int32),
+                    voxel_coords=out["voxel_coords"].numpy().astype(np.int32), voxel_features=out["voxel_features"].numpy())
+        vcnt = seen["cnt"]
+        assert vcnt.max() == 1100 and (vcnt == 257).sum() == 1
+        # ---- DynamicPillarVFE, the pillar setting ------------------------------------------------------------------------
+        pmask, cells = index_outputs(points, PILLAR, True)
+        data.update(pillar_range=np.array(PILLAR["range"], np.float64), pillar_size=np.array(PILLAR["voxel_size"], np.float64),
+                    pillar_grid=grid_of(PILLAR), pillar_point_idx=np.nonzero(pmask)[0].astype(np.int32))
+        state, fcols, report = None, None, []
+        for tag, use_abs, with_dist in PILLAR_CASES:
+            r32, state = run_pillar(pillar_mod, points, use_abs, with_dist, torch.float32, None, None)
+            inv, cnt = seen["inv"].copy(), seen["cnt"].copy()
+            r64, _ = run_pillar(pillar_mod, points, use_abs, with_dist, torch.float64, state, cells[:, :2])
+            assert np.array_equal(inv, seen["inv"]) and np.array_equal(r32["voxel_coords"], r64["voxel_coords"])
+            lead = points[pmask][:, 1:] if use_abs else points[pmask][:, 4:]
+            assert np.array_equal(r32["features"][:, :lead.shape[1]], lead)
+            cols = r32["features"][:, lead.shape[1]:lead.shape[1] + 6]
+            assert fcols is None or np.array_equal(cols, fcols[:, :6])
+            if with_dist:
+                fcols = r32["features"][:, lead.shape[1]:]
+                xyz = points[pmask][:, 1:4]
+                # what torch.norm evaluates on the CPU, and the expression csrc/dyn_voxel.hip writes: fused multiply-adds in
+                # column order (a float64 product of two float32 values is exact, so the float64 sum rounds once more)
+                fma = lambda a, b, c: (a.astype(np.float64) * b + c).astype(np.float32)      # noqa: E731
+                d = np.sqrt(fma(xyz[:, 2], xyz[:, 2], fma(xyz[:, 1], xyz[:, 1], xyz[:, 0] * xyz[:, 0])))
+                assert d.dtype == np.float32 and np.array_equal(d, fcols[:, 6]), "torch.norm is not sqrt(fma(z, z, fma(y, y, x*x)))"
+            data["pillar_unq_inv"], data["pillar_unq_cnt"] = inv.astype(np.int32), cnt.astype(np.int32)
+            data["pillar_coords"] = r32["voxel_coords"].astype(np.int32)
+            for k, v in state.items():
+                data["%s_state.%s" % (tag, k)] = v.numpy()
+            data[tag + "_state_keys"] = np.array(list(state.keys()))
+            for k in r32:
+                if k in ("voxel_coords", "features"):
+                    continue
+                data["%s_%s" % (tag, k)] = r32[k]
+                data["%s_%s_d64" % (tag, k)] = (r64[k] - r32[k].astype(np.float64)).astype(np.float32)
+                data["dev_ref_%s_%s" % (tag, k)] = np.array(np.abs(r64[k] - r32[k].astype(np.float64)).max())
+                report.append("%s %s: shape %s, |f64| max %.3g, dev_ref %.3g"
+                              % (tag, k, r32[k].shape, np.abs(r64[k]).max(), data["dev_ref_%s_%s" % (tag, k)]))
+        data["pillar_fcols"] = fcols
+        xyz = points[pmask][:, 1:4]
+        data["pillar_mean"] = scatter_mean_np(xyz, data["pillar_unq_inv"], len(data["pillar_unq_cnt"]))
+        # ---- scatter_max on its own: small integers, so ties are the rule ------------------------------------------------
+        x = rng.integers(0, 4, (int(pmask.sum()), 8)).astype(np.float32) - 1.0
+        mx, arg = scatter_max_np(x, data["pillar_unq_inv"], len(data["pillar_unq_cnt"]))
+        data.update(smax_x=x, smax_out=mx, smax_arg=arg.astype(np.int32))
+    finally:
+        torch.unique = real_unique
+    np.savez_compressed(OUT, **data)
+    pcnt = data["pillar_unq_cnt"]
+    print("%d rows; scenes %s" % (n, np.bincount(points[:, 0].astype(int)).tolist()))
+    print("voxels: kept %d, %d voxels, largest %s, with one point %d" % (mask.sum(), len(vcnt), np.sort(vcnt)[-3:].tolist(),
+                                                                         (vcnt == 1).sum()))
+    print("pillars: kept %d, %d pillars, largest %s, with one point %d; kept by pillars only %d"
+          % (pmask.sum(), len(pcnt), np.sort(pcnt)[-3:].tolist(), (pcnt == 1).sum(), (pmask & ~mask).sum()))
+    print("\n".join(report))
+    print("wrote %s (%d bytes)" % (OUT, os.path.getsize(OUT)))
+
+
+if __name__ == "__main__":
+    main()
