@@ -153,13 +153,18 @@ __device__ __forceinline__ void group_attention_tile(const TIO* __restrict__ qkv
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int j = acc_row(r, h2);
-            T[r] = key_ok(j) ? T[r] * scale + ((RAGGED && j == lo) ? lnw : 0.f) : -__builtin_inff();
+            T[r] = key_ok(j) ? T[r] * scale : -__builtin_inff();
             m = fmaxf(m, T[r]);
         }
         m = fmaxf(m, __shfl_xor(m, 32));
+        // the log-multiplicity of key 0 joins AFTER the maximum is taken off: added to a score in the thousands it would be
+        // rounded to that score's ulp (2.4e-4 at 3000) on this one key alone, a relative error of the same size in its weight
         float l = 0.f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { P[r] = __expf(T[r] - m); l += P[r]; }
+        for (int r = 0; r < 16; ++r) {
+            P[r] = __expf((T[r] - m) + ((RAGGED && acc_row(r, h2) == lo) ? lnw : 0.f));
+            l += P[r];
+        }
         l += __shfl_xor(l, 32);
         const float inv = 1.f / l;
 #pragma unroll
@@ -171,8 +176,18 @@ __device__ __forceinline__ void group_attention_tile(const TIO* __restrict__ qkv
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int j = acc_row(r, h2);
-            P[r] = key_ok(j) ? __expf(T[r] * scale + ((RAGGED && j == lo) ? lnw : 0.f) - lse_i) : 0.f;
+            P[r] = key_ok(j) ? __expf((T[r] * scale - lse_i) + ((RAGGED && j == lo) ? lnw : 0.f)) : 0.f;
         }
+        // lse is an f32: with scores in the thousands its rounding (half an ulp of ~3000 = 1.2e-4) scales every P of the row by
+        // the same factor, the row no longer sums to 1 and dS = P (dP - sum P dP) keeps 1e-4 |dP| of the term that must cancel.
+        // Renormalising the recomputed row removes the common factor (the forward divides by its own sum in the same way).
+        float l = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) l += P[r];
+        l += __shfl_xor(l, 32);
+        const float inv = l > 0.f ? 1.f / l : 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) P[r] *= inv;
     }
 
     // A operand fetched in accumulator key order: x[key j(t,h2)][dblk*32 + c] (128-byte rows per half wave)

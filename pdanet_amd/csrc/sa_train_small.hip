@@ -243,24 +243,29 @@ struct SsWalk {
     }
 };
 
-__device__ __forceinline__ float ss_half_sum(float v) {     // sum over the 32 lanes of my half (every lane gets it)
+__device__ __forceinline__ double ss_half_sum(double v) {     // sum over the 32 lanes of my half (every lane gets it)
 #pragma unroll
     for (int o = 1; o < 32; o <<= 1) v += __shfl_xor(v, o);
     return v;
 }
 
-// per-lane (sum, weighted sum) registers of NB row blocks -> the workgroup's partial [2][64] (doubles, fixed order)
-template <int NB, int W>
-__device__ __forceinline__ void ss_store_partial(float (&s1)[NB][16], float (&s2)[NB][16], double* __restrict__ part, float* lds) {
+// per-lane (sum, weighted sum) registers of NB row blocks -> the workgroup's partial [2][64] (doubles, fixed order).
+// T = double: the forward statistics (sum z, sum z^2), accumulated in double from the first tile on -- a raw input channel far
+// from zero mean (an intensity of 0-255, a timestamp, an absolute height) puts |mean| / std of z1 in the hundreds, where
+// E[z^2] - mean^2 cancels every digit a float sum of squares holds.  T = float: the backward sums, whose terms are products
+// with the normalised activation (|mean| / std <= 1 whatever the input); they are widened here, before the lanes are added.
+template <int NB, int W, typename T>
+__device__ __forceinline__ void ss_store_partial(T (&s1)[NB][16], T (&s2)[NB][16], double* __restrict__ part, float* lds_f) {
     const int w = wave_id(), lane = lane_id(), h = lane >> 5;
+    double* lds = reinterpret_cast<double*>(lds_f);    // [W][128] doubles: 8 KB of the waves' 16-byte aligned tile area
     __syncthreads();                                   // the tile loop's LDS traffic is over in every wave
-    for (int e = threadIdx.x; e < W * 128; e += blockDim.x) lds[e] = 0.f;
+    for (int e = threadIdx.x; e < W * 128; e += blockDim.x) lds[e] = 0.0;
     __syncthreads();
 #pragma unroll
     for (int b = 0; b < NB; ++b)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const float a = ss_half_sum(s1[b][i]), c = ss_half_sum(s2[b][i]);
+            const double a = ss_half_sum((double)s1[b][i]), c = ss_half_sum((double)s2[b][i]);
             if ((lane & 31) == 0) {
                 const int ch = b * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
                 lds[w * 128 + ch] = a;
@@ -271,7 +276,7 @@ __device__ __forceinline__ void ss_store_partial(float (&s1)[NB][16], float (&s2
     if (threadIdx.x < 128) {
         double a = 0.0;
 #pragma unroll
-        for (int ww = 0; ww < W; ++ww) a += (double)lds[ww * 128 + threadIdx.x];
+        for (int ww = 0; ww < W; ++ww) a += lds[ww * 128 + threadIdx.x];
         part[threadIdx.x] = a;
     }
 }
@@ -346,11 +351,11 @@ __global__ __launch_bounds__(W * 64) void ss_fwd_kernel(const SsParams p) {
     const float* st2 = smem + SS_LDS_WPACK + ss_state_base(2);
     const float* st3 = smem + SS_LDS_WPACK + ss_state_base(3);
     constexpr int NB = STAGE == 3 ? R3 : 1;
-    float s1[NB][16], s2[NB][16];
+    double s1[NB][16], s2[NB][16];     // double from the first tile on (ss_store_partial); the squares are exact
 #pragma unroll
     for (int b = 0; b < NB; ++b)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) { s1[b][i] = 0.f; s2[b][i] = 0.f; }
+        for (int i = 0; i < 16; ++i) { s1[b][i] = 0.0; s2[b][i] = 0.0; }
     // STAGE 4, entry role: lane e <-> (group e / c3 of the tile, channel e % c3); (32 / NS) * c3 == 64
     const int ech = lane % p.c3, eg = lane / p.c3;
     float emu = 0.f, eis = 0.f, ega = 0.f, ebe = 0.f;
@@ -367,14 +372,14 @@ __global__ __launch_bounds__(W * 64) void ss_fwd_kernel(const SsParams p) {
         ss_mm<4, 1>(a1, SsX0{x0}, w1);
         if (STAGE == 1) {
 #pragma unroll
-            for (int i = 0; i < 16; ++i) { s1[0][i] += a1[0][i]; s2[0][i] += a1[0][i] * a1[0][i]; }
+            for (int i = 0; i < 16; ++i) { const double z = a1[0][i]; s1[0][i] += z; s2[0][i] += z * z; }
             continue;
         }
         ss_bn_relu<false>(a1[0], dummy, st1, 32, 0, h);
         ss_mm<16, 1>(a2, SsAcc<1>{a1}, w2);
         if (STAGE == 2) {
 #pragma unroll
-            for (int i = 0; i < 16; ++i) { s1[0][i] += a2[0][i]; s2[0][i] += a2[0][i] * a2[0][i]; }
+            for (int i = 0; i < 16; ++i) { const double z = a2[0][i]; s1[0][i] += z; s2[0][i] += z * z; }
             continue;
         }
         ss_bn_relu<false>(a2[0], dummy, st2, 32, 0, h);
@@ -383,7 +388,7 @@ __global__ __launch_bounds__(W * 64) void ss_fwd_kernel(const SsParams p) {
 #pragma unroll
             for (int b = 0; b < NB; ++b)
 #pragma unroll
-                for (int i = 0; i < 16; ++i) { s1[b][i] += a3[b][i]; s2[b][i] += a3[b][i] * a3[b][i]; }
+                for (int i = 0; i < 16; ++i) { const double z = a3[b][i]; s1[b][i] += z; s2[b][i] += z * z; }
             continue;
         }
         // ---- STAGE 4: transposed z3 tile, then one lane per (group, channel) scans the group's slots in order
@@ -404,7 +409,7 @@ __global__ __launch_bounds__(W * 64) void ss_fwd_kernel(const SsParams p) {
         p.arg[tile * 64 + lane] = (uint8_t)bs;
         ss_wave_fence();                  // my reads are done before the next tile's writes
     }
-    if (STAGE <= 3) ss_store_partial<NB, W>(s1, s2, p.partial + (size_t)blockIdx.x * SS_PART, lds_all);
+    if (STAGE <= 3) ss_store_partial<NB, W, double>(s1, s2, p.partial + (size_t)blockIdx.x * SS_PART, lds_all);
 }
 
 // ---- backward passes --------------------------------------------------------------------------------------------------
@@ -590,7 +595,7 @@ __global__ __launch_bounds__(W * 64) void ss_bwd_kernel(const SsParams p) {
             }
         }
     }
-    if (STAGE >= 2) ss_store_partial<1, W>(s1, s2, p.partial + (size_t)blockIdx.x * SS_PART, lds_all);
+    if (STAGE >= 2) ss_store_partial<1, W, float>(s1, s2, p.partial + (size_t)blockIdx.x * SS_PART, lds_all);
     ss_store_dw<NBW, W>(dw, p.dw_partial + (size_t)blockIdx.x * SS_DW, lds_all);
 }
 

@@ -106,8 +106,15 @@ def test_sa_layers_vs_reference_composition(name, cls_name, mlp_key, feat_key):
     got_idx = sidx.cpu().numpy()
     for b in range(ref_idx.shape[0]):
         assert set(ref_idx[b].tolist()) == set(got_idx[b].tolist())
-    if np.array_equal(ref_idx, got_idx):
-        (close if name == "sa" else close_dense)(nf, G["%s_ctr_new_features" % name])
+    # the sets are equal and top-k indices are distinct: the permutation that takes got_idx[b] to ref_idx[b], applied to the
+    # centre axis of nf (B, C, npoint) -- the features are compared whatever order the ties came out in
+    rows = []
+    for b in range(ref_idx.shape[0]):
+        order = np.argsort(got_idx[b], kind="stable")
+        perm = order[np.searchsorted(got_idx[b][order], ref_idx[b])]
+        assert np.array_equal(got_idx[b][perm], ref_idx[b])
+        rows.append(nf[b].index_select(-1, torch.from_numpy(perm).to(nf.device)))
+    (close if name == "sa" else close_dense)(torch.stack(rows), G["%s_ctr_new_features" % name])
 
 
 @gpu
@@ -136,11 +143,12 @@ def test_fp_module_vs_reference_composition():
     close(out, G["fp_out"])      # north_star: interpolated features within 1e-4
 
 
-@gpu
-@pytest.mark.parametrize("mode", ["eval", "train"])
-def test_backbone_vs_reference_composition(mode):
+@pytest.fixture(scope="module", params=["eval", "train"])
+def backbone_forward(request):
+    """(mode, batch_dict) of one backbone forward on the golden scene, shared by the two tests below."""
     from pdanet_amd import synth, config
     from pdanet_amd.backbone import IASSD_Backbone
+    mode = request.param
     cfg = config.load_yaml("once_pda_ssd.yaml")
     cfg.MODEL.BACKBONE_3D.SA_CONFIG.NPOINT_LIST = META["backbone_npoint_list"]
     model = fill_deterministic(IASSD_Backbone(cfg.MODEL.BACKBONE_3D, num_class=5, input_channels=4)).cuda()
@@ -148,6 +156,16 @@ def test_backbone_vs_reference_composition(mode):
     pts = torch.from_numpy(synth.batch_points(2, 2048, config_id=91, dist="L")).cuda()
     with torch.no_grad():
         bd = model({"batch_size": 2, "points": pts})
+    return mode, bd
+
+
+def _xyz_rows(a):
+    return [tuple(r) for r in a.round(4).tolist()]
+
+
+@gpu
+def test_backbone_vs_reference_composition(backbone_forward):
+    mode, bd = backbone_forward
     # layer 1 samples with D-FPS: coordinates are gathered, so they must match bit for bit
     assert np.array_equal(bd["encoder_xyz"][1].cpu().numpy(), G["bb_%s_encoder_xyz_1" % mode])
     assert np.array_equal(bd["encoder_xyz"][2].cpu().numpy(), G["bb_%s_encoder_xyz_2" % mode])
@@ -162,18 +180,42 @@ def test_backbone_vs_reference_composition(mode):
             a = {tuple(r) for r in ref[b].round(4).tolist()}
             c = {tuple(r) for r in got[b].round(4).tolist()}
             assert len(a & c) >= 0.98 * len(a), (li, len(a & c), len(a))
-    same_order = all(np.array_equal(bd["encoder_xyz"][li].cpu().numpy(), G["bb_%s_encoder_xyz_%d" % (mode, li)])
-                     for li in (3, 4))
-    if same_order:
-        close(bd["centers"], G["bb_%s_centers" % mode], atol=1e-3, rtol=1e-3)
-        close(bd["ctr_offsets"], G["bb_%s_ctr_offsets" % mode], atol=1e-3, rtol=1e-3)
-        close(bd["centers_features"], G["bb_%s_centers_features" % mode], atol=2e-3, rtol=2e-3)
     for li in range(1, 7):
         if li == 5:
             continue  # vote layer's "features" are empty
         ref = float(G["bb_%s_feat_%d_absmean" % (mode, li)][0])
         got = float(bd["encoder_features"][li].abs().mean())
         assert abs(got - ref) <= 2e-3 * max(1.0, abs(ref)), (li, got, ref)
+
+
+@gpu
+def test_backbone_heads_vs_reference_composition(backbone_forward):
+    """centers, ctr_offsets and centers_features behind the top-k layers.  Where the layer-3 and layer-4 centre sets equal
+    the golden's, the rows are matched by their layer-4 coordinates and compared whatever order the top-k left them in;
+    where a set differs (a near-tie of two scores went the other way: other centres, other rows) the test is SKIPPED with
+    the overlap counts, so that the report shows that nothing was compared."""
+    mode, bd = backbone_forward
+    overlap = []
+    for li in (3, 4):
+        ref = G["bb_%s_encoder_xyz_%d" % (mode, li)]
+        got = bd["encoder_xyz"][li].cpu().numpy()
+        for b in range(ref.shape[0]):
+            a, c = set(_xyz_rows(ref[b])), set(_xyz_rows(got[b]))
+            overlap.append((li, b, len(a & c), len(a), a == c))
+    if not all(o[4] for o in overlap):
+        pytest.skip("%s: centre sets differ from the golden's, (layer, scene, common, of): %s"
+                    % (mode, [o[:4] for o in overlap if not o[4]]))
+    ref4, got4 = G["bb_%s_encoder_xyz_4" % mode], bd["encoder_xyz"][4].cpu().numpy()
+    n = ref4.shape[1]
+    perm = []
+    for b in range(ref4.shape[0]):
+        where = {r: i for i, r in enumerate(_xyz_rows(got4[b]))}
+        assert len(where) == n
+        perm += [b * n + where[r] for r in _xyz_rows(ref4[b])]
+    perm = torch.tensor(perm, dtype=torch.long, device=bd["centers"].device)
+    close(bd["centers"][perm], G["bb_%s_centers" % mode], atol=1e-3, rtol=1e-3)
+    close(bd["ctr_offsets"][perm], G["bb_%s_ctr_offsets" % mode], atol=1e-3, rtol=1e-3)
+    close(bd["centers_features"][perm], G["bb_%s_centers_features" % mode], atol=2e-3, rtol=2e-3)
 
 
 @gpu
