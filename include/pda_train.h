@@ -674,6 +674,39 @@ int pda_recall_record(const float *pred_boxes, const int32_t *num_pred, const fl
                       const float *thresh, int n_thresh, int64_t *counters, float *max_iou, int b, int k, int t,
                       pda_stream_t stream);
 
+/* ---- RoI targets of a two-stage head (csrc/roi_targets.hip) ------------------------------------------------------------------
+ * ProposalTargetLayer (roi_heads/target_assigner/proposal_target_layer.py) and the canonical transformation of
+ * RoIHeadTemplate.assign_targets (roi_head_template.py:104-134) for b scenes, two launches, no host read.  rois (b, m, 7)
+ * float32, roi_labels (b, m) int64, gt_boxes (b, t, gt_cols) float32 with gt_cols >= 8: the box in columns 0..6 and the
+ * class label in the LAST column; each scene's GT trimmed as for pda_recall_record.  m <= 4096.  Sizes are checked before
+ * any pointer is used; b == 0 or m == 0 is PDA_OK and touches nothing.
+ *
+ * pda_roi_max_iou: max_overlaps (b, m) float32 and gt_assignment (b, m) int32 = max and arg-max of
+ * boxes_iou3d_gpu(rois, kept GT) over the kept rows (by_class == 0), or over the kept rows whose int64(label) equals the
+ * RoI's label (by_class != 0; 0 / 0 without such a row).  Among equal maxima the lowest row.  t == 0 counts as the
+ * reference's single zero box: 0 / 0. */
+int pda_roi_max_iou(const float *rois, const int64_t *roi_labels, const float *gt_boxes, int gt_cols, int by_class,
+                    float *max_overlaps, int32_t *gt_assignment, int b, int m, int t, pda_stream_t stream);
+/* subsample_rois / sample_bg_inds on max_overlaps, then for the roi_per_image picks of each scene (fg, hard bg, easy bg in
+ * that order): out_rois (b, r, 7), gt_of_rois_src (b, r, 8) the assigned GT row (columns 0..6 and the label),
+ * gt_iou_of_rois (b, r), out_roi_scores (b, r), out_roi_labels (b, r) int64 copied bit for bit; reg_valid_mask (b, r) int64
+ * = iou > reg_fg_thresh; rcnn_cls_labels (b, r) int64 for score_type 0 ('cls') or float32 for score_type 1 ('roi_iou');
+ * gt_of_rois (b, r, 8) the GT in the RoI's canonical frame with the heading folded into [-pi/2, pi/2]; sampled_inds (b, r)
+ * int32 or NULL, the picked RoI of every output row.  Thresholds are rounded to float32 here (torch compares a float32
+ * tensor in float32); fg_per_image = int(np.round(FG_RATIO * ROI_PER_IMAGE)) from the caller.  Draws: either all four of
+ * perm (b, m) int32 (np.random.permutation(fg_num), first fg_num valid), fg_rand (b, r) float64 (np.random.rand),
+ * hard_draw / easy_draw (b, r) int64 (torch.randint, in range) -- the reference's draws, index-exact -- or all four NULL
+ * and the draws come from seed.  status (b) int32: 0, 1 for a scene with neither foreground nor background (the reference
+ * raises; its rows are zero), 2 for a draw or an assignment out of range (replaced by 0, never followed).  One launch. */
+int pda_roi_sample_targets(const float *rois, const float *roi_scores, const int64_t *roi_labels, const float *gt_boxes,
+                           int gt_cols, const float *max_overlaps, const int32_t *gt_assignment, int roi_per_image,
+                           int fg_per_image, double hard_bg_ratio, double reg_fg_thresh, double cls_fg_thresh,
+                           double cls_bg_thresh, double cls_bg_thresh_lo, int score_type, const int32_t *perm,
+                           const double *fg_rand, const int64_t *hard_draw, const int64_t *easy_draw, uint64_t seed,
+                           float *out_rois, float *gt_of_rois_src, float *gt_of_rois, float *gt_iou_of_rois,
+                           float *out_roi_scores, int64_t *out_roi_labels, int64_t *reg_valid_mask, void *rcnn_cls_labels,
+                           int32_t *sampled_inds, int32_t *status, int b, int m, int t, pda_stream_t stream);
+
 /* ---- preparing frames (csrc/frame_stage.hip) ---------------------------------------------------------------------------------
  * KittiDataset's FOV_POINTS_ONLY step (kitti_dataset.py get_fov_flag behind calib.lidar_to_rect / calib.rect_to_img) for
  * `batch` scenes in the layout of pda_input_stage: points (n_total, C >= 3), offsets (batch + 1) int64, at most n_cap rows a

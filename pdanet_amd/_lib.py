@@ -198,6 +198,9 @@ SIGNATURES = {
                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pda_kitti_eval_predictions": [_vp, ctypes.c_int64, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp],
     "pda_recall_record": [_vp, _vp, _vp, _i, ctypes.POINTER(_f), _i, _vp, _vp, _i, _i, _i, _vp],
+    "pda_roi_max_iou": [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp],
+    "pda_roi_sample_targets": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i] + [ctypes.c_double] * 5 + [_i, _vp, _vp, _vp, _vp,
+                               ctypes.c_uint64] + [_vp] * 10 + [_i, _i, _i, _vp],
     "pda_kitti_fov_filter_workspace_bytes": [_i, ctypes.c_int64],
     "pda_kitti_fov_filter": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp],
     "pda_gt_extract_workspace_bytes": [_i, ctypes.c_int64, ctypes.c_int64],

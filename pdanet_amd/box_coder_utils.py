@@ -1,4 +1,8 @@
-"""Box coder of both PDA-SSD yamls (`PointResidual_BinOri_Coder`, pcdet/utils/box_coder_utils.py:224-319): a box is coded
+"""Box coders.  `ResidualCoder` (pcdet/utils/box_coder_utils.py:5-77) is the coder of the two-stage RoI heads
+(roi_head_template.py): residuals against an anchor box, scaled by the anchor's BEV diagonal and height, log size ratios and
+a heading difference (or cos / sin differences).
+
+Box coder of both PDA-SSD yamls (`PointResidual_BinOri_Coder`, pcdet/utils/box_coder_utils.py:224-319): a box is coded
 against the point that predicts it as
 
     [ (centre - point) / (d, d, h) | log(size / (l, w, h)) | heading bin | heading residual in [-1, 1] | extras ]
@@ -62,3 +66,45 @@ class PointResidual_BinOri_Coder(object):  # noqa: N801 (the yaml names the clas
         within = torch.gather(box_encodings[..., 6 + nb:6 + 2 * nb], -1, sector)
         heading = sector.float() * self.bin_inter - math.pi + self.bin_inter / 2
         return torch.cat([centre, size, heading + within * (self.bin_inter / 2)], dim=-1)
+
+
+class ResidualCoder(object):
+    def __init__(self, code_size=7, encode_angle_by_sincos=False, **kwargs):
+        self.code_size = code_size
+        self.encode_angle_by_sincos = encode_angle_by_sincos
+        if self.encode_angle_by_sincos:
+            self.code_size += 1
+
+    def encode_torch(self, boxes, anchors):
+        """boxes (N, 7 + C), anchors (N, 7 + C) -> (N, 7 + C) codes (8 + C with encode_angle_by_sincos).  Sizes are clamped to
+        1e-5 on copies: unlike the reference's (:22-23) this encode leaves its arguments untouched."""
+        xa, ya, za, dxa, dya, dza, ra, *cas = torch.split(anchors, 1, dim=-1)
+        xg, yg, zg, dxg, dyg, dzg, rg, *cgs = torch.split(boxes, 1, dim=-1)
+        dxa, dya, dza = (torch.clamp_min(v, min=1e-5) for v in (dxa, dya, dza))
+        dxg, dyg, dzg = (torch.clamp_min(v, min=1e-5) for v in (dxg, dyg, dzg))
+        diagonal = torch.sqrt(dxa ** 2 + dya ** 2)
+        xt, yt, zt = (xg - xa) / diagonal, (yg - ya) / diagonal, (zg - za) / dza
+        dxt, dyt, dzt = torch.log(dxg / dxa), torch.log(dyg / dya), torch.log(dzg / dza)
+        if self.encode_angle_by_sincos:
+            rts = [torch.cos(rg) - torch.cos(ra), torch.sin(rg) - torch.sin(ra)]
+        else:
+            rts = [rg - ra]
+        cts = [g - a for g, a in zip(cgs, cas)]
+        return torch.cat([xt, yt, zt, dxt, dyt, dzt, *rts, *cts], dim=-1)
+
+    def decode_torch(self, box_encodings, anchors):
+        """box_encodings (B, N, 7 + C) or (N, 7 + C) codes, anchors of the same leading shape -> boxes."""
+        xa, ya, za, dxa, dya, dza, ra, *cas = torch.split(anchors, 1, dim=-1)
+        if not self.encode_angle_by_sincos:
+            xt, yt, zt, dxt, dyt, dzt, rt, *cts = torch.split(box_encodings, 1, dim=-1)
+        else:
+            xt, yt, zt, dxt, dyt, dzt, cost, sint, *cts = torch.split(box_encodings, 1, dim=-1)
+        diagonal = torch.sqrt(dxa ** 2 + dya ** 2)
+        xg, yg, zg = xt * diagonal + xa, yt * diagonal + ya, zt * dza + za
+        dxg, dyg, dzg = torch.exp(dxt) * dxa, torch.exp(dyt) * dya, torch.exp(dzt) * dza
+        if self.encode_angle_by_sincos:
+            rg = torch.atan2(sint + torch.sin(ra), cost + torch.cos(ra))
+        else:
+            rg = rt + ra
+        cgs = [t + a for t, a in zip(cts, cas)]
+        return torch.cat([xg, yg, zg, dxg, dyg, dzg, rg, *cgs], dim=-1)

@@ -11,8 +11,7 @@
 // integer atomic per counter -- order-free, so runs are bit-identical and one buffer can collect a whole epoch.
 #include "pda_common.h"
 #include "bev_overlap.h"
-
-#include <math.h>
+#include "box_iou3d.h"
 
 namespace pda {
 namespace {
@@ -23,35 +22,6 @@ constexpr int RECALL_WAVES = 4;  // GT rows per workgroup
 struct RecallThresh {
     float t[RECALL_MAX_THRESH];  // RECALL_THRESH_LIST rounded to float32: torch compares a float32 tensor in float32
 };
-
-// The reference keeps rows 0..k: k starts at t - 1 and steps down while k > 0 and row k's float32 sum == 0.  Returns
-// that k (0 when t == 0), the same on every lane.  The row is summed left to right; a row whose values cancel to zero only
-// under some summation orders is outside the contract (torch's reduction order is not specified).
-__device__ int trimmed_last_row(const float* __restrict__ gt, int t, int cols, int lane) {
-    for (int base = t - 64; base + 63 >= 1; base -= 64) {
-        const int r = base + lane;  // < t
-        bool nz = false;
-        if (r >= 1) {
-            const float* row = gt + (size_t)r * cols;
-            float s = 0.f;
-            for (int c = 0; c < cols; ++c) s += row[c];
-            nz = s != 0.f;
-        }
-        const uint64_t m = __ballot(nz);
-        if (m) return base + 63 - __clzll((long long)m);
-    }
-    return 0;
-}
-
-// box_overlap(a, b) is exactly 0 for a pair whose BEV circumcircles lie apart: each vertex it collects is an edge
-// intersection (inside both circles) or a corner that in_box2d accepts (inside the other box widened by 1e-2 a side, so
-// inside its circle widened by less than 1.5e-2).  The margin covers that and the rounding of the corners; the 3-D IoU of
-// such a pair is 0 / clamp(vol_a + vol_b, 1e-6) = +0, which the caller uses without evaluating the pair.
-__device__ __forceinline__ bool bev_apart(float xa, float ya, float ra, float xb, float yb, float rb) {
-    const float ddx = xa - xb, ddy = ya - yb;
-    const float reach = (ra + rb) * 1.0001f + 0.1f + 1e-4f * (fabsf(xa) + fabsf(ya) + fabsf(xb) + fabsf(yb));
-    return ddx * ddx + ddy * ddy > reach * reach;
-}
 
 __global__ __launch_bounds__(64 * RECALL_WAVES) void recall_record_kernel(
         const float* __restrict__ pred, const int32_t* __restrict__ num_pred, const float* __restrict__ gt, int cols,
@@ -66,29 +36,16 @@ __global__ __launch_bounds__(64 * RECALL_WAVES) void recall_record_kernel(
     const bool active = g < kept;
     float best = 0.f;
     if (active && n > 0) {
-        // boxes_iou3d_gpu(boxes_a = predictions, boxes_b = GT): box_overlap(pred, gt) in that order (not bit-symmetric),
-        // the rest float32 in torch's order, uncontracted (this file is built with -ffp-contract=off)
-        const float* gb = sgt + (size_t)g * cols;
-        const BevBox bb = make_box(gb);
-        const float b_max = gb[2] + gb[5] / 2, b_min = gb[2] - gb[5] / 2;
-        const float vol_b = (gb[3] * gb[4]) * gb[5];
-        const float rb = 0.5f * sqrtf(gb[3] * gb[3] + gb[4] * gb[4]);
+        // boxes_iou3d_gpu(boxes_a = predictions, boxes_b = GT): box_iou3d.h, uncontracted (this file is built with
+        // -ffp-contract=off)
+        const float* gr = sgt + (size_t)g * cols;
+        const IouSide gb = make_iou_side(gr);
+        const BevBox gbev = make_box(gr);
         float m = -INFINITY;
         for (int j = lane; j < n; j += 64) {
             const float* pa = pred + ((size_t)s * k + j) * 7;
-            const float x = pa[0], y = pa[1], z = pa[2], dx = pa[3], dy = pa[4], dz = pa[5];
-            float iou = 0.f;
-            if (!bev_apart(x, y, 0.5f * sqrtf(dx * dx + dy * dy), bb.x, bb.y, rb)) {
-                const float ov = box_overlap(make_box(pa), bb);
-                const float a_max = z + dz / 2, a_min = z - dz / 2;
-                float h = mn(a_max, b_max) - mx(a_min, b_min);
-                h = h < 0.f ? 0.f : h;                                   // clamp(min=0)
-                const float o3 = ov * h;
-                const float vol_a = (dx * dy) * dz;
-                float den = (vol_a + vol_b) - o3;
-                den = den < 1e-6f ? 1e-6f : den;                         // clamp(min=1e-6)
-                iou = o3 / den;
-            }
+            const IouSide a = make_iou_side(pa);
+            const float iou = iou3d_apart(a, gb) ? 0.f : iou3d_from_overlap(a, gb, box_overlap(make_box(pa), gbev));
             m = iou > m ? iou : m;
         }
 #pragma unroll
