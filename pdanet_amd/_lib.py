@@ -39,12 +39,8 @@ class KittiFrames(ctypes.Structure):
                 ("n_frames", ctypes.c_int), ("max_gt", ctypes.c_int), ("max_det", ctypes.c_int)]
 
 
-# Bumped by anything that writes parameters behind autograd's back (optimization.FlatAdamOneCycle.step updates the flat
-# parameter buffer through a raw pointer, so tensor version counters do not move): caches of derived tensors (bf16 weight
-# copies, BatchNorm folded into convolutions) key on it next to the version counters.
+# The two epochs of param_cache.py (which explains them and owns every read and write inside the package).
 PARAM_EPOCH = [0]
-# The same for the trained PARAMETERS only (bumped by the optimizer step, not by BatchNorm running statistics): packed weight
-# planes made in a forward pass stay valid until the next optimizer step, i.e. through the backward pass of the same iteration.
 WEIGHT_EPOCH = [0]
 
 _vp = ctypes.c_void_p

@@ -17,7 +17,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import pointnet2_modules, pointnet2_utils
+from . import param_cache, pointnet2_modules, pointnet2_utils
 
 
 class IASSD_Backbone(nn.Module):
@@ -85,6 +85,7 @@ class IASSD_Backbone(nn.Module):
         # own buffers: valid until the next forward.  Off by default; bench.py's inference workload switches it on.
         self.graph_tail_infer = False
         self._tail_graph = None
+        self._tail_slots = {}
 
     def _presample(self, xyz, points=None, batch_size=None, limit=None):
         """Sampling of the leading layers that need only coordinates (identity / D-FPS, chained
@@ -218,14 +219,15 @@ class IASSD_Backbone(nn.Module):
     def _run_tail_graphed(self, i0, st):
         """Layers i0.. of an inference forward as one hipGraph replay (captured on first use per input shape and per state
         of the weights).  Inputs are copied into the graph's buffers (three small tensors); the outputs stay in them."""
-        from . import _lib
         n = len(self.SA_modules)
         xyz, feats, cls, bidx = st['encoder_xyz'][i0], st['encoder_features'][i0], st['li_cls_pred'], st['bidx']
-        tail_params = [p for i in range(i0, n) for p in self.SA_modules[i].parameters()]
-        key = (i0, st['batch_size'], tuple(xyz.shape), tuple(feats.shape), None if cls is None else tuple(cls.shape), tuple(bidx.shape),
-               _lib.PARAM_EPOCH[0], _lib.WEIGHT_EPOCH[0], tuple(p._version for p in tail_params), tuple(p.data_ptr() for p in tail_params[:4]))
         if self._tail_graph is None:
             self._tail_graph = {}
+        if i0 not in self._tail_slots:
+            # the parameter and buffer slots of layers i0..: the module tree is walked once, the tensors are read per forward
+            self._tail_slots[i0] = [d for i in range(i0, n) for m in self.SA_modules[i].modules() for d in (m._parameters, m._buffers)]
+        key = (i0, st['batch_size'], tuple(xyz.shape), tuple(feats.shape), None if cls is None else tuple(cls.shape), tuple(bidx.shape),
+               param_cache.stamp([t for d in self._tail_slots[i0] for t in d.values()]))
         if key not in self._tail_graph:
             if len(self._tail_graph) >= 4:                  # a few input shapes in rotation at most; stale weights' graphs go first
                 self._tail_graph.pop(next(iter(self._tail_graph)))

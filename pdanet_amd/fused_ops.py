@@ -12,6 +12,7 @@ import ctypes
 import torch
 
 from . import _lib
+from . import param_cache
 from .pointnet2_modules import PointnetSAModuleMSG_WithSampling
 
 PDA_ERR_UNSUPPORTED = 3
@@ -30,7 +31,7 @@ class FusedSAMlp:
     """Callable stored on the module as `module.fused`."""
 
     def __init__(self):
-        self.cache = {}
+        self.cache = param_cache.Store(under_capture=True)     # one entry per packed scale, owned by its nn.Sequential
         self.unsupported = set()
 
     def _prepare(self, i, module):
@@ -39,13 +40,11 @@ class FusedSAMlp:
         bns = [m for m in seq if isinstance(m, torch.nn.BatchNorm2d)]
         if len(convs) != 3 or len(bns) != 3:
             return None
-        # PARAM_EPOCH: the flat-buffer optimizer and the BN kernels' running-statistics updates write through raw
-        # pointers, which moves neither _version nor data_ptr (eval -> train k steps -> eval must re-pack)
-        key = (_lib.PARAM_EPOCH[0],) + tuple((c.weight._version, c.weight.data_ptr()) for c in convs) + \
-            tuple((b.weight._version, b.bias._version, b.running_mean._version, b.running_var._version) for b in bns)
-        hit = self.cache.get(i)
-        if hit is not None and hit["key"] == key:
-            return hit
+        sources = [c.weight for c in convs] + [t for b in bns for t in (b.weight, b.bias, b.running_mean, b.running_var)]
+        return self.cache.get(seq, sources, lambda: self._pack(convs, bns))
+
+    @staticmethod
+    def _pack(convs, bns):
         lib = _lib.load()
         dev = convs[0].weight.device
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
@@ -62,9 +61,7 @@ class FusedSAMlp:
                 t = b.bias - b.running_mean * s
                 wf.append(packed); scale.append(_pad32(s.float())); shift.append(_pad32(t.float()))
                 dims.append(rows)
-        hit = dict(key=key, wf=wf, scale=scale, shift=shift, dims=dims)
-        self.cache[i] = hit
-        return hit
+        return dict(wf=wf, scale=scale, shift=shift, dims=dims)
 
     def __call__(self, i, module, xyz, new_xyz, features, idx):
         if i in self.unsupported or idx is None:

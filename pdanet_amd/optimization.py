@@ -24,6 +24,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from . import param_cache
 
 BN_TYPES = (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d, nn.SyncBatchNorm)  # fastai_optim.py:12
 
@@ -168,8 +169,7 @@ class FlatAdamOneCycle:
                 mine = {id(p) for p in self.params}
                 for t in [p.data for p in model.parameters() if id(p) not in mine] + list(model.buffers()):
                     dist.broadcast(t, src, group=group)
-            _lib.PARAM_EPOCH[0] += 1
-            _lib.WEIGHT_EPOCH[0] += 1
+            param_cache.parameters_written()
         return self
 
     def exchange_gradients(self):
@@ -234,8 +234,7 @@ class FlatAdamOneCycle:
                                              self._scratch.data_ptr(), stream), "pda_grad_norm")
                 norm_ptr = self._norm.data_ptr()
             self.step_count += 1
-            _lib.PARAM_EPOCH[0] += 1        # parameters change without their version counters moving
-            _lib.WEIGHT_EPOCH[0] += 1
+            param_cache.parameters_written()
             _lib.check(lib.pda_adam_onecycle_step(
                 self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
                 self.n_trained, self.lr, self.mom, self.beta2, self.eps, self.wd, self.step_count, norm_ptr,

@@ -18,6 +18,7 @@ import functools
 import torch
 
 from . import _lib
+from . import param_cache
 
 
 def _chk(t, name, dtype):
@@ -279,11 +280,9 @@ def _io(t, name):
 
 
 def _buffers_written(running):
-    """The kernel about to be launched updates BatchNorm running statistics through raw pointers: tensor version
-    counters do not move, so every cache of tensors derived from them (eval-BN folded into convolutions, the packed
-    weights + scale/shift of the fused SA kernel) must see a new _lib.PARAM_EPOCH."""
+    """The kernel about to be launched updates BatchNorm running statistics through raw pointers."""
     if running is not None:
-        _lib.PARAM_EPOCH[0] += 1
+        param_cache.buffers_written()
 
 
 def bn_relu_fwd(x, gamma, beta, running_mean, running_var, y, mean_invstd, scratch, rows, c, eps, momentum):

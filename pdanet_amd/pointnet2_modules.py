@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
+from . import param_cache
 from . import pointnet2_utils
 
 
@@ -107,23 +107,22 @@ def _bf16_boundary(x, conv, bn):
 FOLD_EVAL_BN = True   # inference: BatchNorm (running statistics) folded into the preceding 1x1 convolution
 
 
+_FOLDED = param_cache.Store(under_capture=True)
+_DENSITYNET_BLOCKS = param_cache.Store(under_capture=True)
+
+
 def _folded_conv_bn(conv, bn):
     """(W', b') with W' x + b' == BN_eval(conv(x)): W' = W * s, b' = (conv.bias - running_mean) * s + beta,
-    s = gamma / sqrt(running_var + eps).  Cached on the BN module, keyed on the version counters of every tensor
-    involved (an optimizer step, a load_state_dict or a training-mode forward invalidates it)."""
-    tensors = (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)
-    key = (_lib.PARAM_EPOCH[0],) + tuple(None if t is None else (t._version, t.data_ptr()) for t in tensors)
-    cache = bn.__dict__.get("_pda_folded")
-    if cache is None or cache[0] != key:
+    s = gamma / sqrt(running_var + eps).  Cached for the BN module (param_cache)."""
+    def fold():
         with torch.no_grad():
             s = bn.weight * torch.rsqrt(bn.running_var + bn.eps)
             w = (conv.weight.flatten(1) * s[:, None]).contiguous()
             b = bn.bias - bn.running_mean * s
             if conv.bias is not None:
                 b = b + conv.bias * s
-        cache = (key, w, b.contiguous())
-        bn.__dict__["_pda_folded"] = cache
-    return cache[1], cache[2]
+        return w, b.contiguous()
+    return _FOLDED.get(bn, (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var), fold)
 
 
 def _can_fold(conv, bn):
@@ -208,19 +207,17 @@ def _densitynet_eval_ok(dn, x):
 def _densitynet_eval(dn, x):
     """DensityNet (pointnet2_modules.py:958-981) in inference on x (..., 1): relu(W3' relu(W2' relu(w1' x + b1') + b2') + b3') with
     the BatchNorms folded in (_folded_conv_bn), one kernel instead of three tiny GEMMs with bias + ReLU epilogues.  The packed
-    parameter block is cached on the module, keyed on the folded tensors (which are themselves re-made when a weight, a BatchNorm
-    parameter or a running statistic changes)."""
-    folded = [_folded_conv_bn(c, b) for c, b in zip(dn.mlp_convs, dn.mlp_bns)]
-    key = tuple((t.data_ptr(), t._version) for wb in folded for t in wb)
-    cache = dn.__dict__.get("_pda_eval_block")
-    if cache is None or cache[0] != key:
+    parameter block is cached for the module (param_cache)."""
+    pairs = list(zip(dn.mlp_convs, dn.mlp_bns))
+
+    def pack():
         with torch.no_grad():
-            block = torch.cat([t.reshape(-1).float() for wb in folded for t in wb]).contiguous()
-        cache = (key, block, folded)       # `folded` kept alive: its addresses are the key
-        dn.__dict__["_pda_eval_block"] = cache
+            return torch.cat([t.reshape(-1).float() for c, b in pairs for t in _folded_conv_bn(c, b)]).contiguous()
+    sources = [t for c, b in pairs for t in (c.weight, c.bias, b.weight, b.bias, b.running_mean, b.running_var)]
+    block = _DENSITYNET_BLOCKS.get(dn, sources, pack)
     x = x.contiguous()
     y = torch.empty_like(x)
-    pointnet2_utils.pointnet2.densitynet_eval(x, cache[1], y, x.numel())
+    pointnet2_utils.pointnet2.densitynet_eval(x, block, y, x.numel())
     return y
 
 

@@ -9,7 +9,6 @@ the kernels underneath are the hand-written gfx950 ones reached through the C AB
     so the ops work under side streams and hipGraph capture;
   * the grouper modules use one multi-radius ball query when asked for several scales.
 """
-import weakref
 from typing import List, Tuple
 
 import os
@@ -19,6 +18,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from . import _lib
+from . import param_cache
 from . import pointnet2_batch_cuda as pointnet2
 
 # Under torch.autocast the dense layers may run in bf16; the point operators always compute in
@@ -623,24 +623,19 @@ def _b16(t):
     return t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16)
 
 
-_B16_PARAMS = {}
+_B16_COPIES = param_cache.Store(under_capture=False)
 
 
 def _b16p(p):
-    """bf16 copy of a parameter (weight / bias), cached until the parameter is written again (its version counter moves:
-    optimizer step, load_state_dict) -- a step uses each weight in 2-3 GEMMs, and each cast is a launch."""
+    """bf16 copy of a parameter (weight / bias), cached while param_cache holds it valid -- a step uses each weight in 2-3
+    GEMMs, and each cast is a launch."""
     if p.dtype == torch.bfloat16:
         return p
-    if p.is_cuda and torch.cuda.is_current_stream_capturing():
-        return p.detach().to(torch.bfloat16)        # the cast belongs INSIDE the graph: a replay must see the new weights
-    key = id(p)
-    stamp = (p._version, p.data_ptr(), _lib.PARAM_EPOCH[0])
-    hit = _B16_PARAMS.get(key)
-    if hit is not None and hit[0] == stamp and hit[1]() is p:
-        return hit[2]
-    pb = p.detach().to(torch.bfloat16)
-    _B16_PARAMS[key] = (stamp, weakref.ref(p, lambda _r, k=key: _B16_PARAMS.pop(k, None)), pb)
-    return pb
+
+    def cast():
+        return p.detach().to(torch.bfloat16)
+    pb = _B16_COPIES.get(p, (p,), cast)
+    return cast() if pb is None else pb
 
 
 # SPLIT_GEMM: f32 contractions run on the bf16 matrix cores with three-term bf16 operands (csrc/gemm_split.hip: f32-grade
@@ -668,21 +663,10 @@ def _rows_in_registers(tokens, k, n_out):
     return k <= 256 and n_out % 128 == 0 and n_out <= 2048 and tokens < ROWS_IN_REGISTERS_MAX_TOKENS
 
 
-# Packed bf16 planes of the PARAMETER weights, keyed on the storage address: {ptr: (tag, planes of W, planes of W^T, weak
-# reference to the owning nn.Parameter, byte offset of the weight inside it)} with tag = (version counter,
-# _lib.WEIGHT_EPOCH, shape).  Training packs both forms in one launch in the forward pass; the backward pass (which sees
-# the weight as an unpacked saved tensor, not as the Parameter) finds the transposed planes by address.  An entry is valid
-# only while its Parameter is alive AND still sits at that address -- then no other tensor can occupy it; a freed model or a
-# re-pointed `.data` (optimization.FlatAdamOneCycle moves the parameters into its flat buffer) invalidates it.  Inference
+# Packed bf16 planes of the PARAMETER weights: one entry [planes of W, planes of W^T] per weight, found by storage address and
+# filled lazily.  Training packs both forms in one launch in the forward pass and the backward pass finds W^T; inference
 # packs once and hits until the weights change.
-_PACKED_PLANES = {}
-
-
-def _owning_parameter(w):
-    if isinstance(w, nn.Parameter):
-        return w
-    base = getattr(w, "_base", None)
-    return base if isinstance(base, nn.Parameter) else None
+_PLANES = param_cache.Store(under_capture=False, weights_only=True)
 
 
 def _split_planes(w, transposed=False):
@@ -693,31 +677,17 @@ def _split_planes(w, transposed=False):
     def pack(t):
         src = wd if wd.is_contiguous() else wd.contiguous()
         return pointnet2.linear_split_pack(src, k, n_out, transposed_source=True) if t else pointnet2.linear_split_pack(src, n_out, k)
-    if not wd.is_contiguous() or torch.cuda.is_current_stream_capturing():
-        return pack(transposed)      # under capture the packing belongs INSIDE the graph: a replay must see the new weights
-    key, tag = wd.data_ptr(), (wd._version, _lib.WEIGHT_EPOCH[0], n_out, k)
-    ent = _PACKED_PLANES.get(key)
-    if ent is not None:
-        owner = ent[3]()
-        if owner is None or owner.data_ptr() + ent[4] != key:
-            del _PACKED_PLANES[key]                       # the parameter is gone or lives elsewhere now
-            ent = None
-        elif ent[0] != tag:
-            ent = None                                    # the weights changed: repack below (if this is the parameter)
-        elif ent[2 if transposed else 1] is not None:
-            return ent[2 if transposed else 1]
-    param = _owning_parameter(w)
-    if param is None:
+    pair = _PLANES.get_at(w, lambda: [None, None], extra=(n_out, k)) if wd.is_contiguous() else None
+    slot = 1 if transposed else 0
+    if pair is not None and pair[slot] is not None:
+        return pair[slot]
+    if pair is None or param_cache.owning_parameter(w) is None:        # (an alias finds an entry; only the Parameter fills it)
         return pack(transposed)
     if w.requires_grad and n_out % 32 == 0 and k >= 128:               # (grad mode is off inside Function.forward: ask the tensor)
-        wf, wft = pointnet2.linear_split_pack_both(wd, n_out, k)       # the backward pass of this iteration wants W^T
-    elif transposed:
-        wf, wft = (ent[1] if ent is not None else None), pack(True)
+        pair[:] = pointnet2.linear_split_pack_both(wd, n_out, k)       # the backward pass of this iteration wants W^T
     else:
-        wf, wft = pack(False), (ent[2] if ent is not None else None)
-    # (the entry goes with its parameter: a callback on the weak reference, as for the bf16 copies above)
-    _PACKED_PLANES[key] = (tag, wf, wft, weakref.ref(param, lambda _r, k=key: _PACKED_PLANES.pop(k, None)), key - param.data_ptr())
-    return wft if transposed else wf
+        pair[slot] = pack(transposed)
+    return pair[slot]
 
 
 def _gemm_nt(x2d, w, bias=None, relu=False):

@@ -98,10 +98,29 @@ def test_fused_weight_update_invalidates_cache():
     assert float((b - c).abs().max()) <= 2e-4 * max(1.0, float(c.abs().max()))
 
 
+def test_fused_replaced_buffer_invalidates_cache():
+    """A BatchNorm buffer REPLACED by a fresh tensor between two eval forwards: the new tensor's version counter is 0 like
+    the old one's after .cuda(), so only its address tells them apart."""
+    from pdanet_amd import synth, fused_ops
+    xyz = torch.from_numpy(synth.batch_xyz(1, 1024, config_id=6)).cuda()
+    feats = torch.randn(1, 1, 1024, device="cuda")
+    layer = make_layer(1, [[16, 16, 32]], [2.0], [16], 256)
+    fused_ops.enable_fused(layer)
+    with torch.no_grad():
+        a = layer(xyz, feats, None)[1].clone()
+        layer.mlps[0][1].running_var = torch.full((16,), 4.0, device="cuda")
+        b = layer(xyz, feats, None)[1]
+        assert not layer.fused.unsupported
+        fused_ops.enable_fused(layer, False)
+        c = layer(xyz, feats, None)[1]
+    assert not torch.allclose(a, b)
+    assert float((b - c).abs().max()) <= 2e-4 * max(1.0, float(c.abs().max()))
+
+
 def test_fused_cache_sees_raw_pointer_updates():
     """eval(fused) -> k training steps of the flat-buffer optimizer -> eval(fused) must equal eval(unfused).
     FlatAdamOneCycle.step and the BN+ReLU kernels' running-statistics updates write through raw pointers: neither
-    _version nor data_ptr of the conv / BN tensors moves, only _lib.PARAM_EPOCH does."""
+    version counter nor address of the conv / BN tensors moves, only the epoch of pdanet_amd.param_cache does."""
     from pdanet_amd import synth, fused_ops, optimization
     xyz = torch.from_numpy(synth.batch_xyz(2, 1024, config_id=8)).cuda()
     feats = torch.randn(2, 1, 1024, device="cuda", generator=torch.Generator("cuda").manual_seed(4))
