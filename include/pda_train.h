@@ -836,6 +836,73 @@ int pda_dyn_pillar_features(const float *points, int64_t n, int columns, const i
                             const int32_t *voxel_coords, const float *mean, const int32_t *counts, const float *voxel_size3,
                             const float *offset3, int absolute_xyz, int with_distance, float *out, pda_stream_t stream);
 
+/* ---- CenterPoint pillar tail (csrc/center_head.hip) --------------------------------------------------------------------------
+ * PointPillarScatter (backbones_2d/map_to_bev/pointpillar_scatter.py) and CenterHead's target assignment, losses and
+ * decoding (dense_heads/center_head.py, model_utils/centernet_utils.py, utils/loss_utils.py:395-517).  Every launch goes on
+ * `stream`, nothing is allocated, sizes are checked before any pointer is used and an empty problem is PDA_OK and touches
+ * nothing.
+ *
+ * pda_pillar_scatter_fwd: features (n, c) float32, coords (n, 4) int32 (b, z, y, x) -> out (b, c, ny, nx), ZERO-FILLED BY THE
+ * CALLER: out[coords[0], :, cell] = features row with cell = c1 + c2 * nx + c3.  A row is skipped when its batch index is
+ * outside [0, b) or its cell outside [0, ny * nx); with count != NULL (a device int32) also the rows from *count on (the
+ * padded form of pda_dyn_voxel_index).  Two rows on one cell are outside the contract.  pda_pillar_scatter_bwd is the gather
+ * of the same cells from grad_out (b, c, ny, nx) into grad_features (n, c), zero for a skipped row; no atomics. */
+int pda_pillar_scatter_fwd(const float *features, const int32_t *coords, const int32_t *count, int64_t n, int c, int b, int ny,
+                           int nx, float *out, pda_stream_t stream);
+int pda_pillar_scatter_bwd(const float *grad_out, const int32_t *coords, const int32_t *count, int64_t n, int c, int b, int ny,
+                           int nx, float *grad_features, pda_stream_t stream);
+/* CenterHead.assign_targets for b scenes and n_heads heads in one launch, no host read.  gt_boxes (b, m, gt_cols) float32,
+ * zero-padded, the label (1-based, 0 = none) in the last column; it is not written.  HOST arrays: head_of_class and
+ * local_of_class (num_class + 1, by label; head -1 = no head), head_classes (n_heads) the classes of each head, and per
+ * head the DEVICE pointers heatmaps[h] (b, head_classes[h], h, w) float32 ZERO-FILLED BY THE CALLER, target_boxes[h]
+ * (b, max_objs, gt_cols) float32, inds[h] and masks[h] (b, max_objs) int64, all three written whole.  Per (scene, head) the
+ * rows of the head's classes are compacted in row order; row k of that list is object k; objects from max_objs on are
+ * dropped; an object with dx <= 0 or dy <= 0 leaves its slot zero.  Per object every operation is a float32 one:
+ * coord = clamp(((x - pcr0) / vs0) / stride, 0, w - 0.5), inds = int(coord_y) * w + int(coord_x), target_boxes =
+ * [coord - int(coord) (2), z, log(dims) (3), cos(ry), sin(ry), columns 7..gt_cols-2] with log, cos and sin evaluated in
+ * double and rounded once, radius = max(int(gaussian_radius(dx / vs0 / stride, dy / vs1 / stride, gaussian_overlap)),
+ * min_radius).  The Gaussian exp(-(i*i + j*j) / (2 sigma^2)), sigma = (2 r + 1) / 6, evaluated in double and rounded, is
+ * written over the clipped window with an integer atomicMax on the bit pattern: the result is independent of any order.
+ * gaussian2D's eps cut-off cannot fire with this sigma (the corner value is about e^-9) and is left out. */
+int pda_center_assign_targets(const float *gt_boxes, int gt_cols, int b, int m, int num_class, int n_heads,
+                              const int32_t *head_of_class, const int32_t *local_of_class, const int32_t *head_classes, int h,
+                              int w, int max_objs, double pcr0, double pcr1, double vs0, double vs1, double stride,
+                              double gaussian_overlap, int min_radius, void *const *heatmaps, void *const *target_boxes,
+                              void *const *inds, void *const *masks, pda_stream_t stream);
+/* FocalLossCenterNet (neg_loss_cornernet) on pred = clamp(sigmoid(logits), 1e-4, 1 - 1e-4) in one pass and one small second
+ * launch: out[0] the loss, out[1] = d loss / d (pos + neg) (-1 / num_pos, or -1 without a cell of heatmap == 1), out[2]
+ * num_pos; grad (n) the derivative of (pos + neg) with respect to the logits, zero where the clamp is active; partials:
+ * 3 * pda_center_focal_blocks(n) float64 of scratch.  Fixed summation order, no float atomics. */
+int64_t pda_center_focal_blocks(int64_t n);
+int pda_center_focal_loss(const float *logits, const float *heatmap, int64_t n, float *grad, double *partials, float *out,
+                          pda_stream_t stream);
+/* out (n) = g (n) * (a[0] * b[0] * c), a and b device scalars: the focal loss's backward. */
+int pda_center_scale(const float *g, const float *a, const float *b, float c, int64_t n, float *out, pda_stream_t stream);
+/* RegLossCenterNet over the n_maps HEAD_ORDER maps as they are: HOST arrays maps (device pointers, map i (b, channels[i], hw)
+ * float32), channels and code_weights (sum of channels <= 16); targets (b, k, code) float32, inds and masks (b, k) int64.
+ * Per code column sum |pred * m - target * m| over (b, k), m = mask * not-NaN(target), / max(sum(mask), 1); out =
+ * [sum(column * code_weight) * loc_weight, max(sum(mask), 1), the columns (code)].  An entry whose target is NaN
+ * contributes 0.  A cell index outside [0, hw) is skipped.  One launch, fixed order.  pda_center_reg_loss_grad adds
+ * sign * m * code_weight * loc_weight / num * grad_out[0] into grad_maps (ZERO-FILLED BY THE CALLER) with a float
+ * atomicAdd, because two objects can share a cell; the sum depends on the order only from three objects on one cell on. */
+int pda_center_reg_loss(const void *const *maps, const int32_t *channels, int n_maps, const float *targets, const int64_t *inds,
+                        const int64_t *masks, const float *code_weights, float loc_weight, int b, int k, int64_t hw,
+                        float *out, pda_stream_t stream);
+int pda_center_reg_loss_grad(const void *const *maps, const int32_t *channels, int n_maps, const float *targets,
+                             const int64_t *inds, const int64_t *masks, const float *code_weights, float loc_weight, int b,
+                             int k, int64_t hw, const float *fwd_out, const float *grad_out, void *const *grad_maps,
+                             pda_stream_t stream);
+/* decode_bbox_from_heatmap behind the top-k selection: top_logits (b, k) float32 and top_inds (b, k) int64 into the
+ * flattened (n_cls * h * w) heat map of a head; center (b, 2, h, w), center_z (b, 1, h, w), dim (b, 3, h, w), rot (b, 2, h, w),
+ * vel (b, 2, h, w) or NULL.  boxes (b, k, 7 or 9) = [(cell_x + center_x) * stride * vs0 + pcr0, y alike, z, exp(dim),
+ * atan2(sin, cos), vel] (exp and atan2 in double, rounded once), scores (b, k) = sigmoid(logit), or -inf for a row outside
+ * limit_range (HOST, 6) or, with use_thresh, not above score_thresh; labels (b, k) int64 = class_map[class] (HOST, n_cls). */
+int pda_center_decode(const float *top_logits, const int64_t *top_inds, const float *center, const float *center_z,
+                      const float *dim, const float *rot, const float *vel, int b, int k, int h, int w, int n_cls,
+                      const int32_t *class_map, double stride, double vs0, double vs1, double pcr0, double pcr1,
+                      const float *limit_range, int use_thresh, double score_thresh, float *boxes, float *scores,
+                      int64_t *labels, pda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

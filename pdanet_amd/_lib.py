@@ -217,6 +217,19 @@ SIGNATURES = {
     "pda_dyn_scatter_max_bwd": [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _vp, _vp],
     "pda_dyn_pillar_features": [_vp, ctypes.c_int64, _i, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_f), ctypes.POINTER(_f), _i,
                                 _i, _vp, _vp],
+    "pda_pillar_scatter_fwd": [_vp, _vp, _vp, ctypes.c_int64, _i, _i, _i, _i, _vp, _vp],
+    "pda_pillar_scatter_bwd": [_vp, _vp, _vp, ctypes.c_int64, _i, _i, _i, _i, _vp, _vp],
+    "pda_center_assign_targets": [_vp, _i, _i, _i, _i, _i] + [ctypes.POINTER(ctypes.c_int32)] * 3 + [_i, _i, _i]
+                                 + [ctypes.c_double] * 6 + [_i] + [ctypes.POINTER(_vp)] * 4 + [_vp],
+    "pda_center_focal_blocks": [ctypes.c_int64],
+    "pda_center_focal_loss": [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp],
+    "pda_center_scale": [_vp, _vp, _vp, _f, ctypes.c_int64, _vp, _vp],
+    "pda_center_reg_loss": [ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _vp, ctypes.POINTER(_f), _f, _i,
+                            _i, ctypes.c_int64, _vp, _vp],
+    "pda_center_reg_loss_grad": [ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _vp, ctypes.POINTER(_f), _f,
+                                 _i, _i, ctypes.c_int64, _vp, _vp, ctypes.POINTER(_vp), _vp],
+    "pda_center_decode": [_vp] * 7 + [_i] * 5 + [ctypes.POINTER(ctypes.c_int32)] + [ctypes.c_double] * 5
+                         + [ctypes.POINTER(_f), _i, ctypes.c_double, _vp, _vp, _vp, _vp],
     # include/pda_pointnet2_stack.h
     "pda_stack_ball_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     "pda_stack_group_points": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -277,6 +290,7 @@ def load():
     lib.pda_gt_extract_workspace_bytes.restype = ctypes.c_int64
     lib.pda_voxel_workspace_bytes.restype = ctypes.c_int64
     lib.pda_dyn_voxel_workspace_bytes.restype = ctypes.c_int64
+    lib.pda_center_focal_blocks.restype = ctypes.c_int64
     lib.pda_abi_version.restype = _i
     lib.pda_last_error.restype = ctypes.c_char_p
     lib.pda_fp_contract_mode.restype = _i

@@ -22,13 +22,15 @@ from .pointnet2_batch_cuda import F32, I32, _call, _chk
 MAX_RECALL_THRESH = 16
 
 
-def class_agnostic_nms_batched(box_scores, box_preds, nms_config, score_thresh=None):
+def class_agnostic_nms_batched(box_scores, box_preds, nms_config, score_thresh=None, valid=None):
     """box_scores (B, N), box_preds (B, N, 7+C).  Returns selected (B, K) int64 indices into N (-1 padded),
-    their scores (B, K) (0 padded) and num_selected (B) int32, K = min(N, NMS_POST_MAXSIZE)."""
+    their scores (B, K) (0 padded) and num_selected (B) int32, K = min(N, NMS_POST_MAXSIZE).  valid (B, N) bool, optional:
+    rows that take part at all (the padded rows of a caller whose scenes hold different numbers of boxes)."""
     B, N = box_scores.shape
     if nms_config["NMS_TYPE"] not in ("nms_gpu", "nms_normal_gpu"):
         raise NotImplementedError(nms_config["NMS_TYPE"])
-    valid = box_scores >= score_thresh if score_thresh is not None else torch.ones_like(box_scores, dtype=torch.bool)
+    ok = box_scores >= score_thresh if score_thresh is not None else torch.ones_like(box_scores, dtype=torch.bool)
+    valid = ok if valid is None else ok & valid
     masked = torch.where(valid, box_scores, torch.full_like(box_scores, float("-inf")))
     sorted_scores, order = masked.sort(dim=1, descending=True)
     num_valid = valid.sum(dim=1).clamp(max=int(nms_config["NMS_PRE_MAXSIZE"])).to(torch.int32)
