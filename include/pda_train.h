@@ -903,6 +903,71 @@ int pda_center_decode(const float *top_logits, const int64_t *top_inds, const fl
                       const float *limit_range, int use_thresh, double score_thresh, float *boxes, float *scores,
                       int64_t *labels, pda_stream_t stream);
 
+/* ---- PointPillar / anchor heads (csrc/anchor_head.hip) ------------------------------------------------------------------------
+ * AxisAlignedTargetAssigner.assign_targets, AnchorHeadTemplate's losses and generate_predicted_boxes
+ * (dense_heads/anchor_head_template.py, target_assigner/axis_aligned_target_assigner.py, utils/loss_utils.py,
+ * utils/box_coder_utils.py ResidualCoder) and the PFN input rows of the hard-voxel PillarVFE (backbones_3d/vfe/pillar_vfe.py).
+ * Every launch goes on `stream`, nothing is allocated, sizes are checked before any pointer is used.
+ *
+ * pda_anchor_assign_targets: all scenes and all anchor classes in two launches (plus two memsets), no host read.
+ * gt_boxes (b, m, 8) float32, zero-padded, the 1-based label in the last column; it is not written.  anchors (n_anchors, 7)
+ * float32 is the table of one scene, the bits of the head's `anchors` in the order of its targets: every cell of the table
+ * holds the classes' anchors class after class, class c owning class_count[c] slots; anchor n belongs to the class that owns
+ * slot n % sum(class_count).  HOST arrays per anchor class (n_cls <= 32, at most 64 slots): class_label (1-based, pairwise
+ * different), matched, unmatched, class_count.  col_max: (b, m) uint32 of scratch.  Outputs, each written whole:
+ * box_cls_labels (b, n_anchors) int32, box_reg_targets (b, n_anchors, 7), reg_weights (b, n_anchors), num_pos (b) int32.
+ * Per (scene, class c, anchor a of c):
+ *  - the participating gts are the rows whose label equals class_label[c].  The reference trims trailing zero rows and maps
+ *    a label-0 row onto the last class; such rows have zero area, therefore IoU 0 with everything, and can never influence a
+ *    label or a target, so here a row with label 0 takes part in no class;
+ *  - iou = boxes3d_nearest_bev_iou in float32, each operation rounded separately: r = |ry - floor(ry / pi + 0.5) * pi|, dims
+ *    swapped when !(r < pi / 4), corners c -+ dim / 2, inter from max / min / clamp_min(., 0), iou = inter /
+ *    max(area_a + area_b - inter, 1e-6);
+ *  - row_max, row_arg: the maximum over the participating gts and its lowest index; col_max[j]: the maximum over the class's
+ *    anchors, an integer atomicMax on the bit pattern (all values >= 0), so it depends on no order; a column maximum of 0
+ *    counts as -1 and matches nothing;
+ *  - the anchor is forced when iou(a, j) == col_max[j] for some participating j; its gt is then row_arg, not j;
+ *  - label = class_label[c] when forced; else 0 when row_max < unmatched[c] or the class has no gt in the scene; else
+ *    class_label[c] when row_max >= matched[c]; else -1.  A forced anchor keeps its label below the unmatched threshold;
+ *  - positives get ResidualCoder.encode_torch(gt[row_arg], anchor): sizes clamped to 1e-5, sqrt and divisions float32, the
+ *    three logs evaluated in double and rounded once; reg_weights 1; every other row is zero; num_pos counts them. */
+int pda_anchor_assign_targets(const float *gt_boxes, int gt_cols, int b, int m, const float *anchors, int n_anchors, int n_cls,
+                              const int32_t *class_label, const float *matched, const float *unmatched,
+                              const int32_t *class_count, uint32_t *col_max, int32_t *box_cls_labels, float *box_reg_targets,
+                              float *reg_weights, int32_t *num_pos, pda_stream_t stream);
+/* get_cls_layer_loss + get_box_reg_layer_loss in one pass and one small finishing launch.  cls_preds (b, n_anchors,
+ * num_class), box_preds (b, n_anchors, 7), dir_cls_preds (b, n_anchors, bins) or NULL, the labels, targets and num_pos of
+ * pda_anchor_assign_targets, anchors (n_anchors, 7) for the headings, code_weights HOST (7).  Per scene norm = max(num_pos, 1).
+ * cls: SigmoidFocalClassificationLoss (alpha 0.25, gamma 2) on the one-hot of the label (num_class == 1: every positive is
+ * class 1), weight (label >= 0) / norm, summed, / b * cls_weight.  loc: add_sin_difference on column 6, WeightedSmoothL1Loss
+ * (beta 1/9, code_weights), weight (label > 0) / norm, a NaN target contributes 0, / b * loc_weight.  dir: target bin
+ * clamp(floor(limit_period(target[6] + anchor[6] - dir_offset, 0, 2 pi) / (2 pi / bins)), 0, bins - 1) in float32, softmax
+ * cross-entropy, weight (label > 0) / norm, / b * dir_weight.  out = [rpn_loss_cls, rpn_loss_loc, rpn_loss_dir, rpn_loss];
+ * grad_cls, grad_box, grad_dir (the shapes of the predictions, written whole) hold d rpn_loss / d prediction; partials:
+ * 3 * pda_anchor_loss_blocks(b * n_anchors) float64 of scratch, summed in a fixed order; no float atomics.  The backward
+ * multiplies the gradients by the incoming scalar with pda_center_scale. */
+int64_t pda_anchor_loss_blocks(int64_t n);
+int pda_anchor_loss(const float *cls_preds, const float *box_preds, const float *dir_cls_preds, const int32_t *box_cls_labels,
+                    const float *box_reg_targets, const int32_t *num_pos, const float *anchors, int b, int n_anchors,
+                    int num_class, int bins, const float *code_weights, double cls_weight, double loc_weight, double dir_weight,
+                    double dir_offset, float *grad_cls, float *grad_box, float *grad_dir, double *partials, float *out,
+                    pda_stream_t stream);
+/* generate_predicted_boxes in one launch: batch_box_preds (b, n_anchors, 7) = ResidualCoder.decode_torch(box_preds, anchors)
+ * in float32 with exp evaluated in double and rounded once; with dir_cls_preds (b, n_anchors, bins) the heading becomes
+ * limit_period(ry - dir_offset, dir_limit_offset, 2 pi / bins) + dir_offset + (2 pi / bins) * argmax(dir), the lowest index
+ * on a tie. */
+int pda_anchor_decode(const float *box_preds, const float *dir_cls_preds, const float *anchors, int b, int n_anchors, int bins,
+                      double dir_offset, double dir_limit_offset, float *batch_box_preds, pda_stream_t stream);
+/* PillarVFE's PFN input rows: voxels (v, p, c) float32 (c >= 3, padded rows zero), voxel_num_points (v) int32, voxel_coords
+ * (v, 4) int32 (b, z, y, x) -> out (v, p, c' ) with c' = (absolute_xyz ? c : c - 3) + 6 + (with_distance ? 1 : 0): [the raw
+ * columns (from column 3 on without absolute_xyz), xyz - mean, xyz - cell centre, |xyz|]; rows from num_points on are exactly
+ * zero.  The mean is the float32 sum over all p rows IN ROW ORDER divided by num_points; the cell centre is
+ * coord * voxel_size3 + offset3 (HOST float32 arrays, offset3 = float32(voxel / 2 + range_lo)), a multiplication and an
+ * addition.  One launch, one wave per voxel. */
+int pda_pillar_features(const float *voxels, const int32_t *voxel_num_points, const int32_t *voxel_coords, int64_t v, int p,
+                        int c, const float *voxel_size3, const float *offset3, int absolute_xyz, int with_distance, float *out,
+                        pda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

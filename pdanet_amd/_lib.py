@@ -230,6 +230,12 @@ SIGNATURES = {
                                  _i, _i, ctypes.c_int64, _vp, _vp, ctypes.POINTER(_vp), _vp],
     "pda_center_decode": [_vp] * 7 + [_i] * 5 + [ctypes.POINTER(ctypes.c_int32)] + [ctypes.c_double] * 5
                          + [ctypes.POINTER(_f), _i, ctypes.c_double, _vp, _vp, _vp, _vp],
+    "pda_anchor_assign_targets": [_vp, _i, _i, _i, _vp, _i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_f),
+                                  ctypes.POINTER(_f), ctypes.POINTER(ctypes.c_int32), _vp, _vp, _vp, _vp, _vp, _vp],
+    "pda_anchor_loss_blocks": [ctypes.c_int64],
+    "pda_anchor_loss": [_vp] * 7 + [_i] * 4 + [ctypes.POINTER(_f)] + [ctypes.c_double] * 4 + [_vp] * 6,
+    "pda_anchor_decode": [_vp, _vp, _vp, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp, _vp],
+    "pda_pillar_features": [_vp, _vp, _vp, ctypes.c_int64, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _i, _i, _vp, _vp],
     # include/pda_pointnet2_stack.h
     "pda_stack_ball_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     "pda_stack_group_points": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -291,6 +297,7 @@ def load():
     lib.pda_voxel_workspace_bytes.restype = ctypes.c_int64
     lib.pda_dyn_voxel_workspace_bytes.restype = ctypes.c_int64
     lib.pda_center_focal_blocks.restype = ctypes.c_int64
+    lib.pda_anchor_loss_blocks.restype = ctypes.c_int64
     lib.pda_abi_version.restype = _i
     lib.pda_last_error.restype = ctypes.c_char_p
     lib.pda_fp_contract_mode.restype = _i

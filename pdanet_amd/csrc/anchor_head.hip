@@ -1,0 +1,557 @@
+// anchor_head.hip -- the anchor head of PointPillar / SECOND / PV-RCNN on the device: AxisAlignedTargetAssigner's target
+// assignment (dense_heads/target_assigner/axis_aligned_target_assigner.py), AnchorHeadTemplate's three losses and box
+// decoding (dense_heads/anchor_head_template.py, utils/loss_utils.py, utils/box_coder_utils.py ResidualCoder) and the PFN
+// input rows of the hard-voxel PillarVFE (backbones_3d/vfe/pillar_vfe.py).
+//
+// Reference: assign_targets loops over scenes and anchor classes on the host; every iteration builds an anchors x gts IoU
+// matrix, takes two argmaxes and several nonzero() compactions and writes through boolean masks; get_loss materialises
+// one-hot tensors and a dozen temporaries and reads four scalars back.
+//
+// Here: anchor_assign_kernel<false> (column maxima through an integer atomicMax on the float's bits, reduced inside the
+// wave first) and anchor_assign_kernel<true> (the same IoUs recomputed by the same code, labels, targets, weights, the
+// positives counted with an integer atomic): no anchors x gts matrix is stored.  anchor_loss_kernel + anchor_loss_finish_kernel:
+// one pass over the anchors for the three terms and their gradients, per-workgroup float64 partials summed in a fixed order.
+// anchor_decode_kernel and pillar_features_kernel are one launch each.  No float atomics anywhere.
+#include "pda_common.h"
+
+#include <math.h>
+
+namespace pda {
+namespace {
+
+constexpr int AH_THREADS = 256;
+constexpr int AH_TILE = 64;           // gt rows staged in LDS at a time
+constexpr int AH_MAX_SLOTS = 64;      // anchors per location, all classes
+constexpr int AH_MAX_CLASSES = 32;    // anchor classes; also num_class of the loss
+constexpr int AH_MAX_BINS = 8;        // NUM_DIR_BINS
+
+struct AnchorAssignCfg {
+    int b, m, cols, n_anchors, slots, n_cls;
+    int label[AH_MAX_CLASSES];          // the 1-based gt label of each anchor class
+    float matched[AH_MAX_CLASSES];
+    float unmatched[AH_MAX_CLASSES];
+    int first_slot[AH_MAX_CLASSES + 1]; // class c owns the slots [first_slot[c], first_slot[c + 1])
+};
+
+// box_utils.boxes3d_lidar_to_aligned_bev_boxes, every operation a separate float32 one (the file is built with
+// -ffp-contract=off): r = |ry - floor(ry / pi + 0.5) * pi|, dims swapped when !(r < pi / 4), corners c -+ dim / 2.
+__device__ __forceinline__ void aligned_bev(float x, float y, float dx, float dy, float ry, float& x1, float& y1, float& x2,
+                                            float& y2) {
+    const float pi = (float)M_PI;
+    const float r = fabsf(ry - floorf(ry / pi + 0.5f) * pi);
+    const bool keep = r < (float)(M_PI / 4);
+    const float cx = keep ? dx : dy, cy = keep ? dy : dx;
+    const float hx = cx / 2.f, hy = cy / 2.f;
+    x1 = x - hx;
+    y1 = y - hy;
+    x2 = x + hx;
+    y2 = y + hy;
+}
+
+// box_utils.boxes_iou_normal for one pair
+__device__ __forceinline__ float iou_normal(float ax1, float ay1, float ax2, float ay2, float area_a, float bx1, float by1,
+                                            float bx2, float by2, float area_b) {
+    const float x_min = fmaxf(ax1, bx1), x_max = fminf(ax2, bx2);
+    const float y_min = fmaxf(ay1, by1), y_max = fminf(ay2, by2);
+    const float x_len = fmaxf(x_max - x_min, 0.f), y_len = fmaxf(y_max - y_min, 0.f);
+    const float inter = x_len * y_len;
+    return inter / fmaxf(area_a + area_b - inter, 1e-6f);
+}
+
+// SECOND == false: col_max[s, j] = max over the anchors of j's class of iou(a, j), through the bit pattern (values >= 0).
+// SECOND == true: the same IoUs again; labels, targets, weights and the scene's positives.
+// grid (ceil(n_anchors / 256), b); anchor n of a scene is row n of `anchors`, its class the owner of slot n % slots.
+template <bool SECOND>
+__global__ __launch_bounds__(AH_THREADS) void anchor_assign_kernel(const float* __restrict__ anchors,
+                                                                   const float* __restrict__ gt, AnchorAssignCfg g,
+                                                                   uint32_t* __restrict__ col_max,
+                                                                   int32_t* __restrict__ labels, float* __restrict__ targets,
+                                                                   float* __restrict__ weights, int32_t* __restrict__ num_pos) {
+    __shared__ float t_x1[AH_TILE], t_y1[AH_TILE], t_x2[AH_TILE], t_y2[AH_TILE], t_area[AH_TILE];
+    __shared__ int t_label[AH_TILE];
+    __shared__ uint32_t t_col[AH_TILE];
+    __shared__ int slot_label[AH_MAX_SLOTS];
+    __shared__ float slot_matched[AH_MAX_SLOTS], slot_unmatched[AH_MAX_SLOTS];
+    const int s = blockIdx.y;
+    const int n = blockIdx.x * AH_THREADS + (int)threadIdx.x;
+    const int lane = (int)(threadIdx.x & 63);
+    const bool live = n < g.n_anchors;
+    if ((int)threadIdx.x < g.slots) {
+        int c = 0;
+        while (c + 1 < g.n_cls && (int)threadIdx.x >= g.first_slot[c + 1]) ++c;
+        slot_label[threadIdx.x] = g.label[c];
+        slot_matched[threadIdx.x] = g.matched[c];
+        slot_unmatched[threadIdx.x] = g.unmatched[c];
+    }
+    float a[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (live) {
+#pragma unroll
+        for (int c = 0; c < 7; ++c) a[c] = anchors[(size_t)n * 7 + c];
+    }
+    float ax1, ay1, ax2, ay2;
+    aligned_bev(a[0], a[1], a[3], a[4], a[6], ax1, ay1, ax2, ay2);
+    const float area_a = (ax2 - ax1) * (ay2 - ay1);
+    __syncthreads();
+    const int slot = live ? n % g.slots : 0;
+    const int my_label = live ? slot_label[slot] : -1;      // a dead lane takes part in nothing
+    const float* sgt = gt + (size_t)s * g.m * g.cols;
+
+    float row_max = -1.f;
+    int row_arg = -1;
+    bool forced = false;
+    for (int t0 = 0; t0 < g.m; t0 += AH_TILE) {
+        const int rows = min(AH_TILE, g.m - t0);
+        if ((int)threadIdx.x < rows) {
+            const float* row = sgt + (size_t)(t0 + threadIdx.x) * g.cols;
+            float x1, y1, x2, y2;
+            aligned_bev(row[0], row[1], row[3], row[4], row[6], x1, y1, x2, y2);
+            t_x1[threadIdx.x] = x1;
+            t_y1[threadIdx.x] = y1;
+            t_x2[threadIdx.x] = x2;
+            t_y2[threadIdx.x] = y2;
+            t_area[threadIdx.x] = (x2 - x1) * (y2 - y1);
+            const float lf = row[g.cols - 1];
+            t_label[threadIdx.x] = (lf >= 1.f && lf <= 1048576.f) ? (int)lf : 0;      // 0: takes part in no class
+            if (SECOND) t_col[threadIdx.x] = col_max[(size_t)s * g.m + t0 + threadIdx.x];
+        }
+        __syncthreads();
+        for (int jj = 0; jj < rows; ++jj) {
+            const bool part = t_label[jj] == my_label;
+            float iou = 0.f;
+            if (part) iou = iou_normal(ax1, ay1, ax2, ay2, area_a, t_x1[jj], t_y1[jj], t_x2[jj], t_y2[jj], t_area[jj]);
+            if (!SECOND) {
+                if (__ballot(iou > 0.f)) {      // wave-uniform: most pairs do not overlap
+                    const float w = wave_max_f32(iou);
+                    if (lane == 0) atomicMax(col_max + (size_t)s * g.m + t0 + jj, __float_as_uint(w));
+                }
+            } else if (part) {
+                if (iou > row_max) {      // strict: the lowest index keeps a tie
+                    row_max = iou;
+                    row_arg = t0 + jj;
+                }
+                const uint32_t cm = t_col[jj];      // a column maximum of 0 counts as -1 and matches nothing
+                forced = forced || (cm != 0u && __float_as_uint(iou) == cm);
+            }
+        }
+        __syncthreads();
+    }
+    if (!SECOND) return;
+
+    bool pos = false;
+    int label = 0;
+    if (live && row_arg >= 0) {
+        if (forced) pos = true;
+        else if (row_max < slot_unmatched[slot]) label = 0;
+        else if (row_max >= slot_matched[slot]) pos = true;
+        else label = -1;
+    }
+    if (live) {
+        float t[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (pos) {
+            label = my_label;
+            const float* row = sgt + (size_t)row_arg * g.cols;
+            // ResidualCoder.encode_torch: sizes clamped to 1e-5, float32 sqrt and divisions, the logs in double
+            const float dxa = fmaxf(a[3], 1e-5f), dya = fmaxf(a[4], 1e-5f), dza = fmaxf(a[5], 1e-5f);
+            const float dxg = fmaxf(row[3], 1e-5f), dyg = fmaxf(row[4], 1e-5f), dzg = fmaxf(row[5], 1e-5f);
+            const float diagonal = sqrtf(dxa * dxa + dya * dya);
+            t[0] = (row[0] - a[0]) / diagonal;
+            t[1] = (row[1] - a[1]) / diagonal;
+            t[2] = (row[2] - a[2]) / dza;
+            t[3] = (float)log((double)(dxg / dxa));
+            t[4] = (float)log((double)(dyg / dya));
+            t[5] = (float)log((double)(dzg / dza));
+            t[6] = row[6] - a[6];
+        }
+        const size_t e = (size_t)s * g.n_anchors + n;
+        labels[e] = label;
+        weights[e] = pos ? 1.f : 0.f;
+#pragma unroll
+        for (int c = 0; c < 7; ++c) targets[e * 7 + c] = t[c];
+    }
+    const uint64_t mask = __ballot(pos);
+    if (lane == 0 && mask) atomicAdd(num_pos + s, (int)__popcll(mask));
+}
+
+// ---- the three losses ----------------------------------------------------------------------------------------------------------
+constexpr int AL_THREADS = 256;
+constexpr int AL_PER_THREAD = 4;
+constexpr int AL_MAX_BLOCKS = 2048;
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__device__ __forceinline__ bool nan_bits(float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
+
+struct AnchorLossCfg {
+    int b, n_anchors, num_class, bins;
+    float code_weight[7];
+    float dir_offset, two_pi, bin_width;      // float32 roundings of DIR_OFFSET, 2 pi, 2 pi / bins
+    double cls_scale, loc_scale, dir_scale;   // weight / b
+};
+
+// One anchor per thread and step.  Per anchor, with norm = max(num_pos[scene], 1):
+//   cls: SigmoidFocalClassificationLoss(alpha 0.25, gamma 2) on the one-hot of the label, weight (label >= 0) / norm;
+//   loc: WeightedSmoothL1Loss(beta 1/9) after add_sin_difference on column 6, weight (label > 0) / norm, a NaN target 0;
+//   dir: softmax cross-entropy against the direction bin, weight (label > 0) / norm.
+// The gradients hold d(rpn_loss) / d(prediction) for an incoming gradient of 1; partials (3, blocks) the unscaled sums.
+__global__ __launch_bounds__(AL_THREADS) void anchor_loss_kernel(
+        const float* __restrict__ cls_preds, const float* __restrict__ box_preds, const float* __restrict__ dir_preds,
+        const int32_t* __restrict__ labels, const float* __restrict__ targets, const int32_t* __restrict__ num_pos,
+        const float* __restrict__ anchors, AnchorLossCfg g, float* __restrict__ grad_cls, float* __restrict__ grad_box,
+        float* __restrict__ grad_dir, double* __restrict__ partials) {
+    __shared__ double red[3][AL_THREADS / 64];
+    double s_cls = 0.0, s_loc = 0.0, s_dir = 0.0;
+    const long long total = (long long)g.b * g.n_anchors;
+    const long long stride = (long long)gridDim.x * AL_THREADS;
+    const double beta = 1.0 / 9.0;
+    for (long long e = (long long)blockIdx.x * AL_THREADS + threadIdx.x; e < total; e += stride) {
+        const int s = (int)(e / g.n_anchors);
+        const int n = (int)(e % g.n_anchors);
+        const int label = labels[e];
+        const double norm = (double)max(num_pos[s], 1);
+        const double w = 1.0 / norm;
+        // classification
+        const int hot = label > 0 ? (g.num_class == 1 ? 1 : label) : 0;      // class-agnostic: every positive is class 1
+        for (int k = 0; k < g.num_class; ++k) {
+            const size_t at = (size_t)e * g.num_class + k;
+            float gr = 0.f;
+            if (label >= 0) {
+                const double x = (double)cls_preds[at];
+                const bool t = hot == k + 1;
+                const double p = 1.0 / (1.0 + exp(-x));
+                const double alpha = t ? 0.25 : 0.75;
+                const double pt = t ? 1.0 - p : p;
+                const double bce = fmax(x, 0.0) - (t ? x : 0.0) + log1p(exp(-fabs(x)));
+                s_cls += alpha * pt * pt * bce * w;
+                const double dpt = t ? -p * (1.0 - p) : p * (1.0 - p);
+                const double dbce = p - (t ? 1.0 : 0.0);
+                gr = (float)(alpha * (2.0 * pt * dpt * bce + pt * pt * dbce) * w * g.cls_scale);
+            }
+            grad_cls[at] = gr;
+        }
+        // regression and direction: positives only
+        float gb[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float gd[AH_MAX_BINS];
+#pragma unroll
+        for (int k = 0; k < AH_MAX_BINS; ++k) gd[k] = 0.f;
+        if (label > 0) {
+            const float* pr = box_preds + (size_t)e * 7;
+            const float* tg = targets + (size_t)e * 7;
+#pragma unroll
+            for (int c = 0; c < 7; ++c) {
+                const float tf = tg[c];
+                if (nan_bits(tf)) continue;
+                double p = (double)pr[c], t = (double)tf, chain = 1.0;
+                if (c == 6) {      // sin(a - b) = sin a cos b - cos a sin b, both halves differentiated in the prediction
+                    const double a0 = p, b0 = t;
+                    p = sin(a0) * cos(b0);
+                    t = cos(a0) * sin(b0);
+                    chain = cos(a0) * cos(b0) + sin(a0) * sin(b0);
+                }
+                const double diff = (p - t) * (double)g.code_weight[c];
+                const double ad = fabs(diff);
+                s_loc += (ad < beta ? 0.5 * ad * ad / beta : ad - 0.5 * beta) * w;
+                const double dl = ad < beta ? diff / beta : (diff > 0.0 ? 1.0 : (diff < 0.0 ? -1.0 : 0.0));
+                gb[c] = (float)(dl * (double)g.code_weight[c] * chain * w * g.loc_scale);
+            }
+            if (dir_preds) {
+                // get_direction_target in float32, as the reference evaluates it
+                const float rot_gt = tg[6] + anchors[(size_t)n * 7 + 6];
+                const float val = rot_gt - g.dir_offset;
+                const float offset_rot = val - floorf(val / g.two_pi + 0.f) * g.two_pi;
+                int bin = (int)floorf(offset_rot / g.bin_width);
+                bin = bin < 0 ? 0 : (bin > g.bins - 1 ? g.bins - 1 : bin);
+                const float* dp = dir_preds + (size_t)e * g.bins;
+                double mx = -INFINITY;
+                for (int k = 0; k < g.bins; ++k) mx = fmax(mx, (double)dp[k]);
+                double z = 0.0;
+                for (int k = 0; k < g.bins; ++k) z += exp((double)dp[k] - mx);
+                const double lse = mx + log(z);
+                s_dir += (lse - (double)dp[bin]) * w;
+#pragma unroll
+                for (int k = 0; k < AH_MAX_BINS; ++k)
+                    if (k < g.bins) gd[k] = (float)((exp((double)dp[k] - lse) - (k == bin ? 1.0 : 0.0)) * w * g.dir_scale);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 7; ++c) grad_box[(size_t)e * 7 + c] = gb[c];
+        if (dir_preds) {
+#pragma unroll
+            for (int k = 0; k < AH_MAX_BINS; ++k)
+                if (k < g.bins) grad_dir[(size_t)e * g.bins + k] = gd[k];
+        }
+    }
+    s_cls = wave_sum_f64(s_cls);
+    s_loc = wave_sum_f64(s_loc);
+    s_dir = wave_sum_f64(s_dir);
+    const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    if (lane == 0) {
+        red[0][wave] = s_cls;
+        red[1][wave] = s_loc;
+        red[2][wave] = s_dir;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double v = 0.0;
+        for (int w = 0; w < AL_THREADS / 64; ++w) v += red[threadIdx.x][w];
+        partials[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = v;
+    }
+}
+
+// out = [rpn_loss_cls, rpn_loss_loc, rpn_loss_dir, rpn_loss]
+__global__ __launch_bounds__(64) void anchor_loss_finish_kernel(const double* __restrict__ partials, int blocks, double cls_scale,
+                                                                double loc_scale, double dir_scale, float* __restrict__ out) {
+    double v[3];
+    for (int q = 0; q < 3; ++q) {
+        double a = 0.0;
+        for (int i = threadIdx.x; i < blocks; i += 64) a += partials[(size_t)q * blocks + i];
+        v[q] = wave_sum_f64(a);
+    }
+    if (threadIdx.x == 0) {
+        const float c = (float)(v[0] * cls_scale), l = (float)(v[1] * loc_scale), d = (float)(v[2] * dir_scale);
+        out[0] = c;
+        out[1] = l;
+        out[2] = d;
+        out[3] = c + (l + d);      // rpn_loss = cls_loss + (loc_loss + dir_loss)
+    }
+}
+
+// ---- decoding ------------------------------------------------------------------------------------------------------------------
+struct AnchorDecodeCfg {
+    int b, n_anchors, bins;
+    float dir_offset, dir_limit_offset, period;
+};
+
+// generate_predicted_boxes: ResidualCoder.decode_torch against the anchors, then the direction classifier's bin.
+__global__ __launch_bounds__(256) void anchor_decode_kernel(const float* __restrict__ box_preds,
+                                                            const float* __restrict__ dir_preds,
+                                                            const float* __restrict__ anchors, AnchorDecodeCfg g,
+                                                            float* __restrict__ out) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)g.b * g.n_anchors) return;
+    const int n = (int)(e % g.n_anchors);
+    const float* a = anchors + (size_t)n * 7;
+    const float* t = box_preds + (size_t)e * 7;
+    float* o = out + (size_t)e * 7;
+    const float dxa = a[3], dya = a[4], dza = a[5];
+    const float diagonal = sqrtf(dxa * dxa + dya * dya);
+    o[0] = t[0] * diagonal + a[0];
+    o[1] = t[1] * diagonal + a[1];
+    o[2] = t[2] * dza + a[2];
+    o[3] = (float)exp((double)t[3]) * dxa;
+    o[4] = (float)exp((double)t[4]) * dya;
+    o[5] = (float)exp((double)t[5]) * dza;
+    float rg = t[6] + a[6];
+    if (dir_preds) {
+        const float* dp = dir_preds + (size_t)e * g.bins;
+        int best = 0;
+        float top = dp[0];
+        for (int k = 1; k < g.bins; ++k)
+            if (dp[k] > top) {      // strict: the lowest index keeps a tie
+                top = dp[k];
+                best = k;
+            }
+        const float val = rg - g.dir_offset;
+        const float dir_rot = val - floorf(val / g.period + g.dir_limit_offset) * g.period;
+        rg = (dir_rot + g.dir_offset) + g.period * (float)best;
+    }
+    o[6] = rg;
+}
+
+// ---- PillarVFE's PFN input rows ------------------------------------------------------------------------------------------------
+struct PillarFeatCfg {
+    long long V;
+    int P, C, absolute_xyz, with_distance, c_out;
+    float vs[3], off[3];      // float32(voxel size), float32(voxel / 2 + range_lo), x y z
+};
+
+// One wave per voxel.  The mean is the sum over all P rows IN ROW ORDER (lanes 0..2, one coordinate each) divided by
+// num_points; rows from num_points on are written as zeros.
+__global__ __launch_bounds__(256) void pillar_features_kernel(const float* __restrict__ voxels,
+                                                              const int32_t* __restrict__ num_points,
+                                                              const int32_t* __restrict__ coords, PillarFeatCfg g,
+                                                              float* __restrict__ out) {
+    const long long v = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (v >= g.V) return;      // wave-uniform
+    const int lane = (int)(threadIdx.x & 63);
+    const int np = num_points[v];
+    const float* vox = voxels + (size_t)v * g.P * g.C;
+    float sum = 0.f;
+    if (lane < 3)
+        for (int p = 0; p < g.P; ++p) sum += vox[(size_t)p * g.C + lane];
+    const float mean = sum / (float)np;
+    const float mx = __shfl(mean, 0), my = __shfl(mean, 1), mz = __shfl(mean, 2);
+    const int32_t* c = coords + (size_t)v * 4;
+    const float cx = (float)c[3] * g.vs[0] + g.off[0];
+    const float cy = (float)c[2] * g.vs[1] + g.off[1];
+    const float cz = (float)c[1] * g.vs[2] + g.off[2];
+    const int first = g.absolute_xyz ? 0 : 3;
+    for (int p = lane; p < g.P; p += 64) {
+        const float* row = vox + (size_t)p * g.C;
+        float* o = out + ((size_t)v * g.P + p) * g.c_out;
+        if (p >= np) {
+            for (int k = 0; k < g.c_out; ++k) o[k] = 0.f;
+            continue;
+        }
+        const float x = row[0], y = row[1], z = row[2];
+        int k = 0;
+        for (int q = first; q < g.C; ++q) o[k++] = row[q];
+        o[k++] = x - mx;
+        o[k++] = y - my;
+        o[k++] = z - mz;
+        o[k++] = x - cx;
+        o[k++] = y - cy;
+        o[k++] = z - cz;
+        if (g.with_distance) o[k++] = sqrtf((x * x + y * y) + z * z);
+    }
+}
+
+}  // namespace
+}  // namespace pda
+
+// ---- C entry points --------------------------------------------------------------------------------------------------------------
+PDA_API int pda_anchor_assign_targets(const float* gt_boxes, int gt_cols, int b, int m, const float* anchors, int n_anchors,
+                                      int n_cls, const int32_t* class_label, const float* matched, const float* unmatched,
+                                      const int32_t* class_count, uint32_t* col_max, int32_t* box_cls_labels,
+                                      float* box_reg_targets, float* reg_weights, int32_t* num_pos, pda_stream_t stream) {
+    PDA_REQUIRE(b >= 0 && m >= 0 && n_anchors >= 0, "pda_anchor_assign_targets: b=%d m=%d n_anchors=%d", b, m, n_anchors);
+    PDA_REQUIRE(gt_cols == 8, "pda_anchor_assign_targets: gt_cols=%d, boxes must have 7 + 1 columns", gt_cols);
+    PDA_REQUIRE(n_cls >= 1 && n_cls <= pda::AH_MAX_CLASSES, "pda_anchor_assign_targets: n_cls=%d outside 1..%d", n_cls,
+                pda::AH_MAX_CLASSES);
+    PDA_REQUIRE(b <= 65535, "pda_anchor_assign_targets: batch %d > 65535", b);
+    PDA_REQUIRE((int64_t)b * n_anchors < ((int64_t)1 << 31) / 8, "pda_anchor_assign_targets: b=%d n_anchors=%d too large", b,
+                n_anchors);
+    PDA_REQUIRE((int64_t)b * m < ((int64_t)1 << 28), "pda_anchor_assign_targets: b=%d m=%d too large", b, m);
+    if (b == 0 || n_anchors == 0) return PDA_OK;
+    PDA_REQUIRE(class_label && matched && unmatched && class_count, "pda_anchor_assign_targets: null class array");
+    pda::AnchorAssignCfg g{};
+    g.b = b;
+    g.m = m;
+    g.cols = gt_cols;
+    g.n_anchors = n_anchors;
+    g.n_cls = n_cls;
+    int slots = 0;
+    for (int c = 0; c < n_cls; ++c) {
+        PDA_REQUIRE(class_label[c] >= 1 && class_label[c] <= 1048576, "pda_anchor_assign_targets: class_label[%d]=%d", c,
+                    class_label[c]);
+        for (int d = 0; d < c; ++d)
+            PDA_REQUIRE(class_label[d] != class_label[c], "pda_anchor_assign_targets: anchor classes %d and %d share label %d",
+                        d, c, class_label[c]);
+        PDA_REQUIRE(class_count[c] >= 1 && class_count[c] <= pda::AH_MAX_SLOTS, "pda_anchor_assign_targets: class_count[%d]=%d",
+                    c, class_count[c]);
+        g.label[c] = class_label[c];
+        g.matched[c] = matched[c];
+        g.unmatched[c] = unmatched[c];
+        g.first_slot[c] = slots;
+        slots += class_count[c];
+        PDA_REQUIRE(slots <= pda::AH_MAX_SLOTS, "pda_anchor_assign_targets: more than %d anchors per location", pda::AH_MAX_SLOTS);
+    }
+    g.first_slot[n_cls] = slots;
+    g.slots = slots;
+    PDA_REQUIRE(n_anchors % slots == 0, "pda_anchor_assign_targets: n_anchors=%d is no multiple of %d anchors per location",
+                n_anchors, slots);
+    PDA_REQUIRE(anchors && box_cls_labels && box_reg_targets && reg_weights && num_pos, "pda_anchor_assign_targets: null pointer");
+    PDA_REQUIRE(m == 0 || (gt_boxes && col_max), "pda_anchor_assign_targets: null gt_boxes or col_max");
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(num_pos, 0, (size_t)b * 4, st) != hipSuccess ||
+        (m > 0 && hipMemsetAsync(col_max, 0, (size_t)b * m * 4, st) != hipSuccess)) {
+        pda::set_error("pda_anchor_assign_targets: hipMemsetAsync failed");
+        return PDA_ERR_LAUNCH;
+    }
+    const dim3 grid(pda::divup(n_anchors, pda::AH_THREADS), b);
+    if (m > 0)
+        hipLaunchKernelGGL(pda::anchor_assign_kernel<false>, grid, dim3(pda::AH_THREADS), 0, st, anchors, gt_boxes, g, col_max,
+                           (int32_t*)nullptr, (float*)nullptr, (float*)nullptr, (int32_t*)nullptr);
+    hipLaunchKernelGGL(pda::anchor_assign_kernel<true>, grid, dim3(pda::AH_THREADS), 0, st, anchors, gt_boxes, g, col_max,
+                       box_cls_labels, box_reg_targets, reg_weights, num_pos);
+    return pda::check_launch("pda_anchor_assign_targets");
+}
+
+PDA_API int64_t pda_anchor_loss_blocks(int64_t n) {
+    if (n <= 0) return 0;
+    const int64_t blocks = pda::divup64(n, (int64_t)pda::AL_THREADS * pda::AL_PER_THREAD);
+    return blocks < pda::AL_MAX_BLOCKS ? blocks : pda::AL_MAX_BLOCKS;
+}
+
+PDA_API int pda_anchor_loss(const float* cls_preds, const float* box_preds, const float* dir_cls_preds,
+                            const int32_t* box_cls_labels, const float* box_reg_targets, const int32_t* num_pos,
+                            const float* anchors, int b, int n_anchors, int num_class, int bins, const float* code_weights,
+                            double cls_weight, double loc_weight, double dir_weight, double dir_offset, float* grad_cls,
+                            float* grad_box, float* grad_dir, double* partials, float* out, pda_stream_t stream) {
+    PDA_REQUIRE(b >= 1 && n_anchors >= 1, "pda_anchor_loss: b=%d n_anchors=%d", b, n_anchors);
+    PDA_REQUIRE((int64_t)b * n_anchors < ((int64_t)1 << 31) / 32, "pda_anchor_loss: b=%d n_anchors=%d too large", b, n_anchors);
+    PDA_REQUIRE(num_class >= 1 && num_class <= pda::AH_MAX_CLASSES, "pda_anchor_loss: num_class=%d outside 1..%d", num_class,
+                pda::AH_MAX_CLASSES);
+    PDA_REQUIRE(!dir_cls_preds || (bins >= 1 && bins <= pda::AH_MAX_BINS), "pda_anchor_loss: bins=%d outside 1..%d", bins,
+                pda::AH_MAX_BINS);
+    PDA_REQUIRE(cls_preds && box_preds && box_cls_labels && box_reg_targets && num_pos && anchors && code_weights && grad_cls &&
+                    grad_box && partials && out,
+                "pda_anchor_loss: null pointer");
+    PDA_REQUIRE(!dir_cls_preds || grad_dir, "pda_anchor_loss: null grad_dir");
+    pda::AnchorLossCfg g{};
+    g.b = b;
+    g.n_anchors = n_anchors;
+    g.num_class = num_class;
+    g.bins = dir_cls_preds ? bins : 0;
+    for (int c = 0; c < 7; ++c) g.code_weight[c] = code_weights[c];
+    g.dir_offset = (float)dir_offset;
+    g.two_pi = (float)(2.0 * M_PI);
+    g.bin_width = (float)(2.0 * M_PI / (dir_cls_preds ? bins : 1));
+    g.cls_scale = cls_weight / b;
+    g.loc_scale = loc_weight / b;
+    g.dir_scale = dir_cls_preds ? dir_weight / b : 0.0;
+    const int blocks = (int)pda_anchor_loss_blocks((int64_t)b * n_anchors);
+    hipLaunchKernelGGL(pda::anchor_loss_kernel, dim3(blocks), dim3(pda::AL_THREADS), 0, (hipStream_t)stream, cls_preds, box_preds,
+                       dir_cls_preds, box_cls_labels, box_reg_targets, num_pos, anchors, g, grad_cls, grad_box, grad_dir,
+                       partials);
+    hipLaunchKernelGGL(pda::anchor_loss_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partials, blocks, g.cls_scale,
+                       g.loc_scale, g.dir_scale, out);
+    return pda::check_launch("pda_anchor_loss");
+}
+
+PDA_API int pda_anchor_decode(const float* box_preds, const float* dir_cls_preds, const float* anchors, int b, int n_anchors,
+                              int bins, double dir_offset, double dir_limit_offset, float* batch_box_preds,
+                              pda_stream_t stream) {
+    PDA_REQUIRE(b >= 0 && n_anchors >= 0 && (int64_t)b * n_anchors < ((int64_t)1 << 31) / 8, "pda_anchor_decode: b=%d n_anchors=%d",
+                b, n_anchors);
+    PDA_REQUIRE(!dir_cls_preds || (bins >= 1 && bins <= pda::AH_MAX_BINS), "pda_anchor_decode: bins=%d outside 1..%d", bins,
+                pda::AH_MAX_BINS);
+    if (b == 0 || n_anchors == 0) return PDA_OK;
+    PDA_REQUIRE(box_preds && anchors && batch_box_preds, "pda_anchor_decode: null pointer");
+    pda::AnchorDecodeCfg g{};
+    g.b = b;
+    g.n_anchors = n_anchors;
+    g.bins = dir_cls_preds ? bins : 0;
+    g.dir_offset = (float)dir_offset;
+    g.dir_limit_offset = (float)dir_limit_offset;
+    g.period = (float)(2.0 * M_PI / (dir_cls_preds ? bins : 1));
+    hipLaunchKernelGGL(pda::anchor_decode_kernel, dim3((unsigned)pda::divup64((int64_t)b * n_anchors, 256)), dim3(256), 0,
+                       (hipStream_t)stream, box_preds, dir_cls_preds, anchors, g, batch_box_preds);
+    return pda::check_launch("pda_anchor_decode");
+}
+
+PDA_API int pda_pillar_features(const float* voxels, const int32_t* voxel_num_points, const int32_t* voxel_coords, int64_t v,
+                                int p, int c, const float* voxel_size3, const float* offset3, int absolute_xyz,
+                                int with_distance, float* out, pda_stream_t stream) {
+    PDA_REQUIRE(v >= 0 && p >= 0 && v <= (int64_t)INT32_MAX, "pda_pillar_features: v=%lld p=%d", (long long)v, p);
+    PDA_REQUIRE(c >= 3 && c <= 64, "pda_pillar_features: c=%d outside 3..64", c);
+    if (v == 0 || p == 0) return PDA_OK;
+    PDA_REQUIRE(voxels && voxel_num_points && voxel_coords && voxel_size3 && offset3 && out, "pda_pillar_features: null pointer");
+    pda::PillarFeatCfg g{};
+    g.V = v;
+    g.P = p;
+    g.C = c;
+    g.absolute_xyz = absolute_xyz ? 1 : 0;
+    g.with_distance = with_distance ? 1 : 0;
+    g.c_out = (absolute_xyz ? c : c - 3) + 6 + (with_distance ? 1 : 0);
+    for (int i = 0; i < 3; ++i) {
+        g.vs[i] = voxel_size3[i];
+        g.off[i] = offset3[i];
+    }
+    hipLaunchKernelGGL(pda::pillar_features_kernel, dim3((unsigned)pda::divup64(v, 4)), dim3(256), 0, (hipStream_t)stream, voxels,
+                       voxel_num_points, voxel_coords, g, out);
+    return pda::check_launch("pda_pillar_features");
+}

@@ -1,7 +1,11 @@
 """The element-wise losses the PDA-SSD head is configured with, in torch (pcdet/utils/loss_utils.py:75-130
 `WeightedClassificationLoss`, :133-194 `WeightedSmoothL1Loss`, :340-363 `get_corner_loss_lidar`).  On the GPU the training
 path computes these terms inside csrc/head_loss.hip (one launch per term, gradient included); this module is the formulation
-those kernels are checked against (tests/test_iassd_head.py) and what runs when the fused path is switched off."""
+those kernels are checked against (tests/test_iassd_head.py) and what runs when the fused path is switched off.
+
+`SigmoidFocalClassificationLoss` (:9-72) and `WeightedCrossEntropyLoss` (:242-267) are the anchor head's classification and
+direction terms under the reference's names, in plain torch for users of those names; AnchorHeadTemplate.get_loss itself
+takes the fused path of csrc/anchor_head.hip (pda_anchor_loss), which tests/test_anchor_head.py checks against them."""
 import math
 
 import torch
@@ -35,6 +39,33 @@ class WeightedClassificationLoss(nn.Module):
         if reduction == 'none':
             return loss
         return loss.sum(dim=-1) if reduction == 'sum' else loss.mean(dim=-1)
+
+
+class SigmoidFocalClassificationLoss(nn.Module):
+    sigmoid_cross_entropy_with_logits = staticmethod(_stable_bce_logits)
+
+    def __init__(self, gamma=2.0, alpha=0.25):
+        super().__init__()
+        self.alpha, self.gamma = alpha, gamma
+
+    def forward(self, input, target, weights):
+        """input, target (B, N, C) logits and one-hot targets, weights (B, N) -> (B, N, C): alpha_t (1 - p_t)^gamma times the
+        sigmoid cross-entropy, times the anchor's weight."""
+        p = torch.sigmoid(input)
+        alpha_t = target * self.alpha + (1 - target) * (1 - self.alpha)
+        miss = target * (1.0 - p) + (1.0 - target) * p                       # 1 - p_t
+        loss = alpha_t * torch.pow(miss, self.gamma) * _stable_bce_logits(input, target)
+        w = weights.unsqueeze(-1) if weights.dim() == loss.dim() - 1 else weights
+        assert w.dim() == loss.dim()
+        return loss * w
+
+
+class WeightedCrossEntropyLoss(nn.Module):
+    def forward(self, input, target, weights):
+        """input (B, N, C) logits, target (B, N, C) one-hot, weights (B, N) -> (B, N): softmax cross-entropy against the
+        arg-max of the target, times the anchor's weight."""
+        logp = torch.log_softmax(input, dim=-1)
+        return -logp.gather(-1, target.argmax(dim=-1, keepdim=True)).squeeze(-1) * weights
 
 
 class WeightedSmoothL1Loss(nn.Module):

@@ -20,6 +20,19 @@ def grid_size(point_cloud_range, voxel_size):
     return np.round((pr[3:6] - pr[0:3]) / np.array(voxel_size)).astype(np.int64)
 
 
+def collate_voxels(voxels, coords, num_points, num_voxels):
+    """The padded per-scene output of VoxelGenerator.generate_batch -> what the hard-voxel models take: voxels (V, P, C),
+    voxel_coords (V, 4) int32 with the batch index in front (b, z, y, x), voxel_num_points (V) int32, scene after scene.
+    One host read, of the B counts: the PFN layers' BatchNorm statistics must not see whole empty voxels, so the padding
+    has to be cut off, and V depends on the data."""
+    B, cap = num_points.shape
+    counts = [min(max(int(v), 0), cap) for v in num_voxels.tolist()]      # the one host read; -1 marks unusable offsets
+    vox = torch.cat([voxels[b, :n] for b, n in enumerate(counts)], dim=0)
+    num = torch.cat([num_points[b, :n] for b, n in enumerate(counts)], dim=0)
+    crd = torch.cat([torch.cat([coords.new_full((n, 1), b), coords[b, :n]], dim=1) for b, n in enumerate(counts)], dim=0)
+    return vox.contiguous(), crd.contiguous(), num.contiguous()
+
+
 class VoxelSpec:
     """The host-side arguments of the voxel entries: range, voxel size and grid as C arrays."""
 
