@@ -836,7 +836,7 @@ int pda_dyn_pillar_features(const float *points, int64_t n, int columns, const i
                             const int32_t *voxel_coords, const float *mean, const int32_t *counts, const float *voxel_size3,
                             const float *offset3, int absolute_xyz, int with_distance, float *out, pda_stream_t stream);
 
-/* ---- CenterPoint pillar tail (csrc/center_head.hip) --------------------------------------------------------------------------
+/* ---- CenterPoint pillar tail (csrc/pillar.hip: the scatter; csrc/center_head.hip: the head) -------------------------------------
  * PointPillarScatter (backbones_2d/map_to_bev/pointpillar_scatter.py) and CenterHead's target assignment, losses and
  * decoding (dense_heads/center_head.py, model_utils/centernet_utils.py, utils/loss_utils.py:395-517).  Every launch goes on
  * `stream`, nothing is allocated, sizes are checked before any pointer is used and an empty problem is PDA_OK and touches
@@ -903,7 +903,7 @@ int pda_center_decode(const float *top_logits, const int64_t *top_inds, const fl
                       const float *limit_range, int use_thresh, double score_thresh, float *boxes, float *scores,
                       int64_t *labels, pda_stream_t stream);
 
-/* ---- PointPillar / anchor heads (csrc/anchor_head.hip) ------------------------------------------------------------------------
+/* ---- PointPillar / anchor heads (csrc/anchor_head.hip; csrc/pillar.hip: pda_pillar_features) ------------------------------------
  * AxisAlignedTargetAssigner.assign_targets, AnchorHeadTemplate's losses and generate_predicted_boxes
  * (dense_heads/anchor_head_template.py, target_assigner/axis_aligned_target_assigner.py, utils/loss_utils.py,
  * utils/box_coder_utils.py ResidualCoder) and the PFN input rows of the hard-voxel PillarVFE (backbones_3d/vfe/pillar_vfe.py).

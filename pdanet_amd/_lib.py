@@ -251,6 +251,15 @@ SIGNATURES = {
                               _i, _i, _i, _vp],
     "pda_stack_vector_pool_grad": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
 }
+# the entries of SIGNATURES that return a size (int64_t) where every other one returns a status (int)
+SIZE_QUERIES = [
+    "pda_nms_mask_words", "pda_ball_query_cells_scratch_bytes", "pda_bn_relu_scratch_bytes",
+    "pda_layer_norm_scratch_bytes", "pda_linear_wgrad_scratch_bytes", "pda_linear_split_packed_bytes",
+    "pda_colsum_scratch_bytes", "pda_gemm_split_bn_tiles", "pda_densitynet_scratch_bytes",
+    "pda_sa_small_train_workspace_bytes", "pda_sa_xyz_grad_scratch_bytes", "pda_input_stage_workspace_bytes",
+    "pda_augment_workspace_bytes", "pda_augment_steps_workspace_bytes", "pda_once_eval_workspace_bytes",
+    "pda_kitti_eval_workspace_bytes", "pda_kitti_fov_filter_workspace_bytes", "pda_gt_extract_workspace_bytes",
+    "pda_voxel_workspace_bytes", "pda_dyn_voxel_workspace_bytes", "pda_center_focal_blocks", "pda_anchor_loss_blocks"]
 INFO_SYMBOLS = ["pda_abi_version", "pda_last_error", "pda_fp_contract_mode", "pda_opt_n_threads",
                 "pda_fps_coop_timeouts", "pda_debug_fps_spin_limit", "pda_debug_fps_exchange_nonzero"]
 
@@ -276,28 +285,8 @@ def load():
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.argtypes = argtypes
         fn.restype = _i
-    lib.pda_nms_mask_words.restype = ctypes.c_int64
-    lib.pda_ball_query_cells_scratch_bytes.restype = ctypes.c_int64
-    lib.pda_bn_relu_scratch_bytes.restype = ctypes.c_int64
-    lib.pda_layer_norm_scratch_bytes.restype = ctypes.c_int64
-    lib.pda_linear_wgrad_scratch_bytes.restype = ctypes.c_int64
-    lib.pda_linear_split_packed_bytes.restype = ctypes.c_int64
-    lib.pda_colsum_scratch_bytes.restype = ctypes.c_int64
-    lib.pda_gemm_split_bn_tiles.restype = ctypes.c_int64
-    lib.pda_densitynet_scratch_bytes.restype = ctypes.c_int64
-    lib.pda_sa_small_train_workspace_bytes.restype = ctypes.c_int64
-    lib.pda_sa_xyz_grad_scratch_bytes.restype = ctypes.c_int64
-    lib.pda_input_stage_workspace_bytes.restype = ctypes.c_int64
-    lib.pda_augment_workspace_bytes.restype = ctypes.c_int64
-    lib.pda_augment_steps_workspace_bytes.restype = ctypes.c_int64
-    lib.pda_once_eval_workspace_bytes.restype = ctypes.c_int64
-    lib.pda_kitti_eval_workspace_bytes.restype = ctypes.c_int64
-    lib.pda_kitti_fov_filter_workspace_bytes.restype = ctypes.c_int64
-    lib.pda_gt_extract_workspace_bytes.restype = ctypes.c_int64
-    lib.pda_voxel_workspace_bytes.restype = ctypes.c_int64
-    lib.pda_dyn_voxel_workspace_bytes.restype = ctypes.c_int64
-    lib.pda_center_focal_blocks.restype = ctypes.c_int64
-    lib.pda_anchor_loss_blocks.restype = ctypes.c_int64
+    for name in SIZE_QUERIES:
+        getattr(lib, name).restype = ctypes.c_int64
     lib.pda_abi_version.restype = _i
     lib.pda_last_error.restype = ctypes.c_char_p
     lib.pda_fp_contract_mode.restype = _i

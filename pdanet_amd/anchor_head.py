@@ -21,17 +21,12 @@ import torch
 import torch.nn as nn
 
 from . import box_coder_utils
-from .pointnet2_batch_cuda import F32, I32, _call, _chk
+from .config import field
+from .pointnet2_batch_cuda import F32, I32, _call, _chk, _partials
 
 MAX_CLASSES = 32          # csrc/anchor_head.hip AH_MAX_CLASSES
 MAX_SLOTS = 64            # AH_MAX_SLOTS
 MAX_BINS = 8              # AH_MAX_BINS
-
-
-def _get(cfg, key, default=None):
-    if isinstance(cfg, dict):
-        return cfg.get(key, default)
-    return getattr(cfg, key, default)
 
 
 class AnchorGenerator(object):
@@ -41,7 +36,7 @@ class AnchorGenerator(object):
         self.anchor_sizes = [config['anchor_sizes'] for config in anchor_generator_config]
         self.anchor_rotations = [config['anchor_rotations'] for config in anchor_generator_config]
         self.anchor_heights = [config['anchor_bottom_heights'] for config in anchor_generator_config]
-        self.align_center = [_get(config, 'align_center', False) for config in anchor_generator_config]
+        self.align_center = [field(config, 'align_center', False) for config in anchor_generator_config]
         assert len(self.anchor_sizes) == len(self.anchor_rotations) == len(self.anchor_heights)
         self.num_of_anchor_sets = len(self.anchor_sizes)
 
@@ -107,7 +102,7 @@ class AxisAlignedTargetAssigner(object):
             raise NotImplementedError("NORM_BY_NUM_EXAMPLES: True")
         if match_height:
             raise NotImplementedError("MATCH_HEIGHT: True (rotated 3D IoU matching)")
-        if _get(model_cfg, 'USE_MULTIHEAD', False):
+        if field(model_cfg, 'USE_MULTIHEAD', False):
             raise NotImplementedError("USE_MULTIHEAD")
         if getattr(box_coder, 'encode_angle_by_sincos', False) or box_coder.code_size != 7:
             raise NotImplementedError("encode_angle_by_sincos / a code size other than 7")
@@ -183,9 +178,7 @@ class _AnchorLoss(torch.autograd.Function):
         out = torch.empty((4,), dtype=F32, device=dev)
         g_cls, g_box = torch.empty_like(cls_preds), torch.empty_like(box_preds)
         g_dir = torch.empty_like(dir_preds) if dir_preds is not None else None
-        from . import _lib
-        blocks = int(_lib.load().pda_anchor_loss_blocks(B * N))
-        partials = torch.empty((3 * blocks,), dtype=torch.float64, device=dev)
+        partials = _partials("pda_anchor_loss_blocks", B * N, dev)
         _call("pda_anchor_loss", cls_preds, cls_preds.data_ptr(), box_preds.data_ptr(),
               None if dir_preds is None else dir_preds.data_ptr(), labels.data_ptr(), targets.data_ptr(), num_pos.data_ptr(),
               table.data_ptr(), B, N, num_class, bins, code_w, cls_w, loc_w, dir_w, dir_offset, g_cls.data_ptr(),
@@ -267,15 +260,15 @@ class AnchorHeadTemplate(nn.Module):
         self.num_class = num_class
         self.class_names = class_names
         self.predict_boxes_when_training = predict_boxes_when_training
-        self.use_multihead = _get(model_cfg, 'USE_MULTIHEAD', False)
+        self.use_multihead = field(model_cfg, 'USE_MULTIHEAD', False)
         if self.use_multihead:
             raise NotImplementedError("USE_MULTIHEAD (AnchorHeadMulti)")
         target_cfg = model_cfg['TARGET_ASSIGNER_CONFIG']
         coder = target_cfg['BOX_CODER']
         if coder != 'ResidualCoder':
             raise NotImplementedError("BOX_CODER %r" % (coder,))
-        self.box_coder = box_coder_utils.ResidualCoder(num_dir_bins=_get(target_cfg, 'NUM_DIR_BINS', 6),
-                                                       **(_get(target_cfg, 'BOX_CODER_CONFIG', None) or {}))
+        self.box_coder = box_coder_utils.ResidualCoder(num_dir_bins=field(target_cfg, 'NUM_DIR_BINS', 6),
+                                                       **(field(target_cfg, 'BOX_CODER_CONFIG', None) or {}))
         if self.box_coder.encode_angle_by_sincos or self.box_coder.code_size != 7:
             raise NotImplementedError("encode_angle_by_sincos / boxes with more than 7 columns")
         generator_cfg = model_cfg['ANCHOR_GENERATOR_CONFIG']
@@ -308,7 +301,7 @@ class AnchorHeadTemplate(nn.Module):
 
     def build_losses(self, losses_cfg):
         from . import loss_utils
-        if _get(losses_cfg, 'REG_LOSS_TYPE', None) not in (None, 'WeightedSmoothL1Loss'):
+        if field(losses_cfg, 'REG_LOSS_TYPE', None) not in (None, 'WeightedSmoothL1Loss'):
             raise NotImplementedError("REG_LOSS_TYPE %r" % (losses_cfg['REG_LOSS_TYPE'],))
         # the reference's modules, for users of its names; get_loss takes the fused path
         self.add_module('cls_loss_func', loss_utils.SigmoidFocalClassificationLoss(alpha=0.25, gamma=2.0))
@@ -364,7 +357,7 @@ class AnchorHeadSingle(AnchorHeadTemplate):
         self.num_anchors_per_location = sum(self.num_anchors_per_location)
         self.conv_cls = nn.Conv2d(input_channels, self.num_anchors_per_location * self.num_class, kernel_size=1)
         self.conv_box = nn.Conv2d(input_channels, self.num_anchors_per_location * self.box_coder.code_size, kernel_size=1)
-        if _get(model_cfg, 'USE_DIRECTION_CLASSIFIER', None) is not None:
+        if field(model_cfg, 'USE_DIRECTION_CLASSIFIER', None) is not None:
             if not 1 <= model_cfg['NUM_DIR_BINS'] <= MAX_BINS:
                 raise ValueError("NUM_DIR_BINS must lie in 1..%d" % MAX_BINS)
             self.conv_dir_cls = nn.Conv2d(input_channels, self.num_anchors_per_location * model_cfg['NUM_DIR_BINS'], kernel_size=1)

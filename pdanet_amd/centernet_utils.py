@@ -16,17 +16,13 @@ import ctypes
 
 import torch
 
-from .pointnet2_batch_cuda import F32, _call, _chk
+from .pointnet2_batch_cuda import F32, _call, _chk, _partials, _ptr_array
 
 I64 = torch.int64
 MAX_OBJS = 2048           # csrc/center_head.hip CH_MAX_OBJS
 MAX_CODE = 16             # CH_MAX_CODE
 MAX_HEADS = 8
 MAX_CLASSES = 32
-
-
-def _ptrs(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
 class HeadLayout:
@@ -78,8 +74,8 @@ def center_targets(gt_boxes, layout, feature_map_size, point_cloud_range, voxel_
     _call("pda_center_assign_targets", gt_boxes, gt_boxes.data_ptr(), cols, B, M, layout.num_class, layout.n_heads,
           layout.head_of_c, layout.local_of_c, layout.head_classes_c, H, W, K, float(point_cloud_range[0]),
           float(point_cloud_range[1]), float(voxel_size[0]), float(voxel_size[1]), float(feature_map_stride),
-          float(gaussian_overlap), int(min_radius), _ptrs(ret['heatmaps']), _ptrs(ret['target_boxes']), _ptrs(ret['inds']),
-          _ptrs(ret['masks']))
+          float(gaussian_overlap), int(min_radius), _ptr_array(ret['heatmaps']), _ptr_array(ret['target_boxes']),
+          _ptr_array(ret['inds']), _ptr_array(ret['masks']))
     return ret
 
 
@@ -90,8 +86,7 @@ class _FocalLoss(torch.autograd.Function):
         out = torch.zeros((3,), dtype=F32, device=logits.device)
         grad = torch.empty_like(logits)
         if n:
-            blocks = _lib_blocks(n)
-            partials = torch.empty((3 * blocks,), dtype=torch.float64, device=logits.device)
+            partials = _partials("pda_center_focal_blocks", n, logits.device)
             _call("pda_center_focal_loss", logits, _chk(logits, "logits", F32), _chk(heatmap, "heatmap", F32), n, grad.data_ptr(),
                   partials.data_ptr(), out.data_ptr())
         else:
@@ -107,11 +102,6 @@ class _FocalLoss(torch.autograd.Function):
         go = grad_out.contiguous().to(F32)
         _call("pda_center_scale", g, g.data_ptr(), out[1:2].data_ptr(), go.data_ptr(), ctx.weight, g.numel(), res.data_ptr())
         return res, None, None
-
-
-def _lib_blocks(n):
-    from . import _lib
-    return int(_lib.load().pda_center_focal_blocks(n))
 
 
 def focal_loss(logits, heatmap, weight=1.0):
@@ -134,7 +124,7 @@ class _RegLoss(torch.autograd.Function):
         w_c = (ctypes.c_float * code)(*[float(w) for w in code_weights])
         out = torch.zeros((2 + code,), dtype=F32, device=targets.device)
         if B * K:
-            _call("pda_center_reg_loss", targets, _ptrs(maps), ch_c, len(maps), targets.data_ptr(), inds.data_ptr(),
+            _call("pda_center_reg_loss", targets, _ptr_array(maps), ch_c, len(maps), targets.data_ptr(), inds.data_ptr(),
                   masks.data_ptr(), w_c, float(loc_weight), B, K, hw, out.data_ptr())
         else:
             out[1] = 1.0
@@ -151,8 +141,8 @@ class _RegLoss(torch.autograd.Function):
         grads = [torch.zeros_like(m) for m in maps]
         if B * K and hw:
             go = grad_loss.contiguous().to(F32)
-            _call("pda_center_reg_loss_grad", targets, _ptrs(maps), ch_c, len(maps), targets.data_ptr(), inds.data_ptr(),
-                  masks.data_ptr(), w_c, loc_weight, B, K, hw, out.data_ptr(), go.data_ptr(), _ptrs(grads))
+            _call("pda_center_reg_loss_grad", targets, _ptr_array(maps), ch_c, len(maps), targets.data_ptr(), inds.data_ptr(),
+                  masks.data_ptr(), w_c, loc_weight, B, K, hw, out.data_ptr(), go.data_ptr(), _ptr_array(grads))
         return (None, None, None, None, None) + tuple(grads)
 
 

@@ -24,6 +24,17 @@ class AttrDict(dict):
         return AttrDict({k: copy.deepcopy(v, memo) for k, v in self.items()})
 
 
+_REQUIRED = object()
+
+
+def field(cfg, key, default=_REQUIRED):
+    """`key` of a dict or attribute of an object.  Without a default a missing one raises what the lookup raises (KeyError,
+    AttributeError); with a default that is returned instead."""
+    if default is _REQUIRED:
+        return cfg[key] if isinstance(cfg, dict) else getattr(cfg, key)
+    return cfg.get(key, default) if isinstance(cfg, dict) else getattr(cfg, key, default)
+
+
 def to_attr(obj):
     if isinstance(obj, dict):
         return AttrDict({k: to_attr(v) for k, v in obj.items()})

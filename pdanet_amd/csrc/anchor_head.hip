@@ -1,7 +1,6 @@
 // anchor_head.hip -- the anchor head of PointPillar / SECOND / PV-RCNN on the device: AxisAlignedTargetAssigner's target
 // assignment (dense_heads/target_assigner/axis_aligned_target_assigner.py), AnchorHeadTemplate's three losses and box
-// decoding (dense_heads/anchor_head_template.py, utils/loss_utils.py, utils/box_coder_utils.py ResidualCoder) and the PFN
-// input rows of the hard-voxel PillarVFE (backbones_3d/vfe/pillar_vfe.py).
+// decoding (dense_heads/anchor_head_template.py, utils/loss_utils.py, utils/box_coder_utils.py ResidualCoder).
 //
 // Reference: assign_targets loops over scenes and anchor classes on the host; every iteration builds an anchors x gts IoU
 // matrix, takes two argmaxes and several nonzero() compactions and writes through boolean masks; get_loss materialises
@@ -10,9 +9,9 @@
 // Here: anchor_assign_kernel<false> (column maxima through an integer atomicMax on the float's bits, reduced inside the
 // wave first) and anchor_assign_kernel<true> (the same IoUs recomputed by the same code, labels, targets, weights, the
 // positives counted with an integer atomic): no anchors x gts matrix is stored.  anchor_loss_kernel + anchor_loss_finish_kernel:
-// one pass over the anchors for the three terms and their gradients, per-workgroup float64 partials summed in a fixed order.
-// anchor_decode_kernel and pillar_features_kernel are one launch each.  No float atomics anywhere.
-#include "pda_common.h"
+// one pass over the anchors for the three terms and their gradients, per-workgroup float64 partials summed in a fixed order
+// (loss_sums.h).  anchor_decode_kernel is one launch.  No float atomics anywhere.
+#include "loss_sums.h"
 
 #include <math.h>
 
@@ -177,14 +176,6 @@ constexpr int AL_THREADS = 256;
 constexpr int AL_PER_THREAD = 4;
 constexpr int AL_MAX_BLOCKS = 2048;
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ bool nan_bits(float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
-
 struct AnchorLossCfg {
     int b, n_anchors, num_class, bins;
     float code_weight[7];
@@ -202,7 +193,6 @@ __global__ __launch_bounds__(AL_THREADS) void anchor_loss_kernel(
         const int32_t* __restrict__ labels, const float* __restrict__ targets, const int32_t* __restrict__ num_pos,
         const float* __restrict__ anchors, AnchorLossCfg g, float* __restrict__ grad_cls, float* __restrict__ grad_box,
         float* __restrict__ grad_dir, double* __restrict__ partials) {
-    __shared__ double red[3][AL_THREADS / 64];
     double s_cls = 0.0, s_loc = 0.0, s_dir = 0.0;
     const long long total = (long long)g.b * g.n_anchors;
     const long long stride = (long long)gridDim.x * AL_THREADS;
@@ -243,7 +233,7 @@ __global__ __launch_bounds__(AL_THREADS) void anchor_loss_kernel(
 #pragma unroll
             for (int c = 0; c < 7; ++c) {
                 const float tf = tg[c];
-                if (nan_bits(tf)) continue;
+                if (is_nan_bits(tf)) continue;
                 double p = (double)pr[c], t = (double)tf, chain = 1.0;
                 if (c == 6) {      // sin(a - b) = sin a cos b - cos a sin b, both halves differentiated in the prediction
                     const double a0 = p, b0 = t;
@@ -284,32 +274,15 @@ __global__ __launch_bounds__(AL_THREADS) void anchor_loss_kernel(
                 if (k < g.bins) grad_dir[(size_t)e * g.bins + k] = gd[k];
         }
     }
-    s_cls = wave_sum_f64(s_cls);
-    s_loc = wave_sum_f64(s_loc);
-    s_dir = wave_sum_f64(s_dir);
-    const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
-    if (lane == 0) {
-        red[0][wave] = s_cls;
-        red[1][wave] = s_loc;
-        red[2][wave] = s_dir;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        double v = 0.0;
-        for (int w = 0; w < AL_THREADS / 64; ++w) v += red[threadIdx.x][w];
-        partials[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = v;
-    }
+    const double sums[3] = {s_cls, s_loc, s_dir};
+    block_sums_to_partials<3, AL_THREADS>(sums, partials);
 }
 
 // out = [rpn_loss_cls, rpn_loss_loc, rpn_loss_dir, rpn_loss]
 __global__ __launch_bounds__(64) void anchor_loss_finish_kernel(const double* __restrict__ partials, int blocks, double cls_scale,
                                                                 double loc_scale, double dir_scale, float* __restrict__ out) {
     double v[3];
-    for (int q = 0; q < 3; ++q) {
-        double a = 0.0;
-        for (int i = threadIdx.x; i < blocks; i += 64) a += partials[(size_t)q * blocks + i];
-        v[q] = wave_sum_f64(a);
-    }
+    finish_partials<3>(partials, blocks, v);
     if (threadIdx.x == 0) {
         const float c = (float)(v[0] * cls_scale), l = (float)(v[1] * loc_scale), d = (float)(v[2] * dir_scale);
         out[0] = c;
@@ -359,54 +332,6 @@ __global__ __launch_bounds__(256) void anchor_decode_kernel(const float* __restr
         rg = (dir_rot + g.dir_offset) + g.period * (float)best;
     }
     o[6] = rg;
-}
-
-// ---- PillarVFE's PFN input rows ------------------------------------------------------------------------------------------------
-struct PillarFeatCfg {
-    long long V;
-    int P, C, absolute_xyz, with_distance, c_out;
-    float vs[3], off[3];      // float32(voxel size), float32(voxel / 2 + range_lo), x y z
-};
-
-// One wave per voxel.  The mean is the sum over all P rows IN ROW ORDER (lanes 0..2, one coordinate each) divided by
-// num_points; rows from num_points on are written as zeros.
-__global__ __launch_bounds__(256) void pillar_features_kernel(const float* __restrict__ voxels,
-                                                              const int32_t* __restrict__ num_points,
-                                                              const int32_t* __restrict__ coords, PillarFeatCfg g,
-                                                              float* __restrict__ out) {
-    const long long v = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (v >= g.V) return;      // wave-uniform
-    const int lane = (int)(threadIdx.x & 63);
-    const int np = num_points[v];
-    const float* vox = voxels + (size_t)v * g.P * g.C;
-    float sum = 0.f;
-    if (lane < 3)
-        for (int p = 0; p < g.P; ++p) sum += vox[(size_t)p * g.C + lane];
-    const float mean = sum / (float)np;
-    const float mx = __shfl(mean, 0), my = __shfl(mean, 1), mz = __shfl(mean, 2);
-    const int32_t* c = coords + (size_t)v * 4;
-    const float cx = (float)c[3] * g.vs[0] + g.off[0];
-    const float cy = (float)c[2] * g.vs[1] + g.off[1];
-    const float cz = (float)c[1] * g.vs[2] + g.off[2];
-    const int first = g.absolute_xyz ? 0 : 3;
-    for (int p = lane; p < g.P; p += 64) {
-        const float* row = vox + (size_t)p * g.C;
-        float* o = out + ((size_t)v * g.P + p) * g.c_out;
-        if (p >= np) {
-            for (int k = 0; k < g.c_out; ++k) o[k] = 0.f;
-            continue;
-        }
-        const float x = row[0], y = row[1], z = row[2];
-        int k = 0;
-        for (int q = first; q < g.C; ++q) o[k++] = row[q];
-        o[k++] = x - mx;
-        o[k++] = y - my;
-        o[k++] = z - mz;
-        o[k++] = x - cx;
-        o[k++] = y - cy;
-        o[k++] = z - cz;
-        if (g.with_distance) o[k++] = sqrtf((x * x + y * y) + z * z);
-    }
 }
 
 }  // namespace
@@ -471,9 +396,7 @@ PDA_API int pda_anchor_assign_targets(const float* gt_boxes, int gt_cols, int b,
 }
 
 PDA_API int64_t pda_anchor_loss_blocks(int64_t n) {
-    if (n <= 0) return 0;
-    const int64_t blocks = pda::divup64(n, (int64_t)pda::AL_THREADS * pda::AL_PER_THREAD);
-    return blocks < pda::AL_MAX_BLOCKS ? blocks : pda::AL_MAX_BLOCKS;
+    return pda::partial_blocks(n, (int64_t)pda::AL_THREADS * pda::AL_PER_THREAD, pda::AL_MAX_BLOCKS);
 }
 
 PDA_API int pda_anchor_loss(const float* cls_preds, const float* box_preds, const float* dir_cls_preds,
@@ -531,27 +454,4 @@ PDA_API int pda_anchor_decode(const float* box_preds, const float* dir_cls_preds
     hipLaunchKernelGGL(pda::anchor_decode_kernel, dim3((unsigned)pda::divup64((int64_t)b * n_anchors, 256)), dim3(256), 0,
                        (hipStream_t)stream, box_preds, dir_cls_preds, anchors, g, batch_box_preds);
     return pda::check_launch("pda_anchor_decode");
-}
-
-PDA_API int pda_pillar_features(const float* voxels, const int32_t* voxel_num_points, const int32_t* voxel_coords, int64_t v,
-                                int p, int c, const float* voxel_size3, const float* offset3, int absolute_xyz,
-                                int with_distance, float* out, pda_stream_t stream) {
-    PDA_REQUIRE(v >= 0 && p >= 0 && v <= (int64_t)INT32_MAX, "pda_pillar_features: v=%lld p=%d", (long long)v, p);
-    PDA_REQUIRE(c >= 3 && c <= 64, "pda_pillar_features: c=%d outside 3..64", c);
-    if (v == 0 || p == 0) return PDA_OK;
-    PDA_REQUIRE(voxels && voxel_num_points && voxel_coords && voxel_size3 && offset3 && out, "pda_pillar_features: null pointer");
-    pda::PillarFeatCfg g{};
-    g.V = v;
-    g.P = p;
-    g.C = c;
-    g.absolute_xyz = absolute_xyz ? 1 : 0;
-    g.with_distance = with_distance ? 1 : 0;
-    g.c_out = (absolute_xyz ? c : c - 3) + 6 + (with_distance ? 1 : 0);
-    for (int i = 0; i < 3; ++i) {
-        g.vs[i] = voxel_size3[i];
-        g.off[i] = offset3[i];
-    }
-    hipLaunchKernelGGL(pda::pillar_features_kernel, dim3((unsigned)pda::divup64(v, 4)), dim3(256), 0, (hipStream_t)stream, voxels,
-                       voxel_num_points, voxel_coords, g, out);
-    return pda::check_launch("pda_pillar_features");
 }

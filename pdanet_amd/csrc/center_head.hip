@@ -1,75 +1,21 @@
-// center_head.hip -- the tail of the CenterPoint pillar model on the device: PointPillarScatter
-// (backbones_2d/map_to_bev/pointpillar_scatter.py) and CenterHead's target assignment, losses and box decoding
-// (dense_heads/center_head.py, model_utils/centernet_utils.py, utils/loss_utils.py:395-517).
+// center_head.hip -- CenterHead on the device: target assignment, losses and box decoding (dense_heads/center_head.py,
+// model_utils/centernet_utils.py, utils/loss_utils.py:395-517).  The pillar scatter in front of it is pillar.hip.
 //
-// Reference: the scatter loops over scenes behind a .item(); assign_targets moves every scene's boxes to the host, loops
-// over heads, scenes and boxes in Python and draws each Gaussian with numpy; get_loss makes about thirty element-wise
-// passes over the heat maps and reads three scalars back; generate_predicted_boxes loops over heads and scenes.
+// Reference: assign_targets moves every scene's boxes to the host, loops over heads, scenes and boxes in Python and draws
+// each Gaussian with numpy; get_loss makes about thirty element-wise passes over the heat maps and reads three scalars back;
+// generate_predicted_boxes loops over heads and scenes.
 //
-// Here: pillar_scatter_kernel, a pillar-by-channel tile transposed through LDS (rows read whole, planes written with the
-// pillar on the lane axis); center_targets_kernel, one workgroup per (scene, head, 32 objects): a ballot compaction of the
-// head's rows, the target rows, and the Gaussians through an integer atomicMax on the bit pattern; center_focal_kernel +
-// center_focal_finish_kernel, one pass over (logits, heat map) with per-workgroup partial sums combined in a fixed order;
-// center_reg_loss_kernel / center_reg_grad_kernel over the HEAD_ORDER maps as they are; center_decode_kernel over the
-// top-K cells of a head.  No float atomics except the one named at center_reg_grad_kernel.
-#include "pda_common.h"
+// Here: center_targets_kernel, one workgroup per (scene, head, 32 objects): a ballot compaction of the head's rows, the
+// target rows, and the Gaussians through an integer atomicMax on the bit pattern; center_focal_kernel +
+// center_focal_finish_kernel, one pass over (logits, heat map) with per-workgroup partial sums combined in a fixed order
+// (loss_sums.h); center_reg_loss_kernel / center_reg_grad_kernel over the HEAD_ORDER maps as they are; center_decode_kernel
+// over the top-K cells of a head.  No float atomics except the one named at center_reg_grad_kernel.
+#include "loss_sums.h"
 
 #include <math.h>
 
 namespace pda {
 namespace {
-
-// ---- PointPillarScatter ------------------------------------------------------------------------------------------------------
-constexpr int PS_TILE = 64;      // pillars and channels of one LDS tile
-constexpr int PS_THREADS = 256;
-
-// BWD == false: out[b, c, cell] = feats[p, c]; BWD == true: feats[p, c] = out[b, c, cell] (0 for a skipped row).  `planes` is
-// (B, C, ny * nx).  A row is skipped when its batch index is outside [0, B), its cell c1 + c2 * nx + c3 outside the grid, or
-// (padded form) its index is not below *count.
-template <bool BWD>
-__global__ __launch_bounds__(PS_THREADS) void pillar_scatter_kernel(
-        float* __restrict__ feats, const int32_t* __restrict__ coords, const int32_t* __restrict__ count, long long n, int C,
-        int B, long long cells, int nx, float* __restrict__ planes) {
-    __shared__ float tile[PS_TILE][PS_TILE + 1];
-    __shared__ long long dest[PS_TILE];
-    const long long p0 = (long long)blockIdx.x * PS_TILE;
-    const long long live = count ? min((long long)max(count[0], 0), n) : n;
-    if (threadIdx.x < PS_TILE) {
-        const long long p = p0 + threadIdx.x;
-        long long d = -1;
-        if (p < live) {
-            const int32_t* c = coords + p * 4;
-            const long long cell = (long long)c[1] + (long long)c[2] * nx + (long long)c[3];
-            if (c[0] >= 0 && c[0] < B && cell >= 0 && cell < cells) d = (long long)c[0] * C * cells + cell;
-        }
-        dest[threadIdx.x] = d;
-    }
-    __syncthreads();
-    for (int c0 = 0; c0 < C; c0 += PS_TILE) {
-        if (!BWD) {
-            for (int e = threadIdx.x; e < PS_TILE * PS_TILE; e += PS_THREADS) {
-                const int p = e / PS_TILE, c = e % PS_TILE;      // the channel on the lane axis: a row is read whole
-                if (p0 + p < n && c0 + c < C && dest[p] >= 0) tile[p][c] = feats[(p0 + p) * C + c0 + c];
-            }
-            __syncthreads();
-            for (int e = threadIdx.x; e < PS_TILE * PS_TILE; e += PS_THREADS) {
-                const int c = e / PS_TILE, p = e % PS_TILE;      // the pillar on the lane axis: neighbouring cells
-                if (c0 + c < C && dest[p] >= 0) planes[dest[p] + (long long)(c0 + c) * cells] = tile[p][c];
-            }
-        } else {
-            for (int e = threadIdx.x; e < PS_TILE * PS_TILE; e += PS_THREADS) {
-                const int c = e / PS_TILE, p = e % PS_TILE;
-                if (c0 + c < C) tile[p][c] = dest[p] >= 0 ? planes[dest[p] + (long long)(c0 + c) * cells] : 0.f;
-            }
-            __syncthreads();
-            for (int e = threadIdx.x; e < PS_TILE * PS_TILE; e += PS_THREADS) {
-                const int p = e / PS_TILE, c = e % PS_TILE;
-                if (p0 + p < n && c0 + c < C) feats[(p0 + p) * C + c0 + c] = tile[p][c];
-            }
-        }
-        __syncthreads();
-    }
-}
 
 // ---- target assignment -------------------------------------------------------------------------------------------------------
 constexpr int CH_MAX_HEADS = 8;
@@ -79,8 +25,6 @@ constexpr int CH_OBJS_PER_BLOCK = 32;
 constexpr int CH_THREADS = 256;
 constexpr int CH_MAX_CODE = 16;
 constexpr int CH_MAX_MAPS = 8;
-
-__device__ __forceinline__ bool nan_bits(float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
 
 struct CenterTargetCfg {
     float pcr0, pcr1, vs0, vs1, stride;      // float32 roundings of the Python scalars
@@ -123,7 +67,7 @@ __device__ __forceinline__ CenterObject center_object(const float* __restrict__ 
     float x = ((row[0] - g.pcr0) / g.vs0) / g.stride;
     float y = ((row[1] - g.pcr1) / g.vs1) / g.stride;
     const float xmax = (float)((double)g.W - 0.5), ymax = (float)((double)g.H - 0.5);
-    const bool bad = nan_bits(x) || nan_bits(y);      // the reference's range test on center_int fails for a NaN
+    const bool bad = is_nan_bits(x) || is_nan_bits(y);      // the reference's range test on center_int fails for a NaN
     x = x < 0.f ? 0.f : (x > xmax ? xmax : x);
     y = y < 0.f ? 0.f : (y > ymax ? ymax : y);
     o.coord_x = x;
@@ -131,12 +75,12 @@ __device__ __forceinline__ CenterObject center_object(const float* __restrict__ 
     o.cx = bad ? 0 : (int)x;
     o.cy = bad ? 0 : (int)y;
     const float dx = (row[3] / g.vs0) / g.stride, dy = (row[4] / g.vs1) / g.stride;
-    o.valid = !bad && !nan_bits(dx) && !nan_bits(dy) && dx > 0.f && dy > 0.f;
+    o.valid = !bad && !is_nan_bits(dx) && !is_nan_bits(dy) && dx > 0.f && dy > 0.f;
     int r = g.min_radius;
     if (o.valid) {
         const float rf = gaussian_radius_f32(dx, dy, g);
         // radius.int() of a NaN or of a value beyond int32 is INT_MIN on the host: clamp_min then gives MIN_RADIUS
-        if (!nan_bits(rf) && rf < 2147483648.f && rf > (float)g.min_radius) r = (int)rf;
+        if (!is_nan_bits(rf) && rf < 2147483648.f && rf > (float)g.min_radius) r = (int)rf;
     }
     o.radius = r;
     int label = (int)row[g.cols - 1];
@@ -227,19 +171,12 @@ constexpr int FL_THREADS = 256;
 constexpr int FL_PER_THREAD = 8;
 constexpr int FL_MAX_BLOCKS = 1024;
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // loss_utils.neg_loss_cornernet on pred = clamp(sigmoid(x), 1e-4, 1 - 1e-4): per workgroup the sums of the positive terms,
 // the negative terms and the cells with gt == 1 (partials (3, blocks) float64), and per element the derivative of
 // (pos + neg) with respect to x, zero where the clamp is active.
 __global__ __launch_bounds__(FL_THREADS) void center_focal_kernel(const float* __restrict__ logits, const float* __restrict__ gt,
                                                                   long long n, float* __restrict__ grad,
                                                                   double* __restrict__ partials) {
-    __shared__ double red[3][FL_THREADS / 64];
     const float lo = 1e-4f, hi = (float)(1.0 - 1e-4);
     double pos = 0.0, neg = 0.0, cnt = 0.0;
     const long long stride = (long long)gridDim.x * FL_THREADS;
@@ -265,32 +202,15 @@ __global__ __launch_bounds__(FL_THREADS) void center_focal_kernel(const float* _
         }
         grad[i] = (float)(d * dp);
     }
-    pos = wave_sum_f64(pos);
-    neg = wave_sum_f64(neg);
-    cnt = wave_sum_f64(cnt);
-    const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
-    if (lane == 0) {
-        red[0][wave] = pos;
-        red[1][wave] = neg;
-        red[2][wave] = cnt;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        double v = 0.0;
-        for (int w = 0; w < FL_THREADS / 64; ++w) v += red[threadIdx.x][w];
-        partials[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = v;
-    }
+    const double sums[3] = {pos, neg, cnt};
+    block_sums_to_partials<3, FL_THREADS>(sums, partials);
 }
 
 // out[0] = the loss, out[1] = d loss / d (pos + neg) = -1 / num_pos (-1 without a positive cell), out[2] = num_pos
 __global__ __launch_bounds__(64) void center_focal_finish_kernel(const double* __restrict__ partials, int blocks,
                                                                  float* __restrict__ out) {
     double v[3];
-    for (int q = 0; q < 3; ++q) {
-        double a = 0.0;
-        for (int i = threadIdx.x; i < blocks; i += 64) a += partials[(size_t)q * blocks + i];
-        v[q] = wave_sum_f64(a);
-    }
+    finish_partials<3>(partials, blocks, v);
     if (threadIdx.x == 0) {
         const float pos = (float)v[0], neg = (float)v[1], num = (float)v[2];
         if (num == 0.f) {
@@ -347,7 +267,7 @@ __global__ __launch_bounds__(RL_THREADS) void center_reg_loss_kernel(CenterMaps 
         for (int i = 0; i < mp.n_maps; ++i) {
             for (int c = 0; c < mp.channels[i]; ++c, ++col) {
                 const float t = targets[(size_t)e * mp.code + col];
-                if (nan_bits(t)) continue;
+                if (is_nan_bits(t)) continue;
                 const float p = mp.map[i][((size_t)b * mp.channels[i] + c) * hw + ind];
                 const float d = fabsf(p * m - t * m);
 #pragma unroll
@@ -399,7 +319,7 @@ __global__ __launch_bounds__(256) void center_reg_grad_kernel(CenterMaps mp, con
     for (int i = 0; i < mp.n_maps; ++i) {
         for (int c = 0; c < mp.channels[i]; ++c, ++col) {
             const float t = targets[(size_t)e * mp.code + col];
-            if (nan_bits(t)) continue;
+            if (is_nan_bits(t)) continue;
             const size_t at = ((size_t)b * mp.channels[i] + c) * hw + ind;
             const float d = mp.map[i][at] * m - t * m;
             const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
@@ -454,7 +374,7 @@ __global__ __launch_bounds__(256) void center_decode_kernel(const float* __restr
         box[8] = g.vel[((size_t)b * 2 + 1) * hw + cell];
     }
     const float score = 1.f / (1.f + expf(-top_logits[e]));
-    bool ok = !nan_bits(xs) && !nan_bits(ys) && !nan_bits(zs) && !nan_bits(score);
+    bool ok = !is_nan_bits(xs) && !is_nan_bits(ys) && !is_nan_bits(zs) && !is_nan_bits(score);
     ok = ok && xs >= g.limit[0] && ys >= g.limit[1] && zs >= g.limit[2] && xs <= g.limit[3] && ys <= g.limit[4] && zs <= g.limit[5];
     if (g.use_thresh) ok = ok && score > g.thresh;
     scores[e] = ok ? score : -INFINITY;
@@ -465,36 +385,6 @@ __global__ __launch_bounds__(256) void center_decode_kernel(const float* __restr
 }  // namespace pda
 
 // ---- C entry points ------------------------------------------------------------------------------------------------------------
-static int pillar_scatter_check(const char* what, int64_t n, int c, int b, int ny, int nx) {
-    PDA_REQUIRE(n >= 0 && c >= 0 && b >= 0 && ny >= 0 && nx >= 0, "%s: n=%lld c=%d b=%d ny=%d nx=%d", what, (long long)n, c, b,
-                ny, nx);
-    PDA_REQUIRE(n <= (int64_t)INT32_MAX * pda::PS_TILE, "%s: n=%lld too large", what, (long long)n);
-    return PDA_OK;
-}
-
-PDA_API int pda_pillar_scatter_fwd(const float* features, const int32_t* coords, const int32_t* count, int64_t n, int c, int b,
-                                   int ny, int nx, float* out, pda_stream_t stream) {
-    if (int st = pillar_scatter_check("pda_pillar_scatter_fwd", n, c, b, ny, nx)) return st;
-    if (n == 0 || c == 0 || b == 0 || ny == 0 || nx == 0) return PDA_OK;
-    PDA_REQUIRE(features && coords && out, "pda_pillar_scatter_fwd: null pointer");
-    hipLaunchKernelGGL(pda::pillar_scatter_kernel<false>, dim3((unsigned)pda::divup64(n, pda::PS_TILE)), dim3(pda::PS_THREADS),
-                       0, (hipStream_t)stream, const_cast<float*>(features), coords, count, (long long)n, c, b,
-                       (long long)ny * nx, nx, out);
-    return pda::check_launch("pda_pillar_scatter_fwd");
-}
-
-PDA_API int pda_pillar_scatter_bwd(const float* grad_out, const int32_t* coords, const int32_t* count, int64_t n, int c, int b,
-                                   int ny, int nx, float* grad_features, pda_stream_t stream) {
-    if (int st = pillar_scatter_check("pda_pillar_scatter_bwd", n, c, b, ny, nx)) return st;
-    if (n == 0 || c == 0) return PDA_OK;
-    PDA_REQUIRE(b > 0 && ny > 0 && nx > 0, "pda_pillar_scatter_bwd: empty grid with n=%lld rows", (long long)n);
-    PDA_REQUIRE(grad_out && coords && grad_features, "pda_pillar_scatter_bwd: null pointer");
-    hipLaunchKernelGGL(pda::pillar_scatter_kernel<true>, dim3((unsigned)pda::divup64(n, pda::PS_TILE)), dim3(pda::PS_THREADS),
-                       0, (hipStream_t)stream, grad_features, coords, count, (long long)n, c, b, (long long)ny * nx, nx,
-                       const_cast<float*>(grad_out));
-    return pda::check_launch("pda_pillar_scatter_bwd");
-}
-
 PDA_API int pda_center_assign_targets(const float* gt_boxes, int gt_cols, int b, int m, int num_class, int n_heads,
                                       const int32_t* head_of_class, const int32_t* local_of_class, const int32_t* head_classes,
                                       int h, int w, int max_objs, double pcr0, double pcr1, double vs0, double vs1,
@@ -562,9 +452,7 @@ PDA_API int pda_center_assign_targets(const float* gt_boxes, int gt_cols, int b,
 }
 
 PDA_API int64_t pda_center_focal_blocks(int64_t n) {
-    if (n <= 0) return 0;
-    const int64_t blocks = pda::divup64(n, (int64_t)pda::FL_THREADS * pda::FL_PER_THREAD);
-    return blocks < pda::FL_MAX_BLOCKS ? blocks : pda::FL_MAX_BLOCKS;
+    return pda::partial_blocks(n, (int64_t)pda::FL_THREADS * pda::FL_PER_THREAD, pda::FL_MAX_BLOCKS);
 }
 
 PDA_API int pda_center_focal_loss(const float* logits, const float* heatmap, int64_t n, float* grad, double* partials,

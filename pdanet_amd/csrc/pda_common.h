@@ -76,6 +76,10 @@ __device__ __forceinline__ float sqdist3(float ax, float ay, float az, float bx,
 #endif
 }
 
+// NaN by the bit pattern: the library is built with -fno-honor-nans, which removes `x != x` and every comparison that could
+// only fail for a NaN, so the bits decide, whatever the compiler assumes about comparisons.
+__device__ __forceinline__ bool is_nan_bits(float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
+
 // wave-uniform wave index inside the workgroup, provably uniform to the compiler
 // Tensor element type at the HBM boundary: float, or bf16 (raw uint16_t) in the dense-bf16 mode, where qkv / dout come
 // straight out of bf16 GEMMs and out / dqkv go straight into them.  All arithmetic is fp32 either way.

@@ -30,9 +30,6 @@ __device__ __forceinline__ bool offsets_ok(const int64_t* off, int b, int64_t to
     return s >= 0 && e >= s && e <= total;
 }
 
-// The library is built with -fno-honor-nans; the bit pattern decides, whatever the compiler assumes about comparisons.
-__device__ __forceinline__ bool is_nan_bits(float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
-
 // host side: the batch and n_cap every stage entry accepts (grid.y = batch; tiles of n_cap fit an int)
 inline bool stage_sizes_ok(int batch, int64_t n_cap) { return batch >= 0 && batch <= 65535 && n_cap >= 1 && n_cap <= (1 << 30); }
 

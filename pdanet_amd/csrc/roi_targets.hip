@@ -106,8 +106,6 @@ __device__ __forceinline__ float torch_mod(float a, float b) {
 
 // NaN by its bits: the library is built with -fno-honor-nans, under which a float comparison of a NaN is undefined, and a
 // scene of NaN IoUs has to land in none of the three lists as it does in the reference
-__device__ __forceinline__ bool nan_bits(float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
-
 // one compacted list: lanes of one wave walk the RoIs in ascending order; returns the list's length
 template <typename Pred>
 __device__ int compact_list(int* __restrict__ list, int m, int lane, Pred pred) {
@@ -135,13 +133,13 @@ __global__ __launch_bounds__(ROI_SAMPLE_THREADS) void roi_sample_targets_kernel(
     if (threadIdx.x == 0) bad = 0;
     // the masks are literal (:117-125): with CLS_FG_THRESH < REG_FG_THRESH a RoI is in both fg and hard_bg
     if (wave == 0) {
-        const int n = compact_list(lists[0], m, lane, [&](int i) { return !nan_bits(ov[i]) && ov[i] >= cfg.fg_thresh; });
+        const int n = compact_list(lists[0], m, lane, [&](int i) { return !is_nan_bits(ov[i]) && ov[i] >= cfg.fg_thresh; });
         if (lane == 0) counts[0] = n;
     } else if (wave == 1) {
-        const int n = compact_list(lists[1], m, lane, [&](int i) { return !nan_bits(ov[i]) && ov[i] < cfg.reg_fg && ov[i] >= cfg.cls_bg_lo; });
+        const int n = compact_list(lists[1], m, lane, [&](int i) { return !is_nan_bits(ov[i]) && ov[i] < cfg.reg_fg && ov[i] >= cfg.cls_bg_lo; });
         if (lane == 0) counts[1] = n;
     } else if (wave == 2) {
-        const int n = compact_list(lists[2], m, lane, [&](int i) { return !nan_bits(ov[i]) && ov[i] < cfg.cls_bg_lo; });
+        const int n = compact_list(lists[2], m, lane, [&](int i) { return !is_nan_bits(ov[i]) && ov[i] < cfg.cls_bg_lo; });
         if (lane == 0) counts[2] = n;
     }
     __syncthreads();

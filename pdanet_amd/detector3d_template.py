@@ -1,0 +1,62 @@
+"""What the pillar detectors share (pcdet/models/detectors/detector3d_template.py, reduced to the pillar family): the dataset
+fields, the check of the four NAME keys, and the run over vfe -> map_to_bev_module -> backbone_2d -> dense_head under the
+reference's module names, so a reference checkpoint loads with strict=True.  A detector names the encoder and head classes
+it accepts (VFE, DENSE_HEAD) and decodes in post_processing.  (detector.py, IASSD with its graph capture, does not build on
+this.)"""
+import numpy as np
+import torch.nn as nn
+
+from .base_bev_backbone import BaseBEVBackbone
+from .config import field
+from .pointpillar_scatter import PointPillarScatter
+from .voxel_utils import grid_size as _grid_size
+
+
+class PillarDetector(nn.Module):
+    VFE = {}             # NAME -> class, the encoders and heads a detector accepts and builds
+    DENSE_HEAD = {}
+
+    def __init__(self, model_cfg, num_class, dataset):
+        """dataset: an object or dict with class_names, point_cloud_range, voxel_size, num_point_features (or the
+        reference's point_feature_encoder.num_point_features) and optionally grid_size."""
+        super().__init__()
+        self.model_cfg, self.num_class = model_cfg, num_class
+        self.class_names = list(field(dataset, 'class_names'))
+        pcr = np.asarray(field(dataset, 'point_cloud_range'), dtype=np.float64)
+        vs = np.asarray(field(dataset, 'voxel_size'), dtype=np.float64)
+        grid = field(dataset, 'grid_size', None)
+        grid = np.asarray(_grid_size(pcr, vs) if grid is None else grid, dtype=np.int64)
+        try:
+            n_feat = field(dataset, 'num_point_features')
+        except (KeyError, AttributeError):
+            n_feat = field(dataset, 'point_feature_encoder').num_point_features
+        for key, names in (('VFE', self.VFE), ('MAP_TO_BEV', ('PointPillarScatter',)),
+                           ('BACKBONE_2D', ('BaseBEVBackbone',)), ('DENSE_HEAD', self.DENSE_HEAD)):
+            if model_cfg[key]['NAME'] not in names:
+                raise NotImplementedError("%s.NAME %r (the sparse-conv backbones and other heads are not part of this project)"
+                                          % (key, model_cfg[key]['NAME']))
+        vfe_cfg, head_cfg = model_cfg['VFE'], model_cfg['DENSE_HEAD']
+        self.vfe = self.VFE[vfe_cfg['NAME']](vfe_cfg, num_point_features=n_feat, voxel_size=vs, grid_size=grid,
+                                             point_cloud_range=pcr)
+        self.map_to_bev_module = PointPillarScatter(model_cfg['MAP_TO_BEV'], grid_size=grid)
+        self.backbone_2d = BaseBEVBackbone(model_cfg['BACKBONE_2D'], input_channels=self.map_to_bev_module.num_bev_features)
+        self.dense_head = self.DENSE_HEAD[head_cfg['NAME']](
+            head_cfg, input_channels=self.backbone_2d.num_bev_features,
+            num_class=num_class if not head_cfg.get('CLASS_AGNOSTIC', False) else 1, class_names=self.class_names,
+            grid_size=grid, point_cloud_range=pcr, voxel_size=vs, predict_boxes_when_training=model_cfg.get('ROI_HEAD', False))
+        self.module_list = [self.vfe, self.map_to_bev_module, self.backbone_2d, self.dense_head]
+
+    def forward(self, batch_dict):
+        for module in self.module_list:
+            batch_dict = module(batch_dict)
+        if self.training:
+            loss, tb_dict, disp_dict = self.get_training_loss()
+            return {'loss': loss}, tb_dict, disp_dict
+        return self.post_processing(batch_dict)
+
+    def get_training_loss(self):
+        loss_rpn, tb_dict = self.dense_head.get_loss()
+        return loss_rpn, dict({'loss_rpn': loss_rpn.detach()}, **tb_dict), {}
+
+    def post_processing(self, batch_dict):
+        raise NotImplementedError

@@ -15,10 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import dyn_voxel_utils as dvu
-
-
-def _cfg(cfg, key):
-    return cfg[key] if isinstance(cfg, dict) else getattr(cfg, key)
+from .config import field
 
 
 class _Sliced:
@@ -72,13 +69,13 @@ class PFNLayerV2(nn.Module):
 class DynamicPillarVFE(VFETemplate):
     def __init__(self, model_cfg, num_point_features, voxel_size, grid_size, point_cloud_range, **kwargs):
         super().__init__(model_cfg=model_cfg)
-        self.use_norm = _cfg(model_cfg, "USE_NORM")
-        self.with_distance = _cfg(model_cfg, "WITH_DISTANCE")
-        self.use_absolute_xyz = _cfg(model_cfg, "USE_ABSLOTE_XYZ")
+        self.use_norm = field(model_cfg, "USE_NORM")
+        self.with_distance = field(model_cfg, "WITH_DISTANCE")
+        self.use_absolute_xyz = field(model_cfg, "USE_ABSLOTE_XYZ")
         num_point_features += 6 if self.use_absolute_xyz else 3
         if self.with_distance:
             num_point_features += 1
-        self.num_filters = _cfg(model_cfg, "NUM_FILTERS")
+        self.num_filters = field(model_cfg, "NUM_FILTERS")
         assert len(self.num_filters) > 0
         num_filters = [num_point_features] + list(self.num_filters)
         self.pfn_layers = nn.ModuleList(

@@ -1,7 +1,7 @@
 """The hard-voxel PillarVFE and PFNLayer of PointPillar (pcdet/models/backbones_3d/vfe/pillar_vfe.py) with the reference's
 constructor signatures, config keys (USE_NORM, WITH_DISTANCE, USE_ABSLOTE_XYZ, NUM_FILTERS), state-dict keys
 (pfn_layers.{i}.linear.weight, pfn_layers.{i}.norm.*) and batch_dict contract.  The PFN input rows -- raw columns,
-offsets from the voxel's mean and from the cell centre, the padding mask -- are one launch of csrc/anchor_head.hip
+offsets from the voxel's mean and from the cell centre, the padding mask -- are one launch of csrc/pillar.hip
 (pda_pillar_features) where the reference makes about a dozen passes; Linear, BatchNorm1d, ReLU and the max over the points
 stay in torch.  Voxels are data: there is no backward into them.
 
@@ -14,7 +14,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .dynamic_vfe import VFETemplate, _cfg
+from .config import field
+from .dynamic_vfe import VFETemplate
 from .pointnet2_batch_cuda import F32, I32, _call, _chk
 
 
@@ -74,13 +75,13 @@ class PFNLayer(nn.Module):
 class PillarVFE(VFETemplate):
     def __init__(self, model_cfg, num_point_features, voxel_size, point_cloud_range, **kwargs):
         super().__init__(model_cfg=model_cfg)
-        self.use_norm = _cfg(model_cfg, "USE_NORM")
-        self.with_distance = _cfg(model_cfg, "WITH_DISTANCE")
-        self.use_absolute_xyz = _cfg(model_cfg, "USE_ABSLOTE_XYZ")
+        self.use_norm = field(model_cfg, "USE_NORM")
+        self.with_distance = field(model_cfg, "WITH_DISTANCE")
+        self.use_absolute_xyz = field(model_cfg, "USE_ABSLOTE_XYZ")
         num_point_features += 6 if self.use_absolute_xyz else 3
         if self.with_distance:
             num_point_features += 1
-        self.num_filters = _cfg(model_cfg, "NUM_FILTERS")
+        self.num_filters = field(model_cfg, "NUM_FILTERS")
         assert len(self.num_filters) > 0
         num_filters = [num_point_features] + list(self.num_filters)
         self.pfn_layers = nn.ModuleList(

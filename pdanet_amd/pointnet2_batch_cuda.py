@@ -66,6 +66,17 @@ def _call(fn_name, tensor, *args):
 F32, I32 = torch.float32, torch.int32
 
 
+def _ptr_array(items):
+    """A void*[] for a pointer-array parameter from tensors (already checked), data_ptr() integers or None."""
+    return (ctypes.c_void_p * len(items))(*[t.data_ptr() if isinstance(t, torch.Tensor) else t for t in items])
+
+
+def _partials(blocks_fn, n, device):
+    """The (3 * blocks) float64 scratch of a loss whose first pass leaves three partial sums per workgroup (csrc/loss_sums.h);
+    `blocks_fn` names the library's size query for n elements."""
+    return torch.empty((3 * int(getattr(_lib.load(), blocks_fn)(n)),), dtype=torch.float64, device=device)
+
+
 def ball_query_wrapper(b, n, m, radius, nsample, new_xyz, xyz, idx):
     _numel_ok(new_xyz, b * m * 3, "new_xyz"); _numel_ok(xyz, b * n * 3, "xyz")
     _numel_ok(idx, b * m * nsample, "idx")
@@ -828,10 +839,6 @@ def sa_small_train_workspace_bytes():
 @functools.lru_cache(maxsize=None)
 def sa_small_train_supported(c, ns, c1, c2, c3, tokens):
     return bool(_lib.load().pda_sa_small_train_supported(int(c), int(ns), int(c1), int(c2), int(c3), int(tokens)))
-
-
-def _ptr_array(ptrs):
-    return (ctypes.c_void_p * len(ptrs))(*ptrs)
 
 
 def sa_small_train_fwd(xyz, new_xyz, feat_pm, idx, weights, gammas, betas, running_means, running_vars, eps, momentum,

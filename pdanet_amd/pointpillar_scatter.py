@@ -1,5 +1,5 @@
 """PointPillarScatter (pcdet/models/backbones_2d/map_to_bev/pointpillar_scatter.py) on the device: pillar features to the
-dense BEV map in one fill and one launch for the whole batch (csrc/center_head.hip pillar_scatter_kernel), where the
+dense BEV map in one fill and one launch for the whole batch (csrc/pillar.hip pillar_scatter_kernel), where the
 reference loops over scenes behind coords[:, 0].max().item().
 
 The forward is a copy and therefore bit-exact; the backward is the gather of the same cells (no atomics).  The cell index
@@ -13,11 +13,8 @@ padded to n rows plus the device count of live pillars), for a caller that wants
 import torch
 import torch.nn as nn
 
+from .config import field
 from .pointnet2_batch_cuda import F32, I32, _call, _chk
-
-
-def _cfg(cfg, key):
-    return cfg[key] if isinstance(cfg, dict) else getattr(cfg, key)
 
 
 def _check(features, coords, count):
@@ -65,7 +62,7 @@ class PointPillarScatter(nn.Module):
     def __init__(self, model_cfg, grid_size, **kwargs):
         super().__init__()
         self.model_cfg = model_cfg
-        self.num_bev_features = _cfg(model_cfg, "NUM_BEV_FEATURES")
+        self.num_bev_features = field(model_cfg, "NUM_BEV_FEATURES")
         self.nx, self.ny, self.nz = (int(v) for v in grid_size)
         assert self.nz == 1
 

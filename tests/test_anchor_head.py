@@ -273,6 +273,13 @@ DATASET = {'class_names': CONFIGS['a']['class_names'], 'point_cloud_range': CONF
            'voxel_size': CONFIGS['a']['voxel_size'], 'num_point_features': 4}
 
 
+def test_pointpillar_state_dict_is_unchanged():
+    """Names and shapes in order, as recorded from the commit before the detectors were folded onto one base class."""
+    with open(os.path.join(HERE, "golden", "pillar_detector_state_dicts.json")) as f:
+        ref = json.load(f)['PointPillar']
+    assert [[k, list(v.shape)] for k, v in PointPillar(to_attr(pointpillar_cfg()), 3, DATASET).state_dict().items()] == ref
+
+
 # ---- GPU -----------------------------------------------------------------------------------------------------------------------
 gpu = pytest.mark.gpu
 
@@ -369,6 +376,51 @@ def test_gpu_losses(c, t):
     check_losses(c, t, tb, {k: v.grad.cpu().numpy() for k, v in leaves.items()})
     assert float(loss.detach()) == float(tb['rpn_loss'])
     assert torch.equal(head.forward_ret_dict['box_cls_labels'], before), "the labels were rewritten"
+
+
+def loss_case(n):
+    """One scene of n anchors of one class, two direction bins: logits around -4, about 5 % ignored anchors, up to five
+    positives (the first and the last anchor among them), one of them with a NaN regression target."""
+    rng = np.random.default_rng(n)
+    table = np.zeros((n, 7), np.float32)
+    table[:, :2] = rng.uniform(-40, 40, (n, 2))
+    table[:, 3:6] = (3.9, 1.6, 1.56)
+    table[:, 6] = rng.choice(np.array([0.0, 1.57], np.float32), n)
+    cls = rng.normal(-4.0, 1.0, (1, n, 1)).astype(np.float32)
+    box = rng.normal(0.0, 0.3, (1, n, 7)).astype(np.float32)
+    dirs = rng.normal(0.0, 1.0, (1, n, 2)).astype(np.float32)
+    labels = np.where(rng.random((1, n)) < 0.05, -1, 0).astype(np.int32)
+    pos = np.unique(np.linspace(0, n - 1, min(n, 5)).astype(np.int64))
+    labels[0, pos] = 1
+    targets = np.zeros((1, n, 7), np.float32)
+    targets[0, pos] = rng.normal(0.0, 0.3, (len(pos), 7))
+    targets[0, pos[0], 2] = np.nan
+    return cls, box, dirs, labels, targets, np.array([len(pos)], np.int32), table
+
+
+LOSS_CASE_WEIGHTS = dict(num_class=1, code_weights=[1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0], cls_weight=1.0, loc_weight=2.0,
+                         dir_weight=0.2, dir_offset=0.78539)
+
+
+@gpu
+@pytest.mark.parametrize("n,blocks", [(1, 1), (1025, 2), (2097153, 2048)])
+def test_gpu_anchor_loss_at_the_block_boundaries(n, blocks):
+    """The sizes at which the shared partial sums (csrc/loss_sums.h) can go wrong: one anchor; one full workgroup of 1024
+    and one anchor; one anchor past the 2048-workgroup cap, where the grid-stride loop wraps.  Against the float64
+    restatement, within test_gpu_losses' bound."""
+    assert _lib.load().pda_anchor_loss_blocks(n) == blocks
+    cls, box, dirs, labels, targets, num_pos, table = loss_case(n)
+    ref = rs.losses(cls, box, dirs, labels, targets, table, **LOSS_CASE_WEIGHTS)
+    leaves = [dev(v).requires_grad_(True) for v in (cls, box, dirs)]
+    loss, out = ah.anchor_loss(*leaves, dev(labels), dev(targets), dev(num_pos), dev(table), **LOSS_CASE_WEIGHTS)
+    loss.backward()
+    d_loss = np.abs(out.cpu().numpy().astype(np.float64) - ref)
+    print("anchor n", n, "losses", ref, "diff", ["%.3g" % v for v in d_loss])
+    assert d_loss.max() <= LOSS_TOL
+    assert float(loss.detach()) == float(out[3])
+    g_box = leaves[1].grad.cpu().numpy()
+    assert all(bool(torch.isfinite(v.grad).all()) for v in leaves) and g_box[0, 0, 2] == 0      # the NaN target
+    assert g_box[0, 0, [0, 1, 3, 4, 5, 6]].all() and not g_box[labels <= 0].any()
 
 
 @gpu

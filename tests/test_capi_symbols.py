@@ -34,6 +34,54 @@ def test_binding_covers_header():
     assert sorted(list(_lib.SIGNATURES) + _lib.INFO_SYMBOLS) == _declared_symbols()
 
 
+def _declarations():
+    """name -> (return type, [parameter types]) of every pda_* declaration in the three headers, as C type strings without
+    the parameter names."""
+    src = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("pda_pointnet2.h", "pda_train.h", "pda_pointnet2_stack.h"))
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\*]*?)\s*\b(pda_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        params = " ".join(params.split())
+        types = [] if params in ("", "void") else [re.sub(r"\s*\b\w+$", "", p.strip()) for p in params.split(",")]
+        assert name not in out, "%s is declared twice" % name
+        out[name] = (" ".join(ret.split()), types)
+    return out
+
+
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+            "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong}
+
+
+def _agrees(c_type, ct):
+    """A C parameter or return type against the ctypes type of the binding."""
+    if "*" in c_type or c_type == "pda_stream_t":
+        return ct in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(ct, type) and issubclass(ct, ctypes._Pointer))
+    assert c_type in _SCALARS, "no rule for the C type %r" % c_type
+    return ct is _SCALARS[c_type]
+
+
+def test_binding_signatures_agree_with_the_headers(lib):
+    """Every entry of _lib.SIGNATURES against its declaration, parameter by parameter and in its return type; every
+    declaration that does not return int has its restype set by load()."""
+    from pdanet_amd import _lib
+    decl = _declarations()
+    assert sorted(decl) == _declared_symbols()
+    mismatches = []
+    for name, argtypes in _lib.SIGNATURES.items():
+        ret, types = decl[name]
+        if len(types) != len(argtypes):
+            mismatches.append("%s: %d parameters declared, %d bound" % (name, len(types), len(argtypes)))
+            continue
+        mismatches += ["%s: parameter %d is %r, bound as %s" % (name, i, t, ct.__name__)
+                       for i, (t, ct) in enumerate(zip(types, argtypes)) if not _agrees(t, ct)]
+    non_int = [name for name, (ret, _) in decl.items() if ret != "int"]
+    mismatches += ["%s: returns %r, restype %s" % (name, decl[name][0], getattr(lib, name).restype)
+                   for name in decl if not _agrees(decl[name][0], getattr(lib, name).restype)]
+    print("entries", len(_lib.SIGNATURES), "mismatches", len(mismatches), "non-int returns", len(non_int))
+    assert not mismatches, "\n".join(mismatches)
+    assert len(_lib.SIGNATURES) >= 172 and len(non_int) >= 24
+
+
 def test_info_entry_points(lib, oracle):
     assert lib.pda_abi_version() == 20
     assert lib.pda_fp_contract_mode() == 1

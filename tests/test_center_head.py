@@ -192,6 +192,39 @@ def test_state_dict_keys_are_the_references():
     assert list(PointPillarScatter(to_attr({'NUM_BEV_FEATURES': 64}), (W, H, 1)).state_dict().keys()) == []
 
 
+def centerpoint_cfg():
+    return {'NAME': 'CenterPoint',
+            'VFE': {'NAME': 'DynPillarVFE', 'WITH_DISTANCE': False, 'USE_ABSLOTE_XYZ': True, 'USE_NORM': True, 'NUM_FILTERS': [32, 32]},
+            'MAP_TO_BEV': {'NAME': 'PointPillarScatter', 'NUM_BEV_FEATURES': 32},
+            'BACKBONE_2D': {'NAME': 'BaseBEVBackbone', 'LAYER_NUMS': [1, 1, 1], 'LAYER_STRIDES': [1, 2, 2], 'NUM_FILTERS': [32, 64, 64],
+                            'UPSAMPLE_STRIDES': [1, 2, 4], 'NUM_UPSAMPLE_FILTERS': [32, 32, 32]},
+            'DENSE_HEAD': dict(json.loads(json.dumps(CONFIGS['a']['head'])), NAME='CenterHead'),
+            'POST_PROCESSING': {'RECALL_THRESH_LIST': [0.3, 0.5, 0.7]}}
+
+
+DATASET = {'class_names': CLASS_NAMES, 'point_cloud_range': CONFIGS['a']['point_cloud_range'], 'voxel_size': CONFIGS['a']['voxel_size'],
+           'num_point_features': 4}
+
+
+def state_shapes(model):
+    return [[k, list(v.shape)] for k, v in model.state_dict().items()]
+
+
+def test_centerpoint_state_dict_is_unchanged():
+    """Names and shapes in order, as recorded from the commit before the detectors were folded onto one base class."""
+    with open(os.path.join(HERE, "golden", "pillar_detector_state_dicts.json")) as f:
+        assert state_shapes(CenterPoint(to_attr(centerpoint_cfg()), 3, DATASET)) == json.load(f)['CenterPoint']
+
+
+def test_centerpoint_refuses_other_modules():
+    for key, name in (('DENSE_HEAD', 'AnchorHeadSingle'), ('VFE', 'MeanVFE'), ('BACKBONE_2D', 'BaseBEVResBackbone')):
+        cfg = centerpoint_cfg()
+        cfg[key]['NAME'] = name
+        with pytest.raises(NotImplementedError) as err:
+            CenterPoint(to_attr(cfg), 3, DATASET)
+        assert str(err.value) == "%s.NAME %r (the sparse-conv backbones and other heads are not part of this project)" % (key, name)
+
+
 @pytest.mark.parametrize("c,t", BATCHES)
 def test_restatement_targets(c, t):
     cfg, tc = CONFIGS[c], CONFIGS[c]['head']['TARGET_ASSIGNER_CONFIG']
@@ -369,6 +402,36 @@ def test_gpu_losses(c, t):
     assert abs(float(tb['rpn_loss']) - float(loss.detach())) == 0
 
 
+def focal_case(n):
+    """Logits around -4 (a heat-map head past its -2.19 initialisation), a sparse heat map with values in [0, 0.95) and up to
+    five cells that are exactly 1, the first and the last among them."""
+    rng = np.random.default_rng(n)
+    logits = rng.normal(-4.0, 1.0, n).astype(np.float32)
+    hm = np.where(rng.random(n) < 0.05, rng.random(n) ** 2 * 0.95, 0.0).astype(np.float32)
+    hm[np.unique(np.linspace(0, n - 1, min(n, 5)).astype(np.int64))] = 1.0
+    return logits, hm
+
+
+@gpu
+@pytest.mark.parametrize("n,blocks", [(1, 1), (2049, 2), (2097153, 1024)])
+def test_gpu_focal_loss_at_the_block_boundaries(n, blocks):
+    """The sizes at which the shared partial sums (csrc/loss_sums.h) can go wrong: one element; one full workgroup of 2048
+    and one element; one element past the 1024-workgroup cap, where the grid-stride loop wraps.  Against the float64
+    restatement, within test_gpu_losses' bound."""
+    assert _lib.load().pda_center_focal_blocks(n) == blocks
+    logits, hm = focal_case(n)
+    ref_loss, ref_grad = rs.focal_loss(logits, hm)
+    x = dev(logits).requires_grad_(True)
+    loss = cu.focal_loss(x, dev(hm))
+    loss.backward()
+    scale = float(np.abs(ref_grad).max())
+    d_loss = abs(float(loss.detach()) - ref_loss)
+    d_g = float(np.abs(x.grad.cpu().numpy().astype(np.float64) - ref_grad).max())
+    print("focal n", n, "loss %.9g diff %.3g grad diff %.3g of %.3g" % (ref_loss, d_loss, d_g, scale))
+    assert d_loss <= LOSS_TOL
+    assert d_g <= LOSS_TOL * scale
+
+
 @gpu
 @pytest.mark.parametrize("c", "ab")
 def test_gpu_decode_and_nms(c):
@@ -460,19 +523,8 @@ def test_gpu_graph_replay_equals_eager():
 @gpu
 def test_gpu_centerpoint_train_and_eval():
     from pdanet_amd import synth
-    cfg = CONFIGS['a']
-    model_cfg = to_attr({
-        'NAME': 'CenterPoint',
-        'VFE': {'NAME': 'DynPillarVFE', 'WITH_DISTANCE': False, 'USE_ABSLOTE_XYZ': True, 'USE_NORM': True, 'NUM_FILTERS': [32, 32]},
-        'MAP_TO_BEV': {'NAME': 'PointPillarScatter', 'NUM_BEV_FEATURES': 32},
-        'BACKBONE_2D': {'NAME': 'BaseBEVBackbone', 'LAYER_NUMS': [1, 1, 1], 'LAYER_STRIDES': [1, 2, 2], 'NUM_FILTERS': [32, 64, 64],
-                        'UPSAMPLE_STRIDES': [1, 2, 4], 'NUM_UPSAMPLE_FILTERS': [32, 32, 32]},
-        'DENSE_HEAD': dict(cfg['head'], NAME='CenterHead'),
-        'POST_PROCESSING': {'RECALL_THRESH_LIST': [0.3, 0.5, 0.7]}})
-    dataset = {'class_names': CLASS_NAMES, 'point_cloud_range': cfg['point_cloud_range'], 'voxel_size': cfg['voxel_size'],
-               'num_point_features': 4}
     torch.manual_seed(3)
-    model = CenterPoint(model_cfg, 3, dataset).cuda()
+    model = CenterPoint(to_attr(centerpoint_cfg()), 3, DATASET).cuda()
     pts = synth.batch_points(B, 2048)
     pts[:, 1:4] *= 0.1                                        # the ONCE range of synth.py into this 15 m x 13 m range
     batch = {'points': dev(pts), 'gt_boxes': dev(G['ax_gt_boxes']), 'batch_size': B}
