@@ -968,6 +968,49 @@ int pda_pillar_features(const float *voxels, const int32_t *voxel_num_points, co
                         int c, const float *voxel_size3, const float *offset3, int absolute_xyz, int with_distance, float *out,
                         pda_stream_t stream);
 
+/* ---- Sparse 3D convolution (csrc/sparse_conv_index.hip: the index stage; csrc/sparse_conv.hip: the feature kernels) --------------
+ * spconv 2.x semantics for SubMConv3d and SparseConv3d (dilation 1) over a sparse tensor of n rows: indices (n, 4) int32
+ * (b, z, y, x) in a grid (d, h, w) of `batch` scenes, features (n, C) float32.  Taps are numbered t = (tz * kh + ty) * kw + tx.
+ * Every launch goes on `stream`, nothing is allocated or read back, sizes are checked before any pointer is used, and an empty
+ * problem (n == 0) is PDA_OK and touches nothing.  batch * d * h * w >= 2^31, for the input or the output grid, is refused
+ * before any launch.
+ *
+ * The index stage reads coordinates only.  stat (2) int32 is written whole: stat[0] the number of output sites (strided form;
+ * it keeps counting past cap), stat[1] flags: 1 = two rows share a coordinate, 2 = a row lies outside the grid.  Such rows
+ * are outside the contract: the caller reads the flags and refuses the tensor.  Only integer work, the only atomics are integer
+ * ones, two runs give the same bits; every grid is sized from n and cap.  workspace: pda_spconv_index_workspace_bytes(n, cap,
+ * candidates) bytes, 256-byte aligned; candidates = prod ceil(k_a / s_a), and (n, 0, 1) for the submanifold form; -1 for bad
+ * sizes.
+ * pda_spconv_index_subm: odd kernel, stride 1: the output sites are the input sites in the input's row order.
+ *   nbr_out (n, T): the row at coord_i + (t - centre), or -1 when that site is inactive or outside the grid.  The map a data
+ *   gradient needs is nbr_out with the taps mirrored (t -> T - 1 - t).
+ * pda_spconv_index_strided: kernel k, stride s, padding p per axis; the output grid is (in + 2p - k) / s + 1 per axis; an output
+ *   site is active when an active input site lies in its window.  out_indices (cap, 4): the output sites in ascending linear key
+ *   ((b * d' + z) * h' + y) * w' + x; rows from min(stat[0], cap) on are not written.  nbr_out (cap, T): the input row at
+ *   o * s - p + t or -1, -1 in the rows from min(stat[0], cap) on.  nbr_in (n, T): the output row that reads input row j through
+ *   tap t, or -1. */
+int64_t pda_spconv_index_workspace_bytes(int64_t n, int64_t cap, int candidates);
+int pda_spconv_index_subm(const int32_t *indices, int64_t n, int batch, int d, int h, int w, int kd, int kh, int kw,
+                          int32_t *nbr_out, int32_t *stat, void *workspace, pda_stream_t stream);
+int pda_spconv_index_strided(const int32_t *indices, int64_t n, int batch, int d, int h, int w, int kd, int kh, int kw, int sd,
+                             int sh, int sw, int pd, int ph, int pw, int64_t cap, int32_t *out_indices, int32_t *nbr_out,
+                             int32_t *nbr_in, int32_t *stat, void *workspace, pda_stream_t stream);
+/* The feature kernels: float32 in, float32 accumulate with the exact f32-input MFMA, no float atomics, fixed summation
+ * orders.  cin in [1, 128], cout a multiple of 16 up to 128; anything else is refused with a message.
+ * pda_spconv_gemm: out[i] = sum_t in[nbr[i][t']] . plane[t] (+ bias), t' = flip ? T - 1 - t : t, a tap with nbr < 0 (or
+ *   >= n_src) dropped.  transposed == 0 is the forward: in (n_src, cin), plane (T, pad16(cin), cout) with plane[t][ci][co] =
+ *   weight[co][t][ci], out (n_rows, cout), bias (cout) or NULL.  transposed == 1 is the data gradient: in = grad_out
+ *   (n_src, cout), plane (T, cout, pad16(cin)) with plane[t][co][ci] = weight[co][t][ci], out = grad_in (n_rows, cin), nbr =
+ *   nbr_in (or nbr_out with flip for the submanifold form).  pad16 rounds up to a multiple of 16; the padding is zero.
+ * pda_spconv_wgrad: grad_weight (cout, T, cin) [t][ci] = sum_i in[nbr_out[i][t]][ci] * grad_out[i][co], grad_bias (cout) or
+ *   NULL the column sums of grad_out (n_out, cout); partial products per (tap, row block) go to the workspace
+ *   (pda_spconv_wgrad_workspace_bytes, -1 for bad sizes) and are added in ascending block order. */
+int pda_spconv_gemm(const float *in, const int32_t *nbr, const float *plane, const float *bias, float *out, int64_t n_rows,
+                    int64_t n_src, int taps, int cin, int cout, int transposed, int flip, pda_stream_t stream);
+int64_t pda_spconv_wgrad_workspace_bytes(int64_t n_out, int taps, int cin, int cout);
+int pda_spconv_wgrad(const float *in, const float *grad_out, const int32_t *nbr_out, int64_t n_out, int64_t n_in, int taps,
+                     int cin, int cout, float *grad_weight, float *grad_bias, void *workspace, pda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

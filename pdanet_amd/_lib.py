@@ -236,6 +236,12 @@ SIGNATURES = {
     "pda_anchor_loss": [_vp] * 7 + [_i] * 4 + [ctypes.POINTER(_f)] + [ctypes.c_double] * 4 + [_vp] * 6,
     "pda_anchor_decode": [_vp, _vp, _vp, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp, _vp],
     "pda_pillar_features": [_vp, _vp, _vp, ctypes.c_int64, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _i, _i, _vp, _vp],
+    "pda_spconv_index_workspace_bytes": [ctypes.c_int64, ctypes.c_int64, _i],
+    "pda_spconv_index_subm": [_vp, ctypes.c_int64] + [_i] * 7 + [_vp, _vp, _vp, _vp],
+    "pda_spconv_index_strided": [_vp, ctypes.c_int64] + [_i] * 13 + [ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pda_spconv_gemm": [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, _i, _i, _i, _vp],
+    "pda_spconv_wgrad_workspace_bytes": [ctypes.c_int64, _i, _i, _i],
+    "pda_spconv_wgrad": [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, _i, _vp, _vp, _vp, _vp],
     # include/pda_pointnet2_stack.h
     "pda_stack_ball_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     "pda_stack_group_points": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -259,7 +265,8 @@ SIZE_QUERIES = [
     "pda_sa_small_train_workspace_bytes", "pda_sa_xyz_grad_scratch_bytes", "pda_input_stage_workspace_bytes",
     "pda_augment_workspace_bytes", "pda_augment_steps_workspace_bytes", "pda_once_eval_workspace_bytes",
     "pda_kitti_eval_workspace_bytes", "pda_kitti_fov_filter_workspace_bytes", "pda_gt_extract_workspace_bytes",
-    "pda_voxel_workspace_bytes", "pda_dyn_voxel_workspace_bytes", "pda_center_focal_blocks", "pda_anchor_loss_blocks"]
+    "pda_voxel_workspace_bytes", "pda_dyn_voxel_workspace_bytes", "pda_center_focal_blocks", "pda_anchor_loss_blocks",
+    "pda_spconv_index_workspace_bytes", "pda_spconv_wgrad_workspace_bytes"]
 INFO_SYMBOLS = ["pda_abi_version", "pda_last_error", "pda_fp_contract_mode", "pda_opt_n_threads",
                 "pda_fps_coop_timeouts", "pda_debug_fps_spin_limit", "pda_debug_fps_exchange_nonzero"]
 

@@ -7,7 +7,7 @@
 //                      the number of kept rows per tile of 256;
 //   dv_scan          : one workgroup, exclusive scan of the tile counts; counts[0] = n_kept;
 //   dv_compact       : point_idx = the kept rows in order (ballot / mbcnt ranks); (key, kept position) pairs for the sort;
-//   dv_digit_count / dv_scan_digit / dv_digit_scatter, ceil(key_bits / 8) times: a stable LSD radix sort of the pairs, 8
+//   dv_digit_count / dv_scan_digit / dv_digit_scatter (radix_sort.h), ceil(key_bits / 8) times: a stable LSD radix sort of the pairs, 8
 //                      bits a pass: a digit histogram per tile of 2048 pairs, stored digit-major; one workgroup per digit
 //                      scans its row of tiles, and the scatter adds the scan of the 256 digit totals, which gives every
 //                      (digit, tile) its first output slot; the rank of a pair among the equal digits of its tile comes
@@ -23,22 +23,17 @@
 // is unrolled so that four rows are in flight.  A thread walks one voxel, never a scene.
 // The file is built with -ffp-contract=off.
 #include "pda_common.h"
+#include "radix_sort.h"
 #include "voxel_cell.h"
 
 namespace pda {
 namespace {
 
-constexpr int DV_TILE = 256;                      // threads of every workgroup but the scan's; rows of a compaction tile
-constexpr int DV_WAVES = DV_TILE / PDA_WAVE;
-constexpr int DV_ITEMS = 8;                       // pairs a thread handles in a sort tile
-constexpr int DV_SORT_TILE = DV_TILE * DV_ITEMS;
-constexpr int DV_RADIX = 256;
 constexpr uint32_t DV_NONE = 0xffffffffu;         // keys are below 2^31
 constexpr int64_t DV_MAX_N = 1 << 30;
 constexpr int DV_MAX_DIM = 1 << 24;               // (float)cells along an axis is exact
 constexpr int DV_MAX_COLS = 256;
 
-static_assert(DV_RADIX == DV_TILE, "thread t owns digit t");
 
 struct DynGrid {
     float lo[3], vs[3];
@@ -47,10 +42,6 @@ struct DynGrid {
     uint32_t scale_b, scale_x, scale_y;      // merge_coords = b * scale_b + cx * scale_x + cy * scale_y + cz (pillars: cz = 0)
 };
 
-__device__ __forceinline__ int live(const int32_t* __restrict__ counts, int which, int64_t cap) {
-    const int32_t v = counts[which];
-    return v < 0 ? 0 : (v > cap ? (int)cap : v);      // a caller's buffer is never left, whatever counts holds
-}
 
 // The key of a row, DV_NONE when it joins nothing: a batch index outside [0, batch) (it is truncated as .int() does), a NaN
 // among x, y, z, or a cell outside the grid (z is not tested for pillars).
@@ -64,30 +55,6 @@ __device__ __forceinline__ uint32_t key_of(const float* __restrict__ p, const Dy
     return (uint32_t)(int)fb * g.scale_b + cx * g.scale_x + cy * g.scale_y + cz;
 }
 
-// Sums a flag over the workgroup's tile of DV_TILE threads and stores it.
-__device__ __forceinline__ void store_tile_count(bool f, int32_t* __restrict__ o) {
-    __shared__ int32_t wc[DV_WAVES];
-    const uint64_t bal = __ballot(f);
-    if (lane_id() == 0) wc[wave_id()] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int32_t s = 0;
-        for (int w = 0; w < DV_WAVES; ++w) s += wc[w];
-        *o = s;
-    }
-}
-
-// Flagged threads of the tile up to and including this one (every thread of the workgroup calls this).
-__device__ __forceinline__ int tile_rank_inclusive(bool f) {
-    __shared__ int32_t wc[DV_WAVES];
-    const uint64_t bal = __ballot(f);
-    const int w = wave_id();
-    if (lane_id() == 0) wc[w] = __popcll(bal);
-    __syncthreads();
-    int pos = rank_below(bal) + (f ? 1 : 0);
-    for (int v = 0; v < w; ++v) pos += wc[v];
-    return pos;
-}
 
 // ---- kept rows ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(DV_TILE) void dv_keys(const float* __restrict__ pts, int n, int c1, DynGrid g,
@@ -101,44 +68,6 @@ __global__ __launch_bounds__(DV_TILE) void dv_keys(const float* __restrict__ pts
     store_tile_count(key != DV_NONE, tile_cnt + blockIdx.x);
 }
 
-// The exclusive scan of a[0 .. m) in place by one workgroup of THREADS threads; thread u owns `per` consecutive entries.
-// Returns the total (valid in every thread).
-template <int THREADS>
-__device__ __forceinline__ int32_t block_scan(int32_t* __restrict__ a, int m) {
-    __shared__ int32_t part[THREADS];
-    const int u = threadIdx.x;
-    const int per = (m + THREADS - 1) / THREADS;
-    const int t0 = min(m, u * per), t1 = min(m, t0 + per);
-    int32_t s = 0;
-    for (int t = t0; t < t1; ++t) s += a[t];
-    part[u] = s;
-    __syncthreads();
-    for (int o = 1; o < THREADS; o <<= 1) {          // Hillis-Steele inclusive scan of the partial sums
-        const int32_t v = u >= o ? part[u - o] : 0;
-        __syncthreads();
-        part[u] += v;
-        __syncthreads();
-    }
-    int32_t run = part[u] - s;
-    for (int t = t0; t < t1; ++t) {
-        const int32_t c = a[t];
-        a[t] = run;
-        run += c;
-    }
-    return part[THREADS - 1];
-}
-
-// One workgroup: the tile counts of a compaction; the total goes to *total.
-__global__ __launch_bounds__(1024) void dv_scan(int32_t* __restrict__ a, int m, int32_t* __restrict__ total) {
-    const int32_t sum = block_scan<1024>(a, m);
-    if (threadIdx.x == 0) *total = sum;
-}
-
-// One workgroup per digit: the scan of the digit's row of tile counts, and the row's total.
-__global__ __launch_bounds__(DV_TILE) void dv_scan_digit(int32_t* __restrict__ hist, int tiles, int32_t* __restrict__ digit_total) {
-    const int32_t sum = block_scan<DV_TILE>(hist + (int64_t)blockIdx.x * tiles, tiles);
-    if (threadIdx.x == 0) digit_total[blockIdx.x] = sum;
-}
 
 // point_idx[pos] = the row of the pos-th kept point; the pair (key, pos) enters the sort.  Thread i also zeroes entry i of
 // the point outputs when i lies beyond the kept count (nobody else writes there).
@@ -164,81 +93,6 @@ __global__ __launch_bounds__(DV_TILE) void dv_compact(int n, const uint32_t* __r
     }
 }
 
-// ---- the sort ----------------------------------------------------------------------------------------------------------
-// hist[d * tiles + t] = the pairs of sort tile t whose digit is d.
-__global__ __launch_bounds__(DV_TILE) void dv_digit_count(int n, int shift, int tiles, const int32_t* __restrict__ counts,
-                                                          const uint32_t* __restrict__ key, int32_t* __restrict__ hist) {
-    __shared__ int32_t h[DV_RADIX];
-    const int t = blockIdx.x, u = threadIdx.x;
-    const int nk = live(counts, 0, n);
-    h[u] = 0;
-    __syncthreads();
-    for (int r = 0; r < DV_ITEMS; ++r) {
-        const int64_t j = (int64_t)t * DV_SORT_TILE + r * DV_TILE + u;
-        if (j < nk) atomicAdd(&h[(key[j] >> shift) & (DV_RADIX - 1)], 1);
-    }
-    __syncthreads();
-    hist[(int64_t)u * tiles + t] = h[u];
-}
-
-// A pair goes to base[digit] (the scanned histogram) + the pairs of its tile with the same digit in front of it: those of
-// earlier rounds (folded into base after every round), of earlier waves of this round (wc) and of lower lanes of this wave.
-__global__ __launch_bounds__(DV_TILE) void dv_digit_scatter(int n, int shift, int tiles, const int32_t* __restrict__ counts,
-                                                            const int32_t* __restrict__ hist,
-                                                            const int32_t* __restrict__ digit_total,
-                                                            const uint32_t* __restrict__ key, const int32_t* __restrict__ val,
-                                                            uint32_t* __restrict__ key_out, int32_t* __restrict__ val_out) {
-    __shared__ int32_t base[DV_RADIX], wc[DV_WAVES][DV_RADIX];
-    const int t = blockIdx.x, u = threadIdx.x, w = wave_id();
-    const int nk = live(counts, 0, n);
-    const int32_t total = digit_total[u];
-    base[u] = total;
-#pragma unroll
-    for (int v = 0; v < DV_WAVES; ++v) wc[v][u] = 0;
-    __syncthreads();
-    for (int o = 1; o < DV_RADIX; o <<= 1) {          // the pairs of all lower digits: the inclusive scan of the totals ...
-        const int32_t v = u >= o ? base[u - o] : 0;
-        __syncthreads();
-        base[u] += v;
-        __syncthreads();
-    }
-    base[u] += hist[(int64_t)u * tiles + t] - total;      // ... made exclusive, plus this digit's pairs in earlier tiles
-    __syncthreads();
-    for (int r = 0; r < DV_ITEMS; ++r) {
-        const int64_t j = (int64_t)t * DV_SORT_TILE + r * DV_TILE + u;
-        const bool valid = j < nk;
-        const uint32_t k = valid ? key[j] : 0u;
-        const int32_t x = valid ? val[j] : 0;
-        const uint32_t d = (k >> shift) & (DV_RADIX - 1);
-        uint64_t same = __ballot(valid);                       // the valid lanes of this wave with my digit
-#pragma unroll
-        for (int bit = 0; bit < 8; ++bit) {
-            const bool one = (d >> bit) & 1u;
-            const uint64_t b = __ballot(one);
-            same &= one ? b : ~b;
-        }
-        const int below = rank_below(same);
-        if (valid && below == 0) wc[w][d] = __popcll(same);
-        __syncthreads();
-        if (valid) {
-            int pos = base[d] + below;
-            for (int v = 0; v < w; ++v) pos += wc[v][d];
-            if (pos < nk) {                                    // always, for a histogram of these very keys
-                key_out[pos] = k;
-                val_out[pos] = x;
-            }
-        }
-        __syncthreads();
-        int32_t s = 0;
-#pragma unroll
-        for (int v = 0; v < DV_WAVES; ++v) {
-            s += wc[v][u];
-            wc[v][u] = 0;
-        }
-        base[u] += s;
-        __syncthreads();
-    }
-}
 
 // ---- the voxels --------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool is_head(const uint32_t* __restrict__ key, int j, int nk) {
@@ -412,7 +266,6 @@ __global__ __launch_bounds__(DV_TILE) void dv_pillar_features(const float* __res
 
 // ---- host --------------------------------------------------------------------------------------------------------------
 int64_t pad256(int64_t x) { return (x + 255) / 256 * 256; }
-int64_t sort_tiles_of(int64_t n) { return divup64(n, DV_SORT_TILE); }
 
 struct Layout {
     int64_t key_a, key_b, val_a, val_b, tile_cnt, hist, digit_total, total;
@@ -478,7 +331,6 @@ PDA_API int pda_dyn_voxel_index(const float* points, int64_t n, int c1, const fl
     const uint64_t range = cells * (uint64_t)batch;      // keys lie in [0, range)
     int key_bits = 1;
     while ((1ull << key_bits) < range) ++key_bits;
-    const int passes = (key_bits + 7) / 8;
 
     const pda::Layout l = pda::layout_of(n);
     char* ws = (char*)workspace;
@@ -488,21 +340,15 @@ PDA_API int pda_dyn_voxel_index(const float* points, int64_t n, int c1, const fl
     int32_t* hist = (int32_t*)(ws + l.hist);
     int32_t* digit_total = (int32_t*)(ws + l.digit_total);
     hipStream_t st = (hipStream_t)stream;
-    const int ni = (int)n, tiles = (int)pda::divup64(n, pda::DV_TILE), stiles = (int)pda::sort_tiles_of(n);
-    const dim3 tgrid((unsigned)tiles), sgrid((unsigned)stiles), block(pda::DV_TILE);
+    const int ni = (int)n, tiles = (int)pda::divup64(n, pda::DV_TILE);
+    const dim3 tgrid((unsigned)tiles), block(pda::DV_TILE);
 
     // the raw keys wait in key[1]: the first pass of the sort reads key[0] and overwrites them
     hipLaunchKernelGGL(pda::dv_keys, tgrid, block, 0, st, points, ni, c1, g, key[1], tile_cnt);
     hipLaunchKernelGGL(pda::dv_scan, dim3(1), dim3(1024), 0, st, tile_cnt, tiles, counts);
     hipLaunchKernelGGL(pda::dv_compact, tgrid, block, 0, st, ni, key[1], tile_cnt, counts, point_idx, unq_inv, seg_points, key[0],
                        val[0]);
-    int cur = 0;
-    for (int p = 0; p < passes; ++p, cur ^= 1) {
-        hipLaunchKernelGGL(pda::dv_digit_count, sgrid, block, 0, st, ni, 8 * p, stiles, counts, key[cur], hist);
-        hipLaunchKernelGGL(pda::dv_scan_digit, dim3(pda::DV_RADIX), block, 0, st, hist, stiles, digit_total);
-        hipLaunchKernelGGL(pda::dv_digit_scatter, sgrid, block, 0, st, ni, 8 * p, stiles, counts, hist, digit_total, key[cur],
-                           val[cur], key[cur ^ 1], val[cur ^ 1]);
-    }
+    const int cur = pda::radix_sort_pairs(ni, key_bits, counts, key, val, hist, digit_total, st);
     hipLaunchKernelGGL(pda::dv_head_count, tgrid, block, 0, st, ni, counts, key[cur], tile_cnt);
     hipLaunchKernelGGL(pda::dv_scan, dim3(1), dim3(1024), 0, st, tile_cnt, tiles, counts + 1);
     hipLaunchKernelGGL(pda::dv_head_scatter, tgrid, block, 0, st, ni, g, counts, key[cur], val[cur], tile_cnt, unq_inv, voxel_coords,

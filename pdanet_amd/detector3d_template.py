@@ -2,12 +2,16 @@
 fields, the check of the four NAME keys, and the run over vfe -> map_to_bev_module -> backbone_2d -> dense_head under the
 reference's module names, so a reference checkpoint loads with strict=True.  A detector names the encoder and head classes
 it accepts (VFE, DENSE_HEAD) and decodes in post_processing.  (detector.py, IASSD with its graph capture, does not build on
-this.)"""
+this.)
+
+VoxelDetector is the same for the sparse-convolution family: vfe -> backbone_3d -> map_to_bev_module (HeightCompression) ->
+backbone_2d -> dense_head."""
 import numpy as np
 import torch.nn as nn
 
 from .base_bev_backbone import BaseBEVBackbone
 from .config import field
+from .height_compression import HeightCompression
 from .pointpillar_scatter import PointPillarScatter
 from .voxel_utils import grid_size as _grid_size
 
@@ -60,3 +64,39 @@ class PillarDetector(nn.Module):
 
     def post_processing(self, batch_dict):
         raise NotImplementedError
+
+
+class VoxelDetector(PillarDetector):
+    """The sparse-convolution family: PillarDetector's forward and loss over five modules instead of four.  The constructor
+    is its own (another NAME check, a 3D backbone between the encoder and the BEV map), so PillarDetector's is not chained."""
+    BACKBONE_3D = {}     # NAME -> class
+
+    def __init__(self, model_cfg, num_class, dataset):
+        nn.Module.__init__(self)
+        self.model_cfg, self.num_class = model_cfg, num_class
+        self.class_names = list(field(dataset, 'class_names'))
+        pcr = np.asarray(field(dataset, 'point_cloud_range'), dtype=np.float64)
+        vs = np.asarray(field(dataset, 'voxel_size'), dtype=np.float64)
+        grid = field(dataset, 'grid_size', None)
+        grid = np.asarray(_grid_size(pcr, vs) if grid is None else grid, dtype=np.int64)
+        try:
+            n_feat = field(dataset, 'num_point_features')
+        except (KeyError, AttributeError):
+            n_feat = field(dataset, 'point_feature_encoder').num_point_features
+        for key, names in (('VFE', self.VFE), ('BACKBONE_3D', self.BACKBONE_3D), ('MAP_TO_BEV', ('HeightCompression',)),
+                           ('BACKBONE_2D', ('BaseBEVBackbone',)), ('DENSE_HEAD', self.DENSE_HEAD)):
+            if model_cfg[key]['NAME'] not in names:
+                raise NotImplementedError("%s.NAME %r is not part of this project (SECONDNet: %s)"
+                                          % (key, model_cfg[key]['NAME'], ", ".join(names)))
+        vfe_cfg, b3d_cfg, head_cfg = model_cfg['VFE'], model_cfg['BACKBONE_3D'], model_cfg['DENSE_HEAD']
+        self.vfe = self.VFE[vfe_cfg['NAME']](vfe_cfg, num_point_features=n_feat, voxel_size=vs, grid_size=grid,
+                                             point_cloud_range=pcr)
+        self.backbone_3d = self.BACKBONE_3D[b3d_cfg['NAME']](b3d_cfg, input_channels=self.vfe.get_output_feature_dim(),
+                                                             grid_size=grid.tolist(), voxel_size=vs, point_cloud_range=pcr)
+        self.map_to_bev_module = HeightCompression(model_cfg['MAP_TO_BEV'], grid_size=grid)
+        self.backbone_2d = BaseBEVBackbone(model_cfg['BACKBONE_2D'], input_channels=self.map_to_bev_module.num_bev_features)
+        self.dense_head = self.DENSE_HEAD[head_cfg['NAME']](
+            head_cfg, input_channels=self.backbone_2d.num_bev_features,
+            num_class=num_class if not head_cfg.get('CLASS_AGNOSTIC', False) else 1, class_names=self.class_names,
+            grid_size=grid, point_cloud_range=pcr, voxel_size=vs, predict_boxes_when_training=model_cfg.get('ROI_HEAD', False))
+        self.module_list = [self.vfe, self.backbone_3d, self.map_to_bev_module, self.backbone_2d, self.dense_head]
