@@ -1011,6 +1011,28 @@ int64_t pda_spconv_wgrad_workspace_bytes(int64_t n_out, int taps, int cin, int c
 int pda_spconv_wgrad(const float *in, const float *grad_out, const int32_t *nbr_out, int64_t n_out, int64_t n_in, int taps,
                      int cin, int cout, float *grad_weight, float *grad_bias, void *workspace, pda_stream_t stream);
 
+/* ---- Fused voxel pooling (csrc/voxel_pool.hip): one scale of NeighborVoxelSAModuleMSG after mlps_in, without the grouped
+ * (M, C, nsample) tensors.  idx (m, nsample) is pda_stack_voxel_query's output as it stands: GLOBAL rows of xyz, idx[i][0] = -1
+ * for an empty ball.  A slot of an empty row, and a slot g outside [0, n), reads nothing and stands for rel = 0, f = 0.
+ *   rel[i][s] = xyz[idx[i][s]] - new_xyz[i]  (the float32 difference),  f[i][s][c] = features_in[idx[i][s]][c]
+ *   out[i][c] = max_s relu(f[i][s][c] + scale[c] * (w[c] . rel[i][s]) + shift[c]),  arg[i][c] = the first s that attains it
+ * c is 32 or 64, nsample in [1, 255]; anything else is refused with a message.
+ * pda_voxel_pool_scratch_doubles: the float64 elements the scratch of the two entries below needs (-1 for bad sizes).
+ * pda_voxel_pool_moments: sums[9] = sum over all m * nsample slots of [x, y, z, xx, xy, xz, yy, yz, zz] of rel, in float64,
+ *   per-workgroup partials added in one fixed order (csrc/loss_sums.h); no atomics.
+ * pda_voxel_pool_bwd: with g = grad_out where out > 0 (else 0) and s* = arg: grad_features_in[idx[i][s*]][c] += g by float
+ *   atomics (the caller zero-fills it; slots that read nothing add nothing), and sums (5, c) float64 = per channel
+ *   [sum g, sum g * (w[c] . rel*), sum g * rel*.x, .y, .z], ordered partials as above. */
+int64_t pda_voxel_pool_scratch_doubles(int m, int c, int nsample);
+int pda_voxel_pool_moments(const int32_t *idx, const float *xyz, const float *new_xyz, double *scratch, double *sums, int n,
+                           int m, int nsample, pda_stream_t stream);
+int pda_voxel_pool_fwd(const float *features_in, const int32_t *idx, const float *xyz, const float *new_xyz, const float *w,
+                       const float *scale, const float *shift, float *out, uint8_t *arg, int n, int m, int c, int nsample,
+                       pda_stream_t stream);
+int pda_voxel_pool_bwd(const float *grad_out, const float *out, const uint8_t *arg, const int32_t *idx, const float *xyz,
+                       const float *new_xyz, const float *w, float *grad_features_in, double *scratch, double *sums, int n,
+                       int m, int c, int nsample, pda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -242,6 +242,10 @@ SIGNATURES = {
     "pda_spconv_gemm": [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, _i, _i, _i, _vp],
     "pda_spconv_wgrad_workspace_bytes": [ctypes.c_int64, _i, _i, _i],
     "pda_spconv_wgrad": [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "pda_voxel_pool_scratch_doubles": [_i, _i, _i],
+    "pda_voxel_pool_moments": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "pda_voxel_pool_fwd": [_vp] * 9 + [_i, _i, _i, _i, _vp],
+    "pda_voxel_pool_bwd": [_vp] * 10 + [_i, _i, _i, _i, _vp],
     # include/pda_pointnet2_stack.h
     "pda_stack_ball_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     "pda_stack_group_points": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -266,7 +270,7 @@ SIZE_QUERIES = [
     "pda_augment_workspace_bytes", "pda_augment_steps_workspace_bytes", "pda_once_eval_workspace_bytes",
     "pda_kitti_eval_workspace_bytes", "pda_kitti_fov_filter_workspace_bytes", "pda_gt_extract_workspace_bytes",
     "pda_voxel_workspace_bytes", "pda_dyn_voxel_workspace_bytes", "pda_center_focal_blocks", "pda_anchor_loss_blocks",
-    "pda_spconv_index_workspace_bytes", "pda_spconv_wgrad_workspace_bytes"]
+    "pda_spconv_index_workspace_bytes", "pda_spconv_wgrad_workspace_bytes", "pda_voxel_pool_scratch_doubles"]
 INFO_SYMBOLS = ["pda_abi_version", "pda_last_error", "pda_fp_contract_mode", "pda_opt_n_threads",
                 "pda_fps_coop_timeouts", "pda_debug_fps_spin_limit", "pda_debug_fps_exchange_nonzero"]
 

@@ -6,10 +6,11 @@ import torch
 
 
 def rotate_points_along_z(points, angle):
-    """common_utils.rotate_points_along_z: points (B, N, 3+C), angle (B) -> rotated about z (x towards y)."""
+    """common_utils.rotate_points_along_z: points (B, N, 3+C), angle (B) -> rotated about z (x towards y), in the
+    points' type (float32 in the reference)."""
     cosa, sina = torch.cos(angle), torch.sin(angle)
     zeros, ones = angle.new_zeros(points.shape[0]), angle.new_ones(points.shape[0])
-    rot = torch.stack((cosa, sina, zeros, -sina, cosa, zeros, zeros, zeros, ones), dim=1).view(-1, 3, 3).float()
+    rot = torch.stack((cosa, sina, zeros, -sina, cosa, zeros, zeros, zeros, ones), dim=1).view(-1, 3, 3).to(points.dtype)
     out = torch.matmul(points[:, :, 0:3], rot)
     return torch.cat((out, points[:, :, 3:]), dim=-1)
 

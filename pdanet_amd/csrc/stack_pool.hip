@@ -1,6 +1,7 @@
 // stack_pool.hip -- the voxel-query and vector-pool half of the pointnet2_stack operator set
 // (include/pda_pointnet2_stack.h): voxel_query_gpu.cu:10-89 and vector_pool_gpu.cu:19-458 of the reference.
-// Never reached by PDA-SSD; built so that the reference's Voxel-RCNN / PV-RCNN++ call sites bind to the same library.
+// Never reached by PDA-SSD.  voxel_query feeds Voxel R-CNN's RoI-grid pooling (voxel_pool.hip, voxel_pool_modules.py); the
+// vector-pool entries are there so that the reference's PV-RCNN++ call sites bind to the same library.
 //
 // Scene lookup, stream, status codes and pda_last_error() as in stack_ops.hip.  The M x N neighbourhood searches stage
 // the scene's points through LDS in 256-point tiles shared by a workgroup of 256 centres.  Instead of the reference's

@@ -5,7 +5,7 @@ it accepts (VFE, DENSE_HEAD) and decodes in post_processing.  (detector.py, IASS
 this.)
 
 VoxelDetector is the same for the sparse-convolution family: vfe -> backbone_3d -> map_to_bev_module (HeightCompression) ->
-backbone_2d -> dense_head."""
+backbone_2d -> dense_head, and -> roi_head for a two-stage detector that names one (ROI_HEAD)."""
 import numpy as np
 import torch.nn as nn
 
@@ -70,6 +70,7 @@ class VoxelDetector(PillarDetector):
     """The sparse-convolution family: PillarDetector's forward and loss over five modules instead of four.  The constructor
     is its own (another NAME check, a 3D backbone between the encoder and the BEV map), so PillarDetector's is not chained."""
     BACKBONE_3D = {}     # NAME -> class
+    ROI_HEAD = {}        # NAME -> class; a model config without ROI_HEAD builds the one-stage detector
 
     def __init__(self, model_cfg, num_class, dataset):
         nn.Module.__init__(self)
@@ -100,3 +101,19 @@ class VoxelDetector(PillarDetector):
             num_class=num_class if not head_cfg.get('CLASS_AGNOSTIC', False) else 1, class_names=self.class_names,
             grid_size=grid, point_cloud_range=pcr, voxel_size=vs, predict_boxes_when_training=model_cfg.get('ROI_HEAD', False))
         self.module_list = [self.vfe, self.backbone_3d, self.map_to_bev_module, self.backbone_2d, self.dense_head]
+        roi_cfg = model_cfg.get('ROI_HEAD', None)
+        if roi_cfg is not None:
+            if roi_cfg['NAME'] not in self.ROI_HEAD:
+                raise NotImplementedError("ROI_HEAD.NAME %r is not part of %s (%s)"
+                                          % (roi_cfg['NAME'], type(self).__name__, ", ".join(self.ROI_HEAD) or "no RoI head"))
+            self.roi_head = self.ROI_HEAD[roi_cfg['NAME']](
+                backbone_channels=self.backbone_3d.backbone_channels, model_cfg=roi_cfg, point_cloud_range=pcr, voxel_size=vs,
+                num_class=num_class if not roi_cfg.get('CLASS_AGNOSTIC', False) else 1)
+            self.module_list.append(self.roi_head)
+
+    def get_training_loss(self):
+        loss, tb_dict, disp_dict = super().get_training_loss()
+        if getattr(self, 'roi_head', None) is not None:
+            loss_rcnn, tb_dict = self.roi_head.get_loss(tb_dict)
+            loss = loss + loss_rcnn
+        return loss, tb_dict, disp_dict

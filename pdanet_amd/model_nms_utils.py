@@ -61,7 +61,11 @@ def post_processing(batch_dict, post_process_cfg, num_class):
     if not batch_dict['cls_preds_normalized']:
         cls_preds = torch.sigmoid(cls_preds)
     scores, labels = torch.max(cls_preds, dim=-1)
-    labels = labels + 1
+    if batch_dict.get('has_class_labels', False):
+        # a two-stage head scores class-agnostically: the labels are the first stage's (detector3d_template.py:238-240)
+        labels = batch_dict['roi_labels' if 'roi_labels' in batch_dict else 'batch_pred_labels'].view(B, -1)
+    else:
+        labels = labels + 1
     selected, sel_scores, num = class_agnostic_nms_batched(scores, box_preds, post_process_cfg["NMS_CONFIG"],
                                                            score_thresh=post_process_cfg["SCORE_THRESH"])
     ok = selected >= 0

@@ -95,3 +95,23 @@ class VoxelGenerator:
         v = int(num_voxels.item())
         out = voxels[0, :v], coords[0, :v], num_points[0, :v]
         return tuple(t.cpu().numpy() for t in out) if as_numpy else out
+
+
+def get_voxel_centers(voxel_coords, downsample_times, voxel_size, point_cloud_range):
+    """common_utils.get_voxel_centers: voxel_coords (N, 3) [z, y, x] of a grid downsampled `downsample_times` -> centres
+    (N, 3) [x, y, z] float32, in the reference's float32 expression."""
+    assert voxel_coords.shape[1] == 3
+    centers = voxel_coords[:, [2, 1, 0]].float()
+    size = torch.tensor([float(v) for v in voxel_size], device=centers.device).float() * downsample_times
+    lo = torch.tensor([float(v) for v in point_cloud_range[0:3]], device=centers.device).float()
+    return (centers + 0.5) * size + lo
+
+
+def generate_voxel2pinds(sparse_tensor):
+    """common_utils.generate_voxel2pinds: (B, Z, Y, X) int32, the row of the active site in each cell and -1 elsewhere.
+    A fill and one indexed store; nothing is read on the host."""
+    ind = sparse_tensor.indices.long()
+    rows = torch.arange(ind.shape[0], device=ind.device, dtype=torch.int32)
+    out = torch.full([sparse_tensor.batch_size] + list(sparse_tensor.spatial_shape), -1, dtype=torch.int32, device=ind.device)
+    out[ind[:, 0], ind[:, 1], ind[:, 2], ind[:, 3]] = rows
+    return out
