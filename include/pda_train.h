@@ -1033,6 +1033,55 @@ int pda_voxel_pool_bwd(const float *grad_out, const float *out, const uint8_t *a
                        const float *new_xyz, const float *w, float *grad_features_in, double *scratch, double *sums, int n,
                        int m, int c, int nsample, pda_stream_t stream);
 
+/* ---- Fused stacked set abstraction (csrc/stack_sa.hip): one scale of StackSAModuleMSG with two Conv-BN-ReLU layers and a max
+ * pool, without the grouped (M, 3 + C_in, nsample) tensor and what follows it.  f (n, c1) = features W1f^T is made by the
+ * caller (W1 = [W1x | W1f], xyz first).  idx (m, nsample) is pda_stack_ball_query's output as it stands: indices LOCAL to the
+ * scene, idx[i][0] = -1 for an empty ball; the scene starts are derived on the device from the two count vectors (b scenes).
+ * A slot of an empty row, and a slot whose index lies outside its scene, reads nothing and stands for rel = 0, f = 0.
+ *   rel = xyz[g] - new_xyz[i];  y1[c] = f[g][c] + ((w1x[c][0] rel.x + w1x[c][1] rel.y) + w1x[c][2] rel.z)
+ *   z1[c] = max(scale1[c] y1[c] + shift1[c], 0);  y2[d] = fma chain over c ascending of w2[d][c] z1[c]
+ * c1 and c2 are 16, 32 or 64, nsample in [1, 255]; anything else is refused with a message.  Nothing is allocated; every sum
+ * is float64 from per-workgroup partials added in one fixed order (csrc/loss_sums.h), no float atomics but grad_f's.
+ * pda_stack_sa_scratch_doubles: the float64 elements `scratch` of the entries below needs (-1 for bad sizes).
+ * pda_stack_sa_moments: sums (2, c1) = per channel [sum y1, sum y1^2] over all m * nsample slots.
+ * pda_stack_sa_fwd: u (m, c2) = the largest y2 over the slots where gamma2[d] >= 0, else the smallest; arg (m, c2) the first
+ *   slot that attains it; sums (2, c2) = [sum y2, sum y2^2] over all slots.
+ * pda_stack_sa_apply: out = max(scale2[d] u + shift2[d], 0).
+ * pda_stack_sa_bwd1: dy2[i][s][d] = (s == arg[i][d] ? scale2[d] g[i][d] : 0) - a2[d] - b2[d] y2[i][s][d];
+ *   e1 (m, nsample, c1) = (sum_d dy2[d] w2[d][c]) where z1[c] > 0, else 0;
+ *   sums = [dW2 transposed (c1, c2): sum dy2[d] z1[c]] [sum e1 (c1)] [sum e1 y1 (c1)].
+ * pda_stack_sa_bwd2: dy1 = (scale1[c] e1 - a1[c]) - b1[c] y1 for the slots that read a row g: grad_f[g][c] += dy1 by float
+ *   atomics (the caller zero-fills it), sums (3, c1) = sum dy1[c] rel.x, .y, .z. */
+int64_t pda_stack_sa_scratch_doubles(int m, int c1, int c2, int nsample);
+int pda_stack_sa_moments(const float *f, const float *xyz, const float *new_xyz, const int32_t *xyz_batch_cnt,
+                         const int32_t *new_xyz_batch_cnt, const int32_t *idx, const float *w1x, double *scratch, double *sums,
+                         int b, int n, int m, int c1, int nsample, pda_stream_t stream);
+int pda_stack_sa_fwd(const float *f, const float *xyz, const float *new_xyz, const int32_t *xyz_batch_cnt,
+                     const int32_t *new_xyz_batch_cnt, const int32_t *idx, const float *w1x, const float *w2,
+                     const float *scale1, const float *shift1, const float *gamma2, float *u, uint8_t *arg, double *scratch,
+                     double *sums, int b, int n, int m, int c1, int c2, int nsample, pda_stream_t stream);
+int pda_stack_sa_apply(const float *u, const float *scale2, const float *shift2, float *out, int m, int c2, pda_stream_t stream);
+int pda_stack_sa_bwd1(const float *f, const float *xyz, const float *new_xyz, const int32_t *xyz_batch_cnt,
+                      const int32_t *new_xyz_batch_cnt, const int32_t *idx, const float *w1x, const float *w2,
+                      const float *scale1, const float *shift1, const uint8_t *arg, const float *g, const float *scale2,
+                      const float *a2, const float *b2, float *e1, double *scratch, double *sums, int b, int n, int m, int c1,
+                      int c2, int nsample, pda_stream_t stream);
+int pda_stack_sa_bwd2(const float *f, const float *xyz, const float *new_xyz, const int32_t *xyz_batch_cnt,
+                      const int32_t *new_xyz_batch_cnt, const int32_t *idx, const float *w1x, const float *e1,
+                      const float *scale1, const float *a1, const float *b1, float *grad_f, double *scratch, double *sums, int b,
+                      int n, int m, int c1, int nsample, pda_stream_t stream);
+
+/* ---- interpolate_from_bev_features of VoxelSetAbstraction (csrc/stack_sa.hip): bilinear_interpolate_torch of the reference.
+ * keypoints (m, 4) [batch, x, y, z] (only the batch column is read), x_idxs / y_idxs (m) the map coordinates the caller
+ * derives with the reference's expressions, bev (b, c, h, w) -> out (m, c).  Indices are floored and then clamped, the
+ * weights come from the CLAMPED corners (at the border they need not sum to 1), the value is
+ * ((Ia wa + Ib wb) + Ic wc) + Id wd in float32.  A batch index outside [0, b) reads nothing (out = 0) and writes nothing.
+ * _bwd adds into grad_bev, which the caller zero-fills, with float atomics. */
+int pda_bev_interpolate_fwd(const float *keypoints, const float *x_idxs, const float *y_idxs, const float *bev, float *out,
+                            int m, int b, int c, int h, int w, pda_stream_t stream);
+int pda_bev_interpolate_bwd(const float *keypoints, const float *x_idxs, const float *y_idxs, const float *grad_out,
+                            float *grad_bev, int m, int b, int c, int h, int w, pda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -246,6 +246,14 @@ SIGNATURES = {
     "pda_voxel_pool_moments": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "pda_voxel_pool_fwd": [_vp] * 9 + [_i, _i, _i, _i, _vp],
     "pda_voxel_pool_bwd": [_vp] * 10 + [_i, _i, _i, _i, _vp],
+    "pda_stack_sa_scratch_doubles": [_i, _i, _i, _i],
+    "pda_stack_sa_moments": [_vp] * 9 + [_i] * 5 + [_vp],
+    "pda_stack_sa_fwd": [_vp] * 15 + [_i] * 6 + [_vp],
+    "pda_stack_sa_apply": [_vp, _vp, _vp, _vp, _i, _i, _vp],
+    "pda_stack_sa_bwd1": [_vp] * 18 + [_i] * 6 + [_vp],
+    "pda_stack_sa_bwd2": [_vp] * 14 + [_i] * 5 + [_vp],
+    "pda_bev_interpolate_fwd": [_vp] * 5 + [_i] * 5 + [_vp],
+    "pda_bev_interpolate_bwd": [_vp] * 5 + [_i] * 5 + [_vp],
     # include/pda_pointnet2_stack.h
     "pda_stack_ball_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     "pda_stack_group_points": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -270,7 +278,8 @@ SIZE_QUERIES = [
     "pda_augment_workspace_bytes", "pda_augment_steps_workspace_bytes", "pda_once_eval_workspace_bytes",
     "pda_kitti_eval_workspace_bytes", "pda_kitti_fov_filter_workspace_bytes", "pda_gt_extract_workspace_bytes",
     "pda_voxel_workspace_bytes", "pda_dyn_voxel_workspace_bytes", "pda_center_focal_blocks", "pda_anchor_loss_blocks",
-    "pda_spconv_index_workspace_bytes", "pda_spconv_wgrad_workspace_bytes", "pda_voxel_pool_scratch_doubles"]
+    "pda_spconv_index_workspace_bytes", "pda_spconv_wgrad_workspace_bytes", "pda_voxel_pool_scratch_doubles",
+    "pda_stack_sa_scratch_doubles"]
 INFO_SYMBOLS = ["pda_abi_version", "pda_last_error", "pda_fp_contract_mode", "pda_opt_n_threads",
                 "pda_fps_coop_timeouts", "pda_debug_fps_spin_limit", "pda_debug_fps_exchange_nonzero"]
 

@@ -5,7 +5,9 @@ it accepts (VFE, DENSE_HEAD) and decodes in post_processing.  (detector.py, IASS
 this.)
 
 VoxelDetector is the same for the sparse-convolution family: vfe -> backbone_3d -> map_to_bev_module (HeightCompression) ->
-backbone_2d -> dense_head, and -> roi_head for a two-stage detector that names one (ROI_HEAD)."""
+backbone_2d -> dense_head, and -> roi_head for a two-stage detector that names one (ROI_HEAD).  A detector with PFE and
+POINT_HEAD tables (PV-RCNN) gets pfe after map_to_bev_module and point_head after dense_head, the reference's module order;
+its batch needs `points` (N, 1 + 3 + C) next to the voxels."""
 import numpy as np
 import torch.nn as nn
 
@@ -71,6 +73,8 @@ class VoxelDetector(PillarDetector):
     is its own (another NAME check, a 3D backbone between the encoder and the BEV map), so PillarDetector's is not chained."""
     BACKBONE_3D = {}     # NAME -> class
     ROI_HEAD = {}        # NAME -> class; a model config without ROI_HEAD builds the one-stage detector
+    PFE = {}             # NAME -> class; built only when the model config has the block (as POINT_HEAD)
+    POINT_HEAD = {}
 
     def __init__(self, model_cfg, num_class, dataset):
         nn.Module.__init__(self)
@@ -95,24 +99,55 @@ class VoxelDetector(PillarDetector):
         self.backbone_3d = self.BACKBONE_3D[b3d_cfg['NAME']](b3d_cfg, input_channels=self.vfe.get_output_feature_dim(),
                                                              grid_size=grid.tolist(), voxel_size=vs, point_cloud_range=pcr)
         self.map_to_bev_module = HeightCompression(model_cfg['MAP_TO_BEV'], grid_size=grid)
+        self.module_list = [self.vfe, self.backbone_3d, self.map_to_bev_module]
+        pfe_cfg = self._optional_block('PFE', self.PFE)
+        if pfe_cfg is not None:
+            self.pfe = self.PFE[pfe_cfg['NAME']](model_cfg=pfe_cfg, voxel_size=vs, point_cloud_range=pcr,
+                                                 num_bev_features=self.map_to_bev_module.num_bev_features,
+                                                 num_rawpoint_features=n_feat)
+            self.module_list.append(self.pfe)
         self.backbone_2d = BaseBEVBackbone(model_cfg['BACKBONE_2D'], input_channels=self.map_to_bev_module.num_bev_features)
         self.dense_head = self.DENSE_HEAD[head_cfg['NAME']](
             head_cfg, input_channels=self.backbone_2d.num_bev_features,
             num_class=num_class if not head_cfg.get('CLASS_AGNOSTIC', False) else 1, class_names=self.class_names,
             grid_size=grid, point_cloud_range=pcr, voxel_size=vs, predict_boxes_when_training=model_cfg.get('ROI_HEAD', False))
-        self.module_list = [self.vfe, self.backbone_3d, self.map_to_bev_module, self.backbone_2d, self.dense_head]
+        self.module_list += [self.backbone_2d, self.dense_head]
+        point_cfg = self._optional_block('POINT_HEAD', self.POINT_HEAD)
+        if point_cfg is not None:
+            if pfe_cfg is None:
+                raise ValueError("POINT_HEAD needs a PFE")
+            before = point_cfg.get('USE_POINT_FEATURES_BEFORE_FUSION', False)
+            self.point_head = self.POINT_HEAD[point_cfg['NAME']](
+                model_cfg=point_cfg, input_channels=self.pfe.num_point_features_before_fusion if before else self.pfe.num_point_features,
+                num_class=num_class if not point_cfg.get('CLASS_AGNOSTIC', False) else 1,
+                predict_boxes_when_training=model_cfg.get('ROI_HEAD', False))
+            self.module_list.append(self.point_head)
         roi_cfg = model_cfg.get('ROI_HEAD', None)
         if roi_cfg is not None:
             if roi_cfg['NAME'] not in self.ROI_HEAD:
                 raise NotImplementedError("ROI_HEAD.NAME %r is not part of %s (%s)"
                                           % (roi_cfg['NAME'], type(self).__name__, ", ".join(self.ROI_HEAD) or "no RoI head"))
+            point_kwargs = {} if pfe_cfg is None else {'input_channels': self.pfe.num_point_features}
             self.roi_head = self.ROI_HEAD[roi_cfg['NAME']](
                 backbone_channels=self.backbone_3d.backbone_channels, model_cfg=roi_cfg, point_cloud_range=pcr, voxel_size=vs,
-                num_class=num_class if not roi_cfg.get('CLASS_AGNOSTIC', False) else 1)
+                num_class=num_class if not roi_cfg.get('CLASS_AGNOSTIC', False) else 1, **point_kwargs)
             self.module_list.append(self.roi_head)
+
+    def _optional_block(self, key, table):
+        """The model config's block `key`, or None when it has none; a block this detector has no class for is refused."""
+        cfg = self.model_cfg.get(key, None)
+        if cfg is None:
+            return None
+        if cfg['NAME'] not in table:
+            raise NotImplementedError("%s.NAME %r is not part of %s (%s)"
+                                      % (key, cfg['NAME'], type(self).__name__, ", ".join(table) or "no such block"))
+        return cfg
 
     def get_training_loss(self):
         loss, tb_dict, disp_dict = super().get_training_loss()
+        if getattr(self, 'point_head', None) is not None:
+            loss_point, tb_dict = self.point_head.get_loss(tb_dict)
+            loss = loss + loss_point
         if getattr(self, 'roi_head', None) is not None:
             loss_rcnn, tb_dict = self.roi_head.get_loss(tb_dict)
             loss = loss + loss_rcnn
