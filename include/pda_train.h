@@ -334,6 +334,13 @@ int pda_roipoint_pool3d_fwd(const float *xyz, const float *boxes3d, const float 
  * 0 / 1, every entry written; the host statement of the test: margin 1e-2, no FMA. */
 int pda_points_in_boxes_mask(const float *boxes, const float *pts, int32_t *mask, int boxes_num, int pts_num,
                              pda_stream_t stream);
+/* What SECONDNetIoU's num_pts_iou_cls score does on the CPU (points_in_boxes_cpu(...).sum(1) per scene), for the batch in
+ * one launch: points (N, stride) float32 rows [batch, x, y, z, ...] with stride >= 4, boxes (B, M, 7) -> counts (B, M) int32,
+ * every entry written, = the points of scene b that the test of pda_points_in_boxes_mask puts inside box (b, m).  A point
+ * whose batch value is outside [0, B) or not a number counts nowhere.  Integer sums: the result depends on no order.
+ * B <= 65535. */
+int pda_points_in_boxes_count(const float *points, int stride, const float *boxes, int32_t *counts, int pts_num,
+                              int batch_size, int boxes_num, pda_stream_t stream);
 /* The point-wise remainder of the IA-SSD head's target assignment (IASSD_head.py:132-277 after the two points_in_boxes
  * queries), one launch per point set: from in_box / in_ext (B, N) = index of the ground-truth box / enlarged box each point
  * lies in (-1: none) and gt_boxes (B, T, 8) [x y z dx dy dz heading class]:
@@ -1081,6 +1088,20 @@ int pda_bev_interpolate_fwd(const float *keypoints, const float *x_idxs, const f
                             int m, int b, int c, int h, int w, pda_stream_t stream);
 int pda_bev_interpolate_bwd(const float *keypoints, const float *x_idxs, const float *y_idxs, const float *grad_out,
                             float *grad_bev, int m, int b, int c, int h, int w, pda_stream_t stream);
+
+
+/* ---- SECONDHead.roi_grid_pool (second_head.py:53-110, csrc/bev_roi_pool.hip): affine_grid + grid_sample (bilinear, zero
+ * padding, align_corners=False) over the BEV map for every RoI of the batch in one launch.  bev (b, c, h, w), rois (b, r, 7)
+ * [x, y, z, dx, dy, dz, ry] -> out (b * r, c, g, g).  float32 throughout; with x1 = (x - dx/2 - min_x) / cell_x,
+ * x2 = (x + dx/2 - min_x) / cell_x (y likewise) theta is the reference's t0..t5 = (x2-x1)/(w-1) cos, (x2-x1)/(w-1) (-sin),
+ * (x1+x2-w+1)/(w-1), (y2-y1)/(h-1) sin, (y2-y1)/(h-1) cos, (y1+y2-h+1)/(h-1); for grid row i, column j: u = (2j+1)/g - 1,
+ * v = (2i+1)/g - 1, gx = t0 u + t1 v + t2, gy = t3 u + t4 v + t5, ix = ((gx+1) w - 1)/2, iy = ((gy+1) h - 1)/2, corners at
+ * floor and floor + 1 with weights from the unclamped position, a corner outside the map contributing nothing.  A position
+ * that is not finite or lies outside [-1, w) x [-1, h) reads nothing and gives 0 (csrc/bev_roi_grid.h).  cell_x / cell_y =
+ * VOXEL_SIZE * DOWNSAMPLE_RATIO.  g in 1..16, c >= 1, r <= 4096, b <= 65535, h and w >= 2; empty b or r returns at once.
+ * No backward: the reference detaches the map. */
+int pda_bev_roi_grid_pool(const float *bev, const float *rois, float *out, int b, int r, int c, int h, int w, int g,
+                          float min_x, float min_y, float cell_x, float cell_y, pda_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -145,6 +145,7 @@ SIGNATURES = {
     "pda_roiaware_pool3d_bwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "pda_roipoint_pool3d_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "pda_points_in_boxes_mask": [_vp, _vp, _vp, _i, _i, _vp],
+    "pda_points_in_boxes_count": [_vp, _i, _vp, _vp, _i, _i, _i, _vp],
     "pda_assign_point_targets": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "pda_sa_gaussian_mask": [_vp, _i, _i, _vp, _vp, _vp, ctypes.c_int64, _vp],
     "pda_head_assign_targets": [_vp, _i, _i, _vp, ctypes.POINTER(ctypes.c_float), _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
@@ -254,6 +255,7 @@ SIGNATURES = {
     "pda_stack_sa_bwd2": [_vp] * 14 + [_i] * 5 + [_vp],
     "pda_bev_interpolate_fwd": [_vp] * 5 + [_i] * 5 + [_vp],
     "pda_bev_interpolate_bwd": [_vp] * 5 + [_i] * 5 + [_vp],
+    "pda_bev_roi_grid_pool": [_vp] * 3 + [_i] * 6 + [_f] * 4 + [_vp],
     # include/pda_pointnet2_stack.h
     "pda_stack_ball_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     "pda_stack_group_points": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],

@@ -1,7 +1,8 @@
 // roi_pool.hip -- the RoI pooling operators of the two-stage heads (include/pda_train.h): roiaware_pool3d forward and
 // backward (roiaware_pool3d_kernel.cu:39-310), roipoint_pool3d forward (roipoint_pool3d_kernel.cu:38-165) and the
-// boxes x points mask of points_in_boxes_cpu (roiaware_pool3d.cpp:128-168).  Never reached by PDA-SSD; built so that the
-// reference's Part-A2 and PointRCNN heads bind to the same library.
+// boxes x points mask of points_in_boxes_cpu (roiaware_pool3d.cpp:128-168), and that mask's row sums for a whole batch without
+// the mask (SECONDNetIoU's num_pts_iou_cls score).  Never reached by PDA-SSD; built so that the reference's Part-A2,
+// PointRCNN and SECOND-IoU heads bind to the same library.
 //
 // The reference writes a boxes x points int mask to HBM, then lets ONE thread per box walk the whole scene.  Here a
 // workgroup owns a box and walks the scene in ascending 256-point tiles: every lane tests one point (box_rec.h, the
@@ -245,6 +246,12 @@ __global__ __launch_bounds__(256) void roipoint_pool_kernel(const float* __restr
 }
 
 // ---- points_in_boxes_cpu: the (boxes, points) mask, margin 1e-2, no FMA -----------------------------------------------------
+// the host statement of the test, shared by the mask and the count: the record of a box row and the predicate on it
+__device__ __forceinline__ BoxRec cpu_box_rec(const float* b) {
+    return make_box_rec(b[0], b[1], b[2], b[3], b[4], b[5], b[6], (double)1e-2f);
+}
+__device__ __forceinline__ bool in_cpu_box(const BoxRec& r, float x, float y, float z) { return in_box_rec<false>(r, x, y, z); }
+
 __global__ __launch_bounds__(256) void points_in_boxes_mask_kernel(const float* __restrict__ boxes,
                                                                    const float* __restrict__ pts, int* __restrict__ out,
                                                                    int boxes_num, int pts_num) {
@@ -257,14 +264,41 @@ __global__ __launch_bounds__(256) void points_in_boxes_mask_kernel(const float* 
         const int nk = min(256, boxes_num - k0);
         __syncthreads();
         if ((int)threadIdx.x < nk) {
-            const float* b = boxes + (size_t)(k0 + threadIdx.x) * 7;
-            const BoxRec r = make_box_rec(b[0], b[1], b[2], b[3], b[4], b[5], b[6], (double)1e-2f);
+            const BoxRec r = cpu_box_rec(boxes + (size_t)(k0 + threadIdx.x) * 7);
             rec[threadIdx.x] = r;
         }
         __syncthreads();
         if (live)
-            for (int k = 0; k < nk; ++k) out[(size_t)(k0 + k) * pts_num + pt] = in_box_rec<false>(rec[k], x, y, z) ? 1 : 0;
+            for (int k = 0; k < nk; ++k) out[(size_t)(k0 + k) * pts_num + pt] = in_cpu_box(rec[k], x, y, z) ? 1 : 0;
     }
+}
+
+// The points of its scene inside each box, counted: a workgroup owns one box of one scene and walks all the points in
+// 256-point tiles; a lane tests the point when its batch column names the scene, the hits are counted by ballot, and the
+// four waves' integers are added once at the end.  Integer sums only, no atomics, no mask.
+__global__ __launch_bounds__(256) void points_in_boxes_count_kernel(const float* __restrict__ pts, int stride,
+                                                                    const float* __restrict__ boxes, int* __restrict__ counts,
+                                                                    int pts_num, int boxes_num) {
+    __shared__ int wave_cnt[ROI_TILE / 64];
+    const int tid = threadIdx.x, lane = lane_id(), wave = wave_id();
+    const int scene = blockIdx.y;
+    const size_t box = (size_t)scene * boxes_num + blockIdx.x;
+    const BoxRec rec = cpu_box_rec(boxes + box * 7);
+    const float scene_f = (float)scene;
+    int cnt = 0;                                   // wave-uniform
+    for (int t0 = 0; t0 < pts_num; t0 += ROI_TILE) {
+        const int pt = t0 + tid;
+        bool hit = false;
+        if (pt < pts_num) {
+            const float* p = pts + (size_t)pt * stride;
+            const float bcol = p[0];
+            if (!is_nan_bits(bcol) && bcol == scene_f) hit = in_cpu_box(rec, p[1], p[2], p[3]);
+        }
+        cnt += __popcll(__ballot(hit));
+    }
+    if (lane == 0) wave_cnt[wave] = cnt;
+    __syncthreads();
+    if (tid == 0) counts[box] = (wave_cnt[0] + wave_cnt[1]) + (wave_cnt[2] + wave_cnt[3]);
 }
 
 inline int roi_group_log(int channels) {
@@ -359,4 +393,17 @@ PDA_API int pda_points_in_boxes_mask(const float* boxes, const float* pts, int32
     hipLaunchKernelGGL(pda::points_in_boxes_mask_kernel, dim3(pda::divup(pts_num, 256)), dim3(256), 0, (hipStream_t)stream,
                        boxes, pts, mask, boxes_num, pts_num);
     return pda::check_launch("pda_points_in_boxes_mask");
+}
+
+PDA_API int pda_points_in_boxes_count(const float* points, int stride, const float* boxes, int32_t* counts, int pts_num,
+                                      int batch_size, int boxes_num, pda_stream_t stream) {
+    PDA_REQUIRE(pts_num >= 0 && batch_size >= 0 && boxes_num >= 0 && stride >= 4,
+                "pda_points_in_boxes_count: bad size points=%d batch=%d boxes=%d stride=%d (>= 4)", pts_num, batch_size, boxes_num,
+                stride);
+    if (batch_size == 0 || boxes_num == 0) return PDA_OK;
+    PDA_REQUIRE(batch_size <= 65535, "pda_points_in_boxes_count: batch %d > 65535", batch_size);
+    PDA_REQUIRE((points || pts_num == 0) && boxes && counts, "pda_points_in_boxes_count: null pointer");
+    hipLaunchKernelGGL(pda::points_in_boxes_count_kernel, dim3(boxes_num, batch_size), dim3(256), 0, (hipStream_t)stream, points,
+                       stride, boxes, counts, pts_num, boxes_num);
+    return pda::check_launch("pda_points_in_boxes_count");
 }

@@ -103,6 +103,115 @@ def to_pred_and_recall_dicts(padded, thresh_list):
     return _split(padded, h[:B]), (recall_dict(h[B:], thresh_list) if B > 0 else {})
 
 
+IOU_SCORE_TYPES = ('iou', 'cls', 'weighted_iou_cls', 'num_pts_iou_cls', 'score_by_class')
+IOU_PRED_KEYS = ('pred_boxes', 'pred_scores', 'pred_labels', 'pred_cls_scores', 'pred_iou_scores')
+
+
+def scores_by_npoints(cls_scores, iou_scores, num_points, cls_thresh=10, iou_thresh=100):
+    """SECONDNetIoU.cal_scores_by_npoints (second_net_iou.py:37-57): the first-stage score up to cls_thresh points in the box,
+    the IoU score from iou_thresh on, and between them alpha = (n - 10) / (iou_thresh - cls_thresh) -- with the literal 10,
+    as the reference has it."""
+    assert iou_thresh >= cls_thresh
+    n = num_points.to(torch.float32)
+    alpha = (n >= iou_thresh).to(torch.float32)
+    if iou_thresh > cls_thresh:
+        between = (n > cls_thresh) & (n < iou_thresh)
+        alpha = torch.where(between, (n - 10) / (iou_thresh - cls_thresh), alpha)
+    return (1 - alpha) * cls_scores + alpha * iou_scores
+
+
+def nms_scores_by_class(iou_preds, cls_preds, label_preds, score_by_class, class_names):
+    """SECONDNetIoU.set_nms_score_by_class (:59-73) for (B, N) tensors without its host read: the reference loops i over
+    range(number of DISTINCT labels in the scene), so only classes i < that number receive a score and the others stay 0.
+    The number is counted on the device from the sorted labels."""
+    for name in class_names:
+        if score_by_class[name] not in ('iou', 'cls'):
+            raise NotImplementedError("SCORE_BY_CLASS[%r] = %r" % (name, score_by_class[name]))
+    nms_scores = torch.zeros_like(iou_preds, dtype=torch.float32)
+    if label_preds.shape[1] == 0:
+        return nms_scores
+    ordered = label_preds.sort(dim=1)[0]
+    n_classes = 1 + (ordered[:, 1:] != ordered[:, :-1]).sum(dim=1, keepdim=True)               # (B, 1)
+    for i, name in enumerate(class_names):
+        mask = (label_preds == (i + 1)) & (n_classes > i)
+        nms_scores = torch.where(mask, iou_preds if score_by_class[name] == 'iou' else cls_preds, nms_scores)
+    return nms_scores
+
+
+def post_processing_iou(batch_dict, post_process_cfg, num_class, class_names):
+    """SECONDNetIoU.post_processing (second_net_iou.py:75-177) for all scenes of a batch at once: batch_cls_preds
+    (B, N, 1 | num_class) is the IoU branch, roi_scores (B, N) the first stage's score, batch_box_preds (B, N, 7) the RoIs.
+    Both scores go through a sigmoid unless cls_preds_normalized; NMS_CONFIG.SCORE_TYPE picks what the NMS ranks by
+    ('iou', also when absent; 'cls'; 'weighted_iou_cls' with SCORE_WEIGHTS; 'num_pts_iou_cls' with SCORE_THRESH and the
+    batch's `points`, counted by roiaware_pool3d_utils.points_in_boxes_count; 'score_by_class' with SCORE_BY_CLASS).
+    Returns post_processing's padded tensors plus pred_cls_scores and pred_iou_scores (B, K) and nms_scores (B, N); recall,
+    when the batch carries gt_boxes, is counted on the RoIs -- all N rows of a scene, as the reference does when
+    batch_dict has 'rois' -- and padded['recall_on_rois'] says so.  No host read."""
+    nms_cfg = post_process_cfg['NMS_CONFIG']
+    if nms_cfg['MULTI_CLASSES_NMS']:
+        raise NotImplementedError("MULTI_CLASSES_NMS")
+    if post_process_cfg.get('OUTPUT_RAW_SCORE', False):
+        raise NotImplementedError("OUTPUT_RAW_SCORE")
+    B = batch_dict['batch_size']
+    box_preds = batch_dict['batch_box_preds'].view(B, -1, batch_dict['batch_box_preds'].shape[-1])
+    N = box_preds.shape[1]
+    iou_preds = batch_dict['batch_cls_preds'].view(B, N, -1)
+    cls_preds = batch_dict['roi_scores'].view(B, N)
+    assert iou_preds.shape[-1] in (1, num_class)
+    if not batch_dict['cls_preds_normalized']:
+        iou_preds = torch.sigmoid(iou_preds)
+        cls_preds = torch.sigmoid(cls_preds)
+    iou_preds, label_preds = torch.max(iou_preds, dim=-1)
+    label_preds = batch_dict['roi_labels'].view(B, N) if batch_dict.get('has_class_labels', False) else label_preds + 1
+
+    score_type = nms_cfg.get('SCORE_TYPE', None)
+    if nms_cfg.get('SCORE_BY_CLASS', None) and score_type == 'score_by_class':
+        nms_scores = nms_scores_by_class(iou_preds, cls_preds, label_preds, nms_cfg['SCORE_BY_CLASS'], class_names)
+    elif score_type == 'iou' or score_type is None:
+        nms_scores = iou_preds
+    elif score_type == 'cls':
+        nms_scores = cls_preds
+    elif score_type == 'weighted_iou_cls':
+        nms_scores = nms_cfg['SCORE_WEIGHTS']['iou'] * iou_preds + nms_cfg['SCORE_WEIGHTS']['cls'] * cls_preds
+    elif score_type == 'num_pts_iou_cls':
+        from .roiaware_pool3d_utils import points_in_boxes_count
+        counts = points_in_boxes_count(batch_dict['points'], box_preds[..., 0:7])
+        nms_scores = scores_by_npoints(cls_preds, iou_preds, counts, nms_cfg['SCORE_THRESH']['cls'], nms_cfg['SCORE_THRESH']['iou'])
+    else:
+        raise NotImplementedError("NMS_CONFIG.SCORE_TYPE %r (%s)" % (score_type, ", ".join(IOU_SCORE_TYPES)))
+
+    selected, sel_scores, num = class_agnostic_nms_batched(nms_scores, box_preds, nms_cfg, score_thresh=post_process_cfg["SCORE_THRESH"])
+    ok = selected >= 0
+    safe = selected.clamp(min=0)
+    pick = lambda x: torch.where(ok, torch.gather(x, 1, safe), torch.zeros_like(x[:, :safe.shape[1]]))
+    pred_boxes = torch.gather(box_preds, 1, safe.unsqueeze(-1).expand(-1, -1, box_preds.shape[-1])) * ok.unsqueeze(-1)
+    padded = {'pred_boxes': pred_boxes, 'pred_scores': sel_scores, 'pred_labels': pick(label_preds), 'num_pred': num,
+              'pred_cls_scores': pick(cls_preds), 'pred_iou_scores': pick(iou_preds), 'nms_scores': nms_scores}
+    if post_process_cfg.get('RECALL_MODE', 'normal') == 'normal' and 'gt_boxes' in batch_dict:
+        on_rois = 'rois' in batch_dict
+        boxes, rows = (box_preds, torch.full_like(num, N)) if on_rois else (pred_boxes, num)
+        padded['recall'] = recall_record(boxes.contiguous(), rows, batch_dict['gt_boxes'], post_process_cfg['RECALL_THRESH_LIST'])
+        padded['recall_on_rois'] = on_rois
+    return padded
+
+
+def to_iou_pred_and_recall_dicts(padded, thresh_list):
+    """SECONDNetIoU.post_processing's return value from post_processing_iou's tensors: pred dicts with the five keys of
+    IOU_PRED_KEYS, and the recall dict, in which roi_<t> equals rcnn_<t> when the recall was counted on the RoIs (the head's
+    boxes ARE its RoIs).  One host read for the batch."""
+    B = padded['num_pred'].shape[0]
+    has_recall = 'recall' in padded
+    h = (torch.cat([padded['num_pred'].to(torch.int64), padded['recall']]) if has_recall else padded['num_pred']).tolist()
+    preds = [{k: padded[k][s, :n] for k in IOU_PRED_KEYS} for s, n in enumerate(h[:B])]
+    if not has_recall or B == 0:
+        return preds, {}
+    ret = recall_dict(h[B:], thresh_list)
+    if padded.get('recall_on_rois', False):
+        for t in thresh_list:
+            ret['roi_%s' % str(t)] = ret['rcnn_%s' % str(t)]
+    return preds, ret
+
+
 def recall_dict(counts, thresh_list):
     """Host counters [gt, rcnn_<t>...] -> generate_recall_record's dict, in its key order (roi_* is 0: no rois)."""
     ret = {'gt': int(counts[0])}

@@ -54,6 +54,23 @@ class roiaware_pool3d_cuda:  # noqa: N801  (the reference's extension module nam
         return 1
 
 
+def points_in_boxes_count(points, boxes):
+    """MI355X extension (csrc/roi_pool.hip): what SECONDNetIoU's num_pts_iou_cls score does on the CPU in every scene
+    (points_in_boxes_cpu(...).sum(dim=1)), for the batch in one launch and without the boxes x points mask.
+    points (N, 1 + 3 + C) float32 [batch, x, y, z, ...] in any order, boxes (B, M, >= 7) float32 -> counts (B, M) int32 of
+    the points of scene b inside box (b, m), by the host statement of the test (margin 1e-2, no FMA).  A point whose batch
+    value is outside [0, B) counts nowhere."""
+    if points.dim() != 2 or points.shape[1] < 4 or boxes.dim() != 3 or boxes.shape[2] < 7:
+        raise ValueError("points must be (N, >= 4) and boxes (B, M, >= 7), got %s and %s" % (tuple(points.shape), tuple(boxes.shape)))
+    points = points.detach().contiguous()
+    boxes = boxes.detach()[..., :7].contiguous()
+    B, M = boxes.shape[0], boxes.shape[1]
+    counts = torch.zeros((B, M), dtype=I32, device=boxes.device)
+    _call("pda_points_in_boxes_count", boxes, _chk(points, "points", F32), int(points.shape[1]), _chk(boxes, "boxes", F32),
+          _chk(counts, "counts", I32), int(points.shape[0]), B, M)
+    return counts
+
+
 def points_in_boxes_gpu(points, boxes):
     """
     :param points: (B, M, 3)

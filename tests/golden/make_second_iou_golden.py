@@ -1,0 +1,453 @@
+#!/usr/bin/env python
+"""Generates tests/golden/second_iou.npz and tests/golden/second_iou_state_dict.json from the REFERENCE's own second_head.py
+and second_net_iou.py, imported from where they lie and run on the CPU.
+
+    python tests/golden/make_second_iou_golden.py <checkout of the reference>
+
+The extension modules are stubs: iou3d_nms_cuda.nms_gpu and boxes_overlap_bev_gpu are the repository's C oracle of the BEV
+overlap (oracle/), roiaware_pool3d_utils.points_in_boxes_cpu is roi_pool_restatement.points_in_boxes_cpu.
+torch.cuda.FloatTensor is pointed at the CPU constructor and Tensor.cuda() stays where it is.  Nothing of the reference is
+copied; what is committed is data.
+
+second_iou.npz
+  lat_*    roi_grid_pool on the lattice: B = 2, C = 5, H = 17, W = 9, G = 4, cell 1.0, heading 0, centres on multiples of 1/8,
+           sizes multiples of 1/2, integer features in [-8, 8]: every product and sum is exact in float32, and the generator
+           asserts that the reference's float32 run equals the float64 restatement bit for bit.
+  gen_*    roi_grid_pool in general position: B = 2, C = 6, H = 25, W = 22, G = 7, cell 0.4, headings in [-4, 4], unit-normal
+           features.
+  head_*   SECONDHead with IN_CHANNEL 8, GRID_SIZE 4, SHARED_FC / IOU_FC [16, 16], DP_RATIO 0 on given rois: parameters and
+           buffers, rcnn_iou in eval mode (before the step) and train mode, each of the three losses on given labels with
+           the gradient of every parameter, and the running statistics after the step.
+  post_*   SECONDNetIoU.post_processing on two scenes, the second holding labels {1, 3} only: for every score type the
+           nms_scores and the final boxes, scores, labels, cls and iou scores (zero-padded, with the counts), and the recall
+           dict.
+second_iou_state_dict.json: keys and shapes, in order, of the reference's SECONDHead for kitti_models/second_iou.yaml, and of
+the whole SECONDNetIoU on the settings of second_state_dict.json with the yaml's ROI_HEAD block.
+"""
+import copy
+import importlib.util
+import json
+import os
+import sys
+import types
+
+import numpy as np
+import torch
+import yaml
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+sys.path.insert(0, ROOT)
+import bev_roi_pool_restatement as bev_rs  # noqa: E402
+import roi_pool_restatement as roi_rs  # noqa: E402
+import oracle  # noqa: E402
+from pdanet_amd.config import to_attr  # noqa: E402
+
+F32, I32 = np.float32, np.int32
+
+
+def _package(name, path=None, **attrs):
+    pkg = types.ModuleType(name)
+    pkg.__path__ = [path] if path else []
+    pkg.__dict__.update(attrs)
+    sys.modules[name] = pkg
+    parent, _, leaf = name.rpartition(".")
+    if parent in sys.modules:
+        setattr(sys.modules[parent], leaf, pkg)
+    return pkg
+
+
+def _module(name, path):
+    spec = importlib.util.spec_from_file_location(name, path)
+    m = importlib.util.module_from_spec(spec)
+    sys.modules[name] = m
+    parent, _, leaf = name.rpartition(".")
+    setattr(sys.modules[parent], leaf, m)
+    spec.loader.exec_module(m)
+    return m
+
+
+def _overlap_bev(boxes_a, boxes_b, ans):
+    oracle.boxes_overlap_bev_gpu(boxes_a.numpy(), boxes_b.numpy(), ans.numpy())   # writes through to the tensor
+
+
+def _nms_gpu(boxes, keep, thresh):
+    return oracle.nms_gpu(np.ascontiguousarray(boxes.numpy()), keep.numpy(), float(thresh))
+
+
+def _points_in_boxes_cpu(points, boxes):
+    out = np.zeros((boxes.shape[0], points.shape[0]), I32)
+    roi_rs.points_in_boxes_cpu(boxes.numpy().astype(F32), points.numpy().astype(F32), out)
+    return torch.from_numpy(out)
+
+
+def load_reference(root):
+    """-> (second_head, second_net_iou) of the reference, as pcdet_ref.*"""
+    pcdet = os.path.join(root, "pcdet")
+    torch.cuda.FloatTensor = torch.FloatTensor
+    torch.Tensor.cuda = lambda self, *a, **k: self
+    sys.modules["SharedArray"] = types.ModuleType("SharedArray")
+    _package("pcdet_ref", pcdet)
+    _package("pcdet_ref.utils", None)
+    _package("pcdet_ref.utils.spconv_utils", None, find_all_spconv_keys=None)
+    _package("pcdet_ref.ops", None)
+    pib = types.ModuleType("roiaware_pool3d_utils")
+    pib.points_in_boxes_cpu = _points_in_boxes_cpu
+    _package("pcdet_ref.ops.roiaware_pool3d", None, roiaware_pool3d_utils=pib)
+    _package("pcdet_ref.ops.iou3d_nms", None)
+    _package("pcdet_ref.ops.iou3d_nms.iou3d_nms_cuda", None, boxes_overlap_bev_gpu=_overlap_bev, nms_gpu=_nms_gpu)
+    for name in ("common_utils", "box_utils", "loss_utils", "box_coder_utils"):
+        _module("pcdet_ref.utils." + name, os.path.join(pcdet, "utils", name + ".py"))
+    _module("pcdet_ref.ops.iou3d_nms.iou3d_nms_utils", os.path.join(pcdet, "ops", "iou3d_nms", "iou3d_nms_utils.py"))
+    _package("pcdet_ref.models", None)
+    for sub in ("backbones_2d", "backbones_3d", "dense_heads", "roi_heads", "model_utils", "detectors"):
+        _package("pcdet_ref.models." + sub, None)
+    _package("pcdet_ref.models.backbones_2d.map_to_bev", None)
+    _package("pcdet_ref.models.backbones_3d.pfe", None)
+    _package("pcdet_ref.models.backbones_3d.vfe", None)
+    _module("pcdet_ref.models.model_utils.model_nms_utils", os.path.join(pcdet, "models", "model_utils", "model_nms_utils.py"))
+    heads = os.path.join(pcdet, "models", "roi_heads")
+    _package("pcdet_ref.models.roi_heads.target_assigner", None)
+    _module("pcdet_ref.models.roi_heads.target_assigner.proposal_target_layer",
+            os.path.join(heads, "target_assigner", "proposal_target_layer.py"))
+    _module("pcdet_ref.models.roi_heads.roi_head_template", os.path.join(heads, "roi_head_template.py"))
+    head = _module("pcdet_ref.models.roi_heads.second_head", os.path.join(heads, "second_head.py"))
+    dets = os.path.join(pcdet, "models", "detectors")
+    _module("pcdet_ref.models.detectors.detector3d_template", os.path.join(dets, "detector3d_template.py"))
+    net = _module("pcdet_ref.models.detectors.second_net_iou", os.path.join(dets, "second_net_iou.py"))
+    return head, net
+
+
+def dataset_cfg(pcr, voxel):
+    return to_attr({'POINT_CLOUD_RANGE': pcr, 'DATA_PROCESSOR': [{'NAME': 'transform_points_to_voxels', 'VOXEL_SIZE': voxel}]})
+
+
+def head_cfg(in_channel, grid, ratio, shared=(256, 256), iou=(256, 256), dp=0.3):
+    return {'CLASS_AGNOSTIC': True, 'SHARED_FC': list(shared), 'IOU_FC': list(iou), 'DP_RATIO': dp,
+            'NMS_CONFIG': {'TRAIN': {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'NMS_PRE_MAXSIZE': 9000,
+                                     'NMS_POST_MAXSIZE': 512, 'NMS_THRESH': 0.8},
+                           'TEST': {'NMS_TYPE': 'nms_gpu', 'MULTI_CLASSES_NMS': False, 'NMS_PRE_MAXSIZE': 1024,
+                                    'NMS_POST_MAXSIZE': 100, 'NMS_THRESH': 0.7}},
+            'ROI_GRID_POOL': {'GRID_SIZE': grid, 'IN_CHANNEL': in_channel, 'DOWNSAMPLE_RATIO': ratio},
+            'TARGET_CONFIG': {'BOX_CODER': 'ResidualCoder', 'ROI_PER_IMAGE': 128, 'FG_RATIO': 0.5, 'SAMPLE_ROI_BY_EACH_CLASS': True,
+                              'CLS_SCORE_TYPE': 'roi_iou', 'CLS_FG_THRESH': 0.75, 'CLS_BG_THRESH': 0.25, 'CLS_BG_THRESH_LO': 0.1,
+                              'HARD_BG_RATIO': 0.8, 'REG_FG_THRESH': 0.55},
+            'LOSS_CONFIG': {'IOU_LOSS': 'BinaryCrossEntropy', 'LOSS_WEIGHTS': {'rcnn_iou_weight': 1.0, 'code_weights': [1.0] * 7}}}
+
+
+def reference_pool(head_mod, bev, rois, grid, pcr, voxel, ratio):
+    head = head_mod.SECONDHead(input_channels=bev.shape[1], model_cfg=to_attr(head_cfg(bev.shape[1], grid, ratio, (8,), (8,), 0.0)),
+                               num_class=1)
+    bd = {'batch_size': bev.shape[0], 'rois': torch.from_numpy(rois.copy()), 'spatial_features_2d': torch.from_numpy(bev.copy()),
+          'dataset_cfg': dataset_cfg(pcr, voxel)}
+    with torch.no_grad():
+        return head.roi_grid_pool(bd).numpy()
+
+
+# ---- the lattice case -------------------------------------------------------------------------------------------------------
+LAT = dict(B=2, C=5, H=17, W=9, G=4, pcr=[0.0, 0.0, -3.0, 9.0, 17.0, 1.0], voxel=[0.125, 0.125, 0.1], ratio=8)
+
+
+def lattice_rois():
+    """16 RoIs per scene, built row by row: [x, y, z, dx, dy, dz, 0] with centres on multiples of 1/8 and sizes multiples of
+    1/2.  The map covers x in [0, 9), y in [0, 17)."""
+    inside = [[4.0, 8.0, 0, 2.0, 3.0, 1.5], [3.125, 5.375, 0, 1.5, 2.5, 1.5], [5.5, 11.25, 0, 1.0, 1.0, 1.5], [4.25, 9.0, 0, 3.0, 6.0, 2],
+              [2.0, 3.0, 0, 0.5, 0.5, 1], [6.0, 13.875, 0, 2.5, 1.5, 1]]
+    cut = [[0.25, 8.0, 0, 2.0, 2.0, 1.5],      # left
+           [0.0, 4.5, 0, 1.5, 3.0, 1.5],       # left
+           [8.875, 8.0, 0, 2.0, 2.0, 1.5],     # right
+           [8.5, 12.125, 0, 3.0, 1.0, 1.5],    # right
+           [4.0, 0.25, 0, 2.0, 2.0, 1.5],      # top
+           [5.125, 0.0, 0, 1.0, 3.5, 1.5],     # top
+           [4.0, 16.875, 0, 2.0, 2.0, 1.5],    # bottom
+           [3.0, 16.5, 0, 1.5, 4.0, 1.5],      # bottom
+           [0.25, 0.25, 0, 2.0, 2.0, 1.5],     # the top left corner
+           [8.75, 16.75, 0, 2.5, 2.5, 1.5]]    # the bottom right corner
+    outside = [[-20.0, 8.0, 0, 2.0, 2.0, 1.5], [30.0, 8.0, 0, 2.0, 2.0, 1.5], [4.0, -20.0, 0, 2.0, 2.0, 1.5], [4.0, 40.0, 0, 2.0, 2.0, 1.5],
+               [-12.5, -12.5, 0, 4.0, 4.0, 1.5]]
+    rows = inside + cut + outside                                              # 21
+    rows += [[4.5, 8.5, 0, 8.0, 16.0, 2], [4.5, 8.5, 0, 12.0, 20.0, 2],         # the whole map; larger than the map
+             [1.0, 15.0, 0, 0.5, 1.0, 1], [7.875, 1.125, 0, 1.0, 0.5, 1], [4.5, 8.5, 0, 0.0, 0.0, 0],
+             [2.625, 7.75, 0, 3.5, 1.5, 1], [6.25, 4.0, 0, 1.0, 5.0, 1], [3.0, 12.0, 0, 2.0, 2.0, 1], [5.0, 6.0, 0, 1.5, 1.5, 1],
+             [4.5, 2.0, 0, 2.5, 0.5, 1]]                                       # 31
+    rois = np.zeros((32, 7), F32)                                              # the last row stays the all-zero padding row
+    rois[:len(rows), :6] = np.array(rows, F32)
+    assert len(rows) == 31 and np.all(rois[:, :2] * 8 == np.round(rois[:, :2] * 8)) and np.all(rois[:, 3:6] * 2 == np.round(rois[:, 3:6] * 2))
+    order = np.random.default_rng(7).permutation(31)
+    rois[:31] = rois[:31][order]
+    return rois.reshape(2, 16, 7)
+
+
+def lattice_part(head_mod, rng, out):
+    c = LAT
+    bev = rng.integers(-8, 9, (c['B'], c['C'], c['H'], c['W'])).astype(F32)
+    rois = lattice_rois()
+    got = reference_pool(head_mod, bev, rois, c['G'], c['pcr'], c['voxel'], c['ratio'])
+    cell = c['voxel'][0] * c['ratio']
+    want = bev_rs.roi_grid_pool(bev, rois, c['G'], c['pcr'][0], c['pcr'][1], cell, cell)
+    assert got.dtype == F32 and np.array_equal(got.astype(np.float64), want), "the float32 run is not exact on the lattice"
+    kinds = bev_rs.classify(rois, c['G'], c['H'], c['W'], c['pcr'][0], c['pcr'][1], cell, cell).reshape(-1)
+    print("lattice:", {k: int((kinds == k).sum()) for k in sorted(set(kinds))})
+    out.update(lat_bev=bev, lat_rois=rois, lat_out=got)
+
+
+# ---- the general case ---------------------------------------------------------------------------------------------------------
+GEN = dict(B=2, C=6, H=25, W=22, G=7, pcr=[0.0, -5.0, -3.0, 8.8, 5.0, 1.0], voxel=[0.05, 0.05, 0.1], ratio=8)
+
+
+def general_rois(rng, R=12):
+    rois = np.zeros((GEN['B'], R, 7), F32)
+    rois[..., 0] = rng.uniform(-0.5, 9.3, (GEN['B'], R))
+    rois[..., 1] = rng.uniform(-5.5, 5.5, (GEN['B'], R))
+    rois[..., 2] = rng.uniform(-1.5, 0.0, (GEN['B'], R))
+    rois[..., 3] = rng.uniform(0.6, 4.5, (GEN['B'], R))
+    rois[..., 4] = rng.uniform(0.5, 2.2, (GEN['B'], R))
+    rois[..., 5] = rng.uniform(1.4, 1.9, (GEN['B'], R))
+    rois[..., 6] = rng.uniform(-4.0, 4.0, (GEN['B'], R))
+    rois[1, -1] = 0                                                            # a zero-padded row
+    return rois
+
+
+def general_part(head_mod, rng, out):
+    c = GEN
+    bev = rng.standard_normal((c['B'], c['C'], c['H'], c['W'])).astype(F32)
+    rois = general_rois(rng)
+    got = reference_pool(head_mod, bev, rois, c['G'], c['pcr'], c['voxel'], c['ratio'])
+    cell = c['voxel'][0] * c['ratio']
+    want = bev_rs.roi_grid_pool(bev, rois, c['G'], c['pcr'][0], c['pcr'][1], cell, cell)
+    print("general: reference in float32 against the float64 restatement, max abs", float(np.abs(got - want).max()),
+          "max |out|", float(np.abs(want).max()), "zero share", float((want == 0).mean()))
+    out.update(gen_bev=bev, gen_rois=rois, gen_out=got)
+
+
+# ---- the head -----------------------------------------------------------------------------------------------------------------
+HEAD = dict(B=2, R=8, C=8, H=12, W=10, G=4, pcr=[0.0, -2.4, -3.0, 4.0, 2.4, 1.0], voxel=[0.05, 0.05, 0.1], ratio=8)
+
+
+def randomise(module, rng):
+    """BatchNorm weights, biases and running statistics away from their initial values, so that each of them matters."""
+    g = torch.Generator().manual_seed(int(rng.integers(1 << 30)))
+    for m in module.modules():
+        if isinstance(m, torch.nn.BatchNorm1d):
+            with torch.no_grad():
+                m.weight.copy_(torch.rand(m.weight.shape, generator=g) + 0.5)
+                m.bias.copy_(torch.randn(m.bias.shape, generator=g) * 0.2)
+                m.running_mean.copy_(torch.randn(m.bias.shape, generator=g) * 0.1)
+                m.running_var.copy_(torch.rand(m.bias.shape, generator=g) + 0.5)
+
+
+def head_part(head_mod, rng, out):
+    c = HEAD
+    cfg = head_cfg(c['C'], c['G'], c['ratio'], (16, 16), (16, 16), 0.0)
+    out["head_cfg"] = np.array(json.dumps(cfg))
+    bev = rng.standard_normal((c['B'], c['C'], c['H'], c['W'])).astype(F32)
+    rois = np.zeros((c['B'], c['R'], 7), F32)
+    rois[..., 0] = rng.uniform(0.3, 3.7, (c['B'], c['R']))
+    rois[..., 1] = rng.uniform(-2.0, 2.0, (c['B'], c['R']))
+    rois[..., 2] = -1.0
+    rois[..., 3] = rng.uniform(0.8, 2.5, (c['B'], c['R']))
+    rois[..., 4] = rng.uniform(0.5, 1.6, (c['B'], c['R']))
+    rois[..., 5] = 1.5
+    rois[..., 6] = rng.uniform(-3.1, 3.1, (c['B'], c['R']))
+    rois[1, -1] = 0
+    labels = rng.uniform(0, 1, (c['B'], c['R'])).astype(F32)
+    labels[0, 2] = 0.0
+    labels[1, 3] = 1.0
+    labels[0, 5] = labels[1, 6] = -1.0                                         # ignored rows
+    torch.manual_seed(21)
+    head = head_mod.SECONDHead(input_channels=c['C'], model_cfg=to_attr(copy.deepcopy(cfg)), num_class=1)
+    randomise(head, rng)
+    for k, v in head.state_dict().items():
+        out["head_sd." + k] = v.detach().numpy().copy()
+    out.update(head_bev=bev, head_rois=rois, head_labels=labels)
+
+    def batch():
+        return {'batch_size': c['B'], 'rois': torch.from_numpy(rois.copy()), 'roi_scores': torch.zeros(c['B'], c['R']),
+                'roi_labels': torch.ones(c['B'], c['R'], dtype=torch.long), 'spatial_features_2d': torch.from_numpy(bev.copy()),
+                'dataset_cfg': dataset_cfg(c['pcr'], c['voxel'])}
+
+    head.eval()
+    with torch.no_grad():
+        bd = head(batch())
+        assert bd['batch_box_preds'] is bd['rois'] and bd['cls_preds_normalized'] is False
+        out["head_rcnn_iou_eval"] = bd['batch_cls_preds'].numpy().copy()
+    head.train()
+    pooled = head.roi_grid_pool(batch())
+    assert not pooled.requires_grad
+    rcnn_iou = head.iou_layers(head.shared_fc_layer(pooled.view(pooled.shape[0], -1, 1))).transpose(1, 2).contiguous().squeeze(dim=1)
+    out["head_pooled"] = pooled.numpy().copy()
+    out["head_rcnn_iou_train"] = rcnn_iou.detach().numpy().copy()
+    names, params = zip(*head.named_parameters())
+    for loss_name in ('BinaryCrossEntropy', 'L2', 'smoothL1'):
+        head.model_cfg.LOSS_CONFIG.IOU_LOSS = loss_name
+        loss, tb = head.get_box_iou_layer_loss({'rcnn_iou': rcnn_iou, 'rcnn_cls_labels': torch.from_numpy(labels.copy())})
+        grads = torch.autograd.grad(loss, params, retain_graph=True)
+        out["head_loss." + loss_name] = np.float32(loss.item())
+        for n, g in zip(names, grads):
+            out["head_grad.%s.%s" % (loss_name, n)] = g.numpy().copy()
+        print("head:", loss_name, float(loss), tb)
+    for k, v in head.named_buffers():
+        out["head_after." + k] = v.detach().numpy().copy()
+
+
+# ---- post-processing ------------------------------------------------------------------------------------------------------------
+CLASS_NAMES = ['Car', 'Pedestrian', 'Cyclist']
+POST_BASE = {'RECALL_THRESH_LIST': [0.3, 0.5, 0.7], 'SCORE_THRESH': 0.3, 'OUTPUT_RAW_SCORE': False, 'EVAL_METRIC': 'kitti',
+             'NMS_CONFIG': {'MULTI_CLASSES_NMS': False, 'NMS_TYPE': 'nms_gpu', 'NMS_THRESH': 0.01, 'NMS_PRE_MAXSIZE': 4096,
+                            'NMS_POST_MAXSIZE': 500}}
+POST_VARIANTS = {
+    'default': {},
+    'iou': {'SCORE_TYPE': 'iou'},
+    'cls': {'SCORE_TYPE': 'cls'},
+    'weighted_iou_cls': {'SCORE_TYPE': 'weighted_iou_cls', 'SCORE_WEIGHTS': {'iou': 0.7, 'cls': 0.3}},
+    'num_pts_iou_cls': {'SCORE_TYPE': 'num_pts_iou_cls', 'SCORE_THRESH': {'cls': 10, 'iou': 40}},
+    'score_by_class': {'SCORE_TYPE': 'score_by_class', 'SCORE_BY_CLASS': {'Car': 'iou', 'Pedestrian': 'cls', 'Cyclist': 'iou'}},
+}
+DIMS = np.array([(3.9, 1.6, 1.56), (0.8, 0.6, 1.73), (1.76, 0.6, 1.73)])
+
+
+def post_inputs(rng):
+    B, N = 2, 24
+    rois = np.zeros((B, N, 7), F32)
+    labels = np.ones((B, N), np.int64)
+    points = []
+    for b in range(B):
+        # 16 sites on a 4 x 4 grid 7 m apart, the first 6 with a second box 0.3 m off; the last two rows stay zero padding
+        sites = np.stack(np.meshgrid(np.arange(4) * 7.0 + 5.0, np.arange(4) * 7.0 - 10.5, indexing='ij'), -1).reshape(-1, 2)
+        sites = sites[rng.permutation(16)]
+        allowed = np.array([1, 2, 3]) if b == 0 else np.array([1, 3])
+        for k in range(22):
+            site = sites[k] if k < 16 else sites[k - 16] + rng.uniform(0.2, 0.4, 2)
+            cls = int(rng.choice(allowed)) if k < 16 else int(labels[b, k - 16])
+            labels[b, k] = cls
+            rois[b, k] = np.concatenate([site + rng.uniform(-0.5, 0.5, 2), [rng.uniform(-1.2, -0.6)], DIMS[cls - 1] * rng.uniform(0.9, 1.1, 3),
+                                         [rng.uniform(-3.1, 3.1)]])
+            if k >= 16:
+                rois[b, k, 6] = rois[b, k - 16, 6] + rng.uniform(-0.1, 0.1)
+        # points: a cluster in every box (0, 4, 12, 25, 60 or 150 of them), kept inside by the 0.8 factor, and background
+        for k in range(22):
+            n = int(rng.choice([0, 4, 12, 25, 60, 150]))
+            local = rng.uniform(-0.4, 0.4, (n, 3)) * rois[b, k, 3:6]
+            ca, sa = np.cos(rois[b, k, 6]), np.sin(rois[b, k, 6])
+            xy = np.stack([local[:, 0] * ca - local[:, 1] * sa, local[:, 0] * sa + local[:, 1] * ca], 1) + rois[b, k, :2]
+            points.append(np.concatenate([np.full((n, 1), b), xy, local[:, 2:3] + rois[b, k, 2], rng.random((n, 1))], 1))
+        bg = np.concatenate([np.full((300, 1), b), rng.uniform([0, -14, -2], [30, 14, 0.5], (300, 3)), rng.random((300, 1))], 1)
+        points.append(bg)
+    points = np.concatenate(points).astype(F32)
+    points = points[rng.permutation(len(points))]
+    gt = np.zeros((B, 6, 8), F32)
+    for b in range(B):
+        for j in range(4):
+            k = 3 * j
+            gt[b, j, :7] = rois[b, k] + np.concatenate([rng.normal(0, 0.12, 3), rng.normal(0, 0.05, 3), [rng.normal(0, 0.05)]]).astype(F32)
+            gt[b, j, 7] = labels[b, k]
+    iou_logits = rng.normal(0.3, 1.5, (B, N, 1)).astype(F32)
+    cls_logits = rng.normal(0.5, 1.5, (B, N)).astype(F32)
+    return rois, labels, points, gt, iou_logits, cls_logits
+
+
+def post_part(net_mod, rng, out):
+    recorded = []
+    real_nms = net_mod.class_agnostic_nms
+
+    def recording_nms(box_scores, box_preds, nms_config, score_thresh=None):
+        recorded.append(box_scores.detach().numpy().copy())
+        return real_nms(box_scores=box_scores, box_preds=box_preds, nms_config=nms_config, score_thresh=score_thresh)
+
+    net_mod.class_agnostic_nms = recording_nms
+    for attempt in range(50):
+        rois, labels, points, gt, iou_logits, cls_logits = post_inputs(rng)
+        B, N = labels.shape
+        results, ok = {}, True
+        for name, extra in POST_VARIANTS.items():
+            cfg = copy.deepcopy(POST_BASE)
+            cfg['NMS_CONFIG'].update(extra)
+            model = net_mod.SECONDNetIoU.__new__(net_mod.SECONDNetIoU)
+            torch.nn.Module.__init__(model)
+            model.model_cfg, model.num_class, model.class_names = to_attr({'POST_PROCESSING': cfg}), 3, CLASS_NAMES
+            t = torch.from_numpy
+            bd = {'batch_size': B, 'batch_box_preds': t(rois.copy()), 'batch_cls_preds': t(iou_logits.copy()), 'roi_scores': t(cls_logits.copy()),
+                  'roi_labels': t(labels.copy()), 'rois': t(rois.copy()), 'has_class_labels': True, 'cls_preds_normalized': False,
+                  'points': t(points.copy()), 'gt_boxes': t(gt.copy())}
+            del recorded[:]
+            with torch.no_grad():
+                preds, recall = model.post_processing(bd)
+            nms_scores = np.stack(recorded)
+            # a decision within rounding of a threshold or a tie would make the fixture depend on the last bit of a sigmoid
+            live = np.sort(nms_scores[nms_scores > 0.05].ravel())
+            if np.abs(nms_scores - cfg['SCORE_THRESH']).min() < 1e-3 or (len(live) > 1 and np.diff(live).min() < 1e-6):
+                ok = False
+                break
+            results[name] = (cfg, nms_scores, preds, recall)
+        if ok:
+            break
+    assert ok, "no draw with clear decisions"
+    assert sorted(set(labels[1].tolist())) == [1, 3] and sorted(set(labels[0].tolist())) == [1, 2, 3]
+    out.update(post_rois=rois, post_labels=labels, post_points=points, post_gt=gt, post_iou_logits=iou_logits, post_cls_logits=cls_logits)
+    out["post_class_names"] = np.array(CLASS_NAMES)
+    for name, (cfg, nms_scores, preds, recall) in results.items():
+        K = max(len(p['pred_scores']) for p in preds)
+        pad = lambda key, shape, dtype: np.stack([np.concatenate([p[key].numpy().astype(dtype),
+                                                                  np.zeros((K - len(p[key]),) + shape, dtype)]) for p in preds])
+        out["post.%s.cfg" % name] = np.array(json.dumps(cfg))
+        out["post.%s.nms_scores" % name] = nms_scores
+        out["post.%s.num" % name] = np.array([len(p['pred_scores']) for p in preds], I32)
+        out["post.%s.pred_boxes" % name] = pad('pred_boxes', (7,), F32)
+        out["post.%s.pred_scores" % name] = pad('pred_scores', (), F32)
+        out["post.%s.pred_labels" % name] = pad('pred_labels', (), np.int64)
+        out["post.%s.pred_cls_scores" % name] = pad('pred_cls_scores', (), F32)
+        out["post.%s.pred_iou_scores" % name] = pad('pred_iou_scores', (), F32)
+        out["post.%s.recall_keys" % name] = np.array(list(recall.keys()), dtype='<U40')
+        out["post.%s.recall_vals" % name] = np.array([recall[k] for k in recall], np.int64)
+        print("post:", name, "kept", out["post.%s.num" % name].tolist(), recall)
+    cnt = np.zeros((B, N), I32)
+    for b in range(B):
+        m = np.zeros((N, int((points[:, 0] == b).sum())), I32)
+        roi_rs.points_in_boxes_cpu(rois[b], points[points[:, 0] == b, 1:4], m)
+        cnt[b] = m.sum(1)
+    out["post_point_counts"] = cnt
+    print("post: points per box", cnt.tolist())
+    net_mod.class_agnostic_nms = real_nms
+
+
+def shapes(module, prefix=""):
+    return [[prefix + k, list(v.shape)] for k, v in module.state_dict().items()]
+
+
+def state_dict_part(root, head_mod):
+    with open(os.path.join(root, "tools", "cfgs", "kitti_models", "second_iou.yaml")) as f:
+        model_yaml = yaml.safe_load(f)["MODEL"]
+    with open(os.path.join(HERE, "second_state_dict.json")) as f:
+        second = json.load(f)
+    roi_cfg = model_yaml["ROI_HEAD"]
+    head = head_mod.SECONDHead(input_channels=roi_cfg['ROI_GRID_POOL']['IN_CHANNEL'], model_cfg=to_attr(copy.deepcopy(roi_cfg)), num_class=1)
+    model_cfg = dict(second["config"]["MODEL"], NAME="SECONDNetIoU", ROI_HEAD=roi_cfg)
+    out = {"config": {"MODEL": model_cfg, "dataset": second["config"]["dataset"], "grid_size": second["config"]["grid_size"]},
+           "SECONDHead": shapes(head), "SECONDNetIoU": second["SECONDNet"] + shapes(head, "roi_head.")}
+    path = os.path.join(HERE, "second_iou_state_dict.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=0)
+    print(path, {k: len(v) for k, v in out.items()})
+
+
+def main():
+    root = sys.argv[1] if len(sys.argv) > 1 else os.environ.get("PDA_REFERENCE_ROOT")
+    if not root:
+        sys.exit(__doc__)
+    oracle.build()
+    head_mod, net_mod = load_reference(root)
+    rng = np.random.default_rng(2026)
+    out = {}
+    lattice_part(head_mod, rng, out)
+    general_part(head_mod, rng, out)
+    head_part(head_mod, rng, out)
+    post_part(net_mod, rng, out)
+    path = os.path.join(HERE, "second_iou.npz")
+    np.savez_compressed(path, **out)
+    print(path, os.path.getsize(path), "bytes")
+    state_dict_part(root, head_mod)
+
+
+if __name__ == "__main__":
+    main()
