@@ -44,6 +44,11 @@ int pda_bn_relu_fwd(const float *x, const float *gamma, const float *beta, float
 int pda_bn_relu_bwd(const float *x, const float *grad_y, const float *gamma, const float *beta,
                     const float *mean_invstd, float *grad_x, float *grad_gamma, float *grad_beta,
                     void *scratch, int64_t rows, int c, pda_stream_t stream);
+/* The reduction half of pda_bn_relu_bwd alone: grad_gamma, grad_beta and sums (2, C) = the per-channel means of the masked
+ * gradient and of its product with the normalised input, for a consumer that forms grad_x itself (pda_sa_point_grad_bn). */
+int pda_bn_relu_bwd_reduce(const float *x, const float *grad_y, const float *gamma, const float *beta,
+                           const float *mean_invstd, float *grad_gamma, float *grad_beta, float *sums, void *scratch,
+                           int64_t rows, int c, pda_stream_t stream);
 /* Dense-bf16 mode variants (same kernels and fp32 / double arithmetic): x may be the bf16 output of a GEMM, y may be
  * written as bf16 (when it only feeds the next GEMM), grad_y may be bf16; grad_x has the element type of x. */
 int pda_bn_relu_fwd_mixed(const void *x, int x_is_bf16, const float *gamma, const float *beta, float *running_mean,
@@ -450,6 +455,23 @@ int pda_sa_point_gather(const float *point_rows, const float *xyz, const float *
 int pda_sa_xyz_grad(const float *grad_z1, const float *xyz, const float *new_xyz, const int32_t *idx, const float *w, int ldw,
                     float *dw, int lddw, float *grad_new_xyz, void *scratch, int b, int n, int m, int nsample, int c1,
                     pda_stream_t stream);
+/* Training: pda_sa_point_gather (no bias, no ReLU; the same z bit for bit) that also emits the BatchNorm statistics of what it
+ * stores: partial [pda_sa_point_gather_stats_blocks(b*m*nsample, c1)][2][c1] doubles = per-channel sum and sum of squares per
+ * workgroup, fixed summation order; finish with pda_bn_finalize_fwd (count = b*m*nsample). */
+int64_t pda_sa_point_gather_stats_blocks(int64_t tokens, int c1);
+int pda_sa_point_gather_stats(const float *point_rows, const float *xyz, const float *new_xyz, const int32_t *idx,
+                              const float *w, int ldw, float *z, double *partial, int b, int n, int m, int nsample, int c1,
+                              pda_stream_t stream);
+/* The whole backward of that layer behind a training-mode BatchNorm + ReLU in one pass.  grad_a1 (b*m*nsample, c1): the gradient
+ * at relu(bn(z1)); z1, mean_invstd (2, c1), gamma, beta: the layer's forward; bwd_sums (2, c1): pda_bn_relu_bwd_reduce's.  The
+ * gradient at z1 is formed per element (pda_bn_relu_bwd's expression) and never written: it yields dw[:, 0:3] and grad_new_xyz
+ * (may be NULL) as pda_sa_xyz_grad does, and is scatter-added onto grad_points (b, n, c1) by idx -- the gradient of point_rows,
+ * cleared by this call (float atomics: the order of the additions to one point is not fixed).
+ * scratch: pda_sa_xyz_grad_scratch_bytes(c1).  c1 <= 1024. */
+int pda_sa_point_grad_bn(const float *grad_a1, const float *z1, const float *mean_invstd, const float *gamma,
+                         const float *beta, const float *bwd_sums, const float *xyz, const float *new_xyz, const int32_t *idx,
+                         const float *w, int ldw, float *dw, int lddw, float *grad_new_xyz, float *grad_points, void *scratch,
+                         int b, int n, int m, int nsample, int c1, pda_stream_t stream);
 
 /* ---- the input stage of the data loader (csrc/input_stage.hip; the reference's DataProcessor
  * mask_points_and_boxes_outside_range -> sample_points -> shuffle_points chain and collate_batch, on the device) ----------

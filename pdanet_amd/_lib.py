@@ -112,6 +112,7 @@ SIGNATURES = {
     "pda_bn_stats_fwd": [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _i, _f, _f, _vp],
     "pda_bn_finalize_fwd": [_vp, _i, _i, ctypes.c_int64, _f, _f, _vp, _vp, _vp, _vp],
     "pda_bn_relu_max_pool_apply": [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _i, _i, _vp],
+    "pda_bn_relu_bwd_reduce": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _i, _vp],
     "pda_colsum_scratch_bytes": [_i],
     "pda_colsum_bf16": [_vp, _vp, _vp, ctypes.c_int64, _i, _vp],
     "pda_assemble_tokens": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
@@ -165,6 +166,9 @@ SIGNATURES = {
     "pda_sa_xyz_grad_scratch_bytes": [_i],
     "pda_sa_point_gather": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "pda_sa_xyz_grad": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "pda_sa_point_gather_stats_blocks": [ctypes.c_int64, _i],
+    "pda_sa_point_gather_stats": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "pda_sa_point_grad_bn": [_vp] * 10 + [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "pda_adam_onecycle_step": [_vp, _vp, _vp, _vp, ctypes.c_int64, _f, _f, _f, _f, _f, _i, _vp, _f, _vp],
     "pda_input_stage_workspace_bytes": [_i, ctypes.c_int64],
     "pda_input_stage": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, ctypes.POINTER(_f), _i, _vp, _vp, _vp,
@@ -276,7 +280,8 @@ SIZE_QUERIES = [
     "pda_nms_mask_words", "pda_ball_query_cells_scratch_bytes", "pda_bn_relu_scratch_bytes",
     "pda_layer_norm_scratch_bytes", "pda_linear_wgrad_scratch_bytes", "pda_linear_split_packed_bytes",
     "pda_colsum_scratch_bytes", "pda_gemm_split_bn_tiles", "pda_densitynet_scratch_bytes",
-    "pda_sa_small_train_workspace_bytes", "pda_sa_xyz_grad_scratch_bytes", "pda_input_stage_workspace_bytes",
+    "pda_sa_small_train_workspace_bytes", "pda_sa_xyz_grad_scratch_bytes", "pda_sa_point_gather_stats_blocks",
+    "pda_input_stage_workspace_bytes",
     "pda_augment_workspace_bytes", "pda_augment_steps_workspace_bytes", "pda_once_eval_workspace_bytes",
     "pda_kitti_eval_workspace_bytes", "pda_kitti_fov_filter_workspace_bytes", "pda_gt_extract_workspace_bytes",
     "pda_voxel_workspace_bytes", "pda_dyn_voxel_workspace_bytes", "pda_center_focal_blocks", "pda_anchor_loss_blocks",

@@ -386,6 +386,26 @@ PDA_API int pda_bn_relu_bwd(const float* x, const float* grad_y, const float* ga
                                                  (hipStream_t)stream, "pda_bn_relu_bwd");
 }
 
+// The reduction half of pda_bn_relu_bwd alone: grad_gamma, grad_beta and sums (2, C) = the per-channel means that the gradient
+// expression needs, for a consumer that forms grad_x itself (pda_sa_point_grad_bn, csrc/sa_xyz_grad.hip).
+PDA_API int pda_bn_relu_bwd_reduce(const float* x, const float* grad_y, const float* gamma, const float* beta, const float* mean_invstd,
+                                   float* grad_gamma, float* grad_beta, float* sums, void* scratch, int64_t rows, int c,
+                                   pda_stream_t stream) {
+    const char* what = "pda_bn_relu_bwd_reduce";
+    pda::BnShape s;
+    if (int rc = pda::bn_shape(rows, c, s, what)) return rc;
+    PDA_REQUIRE(x && grad_y && gamma && beta && mean_invstd && grad_gamma && grad_beta && sums && scratch, "%s: null pointer", what);
+    PDA_REQUIRE(pda::bn_aligned(x) && pda::bn_aligned(grad_y) && (((uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)mean_invstd) & 15) == 0,
+                "%s: pointers must be 16-byte aligned", what);
+    const int grid = pda::bn_grid(s);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL((pda::bn_reduce_kernel<true, float, float>), dim3(grid), dim3(256), 0, st, x, grad_y, mean_invstd, gamma, beta,
+                       (double*)scratch, s);
+    hipLaunchKernelGGL(pda::bn_finalize_bwd_kernel, dim3(pda::divup(c, 32)), dim3(512), 0, st, (const double*)scratch, grid, c, s.count,
+                       grad_gamma, grad_beta, sums);
+    return pda::check_launch(what);
+}
+
 PDA_API int pda_bn_relu_fwd_weighted(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
                                      float* y, float* mean_invstd, void* scratch, int64_t rows, int c, float eps, float momentum,
                                      const float* row_weight, int64_t count, pda_stream_t stream) {

@@ -329,6 +329,17 @@ def bn_relu_bwd(x, grad_y, gamma, beta, mean_invstd, grad_x, grad_gamma, grad_be
     return 1
 
 
+def bn_relu_bwd_reduce(x, grad_y, gamma, beta, mean_invstd, grad_gamma, grad_beta, sums, scratch, rows, c):
+    """The reduction half of bn_relu_bwd alone (fp32): grad_gamma, grad_beta and sums (2, C), the per-channel means its gradient
+    expression needs; grad_x is left to the consumer (sa_point_grad_bn)."""
+    _numel_ok(x, rows * c, "x"); _numel_ok(grad_y, rows * c, "grad_y"); _numel_ok(sums, 2 * c, "sums")
+    _numel_ok(grad_gamma, c, "grad_gamma"); _numel_ok(grad_beta, c, "grad_beta"); _numel_ok(mean_invstd, 2 * c, "mean_invstd")
+    _call("pda_bn_relu_bwd_reduce", x, _chk(x, "x", F32), _chk(grad_y, "grad_y", F32), _chk(gamma, "gamma", F32), _chk(beta, "beta", F32),
+          _chk(mean_invstd, "mean_invstd", F32), _chk(grad_gamma, "grad_gamma", F32), _chk(grad_beta, "grad_beta", F32),
+          _chk(sums, "sums", F32), _chk(scratch, "scratch", torch.uint8), rows, c)
+    return 1
+
+
 def bn_relu_max_pool_fwd(x, gamma, beta, running_mean, running_var, out, arg, mean_invstd, scratch, groups, ns, c, eps, momentum):
     """MI355X extension: relu(bn(x)) (training mode) + max over the ns rows of each group, y never written (csrc/bn_relu.hip)."""
     _numel_ok(x, groups * ns * c, "x"); _numel_ok(out, groups * c, "out"); _numel_ok(arg, groups * c, "arg"); _numel_ok(mean_invstd, 2 * c, "mean_invstd")
@@ -908,4 +919,42 @@ def sa_point_gather(point_rows, xyz, new_xyz, idx, w, z, b, n, m, ns, c1, bias=N
     _call("pda_sa_point_gather", xyz, _chk(point_rows, "point_rows", F32), _chk(xyz, "xyz", F32), _chk(new_xyz, "new_xyz", F32),
           _chk(idx, "idx", I32), _chk(w, "w", F32), int(w.shape[1]), None if bias is None else _chk(bias, "bias", F32),
           1 if relu else 0, _chk(z, "z", F32), b, n, m, ns, c1)
+    return 1
+
+
+@functools.lru_cache(maxsize=None)
+def sa_point_gather_stats_blocks(tokens, c1):
+    return int(_lib.load().pda_sa_point_gather_stats_blocks(int(tokens), int(c1)))
+
+
+def sa_point_gather_stats(point_rows, xyz, new_xyz, idx, w, z, partial, b, n, m, ns, c1):
+    """sa_point_gather (training: no bias, no ReLU) that also writes the BatchNorm statistics of z per workgroup: partial
+    [sa_point_gather_stats_blocks(b*m*ns, c1)][2][c1] float64, the layout bn_finalize_fwd reads."""
+    _numel_ok(point_rows, b * n * c1, "point_rows"); _numel_ok(z, b * m * ns * c1, "z"); _numel_ok(idx, b * m * ns, "idx")
+    _numel_ok(xyz, b * n * 3, "xyz"); _numel_ok(new_xyz, b * m * 3, "new_xyz")
+    _numel_ok(partial, sa_point_gather_stats_blocks(b * m * ns, c1) * 2 * c1, "partial")
+    assert w.shape[0] == c1 and w.shape[1] >= 3
+    _call("pda_sa_point_gather_stats", xyz, _chk(point_rows, "point_rows", F32), _chk(xyz, "xyz", F32), _chk(new_xyz, "new_xyz", F32),
+          _chk(idx, "idx", I32), _chk(w, "w", F32), int(w.shape[1]), _chk(z, "z", F32), _chk(partial, "partial", torch.float64),
+          b, n, m, ns, c1)
+    return 1
+
+
+def sa_point_grad_bn(grad_a1, z1, mean_invstd, gamma, beta, bwd_sums, xyz, new_xyz, idx, w, dw, grad_new_xyz, grad_points, b, n, m, ns, c1):
+    """The backward of sa_point_gather behind a training-mode BatchNorm + ReLU in one pass (csrc/sa_xyz_grad.hip): from grad_a1, the
+    gradient at relu(bn(z1)), and bn_relu_bwd_reduce's bwd_sums: dw[:, 0:3], grad_new_xyz (b, m, 3; may be None) and grad_points
+    (b, n, c1) = the gradient at z1 scatter-added by idx (cleared by the call).  The gradient at z1 is never written."""
+    t = b * m * ns
+    _numel_ok(grad_a1, t * c1, "grad_a1"); _numel_ok(z1, t * c1, "z1"); _numel_ok(idx, t, "idx")
+    _numel_ok(mean_invstd, 2 * c1, "mean_invstd"); _numel_ok(gamma, c1, "gamma"); _numel_ok(beta, c1, "beta"); _numel_ok(bwd_sums, 2 * c1, "bwd_sums")
+    _numel_ok(xyz, b * n * 3, "xyz"); _numel_ok(new_xyz, b * m * 3, "new_xyz"); _numel_ok(grad_points, b * n * c1, "grad_points")
+    if grad_new_xyz is not None:
+        _numel_ok(grad_new_xyz, b * m * 3, "grad_new_xyz")
+    assert w.shape[0] == c1 and dw.shape == w.shape and w.shape[1] >= 3
+    scratch = torch.empty((sa_xyz_grad_scratch_bytes(c1),), dtype=torch.uint8, device=xyz.device)
+    _call("pda_sa_point_grad_bn", xyz, _chk(grad_a1, "grad_a1", F32), _chk(z1, "z1", F32), _chk(mean_invstd, "mean_invstd", F32),
+          _chk(gamma, "gamma", F32), _chk(beta, "beta", F32), _chk(bwd_sums, "bwd_sums", F32), _chk(xyz, "xyz", F32),
+          _chk(new_xyz, "new_xyz", F32), _chk(idx, "idx", I32), _chk(w, "w", F32), int(w.shape[1]), _chk(dw, "dw", F32), int(dw.shape[1]),
+          None if grad_new_xyz is None else _chk(grad_new_xyz, "grad_new_xyz", F32), _chk(grad_points, "grad_points", F32),
+          _chk(scratch, "scratch", torch.uint8), b, n, m, ns, c1)
     return 1

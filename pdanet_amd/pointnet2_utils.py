@@ -1302,6 +1302,11 @@ def sa_small_chain_train(xyz, new_xyz, feats_pm, idx, mlp):
 # 131072 x 512 x 512 against 0.10 ms, and was removed.)
 SA_WIDE_CHAIN = os.environ.get("PDA_SA_WIDE_CHAIN", "1") != "0"
 WIDE_CHAIN_DGRAD_FIRST = os.environ.get("PDA_WIDE_CHAIN_DGRAD_FIRST", "1") != "0"
+# SA_WIDE_FUSED_ENDS: the two ends of the chain without their re-reads of a (tokens, c1) tensor -- z1's statistics come out of the
+# gather that writes it (pda_sa_point_gather_stats) and layer 1's backward is one kernel that forms the gradient at z1 in registers
+# and never writes it (pda_sa_point_grad_bn).  0: the launches of before (statistics pass; BatchNorm-backward apply, sa_xyz_grad,
+# fill + group_rows_grad).
+SA_WIDE_FUSED_ENDS = os.environ.get("PDA_SA_WIDE_FUSED_ENDS", "1") != "0"
 SA_WIDE_CHAIN_MIN_TOKENS = int(os.environ.get("PDA_SA_WIDE_CHAIN_MIN_TOKENS", "32768"))   # (at 32768 tokens the 256 x 256 tiles take 50 us against lin_split's 35 and the passes saved are still worth more; at 16384 they are not)
 
 
@@ -1346,10 +1351,16 @@ class SaWideChainTrain(Function):
         # layer 1: per-point projection + row gather (SaPointLinear), then its statistics
         rows = _gemm_nt(feats_pm.view(B * N, C), w1d[:, 3:].contiguous())
         z1 = torch.empty((T, c1), dtype=torch.float32, device=dev)
-        pointnet2.sa_point_gather(rows, xyz, new_xyz, idx, w1d, z1, B, N, M, ns, c1)
         mi1 = torch.empty((2 * c1,), dtype=torch.float32, device=dev)
-        scratch = torch.empty((pointnet2.bn_relu_scratch_bytes(c1),), dtype=torch.uint8, device=dev)
-        pointnet2.bn_stats_fwd(z1, stats[0][0], stats[0][1], mi1, scratch, T, c1, bns[0].eps, bns[0].momentum)
+        if SA_WIDE_FUSED_ENDS:
+            nb1 = pointnet2.sa_point_gather_stats_blocks(T, c1)
+            part1 = torch.empty((nb1 * 2 * c1,), dtype=torch.float64, device=dev)
+            pointnet2.sa_point_gather_stats(rows, xyz, new_xyz, idx, w1d, z1, part1, B, N, M, ns, c1)
+            pointnet2.bn_finalize_fwd(part1, nb1, c1, T, bns[0].eps, bns[0].momentum, mi1, stats[0][0], stats[0][1])
+        else:
+            pointnet2.sa_point_gather(rows, xyz, new_xyz, idx, w1d, z1, B, N, M, ns, c1)
+            scratch = torch.empty((pointnet2.bn_relu_scratch_bytes(c1),), dtype=torch.uint8, device=dev)
+            pointnet2.bn_stats_fwd(z1, stats[0][0], stats[0][1], mi1, scratch, T, c1, bns[0].eps, bns[0].momentum)
         # layers 2 and 3: z = relu(bn(z_prev)) W^T with the statistics of z in the epilogue
         tiles = pointnet2.gemm_split_bn_tiles(T)
 
@@ -1387,8 +1398,10 @@ class SaWideChainTrain(Function):
             scratch = torch.empty((pointnet2.bn_relu_scratch_bytes(c3),), dtype=torch.uint8, device=dev)
             pointnet2.bn_relu_max_pool_bwd(z3, grad_out.contiguous().float(), arg, g3c, b3c, mi3, gz3, dg3, db3, scratch, B * M, ns, c3)
 
-            def layer(gz, w, z_in, mi_in, gi, bi, k_in, n_out):
-                """gz (T, n_out) = gradient at this layer's output z; returns (dW, gradient at z_in, dgamma_in, dbeta_in)."""
+            def layer(gz, w, z_in, mi_in, gi, bi, k_in, n_out, sums=None):
+                """gz (T, n_out) = gradient at this layer's output z; returns (dW, gradient at z_in, dgamma_in, dbeta_in).  With
+                `sums` (2, k_in) only the reduction half of the BatchNorm backward runs: the tensor returned is then the gradient
+                at relu(bn(z_in)) and `sums` holds what turns it into the gradient at z_in."""
                 dw = torch.empty((n_out, k_in), dtype=torch.float32, device=dev)
                 ga = torch.empty((T, k_in), dtype=torch.float32, device=dev)
                 if WIDE_CHAIN_DGRAD_FIRST:
@@ -1399,19 +1412,27 @@ class SaWideChainTrain(Function):
                     _lin_cols(gz, w, ga, T, n_out, k_in, True)
                 dg, db = torch.empty_like(gi), torch.empty_like(bi)
                 scratch = torch.empty((pointnet2.bn_relu_scratch_bytes(k_in),), dtype=torch.uint8, device=dev)
-                pointnet2.bn_relu_bwd(z_in, ga, gi, bi, mi_in, ga, dg, db, scratch, T, k_in)   # in place: a thread reads what it writes
+                if sums is not None:
+                    pointnet2.bn_relu_bwd_reduce(z_in, ga, gi, bi, mi_in, dg, db, sums, scratch, T, k_in)
+                else:
+                    pointnet2.bn_relu_bwd(z_in, ga, gi, bi, mi_in, ga, dg, db, scratch, T, k_in)   # in place: a thread reads what it writes
                 return dw, ga, dg, db
             dw3, gz2, dg2, db2 = layer(gz3, w3, z2, mi2, g2c, b2c, c2, c3)
             del gz3
-            dw2, gz1, dg1, db1 = layer(gz2, w2, z1, mi1, g1c, b1c, c1, c2)
+            sums1 = torch.empty((2 * c1,), dtype=torch.float32, device=dev) if SA_WIDE_FUSED_ENDS else None
+            dw2, gz1, dg1, db1 = layer(gz2, w2, z1, mi1, g1c, b1c, c1, c2, sums1)
             del gz2
             # layer 1 (SaPointLinear.backward): coordinate columns and centres, then the feature columns through the points
             w1c = w1.contiguous()
             dw1 = torch.empty_like(w1c)
             g_new = torch.empty_like(new_xyz) if ctx.needs_input_grad[1] else None
-            pointnet2.sa_xyz_grad(gz1, xyz, new_xyz, idx, w1c, dw1, g_new, B, N, M, ns, c1)
-            g_pts = torch.zeros((B, N, c1), dtype=torch.float32, device=dev)
-            pointnet2.group_rows_grad(B, N, c1, M * ns, gz1, idx, g_pts)
+            if SA_WIDE_FUSED_ENDS:
+                g_pts = torch.empty((B, N, c1), dtype=torch.float32, device=dev)
+                pointnet2.sa_point_grad_bn(gz1, z1, mi1, g1c, b1c, sums1, xyz, new_xyz, idx, w1c, dw1, g_new, g_pts, B, N, M, ns, c1)
+            else:
+                pointnet2.sa_xyz_grad(gz1, xyz, new_xyz, idx, w1c, dw1, g_new, B, N, M, ns, c1)
+                g_pts = torch.zeros((B, N, c1), dtype=torch.float32, device=dev)
+                pointnet2.group_rows_grad(B, N, c1, M * ns, gz1, idx, g_pts)
             g_pts = g_pts.view(B * N, c1)
             dw1[:, 3:] = _wgrad(feats_pm.view(B * N, C), g_pts, torch.empty((c1, C), dtype=torch.float32, device=dev), False)[0]
             g_feats = _gemm_nn(g_pts, w1c[:, 3:].contiguous()).view(B, N, C) if ctx.needs_input_grad[2] else None
