@@ -1125,6 +1125,22 @@ int pda_bev_interpolate_bwd(const float *keypoints, const float *x_idxs, const f
 int pda_bev_roi_grid_pool(const float *bev, const float *rois, float *out, int b, int r, int c, int h, int w, int g,
                           float min_x, float min_y, float cell_x, float cell_y, pda_stream_t stream);
 
+/* ---- PointRCNNHead.roipool3d_gpu (pointrcnn_head.py:85-130, csrc/roi_pool.hip): the RoI head's input in one launch.
+ * xyz (B,N,3), scores (B,N), feat (B,N,C), rois (B,M,7) NOT enlarged, extra: 3 host floats (POOL_EXTRA_WIDTH) ->
+ * pooled (B,M,S,5+C) and empty_flag (B,M) int32, both written in full (the caller fills nothing).
+ * Selection: the test and the slot order of pda_roipoint_pool3d_fwd on the RoI with extra[k] added to its three extents in
+ * float32 (box_utils.enlarge_box3d): the first S points inside in ascending index, slot k >= cnt repeating slot k % cnt.
+ * Row of slot k for point p: [x', y', z', scores[p], |xyz[p]| / depth_normalizer - 0.5, feat[p][0..C)] with
+ * (dx, dy, dz) = xyz[p] - roi[0:3], cosa = cosf(-roi[6]), sina = sinf(-roi[6]) taken once per RoI,
+ * x' = dx * cosa + dy * (-sina), y' = dx * sina + dy * cosa, z' = dz, |p| = sqrtf((x x + y y) + z z); float32, no FMA.
+ * A RoI that holds no point has empty_flag 1 and an all-zero block.  So has a row with a value that is not finite: it is
+ * recognised on its bit pattern and reaches neither the box test nor cosf / sinf.  points == 0 makes every RoI empty.
+ * S in 1..15360, B <= 65535, C >= 0; B == 0 or M == 0 returns at once and touches nothing.  No backward: the reference
+ * pools under no_grad.  Two runs give the same bits. */
+int pda_roipoint_pool3d_canonical_fwd(const float *xyz, const float *scores, const float *feat, const float *rois,
+                                      const float *extra, float depth_normalizer, float *pooled, int32_t *empty_flag,
+                                      int batch, int points, int boxes, int channels, int sampled, pda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

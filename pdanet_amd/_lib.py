@@ -260,6 +260,7 @@ SIGNATURES = {
     "pda_bev_interpolate_fwd": [_vp] * 5 + [_i] * 5 + [_vp],
     "pda_bev_interpolate_bwd": [_vp] * 5 + [_i] * 5 + [_vp],
     "pda_bev_roi_grid_pool": [_vp] * 3 + [_i] * 6 + [_f] * 4 + [_vp],
+    "pda_roipoint_pool3d_canonical_fwd": [_vp] * 4 + [ctypes.POINTER(_f), _f, _vp, _vp] + [_i] * 5 + [_vp],
     # include/pda_pointnet2_stack.h
     "pda_stack_ball_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     "pda_stack_group_points": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],

@@ -68,6 +68,57 @@ class PointResidual_BinOri_Coder(object):  # noqa: N801 (the yaml names the clas
         return torch.cat([centre, size, heading + within * (self.bin_inter / 2)], dim=-1)
 
 
+class PointResidualCoder(object):
+    """pcdet/utils/box_coder_utils.py:144-221, the coder of PointHeadBox: a box against the point that predicts it as
+    [(centre - point) / (d, d, h) | log(size / (l, w, h)) | cos heading | sin heading | extras], (l, w, h) the mean size of
+    the class and d = sqrt(l^2 + w^2); without mean sizes plain differences and log sizes."""
+
+    def __init__(self, code_size=8, use_mean_size=True, **kwargs):
+        self.code_size = code_size
+        self.use_mean_size = use_mean_size
+        self.mean_size = None
+        if use_mean_size:
+            self.mean_size = torch.tensor(kwargs['mean_size'], dtype=torch.float32)
+            assert self.mean_size.min() > 0
+
+    def _anchor(self, classes, like):
+        """The (N, 3) mean sizes of the 1-based classes, in `like`'s device and type."""
+        if self.mean_size.device != like.device:
+            self.mean_size = self.mean_size.to(like.device)
+        return self.mean_size.to(like.dtype)[classes - 1]
+
+    def encode_torch(self, gt_boxes, points, gt_classes=None):
+        """(N, 7 + C) boxes, (N, 3) points, (N) classes in [1, num_class] -> (N, 8 + C) codes.  The sizes are clamped to 1e-5 on
+        a copy: unlike the reference's (:162) this encode leaves its argument untouched."""
+        xg, yg, zg, dxg, dyg, dzg, rg, *cgs = torch.split(gt_boxes, 1, dim=-1)
+        dxg, dyg, dzg = (torch.clamp_min(v, min=1e-5) for v in (dxg, dyg, dzg))
+        xa, ya, za = torch.split(points, 1, dim=-1)
+        if self.use_mean_size:
+            dxa, dya, dza = torch.split(self._anchor(gt_classes, gt_boxes), 1, dim=-1)
+            diagonal = torch.sqrt(dxa ** 2 + dya ** 2)
+            xt, yt, zt = (xg - xa) / diagonal, (yg - ya) / diagonal, (zg - za) / dza
+            dxt, dyt, dzt = torch.log(dxg / dxa), torch.log(dyg / dya), torch.log(dzg / dza)
+        else:
+            xt, yt, zt = xg - xa, yg - ya, zg - za
+            dxt, dyt, dzt = torch.log(dxg), torch.log(dyg), torch.log(dzg)
+        return torch.cat([xt, yt, zt, dxt, dyt, dzt, torch.cos(rg), torch.sin(rg), *cgs], dim=-1)
+
+    def decode_torch(self, box_encodings, points, pred_classes=None):
+        """(N, 8 + C) codes, (N, 3) points, (N) classes in [1, num_class] -> (N, 7 + C) boxes."""
+        xt, yt, zt, dxt, dyt, dzt, cost, sint, *cts = torch.split(box_encodings, 1, dim=-1)
+        xa, ya, za = torch.split(points, 1, dim=-1)
+        if self.use_mean_size:
+            dxa, dya, dza = torch.split(self._anchor(pred_classes, box_encodings), 1, dim=-1)
+            diagonal = torch.sqrt(dxa ** 2 + dya ** 2)
+            xg, yg, zg = xt * diagonal + xa, yt * diagonal + ya, zt * dza + za
+            dxg, dyg, dzg = torch.exp(dxt) * dxa, torch.exp(dyt) * dya, torch.exp(dzt) * dza
+        else:
+            xg, yg, zg = xt + xa, yt + ya, zt + za
+            dxg, dyg, dzg = torch.exp(dxt), torch.exp(dyt), torch.exp(dzt)
+        rg = torch.atan2(sint, cost)
+        return torch.cat([xg, yg, zg, dxg, dyg, dzg, rg, *cts], dim=-1)
+
+
 class ResidualCoder(object):
     def __init__(self, code_size=7, encode_angle_by_sincos=False, **kwargs):
         self.code_size = code_size

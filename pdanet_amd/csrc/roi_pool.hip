@@ -1,8 +1,9 @@
 // roi_pool.hip -- the RoI pooling operators of the two-stage heads (include/pda_train.h): roiaware_pool3d forward and
 // backward (roiaware_pool3d_kernel.cu:39-310), roipoint_pool3d forward (roipoint_pool3d_kernel.cu:38-165) and the
 // boxes x points mask of points_in_boxes_cpu (roiaware_pool3d.cpp:128-168), and that mask's row sums for a whole batch without
-// the mask (SECONDNetIoU's num_pts_iou_cls score).  Never reached by PDA-SSD; built so that the reference's Part-A2,
-// PointRCNN and SECOND-IoU heads bind to the same library.
+// the mask (SECONDNetIoU's num_pts_iou_cls score), and PointRCNNHead's whole input stage in one launch (the pooling with the
+// canonical transformation, the score and depth columns and the zeroing of empty RoIs).  Never reached by PDA-SSD; built so
+// that the reference's Part-A2, PointRCNN and SECOND-IoU heads bind to the same library.
 //
 // The reference writes a boxes x points int mask to HBM, then lets ONE thread per box walk the whole scene.  Here a
 // workgroup owns a box and walks the scene in ascending 256-point tiles: every lane tests one point (box_rec.h, the
@@ -203,17 +204,12 @@ __global__ __launch_bounds__(256) void roiaware_max_grad_kernel(const int* __res
 }
 
 // ---- roipoint_pool3d -------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void roipoint_pool_kernel(const float* __restrict__ xyz, const float* __restrict__ boxes,
-                                                            const float* __restrict__ feat, float* __restrict__ pooled,
-                                                            int* __restrict__ empty_flag, int pts_num, int boxes_num,
-                                                            int channels, int n_sample) {
-    extern __shared__ __attribute__((aligned(16))) int picked[];           // n_sample point indices
-    __shared__ int wave_cnt[2][ROI_TILE / 64];
+// The walk both pooling kernels share: the scene in ascending 256-point tiles, every lane testing one point, the tile's hits
+// compacted in point order with ballots and a prefix over the four waves, until n_sample indices stand in picked[].
+// Returns the workgroup-uniform count (<= n_sample); the caller puts a barrier in front of its first read of picked[].
+__device__ __forceinline__ int roipoint_walk(const BoxRec& rec, const float* __restrict__ my_xyz, int pts_num, int n_sample,
+                                             int* picked, int (*wave_cnt)[ROI_TILE / 64]) {
     const int tid = threadIdx.x, lane = lane_id(), wave = wave_id();
-    const size_t scene = blockIdx.y, box = scene * boxes_num + blockIdx.x;
-    const float* b = boxes + box * 7;
-    const BoxRec rec = make_box_rec(b[0], b[1], b[2], b[3], b[4], b[5], b[6], (double)1e-5f);
-    const float* my_xyz = xyz + scene * pts_num * 3;
     int cnt = 0, it = 0;                           // workgroup-uniform
     for (int t0 = 0; t0 < pts_num && cnt < n_sample; t0 += ROI_TILE, it ^= 1) {
         const int pt = t0 + tid;
@@ -229,6 +225,21 @@ __global__ __launch_bounds__(256) void roipoint_pool_kernel(const float* __restr
         if (hit && pos < n_sample) picked[pos] = pt;
         cnt = min(cnt + n_hits, n_sample);
     }
+    return cnt;
+}
+
+__global__ __launch_bounds__(256) void roipoint_pool_kernel(const float* __restrict__ xyz, const float* __restrict__ boxes,
+                                                            const float* __restrict__ feat, float* __restrict__ pooled,
+                                                            int* __restrict__ empty_flag, int pts_num, int boxes_num,
+                                                            int channels, int n_sample) {
+    extern __shared__ __attribute__((aligned(16))) int picked[];           // n_sample point indices
+    __shared__ int wave_cnt[2][ROI_TILE / 64];
+    const int tid = threadIdx.x, lane = lane_id(), wave = wave_id();
+    const size_t scene = blockIdx.y, box = scene * boxes_num + blockIdx.x;
+    const float* b = boxes + box * 7;
+    const BoxRec rec = make_box_rec(b[0], b[1], b[2], b[3], b[4], b[5], b[6], (double)1e-5f);
+    const float* my_xyz = xyz + scene * pts_num * 3;
+    const int cnt = roipoint_walk(rec, my_xyz, pts_num, n_sample, picked, wave_cnt);
     __syncthreads();
     if (cnt == 0) {
         if (tid == 0) empty_flag[box] = 1;         // the rows stay as the caller filled them
@@ -242,6 +253,65 @@ __global__ __launch_bounds__(256) void roipoint_pool_kernel(const float* __restr
         float* row = rows + (size_t)k * width;
         for (int j = lane; j < width; j += 64)
             row[j] = j < 3 ? my_xyz[(size_t)p * 3 + j] : my_feat[(size_t)p * channels + (j - 3)];
+    }
+}
+
+__device__ __forceinline__ bool roi_finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+// PointRCNNHead.roipool3d_gpu (pointrcnn_head.py:85-130) in one launch: the same walk on the RoI enlarged here, then every
+// slot's row [canonical xyz | score | depth | features] written whole, consecutive lanes on consecutive floats.  An empty
+// RoI -- no point inside, or a row that is not finite, which never reaches the box test or cosf / sinf -- zeroes its own
+// block, so the output needs no fill.  Every flag is written.
+__global__ __launch_bounds__(256) void roipoint_pool_canonical_kernel(const float* __restrict__ xyz, const float* __restrict__ scores,
+                                                                      const float* __restrict__ feat, const float* __restrict__ rois,
+                                                                      float ex, float ey, float ez, float depth_normalizer,
+                                                                      float* __restrict__ pooled, int* __restrict__ empty_flag,
+                                                                      int pts_num, int boxes_num, int channels, int n_sample) {
+    extern __shared__ __attribute__((aligned(16))) int picked[];           // n_sample point indices
+    __shared__ int wave_cnt[2][ROI_TILE / 64];
+    const int tid = threadIdx.x, lane = lane_id(), wave = wave_id();
+    const size_t scene = blockIdx.y, box = scene * boxes_num + blockIdx.x;
+    const float* b = rois + box * 7;
+    float r[7];
+    bool sane = true;                              // workgroup-uniform: every lane reads the same row
+#pragma unroll
+    for (int k = 0; k < 7; ++k) { r[k] = b[k]; sane = sane && roi_finite_bits(r[k]); }
+    const int width = 5 + channels;
+    float* rows = pooled + box * n_sample * width;
+    const float* my_xyz = xyz + scene * pts_num * 3;
+    int cnt = 0;
+    if (sane) {
+        const BoxRec rec = make_box_rec(r[0], r[1], r[2], r[3] + ex, r[4] + ey, r[5] + ez, r[6], (double)1e-5f);
+        cnt = roipoint_walk(rec, my_xyz, pts_num, n_sample, picked, wave_cnt);
+    }
+    __syncthreads();
+    if (tid == 0) empty_flag[box] = cnt == 0 ? 1 : 0;
+    if (cnt == 0) {
+        const size_t total = (size_t)n_sample * width;
+        for (size_t e = tid; e < total; e += ROI_TILE) rows[e] = 0.f;
+        return;
+    }
+    const float cosa = cosf(-r[6]), sina = sinf(-r[6]);
+    const float* my_scores = scores + scene * pts_num;
+    const float* my_feat = feat + scene * pts_num * channels;
+    for (int k = wave; k < n_sample; k += ROI_TILE / 64) {
+        const int p = picked[k % cnt];             // slot k >= cnt repeats slot k % cnt
+        float* row = rows + (size_t)k * width;
+        for (int j = lane; j < width; j += 64) {
+            float v;
+            if (j < 5) {
+                const float x = my_xyz[(size_t)p * 3 + 0], y = my_xyz[(size_t)p * 3 + 1], z = my_xyz[(size_t)p * 3 + 2];
+                const float dx = x - r[0], dy = y - r[1];
+                if (j == 0) v = dx * cosa + dy * (-sina);
+                else if (j == 1) v = dx * sina + dy * cosa;
+                else if (j == 2) v = z - r[2];
+                else if (j == 3) v = my_scores[p];
+                else v = sqrtf((x * x + y * y) + z * z) / depth_normalizer - 0.5f;
+            } else {
+                v = my_feat[(size_t)p * channels + (j - 5)];
+            }
+            row[j] = v;
+        }
     }
 }
 
@@ -383,6 +453,24 @@ PDA_API int pda_roipoint_pool3d_fwd(const float* xyz, const float* boxes3d, cons
                        (size_t)sampled_pts_num * sizeof(int), (hipStream_t)stream, xyz, boxes3d, pts_feature, pooled_features,
                        pooled_empty_flag, pts_num, boxes_num, channels, sampled_pts_num);
     return pda::check_launch("pda_roipoint_pool3d_fwd");
+}
+
+PDA_API int pda_roipoint_pool3d_canonical_fwd(const float* xyz, const float* scores, const float* feat, const float* rois,
+                                              const float* extra, float depth_normalizer, float* pooled, int32_t* empty_flag,
+                                              int batch, int points, int boxes, int channels, int sampled, pda_stream_t stream) {
+    PDA_REQUIRE(batch >= 0 && points >= 0 && boxes >= 0 && channels >= 0 && sampled >= 1,
+                "pda_roipoint_pool3d_canonical_fwd: bad size batch=%d points=%d boxes=%d channels=%d sampled=%d", batch, points,
+                boxes, channels, sampled);
+    PDA_REQUIRE(sampled <= pda::ROIPOINT_MAX_S, "pda_roipoint_pool3d_canonical_fwd: %d sampled points do not fit the %d of LDS",
+                sampled, pda::ROIPOINT_MAX_S);
+    PDA_REQUIRE(batch <= 65535, "pda_roipoint_pool3d_canonical_fwd: batch %d > 65535", batch);
+    if (batch == 0 || boxes == 0) return PDA_OK;
+    PDA_REQUIRE(rois && extra && pooled && empty_flag && (points == 0 || (xyz && scores && (feat || channels == 0))),
+                "pda_roipoint_pool3d_canonical_fwd: null pointer");
+    hipLaunchKernelGGL(pda::roipoint_pool_canonical_kernel, dim3(boxes, batch), dim3(256), (size_t)sampled * sizeof(int),
+                       (hipStream_t)stream, xyz, scores, feat, rois, extra[0], extra[1], extra[2], depth_normalizer, pooled,
+                       empty_flag, points, boxes, channels, sampled);
+    return pda::check_launch("pda_roipoint_pool3d_canonical_fwd");
 }
 
 PDA_API int pda_points_in_boxes_mask(const float* boxes, const float* pts, int32_t* mask, int boxes_num, int pts_num,

@@ -18,6 +18,17 @@ from .pointpillar_scatter import PointPillarScatter
 from .voxel_utils import grid_size as _grid_size
 
 
+def optional_block(detector, key, table):
+    """The model config's block `key`, or None when it has none; a block the detector has no class for is refused."""
+    cfg = detector.model_cfg.get(key, None)
+    if cfg is None:
+        return None
+    if cfg['NAME'] not in table:
+        raise NotImplementedError("%s.NAME %r is not part of %s (%s)"
+                                  % (key, cfg['NAME'], type(detector).__name__, ", ".join(table) or "no such block"))
+    return cfg
+
+
 class PillarDetector(nn.Module):
     VFE = {}             # NAME -> class, the encoders and heads a detector accepts and builds
     DENSE_HEAD = {}
@@ -135,13 +146,7 @@ class VoxelDetector(PillarDetector):
 
     def _optional_block(self, key, table):
         """The model config's block `key`, or None when it has none; a block this detector has no class for is refused."""
-        cfg = self.model_cfg.get(key, None)
-        if cfg is None:
-            return None
-        if cfg['NAME'] not in table:
-            raise NotImplementedError("%s.NAME %r is not part of %s (%s)"
-                                      % (key, cfg['NAME'], type(self).__name__, ", ".join(table) or "no such block"))
-        return cfg
+        return optional_block(self, key, table)
 
     def get_training_loss(self):
         loss, tb_dict, disp_dict = super().get_training_loss()
@@ -152,3 +157,47 @@ class VoxelDetector(PillarDetector):
             loss_rcnn, tb_dict = self.roi_head.get_loss(tb_dict)
             loss = loss + loss_rcnn
         return loss, tb_dict, disp_dict
+
+
+class PointDetector(PillarDetector):
+    """The point-based family: backbone_3d over the raw points -> point_head -> roi_head, the reference's module order for
+    PointRCNN.  No voxels, no BEV map, no dense head; the constructor is its own, PillarDetector gives the forward.  The batch
+    carries `points` (N, 1 + 3 + C) [bs_idx, x, y, z, ...] ordered by scene with equally many rows per scene."""
+    BACKBONE_3D = {}     # NAME -> class
+    POINT_HEAD = {}
+    ROI_HEAD = {}        # a model config without ROI_HEAD builds the one-stage detector
+
+    def __init__(self, model_cfg, num_class, dataset):
+        nn.Module.__init__(self)
+        self.model_cfg, self.num_class = model_cfg, num_class
+        self.class_names = list(field(dataset, 'class_names'))
+        try:
+            n_feat = field(dataset, 'num_point_features')
+        except (KeyError, AttributeError):
+            n_feat = field(dataset, 'point_feature_encoder').num_point_features
+        for key, names in (('BACKBONE_3D', self.BACKBONE_3D), ('POINT_HEAD', self.POINT_HEAD)):
+            if model_cfg.get(key, None) is None:
+                raise ValueError("%s needs MODEL.%s" % (type(self).__name__, key))
+            if model_cfg[key]['NAME'] not in names:
+                raise NotImplementedError("%s.NAME %r is not part of %s (%s)"
+                                          % (key, model_cfg[key]['NAME'], type(self).__name__, ", ".join(names)))
+        b3d_cfg, point_cfg = model_cfg['BACKBONE_3D'], model_cfg['POINT_HEAD']
+        self.backbone_3d = self.BACKBONE_3D[b3d_cfg['NAME']](model_cfg=b3d_cfg, input_channels=n_feat)
+        n_point = self.backbone_3d.num_point_features
+        self.point_head = self.POINT_HEAD[point_cfg['NAME']](
+            model_cfg=point_cfg, input_channels=n_point, num_class=num_class if not point_cfg.get('CLASS_AGNOSTIC', False) else 1,
+            predict_boxes_when_training=model_cfg.get('ROI_HEAD', False))
+        self.module_list = [self.backbone_3d, self.point_head]
+        roi_cfg = optional_block(self, 'ROI_HEAD', self.ROI_HEAD)
+        if roi_cfg is not None:
+            self.roi_head = self.ROI_HEAD[roi_cfg['NAME']](
+                model_cfg=roi_cfg, input_channels=n_point, num_class=num_class if not roi_cfg.get('CLASS_AGNOSTIC', False) else 1)
+            self.module_list.append(self.roi_head)
+
+    def get_training_loss(self):
+        loss_point, tb_dict = self.point_head.get_loss()
+        loss = loss_point
+        if getattr(self, 'roi_head', None) is not None:
+            loss_rcnn, tb_dict = self.roi_head.get_loss(tb_dict)
+            loss = loss + loss_rcnn
+        return loss, tb_dict, {}

@@ -3,6 +3,7 @@
 Mirrors, by name, constructor signature, forward signature, return values and state-dict key
 layout, the classes of /root/reference/pcdet/ops/pointnet2/pointnet2_batch/:
   TransformerEncoderLayerPreNorm                  PointFormer.py:7-38
+  PointnetSAModuleMSG / PointnetSAModule          pointnet2_modules.py:47-128, :1756-1773  (PointRCNN's SA layers)
   PointnetSAModuleMSG_WithSampling                pointnet2_modules.py:1417-1686  (vanilla SA)
   PointnetSAModuleMSG_WithSampling_Ellipsoid      pointnet2_modules.py:541-954    (the PDA layer)
   DensityNet / PointConvDensitySetAbstraction     pointnet2_modules.py:958-1006
@@ -367,6 +368,79 @@ class _SAModuleBase(nn.Module):
         return pointnet2_utils.ball_query_multi([g.radius for g in self.groupers],
                                                 [g.nsample for g in self.groupers], xyz, new_xyz)
 
+    def _scale_features(self, xyz, new_xyz, features, pre_idxs=None):
+        """The scale loop of the vanilla SA layers: per scale [group -> MLP -> pool over nsample] through the fused,
+        recomputing or channels-last form its supported() rule accepts, else the reference's composition.  Returns the
+        per-scale (B, mlp[-1], npoint) tensors."""
+        new_features_list = []
+        plain_ball = (not self.dilated_group) and isinstance(self.groupers[0], pointnet2_utils.QueryAndGroup)
+        idxs = pre_idxs if (pre_idxs is not None and plain_ball) else \
+            (self._ball_queries(xyz, new_xyz) if plain_ball else [None] * len(self.groupers))
+        use_cl = CHANNELS_LAST and plain_ball and self.pool_method == 'max_pool' and \
+            getattr(self, "channels_last", True) and xyz.is_cuda
+        feats_pm = features.transpose(1, 2).contiguous() if (use_cl and features is not None) else None
+        for i in range(len(self.groupers)):
+            if self.fused is not None and plain_ball and self.pool_method == 'max_pool' \
+                    and not self.training and not torch.is_grad_enabled():
+                seq = list(self.mlps[i])
+                if (use_cl and feats_pm is not None and feats_pm.shape[-1] >= 128 and len(seq) == 9
+                        and all(_can_fold(seq[3 * k], seq[3 * k + 1]) for k in range(3))):
+                    # wide scale (layer 5): per-point first layer + split-bf16 GEMMs beat the fused f32-MFMA kernel
+                    g = pointnet2_utils.sa_wide_scale_infer(xyz, new_xyz, feats_pm, idxs[i],
+                                                            [_folded_conv_bn(seq[3 * k], seq[3 * k + 1]) for k in range(3)])
+                    if g is not None:
+                        new_features_list.append(g.transpose(1, 2))
+                        continue
+                pooled = self.fused(i, self, xyz, new_xyz, features, idxs[i])  # (B, mlp[-1], npoint) | None
+                if pooled is not None:
+                    new_features_list.append(pooled)
+                    continue
+            if use_cl and self.groupers[i].use_xyz:
+                if (self.training and torch.is_grad_enabled()
+                        and pointnet2_utils.SaSmallChainTrain.supported(xyz, new_xyz, feats_pm, idxs[i], self.mlps[i])):
+                    # narrow chains (layer 0): recompute passes over the neighbour lists, nothing grouped reaches HBM
+                    g = pointnet2_utils.sa_small_chain_train(xyz, new_xyz, feats_pm, idxs[i], self.mlps[i])
+                    new_features_list.append(g.transpose(1, 2))             # (B, mlp[-1], M) view
+                    continue
+                if (self.training and torch.is_grad_enabled()
+                        and pointnet2_utils.SaWideChainTrain.supported(xyz, new_xyz, feats_pm, idxs[i], self.mlps[i])):
+                    # wide chains (layer 5): BatchNorm statistics in the GEMM epilogues, normalisation in the operand loads
+                    g = pointnet2_utils.sa_wide_chain_train(xyz, new_xyz, feats_pm, idxs[i], self.mlps[i])
+                    new_features_list.append(g.transpose(1, 2))             # (B, mlp[-1], M) view
+                    continue
+                conv1 = self.mlps[i][0]
+                w1 = conv1.weight.flatten(1)
+                if (torch.is_grad_enabled() and isinstance(conv1, nn.Conv2d) and conv1.bias is None
+                        and pointnet2_utils.SaGatherLinear.supported(xyz, feats_pm, w1)):
+                    # the first contraction never sees a grouped (B, M, ns, 3 + C) tensor: per-point projection + row gather
+                    # (SaPointLinear), or the grouping fused into the contraction (SaGatherLinear)
+                    first = (pointnet2_utils.SaPointLinear if pointnet2_utils.SaPointLinear.supported(xyz, feats_pm, w1)
+                             else pointnet2_utils.SaGatherLinear)
+                    g = first.apply(xyz, new_xyz, feats_pm, idxs[i], w1)
+                    g = _mlp_lastdim(list(self.mlps[i])[1:], g, pool=True, mfma=True)
+                    new_features_list.append(g.transpose(1, 2))
+                    continue
+                # (B, M, ns, 3 + C): [xyz - centre | features], neighbours gathered as rows
+                g = pointnet2_utils.group_rows(xyz, idxs[i]) - new_xyz.unsqueeze(2)
+                if feats_pm is not None:
+                    g = torch.cat([g, pointnet2_utils.group_rows(feats_pm, idxs[i])], dim=-1)
+                g = _mlp_lastdim(self.mlps[i], g, pool=True, mfma=True)   # (B, M, mlp[-1]): MLP + max over nsample
+                new_features_list.append(g.transpose(1, 2))             # (B, mlp[-1], M) view
+                continue
+            if plain_ball:
+                new_features = self.groupers[i](xyz, new_xyz, features, idx=idxs[i])
+            else:
+                new_features = self.groupers[i](xyz, new_xyz, features)  # (B, C, npoint, nsample)
+            new_features = self.mlps[i](new_features)  # (B, mlp[-1], npoint, nsample)
+            if self.pool_method == 'max_pool':
+                new_features = F.max_pool2d(new_features, kernel_size=[1, new_features.size(3)])
+            elif self.pool_method == 'avg_pool':
+                new_features = F.avg_pool2d(new_features, kernel_size=[1, new_features.size(3)])
+            else:
+                raise NotImplementedError
+            new_features_list.append(new_features.squeeze(-1))  # (B, mlp[-1], npoint)
+        return new_features_list
+
 
 class PointnetSAModuleMSG_WithSampling(_SAModuleBase):
     """Vanilla SA layer with sampling + multi-scale grouping (pointnet2_modules.py:1417-1686):
@@ -429,73 +503,7 @@ class PointnetSAModuleMSG_WithSampling(_SAModuleBase):
             new_xyz = ctr_xyz
 
         if len(self.groupers) > 0:
-            new_features_list = []
-            plain_ball = (not self.dilated_group) and isinstance(self.groupers[0], pointnet2_utils.QueryAndGroup)
-            idxs = pre_idxs if (pre_idxs is not None and plain_ball) else \
-                (self._ball_queries(xyz, new_xyz) if plain_ball else [None] * len(self.groupers))
-            use_cl = CHANNELS_LAST and plain_ball and self.pool_method == 'max_pool' and \
-                getattr(self, "channels_last", True) and xyz.is_cuda
-            feats_pm = features.transpose(1, 2).contiguous() if (use_cl and features is not None) else None
-            for i in range(len(self.groupers)):
-                if self.fused is not None and plain_ball and self.pool_method == 'max_pool' \
-                        and not self.training and not torch.is_grad_enabled():
-                    seq = list(self.mlps[i])
-                    if (use_cl and feats_pm is not None and feats_pm.shape[-1] >= 128 and len(seq) == 9
-                            and all(_can_fold(seq[3 * k], seq[3 * k + 1]) for k in range(3))):
-                        # wide scale (layer 5): per-point first layer + split-bf16 GEMMs beat the fused f32-MFMA kernel
-                        g = pointnet2_utils.sa_wide_scale_infer(xyz, new_xyz, feats_pm, idxs[i],
-                                                                [_folded_conv_bn(seq[3 * k], seq[3 * k + 1]) for k in range(3)])
-                        if g is not None:
-                            new_features_list.append(g.transpose(1, 2))
-                            continue
-                    pooled = self.fused(i, self, xyz, new_xyz, features, idxs[i])  # (B, mlp[-1], npoint) | None
-                    if pooled is not None:
-                        new_features_list.append(pooled)
-                        continue
-                if use_cl and self.groupers[i].use_xyz:
-                    if (self.training and torch.is_grad_enabled()
-                            and pointnet2_utils.SaSmallChainTrain.supported(xyz, new_xyz, feats_pm, idxs[i], self.mlps[i])):
-                        # narrow chains (layer 0): recompute passes over the neighbour lists, nothing grouped reaches HBM
-                        g = pointnet2_utils.sa_small_chain_train(xyz, new_xyz, feats_pm, idxs[i], self.mlps[i])
-                        new_features_list.append(g.transpose(1, 2))             # (B, mlp[-1], M) view
-                        continue
-                    if (self.training and torch.is_grad_enabled()
-                            and pointnet2_utils.SaWideChainTrain.supported(xyz, new_xyz, feats_pm, idxs[i], self.mlps[i])):
-                        # wide chains (layer 5): BatchNorm statistics in the GEMM epilogues, normalisation in the operand loads
-                        g = pointnet2_utils.sa_wide_chain_train(xyz, new_xyz, feats_pm, idxs[i], self.mlps[i])
-                        new_features_list.append(g.transpose(1, 2))             # (B, mlp[-1], M) view
-                        continue
-                    conv1 = self.mlps[i][0]
-                    w1 = conv1.weight.flatten(1)
-                    if (torch.is_grad_enabled() and isinstance(conv1, nn.Conv2d) and conv1.bias is None
-                            and pointnet2_utils.SaGatherLinear.supported(xyz, feats_pm, w1)):
-                        # the first contraction never sees a grouped (B, M, ns, 3 + C) tensor: per-point projection + row gather
-                        # (SaPointLinear), or the grouping fused into the contraction (SaGatherLinear)
-                        first = (pointnet2_utils.SaPointLinear if pointnet2_utils.SaPointLinear.supported(xyz, feats_pm, w1)
-                                 else pointnet2_utils.SaGatherLinear)
-                        g = first.apply(xyz, new_xyz, feats_pm, idxs[i], w1)
-                        g = _mlp_lastdim(list(self.mlps[i])[1:], g, pool=True, mfma=True)
-                        new_features_list.append(g.transpose(1, 2))
-                        continue
-                    # (B, M, ns, 3 + C): [xyz - centre | features], neighbours gathered as rows
-                    g = pointnet2_utils.group_rows(xyz, idxs[i]) - new_xyz.unsqueeze(2)
-                    if feats_pm is not None:
-                        g = torch.cat([g, pointnet2_utils.group_rows(feats_pm, idxs[i])], dim=-1)
-                    g = _mlp_lastdim(self.mlps[i], g, pool=True, mfma=True)   # (B, M, mlp[-1]): MLP + max over nsample
-                    new_features_list.append(g.transpose(1, 2))             # (B, mlp[-1], M) view
-                    continue
-                if plain_ball:
-                    new_features = self.groupers[i](xyz, new_xyz, features, idx=idxs[i])
-                else:
-                    new_features = self.groupers[i](xyz, new_xyz, features)  # (B, C, npoint, nsample)
-                new_features = self.mlps[i](new_features)  # (B, mlp[-1], npoint, nsample)
-                if self.pool_method == 'max_pool':
-                    new_features = F.max_pool2d(new_features, kernel_size=[1, new_features.size(3)])
-                elif self.pool_method == 'avg_pool':
-                    new_features = F.avg_pool2d(new_features, kernel_size=[1, new_features.size(3)])
-                else:
-                    raise NotImplementedError
-                new_features_list.append(new_features.squeeze(-1))  # (B, mlp[-1], npoint)
+            new_features_list = self._scale_features(xyz, new_xyz, features, pre_idxs)
             new_features = torch.cat(new_features_list, dim=1)
             if self.aggregation_layer is not None:
                 new_features = self.aggregation_layer(new_features)
@@ -515,6 +523,50 @@ class PointnetSAModuleMSG_WithSampling(_SAModuleBase):
         if self.dilated_group or len(self.groupers) == 0 or not isinstance(self.groupers[0], pointnet2_utils.QueryAndGroup):
             return None
         return {'idxs': self._ball_queries(xyz, new_xyz), 'parts': None, 'totals': None}
+
+
+class PointnetSAModuleMSG(_SAModuleBase):
+    """Set abstraction with multi-scale grouping (pointnet2_modules.py:86-128 over _PointnetSAModuleBase.forward, :47-83):
+    D-FPS to npoint (GroupAll when npoint is None) -> per scale [QueryAndGroup -> (Conv2d 1x1 no bias, BN2d, ReLU)*k -> max or
+    average over nsample] -> concat.  `bn` is accepted and ignored, as in the reference: every layer has its BatchNorm."""
+
+    def __init__(self, *, npoint: int, radii: List[float], nsamples: List[int], mlps: List[List[int]], bn: bool = True,
+                 use_xyz: bool = True, pool_method='max_pool'):
+        super().__init__()
+        assert len(radii) == len(nsamples) == len(mlps)
+        self.npoint = npoint
+        self.dilated_group = False
+        self.groupers = nn.ModuleList()
+        self.mlps = nn.ModuleList()
+        for i in range(len(radii)):
+            self.groupers.append(pointnet2_utils.QueryAndGroup(radii[i], nsamples[i], use_xyz=use_xyz)
+                                 if npoint is not None else pointnet2_utils.GroupAll(use_xyz))
+            mlp_spec = list(mlps[i])               # (the reference adds the 3 into its caller's list, :116)
+            if use_xyz:
+                mlp_spec[0] += 3
+            shared_mlps = []
+            for k in range(len(mlp_spec) - 1):
+                shared_mlps.extend([nn.Conv2d(mlp_spec[k], mlp_spec[k + 1], kernel_size=1, bias=False),
+                                    nn.BatchNorm2d(mlp_spec[k + 1]), nn.ReLU()])
+            self.mlps.append(nn.Sequential(*shared_mlps))
+        self.pool_method = pool_method
+        self.fused = None  # as PointnetSAModuleMSG_WithSampling.fused
+
+    def forward(self, xyz: torch.Tensor, features: torch.Tensor = None, new_xyz=None):
+        """xyz (B,N,3), features (B,C,N) -> new_xyz (B,npoint,3) | None, new_features (B, sum mlps[k][-1], npoint | 1)."""
+        if new_xyz is None and self.npoint is not None:
+            idx = pointnet2_utils.furthest_point_sample(xyz.contiguous(), self.npoint)
+            new_xyz = pointnet2_utils.gather_operation(xyz.transpose(1, 2).contiguous(), idx).transpose(1, 2).contiguous()
+        return new_xyz, torch.cat(self._scale_features(xyz, new_xyz, features), dim=1)
+
+
+class PointnetSAModule(PointnetSAModuleMSG):
+    """Single-scale set abstraction (pointnet2_modules.py:1756-1773)."""
+
+    def __init__(self, *, mlp: List[int], npoint: int = None, radius: float = None, nsample: int = None, bn: bool = True,
+                 use_xyz: bool = True, pool_method='max_pool'):
+        super().__init__(mlps=[mlp], npoint=npoint, radii=[radius], nsamples=[nsample], bn=bn, use_xyz=use_xyz,
+                         pool_method=pool_method)
 
 
 class DensityNet(nn.Module):
