@@ -557,6 +557,8 @@ int pda_augment_paste(const float *points, const int64_t *offsets, int64_t n_tot
  *   0 flip_x, 1 flip_y, 2 world rotation, 3 world scaling, 4 world translation (arg: axis 0..2), 5 world frustum dropout
  *   (arg: 0 top, 1 bottom, 2 left, 3 right; at most 4 such ops), 6 local translation (arg: axis), 7 local rotation,
  *   8 local scaling, 9 local frustum dropout (arg: direction).
+ *   10 hold (arg 0), as the LAST op only: it is one of the n_ops <= 32 ops, but no step and no column of scene_draws
+ *   (which is (batch, n_ops - 1) then); the boxes leave with their headings as they are and class 0 kept, for pda_pyramid_aug behind it.
  * scene_draws (batch, n_ops) float64 on the device: the scene's draw of op i (flip 0 / 1, angle with 0 = off, scale with
  *   1 = off, translation offset, dropout intensity; unused for local ops).  box_draws (batch, n_local, draw_cap) float64:
  *   row l belongs to the l-th local op (codes 6..9) of the program; draw j of a row belongs to the j-th box alive at
@@ -575,6 +577,45 @@ int pda_augment_steps(const float *points, const int64_t *offsets, int64_t n_tot
                       const double *scene_draws, const double *box_draws, int draw_cap, int box_slots,
                       const int32_t *info_in, float *out_points, int64_t out_cap, int64_t *out_offsets, float *out_boxes,
                       int64_t out_box_cap, int64_t *out_box_offsets, int32_t *info, void *workspace, pda_stream_t stream);
+
+/* ---- random_local_pyramid_aug (csrc/augment_steps.hip; the reference's local_pyramid_dropout -> local_pyramid_sparsify ->
+ * local_pyramid_swap of augmentor_utils.py, then limit_period and prepare_data's class filter) ---------------------------
+ * Scenes and boxes as pda_augment_steps leaves them behind a hold op: boxes (m_total, 8), class 0 takes part and is
+ * dropped at the end; boxes are never changed.  C >= 4: the swap rescales the LAST column.  A box is six pyramids (apex the
+ * centre, base a face: 0 +x, 1 +z, 2 -x, 3 -z, 4 -y, 5 +y in the box frame); a point is in the pyramid of the largest of
+ * |lx / (dx / 2)|, |ly / (dy / 2)|, |sz / (dz / 2)| when all are <= 1 (get_points_in_box's rotation, no margin).
+ * Draws (device), draw_cap <= 256 columns a row, n_draws (batch, 3) int32 the draws present in the dropout / sparsify /
+ * swap rows of a scene:
+ *   draws_f64 (batch, 5, draw_cap): dropout u, sparsify u, swap u, swap face u, swap partner u (the last two in [0, 1)).
+ *   draws_i32 (batch, 4, draw_cap): dropout face, sparsify face (0..5), explicit swap face or -1, explicit swap partner
+ *     (an index among the boxes in front of the swap) or -1.
+ *   sparsify_key (batch, draw_cap) uint64; sparsify_keep (batch, draw_cap, 1 + sparsify_max) int32 or NULL: [length,
+ *     ranks...], length 0 = use the key.
+ * Draw j of the dropout row belongs to box j; of the sparsify row to the j-th box not dropped; of the swap rows to the j-th
+ * box neither dropped nor selected by the sparsify.  probs (HOST) double[3] = DROP_PROB, SPARSIFY_PROB, SWAP_PROB (u <= p
+ * selects).  A dropped box loses the points of its drawn pyramid.  A sparsify-selected pyramid with more than
+ * sparsify_max points (counted after the dropout, ranked in scene order) keeps the ranks of its keep list, or rank r iff
+ * keyed_bijection(key, count, r) < sparsify_max; a point is thinned away iff it lies in a thinned pyramid and none that
+ * holds it keeps it.  A swap-selected box takes face floor(u * k) of its k faces with count > swap_max (counts and
+ * min / max of the last column on the survivors), then partner floor(u * k) of the k boxes left whose same face has
+ * count > swap_max and is no to-swap pyramid, or itself without one; the points of both pyramids change places by their
+ * ratios in the pyramid frames, the last column rescaled to the other pyramid's range.  Pairs act in ascending box order:
+ * a self pair and a pair whose partner pyramid an earlier pair holds do nothing, a point in pyramids of several pairs is
+ * moved by the first.  A scene never grows.
+ * Status bit 16: a row with fewer draws than boxes, a face outside 0..5, a keep list of the wrong length or with a
+ * repeated or out-of-range rank, an explicit face without count > swap_max, an explicit partner that is no candidate
+ * (without candidates: not the box itself); the scene is written empty.  Output, info, info_in, capacities and the other
+ * status bits as for pda_augment_steps; points come out in scene order.
+ * workspace: pda_pyramid_aug_workspace_bytes(batch, n_cap, box_slots) bytes, 256-byte aligned (-1: bad sizes).  Seven
+ * launches, no allocation, no host synchronisation. */
+int64_t pda_pyramid_aug_workspace_bytes(int batch, int64_t n_cap, int box_slots);
+int pda_pyramid_aug(const float *points, const int64_t *offsets, int64_t n_total, int batch, int c, int64_t n_cap,
+                    const float *boxes, const int64_t *box_offsets, int64_t m_total, const double *draws_f64,
+                    const int32_t *draws_i32, const uint64_t *sparsify_key, const int32_t *sparsify_keep,
+                    const int32_t *n_draws, int draw_cap, const double *probs, int sparsify_max, int swap_max,
+                    int box_slots, const int32_t *info_in, float *out_points, int64_t out_cap, int64_t *out_offsets,
+                    float *out_boxes, int64_t out_box_cap, int64_t *out_box_offsets, int32_t *info, void *workspace,
+                    pda_stream_t stream);
 
 /* ---- ONCE evaluation (csrc/once_eval.hip; the reference's once_eval get_evaluation_results on the device) ------------
  * Frames: GT boxes (n_gt_total, 7) float64 [x, y, z, dx, dy, dz, heading] with gt_name (n_gt_total) int32 name ids and

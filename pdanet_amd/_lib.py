@@ -185,6 +185,10 @@ SIGNATURES = {
     "pda_augment_steps": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp, _vp, ctypes.c_int64,
                           ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _i, _i, _vp, _vp, ctypes.c_int64, _vp, _vp,
                           ctypes.c_int64, _vp, _vp, _vp, _vp],
+    "pda_pyramid_aug_workspace_bytes": [_i, ctypes.c_int64, _i],
+    "pda_pyramid_aug": [_vp, _vp, ctypes.c_int64, _i, _i, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _i,
+                        ctypes.POINTER(ctypes.c_double), _i, _i, _i, _vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp,
+                        _vp, _vp, _vp],
     "pda_once_eval_workspace_bytes": [_i, ctypes.c_int64, _i],
     "pda_once_eval_iou": [ctypes.POINTER(OnceFrames), _i, _vp, _vp, _vp],
     "pda_once_eval_accumulate": [ctypes.POINTER(OnceFrames), _vp, _vp, _i, _i, ctypes.POINTER(ctypes.c_double), _i, _vp, _vp,
@@ -283,7 +287,8 @@ SIZE_QUERIES = [
     "pda_colsum_scratch_bytes", "pda_gemm_split_bn_tiles", "pda_densitynet_scratch_bytes",
     "pda_sa_small_train_workspace_bytes", "pda_sa_xyz_grad_scratch_bytes", "pda_sa_point_gather_stats_blocks",
     "pda_input_stage_workspace_bytes",
-    "pda_augment_workspace_bytes", "pda_augment_steps_workspace_bytes", "pda_once_eval_workspace_bytes",
+    "pda_augment_workspace_bytes", "pda_augment_steps_workspace_bytes", "pda_pyramid_aug_workspace_bytes",
+    "pda_once_eval_workspace_bytes",
     "pda_kitti_eval_workspace_bytes", "pda_kitti_fov_filter_workspace_bytes", "pda_gt_extract_workspace_bytes",
     "pda_voxel_workspace_bytes", "pda_dyn_voxel_workspace_bytes", "pda_center_focal_blocks", "pda_anchor_loss_blocks",
     "pda_spconv_index_workspace_bytes", "pda_spconv_wgrad_workspace_bytes", "pda_voxel_pool_scratch_doubles",

@@ -21,6 +21,10 @@ random_local_translation, random_local_rotation, random_local_scaling, random_lo
 path: the paste alone (pda_augment_paste), then every step in the order the yaml lists it as one ordered program on the
 device (csrc/augment_steps.hip, pda_augment_steps).  A list of only the four steps above takes the path above, unchanged.
 
+random_local_pyramid_aug (the SE-SSD part-aware step: pyramid dropout, sparsify and swap) is a step of that path too, as
+the last step of the list: the program ends in a hold op that keeps class 0 and the headings as they are, and
+pda_pyramid_aug runs on what it leaves, then limit_period and the class filter.
+
 A scene the augmentor leaves without a box is only flagged (info[:, 3] bit 1): the reference's prepare_data draws
 another scene there, which a batch-level loader has to decide for itself.
 """
@@ -36,11 +40,13 @@ from .stage_common import (STATUS_BAD_OFFSETS, STATUS_OVER_CAP, cfg_get, current
                            raise_on_status, upload, workspace)
 
 # info[:, 3] status bits (include/pda_train.h pda_augment) next to the two shared ones, and what check=True raises
-STATUS_NO_BOX, STATUS_BAD_CAND = 1, 8
+STATUS_NO_BOX, STATUS_BAD_CAND, STATUS_BAD_PYRAMID_DRAW = 1, 8, 16
 _RULES = [(STATUS_BAD_OFFSETS, ": offsets outside the packed points or boxes"),
           (STATUS_OVER_CAP, ": more than n_cap points, an output capacity exceeded, or (program path) more boxes than the cap or "
                             "than draws"),
-          (STATUS_BAD_CAND, ": a candidate id outside the database or candidate groups out of order")]
+          (STATUS_BAD_CAND, ": a candidate id outside the database or candidate groups out of order"),
+          (STATUS_BAD_PYRAMID_DRAW, ": random_local_pyramid_aug with fewer draws than boxes or an invalid explicit draw (a keep "
+                                    "list, a swap face or a swap partner)")]
 MAX_CANDIDATES = 256
 MAX_SCENE_BOXES = 256            # boxes per scene (its own plus the candidates) on the program path
 _STEPS = ("gt_sampling", "random_world_flip", "random_world_rotation", "random_world_scaling")
@@ -50,9 +56,14 @@ _PROGRAM_STEPS = {"random_world_translation": ("NOISE_TRANSLATE_STD", "ALONG_AXI
                   "random_local_translation": ("LOCAL_TRANSLATION_RANGE", "ALONG_AXIS_LIST"),
                   "random_local_rotation": ("LOCAL_ROT_ANGLE",),
                   "random_local_scaling": ("LOCAL_SCALE_RANGE",),
-                  "random_local_frustum_dropout": ("INTENSITY_RANGE", "DIRECTION")}
-# op codes of pda_augment_steps (include/pda_train.h)
-OP_FLIP_X, OP_FLIP_Y, OP_ROT, OP_SCALE, OP_TRANS, OP_WDROP, OP_LTRANS, OP_LROT, OP_LSCALE, OP_LDROP = range(10)
+                  "random_local_frustum_dropout": ("INTENSITY_RANGE", "DIRECTION"),
+                  "random_local_pyramid_aug": ("DROP_PROB", "SPARSIFY_PROB", "SPARSIFY_MAX_NUM", "SWAP_PROB", "SWAP_MAX_NUM")}
+# op codes of pda_augment_steps (include/pda_train.h); OP_HOLD ends the program in front of pda_pyramid_aug
+OP_FLIP_X, OP_FLIP_Y, OP_ROT, OP_SCALE, OP_TRANS, OP_WDROP, OP_LTRANS, OP_LROT, OP_LSCALE, OP_LDROP, OP_HOLD = range(11)
+MAX_SPARSIFY_NUM = 1024          # SPARSIFY_MAX_NUM at most (pda_pyramid_aug)
+# the per-box rows of random_local_pyramid_aug's plan, in the row order of pda_pyramid_aug's draws_f64 / draws_i32
+_PYRAMID_F64 = ("pyramid_drop_u", "pyramid_sparsify_u", "pyramid_swap_u", "pyramid_swap_face_u", "pyramid_swap_partner_u")
+_PYRAMID_I32 = ("pyramid_drop_face", "pyramid_sparsify_face", "pyramid_swap_face", "pyramid_swap_partner")
 _AXES = {"x": 0, "y": 1, "z": 2}
 _DIRECTIONS = {"top": 0, "bottom": 1, "left": 2, "right": 3}
 
@@ -215,13 +226,15 @@ class DataAugmentor:
     random_world_flip, random_world_rotation, random_world_scaling, random_world_translation,
     random_world_frustum_dropout, random_local_translation, random_local_rotation, random_local_scaling and
     random_local_frustum_dropout, in the order the list gives, each at most once; gt_sampling must come first (the
-    transforms follow the paste).  Any other step (random_image_flip, random_local_pyramid_aug) raises
-    NotImplementedError.
+    transforms follow the paste).  random_local_pyramid_aug runs as the LAST step of the list (its place in
+    pointpillar_pyramid_aug.yaml); anywhere else it raises NotImplementedError.  Its SPARSIFY_MAX_NUM is at most 1024
+    (an explicit keep list is validated rank against rank on the device) and its point rows need C >= 4; a larger
+    SPARSIFY_MAX_NUM raises ValueError.  Any other step (random_image_flip) raises NotImplementedError.
 
-    An entry of one of the last six steps that lacks a parameter the step needs cannot be run and raises
+    An entry of one of the last seven steps that lacks a parameter the step needs cannot be run and raises
     NotImplementedError naming the step and the key: NOISE_TRANSLATE_STD and ALONG_AXIS_LIST (world translation),
     LOCAL_TRANSLATION_RANGE and ALONG_AXIS_LIST (local translation), LOCAL_ROT_ANGLE, LOCAL_SCALE_RANGE, INTENSITY_RANGE
-    and DIRECTION (both dropouts).
+    and DIRECTION (both dropouts), DROP_PROB, SPARSIFY_PROB, SPARSIFY_MAX_NUM, SWAP_PROB and SWAP_MAX_NUM (pyramid aug).
 
     A list of only the first four steps runs as pda_augment (flip, rotation, scaling in that fixed place); a list with
     one of the others runs the paste, then `program`: one op per step, axis or direction, in yaml order.
@@ -237,6 +250,7 @@ class DataAugmentor:
         self.flip_axes, self.flip_prob = [], 0.5
         self.rot_range, self.rot_prob = None, 1.0
         self.scale_range, self.scale_prob = None, 1.0
+        self.pyramid = None              # random_local_pyramid_aug's parameters
         seen = []
         steps = []                       # (op code, arg, step name, its parameters), in yaml order
         for cfg in cfg_list:
@@ -252,6 +266,8 @@ class DataAugmentor:
                 raise NotImplementedError("DATA_AUGMENTOR step %r appears twice" % name)
             if name == 'gt_sampling' and seen:
                 raise NotImplementedError("gt_sampling must be the first DATA_AUGMENTOR step")
+            if self.pyramid is not None:
+                raise NotImplementedError("random_local_pyramid_aug runs as the last DATA_AUGMENTOR step only: %r follows it" % name)
             seen.append(name)
             if name == 'gt_sampling':
                 self.sampler_cfg = cfg
@@ -289,6 +305,12 @@ class DataAugmentor:
                 r = [float(x) for x in cfg['LOCAL_SCALE_RANGE']]
                 if r[1] - r[0] >= 1e-3:          # the reference skips the step as a whole, without a draw
                     steps.append((OP_LSCALE, 0, name, r))
+            elif name == 'random_local_pyramid_aug':
+                self.pyramid = dict(drop_prob=float(cfg['DROP_PROB']), sparsify_prob=float(cfg['SPARSIFY_PROB']),
+                                    sparsify_max=int(cfg['SPARSIFY_MAX_NUM']), swap_prob=float(cfg['SWAP_PROB']),
+                                    swap_max=int(cfg['SWAP_MAX_NUM']))
+                if not 0 <= self.pyramid['sparsify_max'] <= MAX_SPARSIFY_NUM or self.pyramid['swap_max'] < 0:
+                    raise ValueError("random_local_pyramid_aug takes SPARSIFY_MAX_NUM in [0, %d] and SWAP_MAX_NUM >= 0" % MAX_SPARSIFY_NUM)
             else:
                 dirs = list(cfg['DIRECTION'])
                 if any(d not in _DIRECTIONS for d in dirs):
@@ -300,7 +322,7 @@ class DataAugmentor:
         self.program = steps if any(n in _PROGRAM_STEPS for n in seen) else None
         if self.program is not None and sum(1 for st in steps if st[0] == OP_WDROP) > 4:
             raise ValueError("random_world_frustum_dropout takes at most four directions")
-        if self.program is not None and len(steps) > 32:
+        if self.program is not None and len(steps) + (self.pyramid is not None) > 32:      # the hold op is one of the 32
             raise ValueError("more than 32 ops in the DATA_AUGMENTOR program")
         self.database = database
         self.groups, self.limit_whole_scene, self.use_road_plane = [], False, False
@@ -356,7 +378,11 @@ class DataAugmentor:
         path also: translation (B, axes) normal(0, NOISE_TRANSLATE_STD), world_dropout (B, directions), and for the local
         steps one row of D draws per scene and sub-step -- local_translation (B, axes, D), local_rotation (B, D),
         local_scaling (B, D), local_dropout (B, directions, D) -- with D = the most boxes a scene can hold (its own plus
-        its candidates): how many survive the collision test is known on the device only, and the draws are i.i.d."""
+        its candidates): how many survive the collision test is known on the device only, and the draws are i.i.d.
+        With random_local_pyramid_aug also, each (B, D): pyramid_drop_face and pyramid_sparsify_face (integers 0..5),
+        pyramid_drop_u, pyramid_sparsify_u, pyramid_swap_u, pyramid_swap_face_u and pyramid_swap_partner_u (uniform [0, 1))
+        and pyramid_sparsify_key (uint64); the explicit pyramid_sparsify_keep / pyramid_swap_face / pyramid_swap_partner
+        are never drawn."""
         if rng is None:
             rng = np.random.default_rng(int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
         B = len(gt_classes)
@@ -389,7 +415,75 @@ class DataAugmentor:
                 else:
                     val = rng.uniform(ops[0][3][0], ops[0][3][1], shape)
                 plan[key] = val[:, 0] if code in (OP_LROT, OP_LSCALE) else val
+            if self.pyramid is not None:
+                plan.update(pyramid_drop_face=rng.integers(0, 6, (B, D)), pyramid_drop_u=rng.random((B, D)),
+                            pyramid_sparsify_face=rng.integers(0, 6, (B, D)), pyramid_sparsify_u=rng.random((B, D)),
+                            pyramid_sparsify_key=rng.integers(0, 2 ** 64, (B, D), dtype=np.uint64),
+                            pyramid_swap_u=rng.random((B, D)), pyramid_swap_face_u=rng.random((B, D)),
+                            pyramid_swap_partner_u=rng.random((B, D)))
         return plan
+
+    def _pyramid_draws(self, plan, B):
+        """The pyramid rows of the plan as pda_pyramid_aug takes them: draws_f64 (B, 5, D), draws_i32 (B, 4, D), keys
+        (B, D) uint64, keep (B, D, 1 + SPARSIFY_MAX_NUM) int32 [length, ranks] (empty without pyramid_sparsify_keep in the
+        plan), n_draws (B, 3) int32 and D.  A row may be
+        shorter than D; the rows of a scene that follow another in length are cut or padded to it (a missing override
+        is -1, a missing face u or key 0)."""
+        smax = self.pyramid['sparsify_max']
+        rows = {}
+        for key in _PYRAMID_F64 + _PYRAMID_I32 + ("pyramid_sparsify_key",):
+            val = plan.get(key)
+            if val is None:
+                if key in ("pyramid_swap_face", "pyramid_swap_partner", "pyramid_swap_face_u", "pyramid_swap_partner_u",
+                           "pyramid_sparsify_key"):
+                    continue
+                raise ValueError("the plan lacks %r" % key)
+            if len(val) != B:
+                raise ValueError("plan[%r] needs one entry per scene" % key)
+            rows[key] = [np.asarray(r).reshape(-1) for r in val]
+        n = np.zeros((B, 3), np.int32)
+        for j, (a, c) in enumerate((("pyramid_drop_u", "pyramid_drop_face"), ("pyramid_sparsify_u", "pyramid_sparsify_face"),
+                                    ("pyramid_swap_u", None))):
+            for b in range(B):
+                n[b, j] = len(rows[a][b])
+                if c is not None and len(rows[c][b]) != n[b, j]:
+                    raise ValueError("plan[%r][%d] and plan[%r][%d] differ in length" % (a, b, c, b))
+        D = int(n.max()) if B else 0
+        if D > MAX_SCENE_BOXES:
+            raise ValueError("more than %d draws in one row of random_local_pyramid_aug" % MAX_SCENE_BOXES)
+        W = max(D, 1)
+        f64 = np.zeros((B, 5, W), np.float64)
+        i32 = np.zeros((B, 4, W), np.int32)
+        i32[:, 2:] = -1
+        keys = np.zeros((B, W), np.uint64)
+        keep_rows = plan.get("pyramid_sparsify_keep")
+        # without explicit lists nothing is built or uploaded: the kernel takes a null pointer and uses the keys
+        keep = np.zeros((B, W, 1 + smax) if keep_rows is not None else (0, 0, 0), np.int32)
+        if keep_rows is not None and len(keep_rows) != B:
+            raise ValueError("plan['pyramid_sparsify_keep'] needs one entry per scene")
+        for b in range(B):
+            for j, key in enumerate(_PYRAMID_F64):
+                if key in rows:
+                    r = rows[key][b][:n[b, min(j, 2)]]
+                    f64[b, j, :len(r)] = r
+            for j, key in enumerate(_PYRAMID_I32):
+                if key in rows:
+                    r = rows[key][b][:n[b, min(j, 2)]]
+                    i32[b, j, :len(r)] = r
+            if "pyramid_sparsify_key" in rows:
+                r = rows["pyramid_sparsify_key"][b][:n[b, 1]]
+                keys[b, :len(r)] = r.astype(np.uint64)
+            if keep_rows is not None:
+                if len(keep_rows[b]) > n[b, 1]:
+                    raise ValueError("plan['pyramid_sparsify_keep'][%d] holds more lists than sparsify draws" % b)
+                for j, lst in enumerate(keep_rows[b]):
+                    lst = np.asarray(lst, np.int64).reshape(-1)
+                    if len(lst) == 0:
+                        continue
+                    # a list of another length than SPARSIFY_MAX_NUM is invalid: the device flags it by its length
+                    keep[b, j, 0] = len(lst)
+                    keep[b, j, 1:1 + min(len(lst), smax)] = lst[:smax]
+        return f64, i32, keys.view(np.int64), keep, n, D
 
     def _program_draws(self, plan, B, fx, fy, angle, scale):
         """The plan as pda_augment_steps takes it: ops (n_ops, 2) int32, scene_draws (B, n_ops) float64 and box_draws
@@ -464,6 +558,15 @@ class DataAugmentor:
         to the j-th box alive at that sub-step, in order (the scene's own boxes, then the accepted candidates, minus what
         a world dropout removed): the order in which the reference consumes np.random.uniform.  A scene with more alive
         boxes than draws in a row, or more than 256 boxes, is flagged (status 4) and written empty.
+        With random_local_pyramid_aug also, per scene, rows of per-box draws: pyramid_drop_face (0..5) and pyramid_drop_u
+        (draw j for box j of the boxes alive there, class 0 included); pyramid_sparsify_face, pyramid_sparsify_u and
+        optionally pyramid_sparsify_key (uint64) and pyramid_sparsify_keep (a list per slot: SPARSIFY_MAX_NUM ranks into
+        the pyramid's points in scene order, np.random.choice's result, or empty = the key decides), draw j for the j-th
+        box not dropped; pyramid_swap_u and optionally pyramid_swap_face_u / pyramid_swap_partner_u in [0, 1) (index
+        floor(u * k) among the k valid options in ascending order) or the explicit pyramid_swap_face (a face or -1) /
+        pyramid_swap_partner (an index among the boxes in front of the swap, or -1), draw j for the j-th box neither
+        dropped nor selected by the sparsify.  A scene with fewer draws than boxes in a row or an invalid explicit draw
+        is flagged (status 16) and written empty.
         None: drawn by make_plan(gt_classes, rng), which advances the sampler.
         road_planes / calib: per scene, required by USE_ROAD_PLANE (the reference's road_plane [a, b, c, d] and a
         calibration with lidar_to_rect / rect_to_lidar).
@@ -547,6 +650,9 @@ class DataAugmentor:
         if self.program is not None:
             ops, scene_draws, box_draws, D = self._program_draws(plan, B, fx, fy, angle, scale)
             parts += [scene_draws, box_draws]
+            if self.pyramid is not None:
+                py = self._pyramid_draws(plan, B)
+                parts += list(py[:5])
         views = upload(parts, dev, pinned=True)
         d_cand, d_grp, d_dz, d_flip, d_angle, d_scale, d_cls = views[:7]
         if not dev_in:
@@ -577,6 +683,10 @@ class DataAugmentor:
                   out_boffs.data_ptr(), info.data_ptr(), ws.data_ptr())
             # the pasted scenes through the ordered program
             n_ops = len(self.program)
+            if self.pyramid is not None:             # the hold: class 0 and the headings stay for pda_pyramid_aug
+                ops = np.concatenate([ops, np.array([[OP_HOLD, 0]], np.int32)], 0)
+                n_ops += 1
+            d_scene, d_box = views[11 if not dev_in else 7], views[12 if not dev_in else 8]
             slots = min(MAX_SCENE_BOXES, max([len(c) + int((cand[b] >= 0).sum()) for b, c in enumerate(cls_rows)] + [0]))
             ws2 = workspace("pda_augment_steps_workspace_bytes", (B, n_cap + paste_cap, slots, n_ops),
                             "batch %d / n_cap %d / %d ops out of range" % (B, n_cap + paste_cap, n_ops), dev)
@@ -584,8 +694,22 @@ class DataAugmentor:
             out_offs2, out_boffs2, info2 = torch.empty_like(out_offs), torch.empty_like(out_boffs), torch.empty_like(info)
             _call("pda_augment_steps", out, out.data_ptr(), out_offs.data_ptr(), out_cap, B, C, n_cap + paste_cap,
                   out_boxes.data_ptr(), out_boffs.data_ptr(), box_cap, ops.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n_ops,
-                  views[-2].data_ptr(), views[-1].data_ptr(), D, slots, info.data_ptr(), out2.data_ptr(), out_cap,
+                  d_scene.data_ptr(), d_box.data_ptr(), D, slots, info.data_ptr(), out2.data_ptr(), out_cap,
                   out_offs2.data_ptr(), out_boxes2.data_ptr(), box_cap, out_boffs2.data_ptr(), info2.data_ptr(), ws2.data_ptr())
+            if self.pyramid is not None:
+                pr = self.pyramid
+                ws3 = workspace("pda_pyramid_aug_workspace_bytes", (B, n_cap + paste_cap, slots),
+                                "batch %d / n_cap %d / %d boxes out of range" % (B, n_cap + paste_cap, slots), dev)
+                out3, out_boxes3 = torch.empty_like(out), torch.empty_like(out_boxes)
+                out_offs3, out_boffs3, info3 = torch.empty_like(out_offs), torch.empty_like(out_boffs), torch.empty_like(info)
+                d_f64, d_i32, d_key, d_keep, d_n = views[-5:]
+                probs = (ctypes.c_double * 3)(pr['drop_prob'], pr['sparsify_prob'], pr['swap_prob'])
+                _call("pda_pyramid_aug", out2, out2.data_ptr(), out_offs2.data_ptr(), out_cap, B, C, n_cap + paste_cap,
+                      out_boxes2.data_ptr(), out_boffs2.data_ptr(), box_cap, d_f64.data_ptr(), d_i32.data_ptr(), d_key.data_ptr(),
+                      d_keep.data_ptr() if d_keep.numel() else None, d_n.data_ptr(), py[5], probs,
+                      pr['sparsify_max'], pr['swap_max'], slots, info2.data_ptr(), out3.data_ptr(), out_cap, out_offs3.data_ptr(),
+                      out_boxes3.data_ptr(), box_cap, out_boffs3.data_ptr(), info3.data_ptr(), ws3.data_ptr())
+                out2, out_offs2, out_boxes2, out_boffs2, info2 = out3, out_offs3, out_boxes3, out_boffs3, info3
             if check:
                 raise_on_status(info2.cpu(), _RULES)
             return (out2, out_offs2, n_cap + paste_cap), (out_boxes2, out_boffs2), info2
