@@ -386,6 +386,15 @@ int pda_boxes_iou_bev(const float *boxes_a, const float *boxes_b, float *ans_iou
 int64_t pda_nms_mask_words(int n);
 int pda_nms_bev(const float *boxes, const int32_t *num_valid, int64_t *keep, int32_t *num_keep,
                 uint64_t *mask_scratch, int b, int n, float thresh, int normal, pda_stream_t stream);
+/* The result of model_nms_utils.multi_classes_nms for a batch, in one launch behind one pda_nms_bev over b * c problems (scene
+ * s, problem p = a class column of a head, head after head): boxes (b * c, k, 7) and scores (b * c, k) sorted as pda_nms_bev
+ * saw them, keep (b * c, k) and num_keep (b * c) its outputs, label_map (c) int32 the 1-based label of each problem.  Scene s
+ * receives, problem after problem, the first min(num_keep, post_max) kept boxes of each in score order: pred_boxes
+ * (b, c * cap, 7), pred_scores (b, c * cap), pred_labels (b, c * cap) int64, cap = min(post_max, k); the rows behind them
+ * are zero (label 0 = padding); num_pred (b) int32.  c <= 256. */
+int pda_multi_nms_compact(const float *boxes, const float *scores, const int64_t *keep, const int32_t *num_keep,
+                          const int32_t *label_map, int b, int c, int k, int post_max, float *pred_boxes, float *pred_scores,
+                          int64_t *pred_labels, int32_t *num_pred, pda_stream_t stream);
 
 /* ---- loss terms of the IA-SSD head, one launch each: the term AND its gradient (csrc/head_loss.hip) --------------------------
  * Replace the elementwise torch chains of IASSD_head.py:525-735, :1239-1321 and loss_utils.py:75-194, :340-363.  All tensors
@@ -1028,6 +1037,36 @@ int pda_anchor_loss(const float *cls_preds, const float *box_preds, const float 
  * on a tie. */
 int pda_anchor_decode(const float *box_preds, const float *dir_cls_preds, const float *anchors, int b, int n_anchors, int bins,
                       double dir_offset, double dir_limit_offset, float *batch_box_preds, pda_stream_t stream);
+/* AnchorHeadMulti (dense_heads/anchor_head_multi.py, USE_MULTIHEAD): the table is class-major, the reference's
+ * cat over the classes of anchors.permute(3, 4, 0, 1, 2, 5).view(-1, 7), so class c owns the class_rows[c] contiguous rows behind
+ * those of the classes before it (sum = n_anchors) and classes may differ in stride and in their number of rotations.
+ * pda_anchor_multi_assign_targets is pda_anchor_assign_targets with that one difference: every other argument, every output and
+ * the per-(scene, class, anchor) rule are the same, and so are the two launches, the integer atomicMax and the untouched
+ * gt_boxes.  The class-major table with pda_anchor_decode decodes the concatenated box / direction predictions.
+ *
+ * pda_anchor_multi_loss: get_cls_layer_loss + get_box_reg_layer_loss of anchor_head_multi.py in one pass and one finishing
+ * launch over n_heads <= 32 heads whose predictions are tensors of their own.  HOST arrays per head: cls_preds[h]
+ * (b, head_rows[h], head_cols[h]), box_preds[h] (b, head_rows[h], 7), dir_cls_preds[h] (b, head_rows[h], bins) (the array NULL:
+ * no direction classifier), the gradients grad_*[h] of the same shapes, written whole; head h owns the head_rows[h] rows of the
+ * table behind those of the heads before it (sum = n_anchors); a positive of label l is hot at column l - 1 - head_col_base[h]
+ * (SEPARATE_MULTIHEAD: the head's first class; otherwise 0 with head_cols = num_class); num_class == 1: every positive is
+ * hot at column 0.  labels, targets, num_pos (of all heads together, the reference's normaliser), anchors, code_weights and
+ * the terms are pda_anchor_loss's, each head's sum / b * weight, with two departures the reference makes: the classification
+ * weight of a positive is pos_cls_weight / norm and of a negative neg_cls_weight / norm, and the sin difference is taken
+ * only behind a direction classifier.  out = [rpn_loss_cls, rpn_loss_loc, rpn_loss_dir, rpn_loss]; partials: 3 *
+ * pda_anchor_multi_loss_blocks(b * n_anchors) float64. */
+int pda_anchor_multi_assign_targets(const float *gt_boxes, int gt_cols, int b, int m, const float *anchors, int n_anchors,
+                                    int n_cls, const int32_t *class_label, const float *matched, const float *unmatched,
+                                    const int32_t *class_rows, uint32_t *col_max, int32_t *box_cls_labels,
+                                    float *box_reg_targets, float *reg_weights, int32_t *num_pos, pda_stream_t stream);
+int64_t pda_anchor_multi_loss_blocks(int64_t n);
+int pda_anchor_multi_loss(const float *const *cls_preds, const float *const *box_preds, const float *const *dir_cls_preds,
+                          int n_heads, const int32_t *head_rows, const int32_t *head_cols, const int32_t *head_col_base,
+                          const int32_t *box_cls_labels, const float *box_reg_targets, const int32_t *num_pos,
+                          const float *anchors, int b, int n_anchors, int num_class, int bins, const float *code_weights,
+                          double cls_weight, double loc_weight, double dir_weight, double dir_offset, double pos_cls_weight,
+                          double neg_cls_weight, float *const *grad_cls, float *const *grad_box, float *const *grad_dir,
+                          double *partials, float *out, pda_stream_t stream);
 /* PillarVFE's PFN input rows: voxels (v, p, c) float32 (c >= 3, padded rows zero), voxel_num_points (v) int32, voxel_coords
  * (v, 4) int32 (b, z, y, x) -> out (v, p, c' ) with c' = (absolute_xyz ? c : c - 3) + 6 + (with_distance ? 1 : 0): [the raw
  * columns (from column 3 on without absolute_xyz), xyz - mean, xyz - cell centre, |xyz|]; rows from num_points on are exactly

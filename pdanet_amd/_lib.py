@@ -244,6 +244,12 @@ SIGNATURES = {
     "pda_anchor_loss_blocks": [ctypes.c_int64],
     "pda_anchor_loss": [_vp] * 7 + [_i] * 4 + [ctypes.POINTER(_f)] + [ctypes.c_double] * 4 + [_vp] * 6,
     "pda_anchor_decode": [_vp, _vp, _vp, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp, _vp],
+    "pda_anchor_multi_assign_targets": [_vp, _i, _i, _i, _vp, _i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_f),
+                                        ctypes.POINTER(_f), ctypes.POINTER(ctypes.c_int32), _vp, _vp, _vp, _vp, _vp, _vp],
+    "pda_anchor_multi_loss_blocks": [ctypes.c_int64],
+    "pda_anchor_multi_loss": [ctypes.POINTER(_vp)] * 3 + [_i] + [ctypes.POINTER(ctypes.c_int32)] * 3 + [_vp] * 4 + [_i] * 4
+                             + [ctypes.POINTER(_f)] + [ctypes.c_double] * 6 + [ctypes.POINTER(_vp)] * 3 + [_vp] * 3,
+    "pda_multi_nms_compact": [_vp] * 5 + [_i] * 4 + [_vp] * 5,
     "pda_pillar_features": [_vp, _vp, _vp, ctypes.c_int64, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _i, _i, _vp, _vp],
     "pda_spconv_index_workspace_bytes": [ctypes.c_int64, ctypes.c_int64, _i],
     "pda_spconv_index_subm": [_vp, ctypes.c_int64] + [_i] * 7 + [_vp, _vp, _vp, _vp],
@@ -291,6 +297,7 @@ SIZE_QUERIES = [
     "pda_once_eval_workspace_bytes",
     "pda_kitti_eval_workspace_bytes", "pda_kitti_fov_filter_workspace_bytes", "pda_gt_extract_workspace_bytes",
     "pda_voxel_workspace_bytes", "pda_dyn_voxel_workspace_bytes", "pda_center_focal_blocks", "pda_anchor_loss_blocks",
+    "pda_anchor_multi_loss_blocks",
     "pda_spconv_index_workspace_bytes", "pda_spconv_wgrad_workspace_bytes", "pda_voxel_pool_scratch_doubles",
     "pda_stack_sa_scratch_doubles"]
 INFO_SYMBOLS = ["pda_abi_version", "pda_last_error", "pda_fp_contract_mode", "pda_opt_n_threads",

@@ -12,8 +12,8 @@ z += dz / 2), so the tensors are bit-identical; they are uploaded once as one (N
 Departures from the reference: tb_dict holds 0-dim device tensors; box_cls_labels is not rewritten
 for num_class == 1; a gt row with label 0 takes part in no class (the reference maps it onto the last class, where its zero
 area can influence nothing).  Out of contract, raised as NotImplementedError: POS_FRACTION >= 0, NORM_BY_NUM_EXAMPLES,
-MATCH_HEIGHT, NAME: ATSS, USE_MULTIHEAD, boxes with more than 7 + 1 columns, encode_angle_by_sincos, anchor classes with
-different feature_map_stride."""
+MATCH_HEIGHT, NAME: ATSS, boxes with more than 7 + 1 columns, encode_angle_by_sincos, and on AnchorHeadSingle USE_MULTIHEAD
+and anchor classes with different feature_map_stride (anchor_head_multi.py has the head of USE_MULTIHEAD)."""
 import ctypes
 
 import numpy as np
@@ -88,6 +88,9 @@ def anchor_table(anchors):
 
 
 class AxisAlignedTargetAssigner(object):
+    CLASS_MAJOR = False       # anchor_head_multi.ClassMajorTargetAssigner: the table of USE_MULTIHEAD
+    ENTRY = "pda_anchor_assign_targets"
+
     def __init__(self, model_cfg, class_names, box_coder, match_height=False):
         generator_cfg = model_cfg['ANCHOR_GENERATOR_CONFIG']
         target_cfg = model_cfg['TARGET_ASSIGNER_CONFIG']
@@ -102,8 +105,9 @@ class AxisAlignedTargetAssigner(object):
             raise NotImplementedError("NORM_BY_NUM_EXAMPLES: True")
         if match_height:
             raise NotImplementedError("MATCH_HEIGHT: True (rotated 3D IoU matching)")
-        if field(model_cfg, 'USE_MULTIHEAD', False):
-            raise NotImplementedError("USE_MULTIHEAD")
+        if bool(field(model_cfg, 'USE_MULTIHEAD', False)) != self.CLASS_MAJOR:
+            raise NotImplementedError("USE_MULTIHEAD: %s (anchor_head_multi.AnchorHeadMulti has the class-major assigner)"
+                                      % field(model_cfg, 'USE_MULTIHEAD', False))
         if getattr(box_coder, 'encode_angle_by_sincos', False) or box_coder.code_size != 7:
             raise NotImplementedError("encode_angle_by_sincos / a code size other than 7")
         self.pos_fraction = None
@@ -111,7 +115,7 @@ class AxisAlignedTargetAssigner(object):
         self.norm_by_num_examples = False
         self.matched_thresholds = {c['class_name']: c['matched_threshold'] for c in generator_cfg}
         self.unmatched_thresholds = {c['class_name']: c['unmatched_threshold'] for c in generator_cfg}
-        self.use_multihead = False
+        self.use_multihead = self.CLASS_MAJOR
         names = self.anchor_class_names
         if not 1 <= len(names) <= MAX_CLASSES or len(set(names)) != len(names):
             raise ValueError("1..%d anchor classes with different names, got %s" % (MAX_CLASSES, names))
@@ -121,14 +125,19 @@ class AxisAlignedTargetAssigner(object):
         self._unmatched_c = (ctypes.c_float * len(names))(*[float(self.unmatched_thresholds[n]) for n in names])
         self._table = {}
 
+    def build_table(self, anchors):
+        """The host table of the per-class anchors and what each class owns of it: here its slots at every location."""
+        tab, counts = anchor_table(anchors)
+        if sum(counts) > MAX_SLOTS:
+            raise ValueError("at most %d anchors per location, got %d" % (MAX_SLOTS, sum(counts)))
+        return tab, counts
+
     def table(self, all_anchors, device):
         """The (N, 7) device table of `all_anchors` (the head's list) and the per-class slot counts, uploaded once."""
         key = (id(all_anchors), str(device))
         hit = self._table.get(key)
         if hit is None:
-            tab, counts = anchor_table([a.detach().cpu() for a in all_anchors])
-            if sum(counts) > MAX_SLOTS:
-                raise ValueError("at most %d anchors per location, got %d" % (MAX_SLOTS, sum(counts)))
+            tab, counts = self.build_table([a.detach().cpu() for a in all_anchors])
             hit = self._table[key] = (tab.to(device), (ctypes.c_int32 * len(counts))(*counts), all_anchors)
         return hit[0], hit[1]
 
@@ -153,7 +162,7 @@ class AxisAlignedTargetAssigner(object):
         num_pos = torch.empty((B,), dtype=I32, device=dev)
         col_max = torch.empty((B, max(M, 1)), dtype=I32, device=dev)
         if B and N:
-            _call("pda_anchor_assign_targets", gt, gt.data_ptr(), 8, B, M, table.data_ptr(), N, len(self.anchor_class_names),
+            _call(self.ENTRY, gt, gt.data_ptr(), 8, B, M, table.data_ptr(), N, len(self.anchor_class_names),
                   self._label_c, self._matched_c, self._unmatched_c, counts, col_max.data_ptr(), labels.data_ptr(),
                   targets.data_ptr(), weights.data_ptr(), num_pos.data_ptr())
         return {'box_cls_labels': labels, 'box_reg_targets': targets, 'reg_weights': weights, 'num_pos': num_pos}
@@ -254,6 +263,8 @@ def anchor_decode(box_preds, dir_cls_preds, table, dir_offset=0.0, dir_limit_off
 
 
 class AnchorHeadTemplate(nn.Module):
+    MULTIHEAD = False         # anchor_head_multi.AnchorHeadMulti: USE_MULTIHEAD, the class-major table
+
     def __init__(self, model_cfg, num_class, class_names, grid_size, point_cloud_range, predict_boxes_when_training):
         super().__init__()
         self.model_cfg = model_cfg
@@ -261,8 +272,9 @@ class AnchorHeadTemplate(nn.Module):
         self.class_names = class_names
         self.predict_boxes_when_training = predict_boxes_when_training
         self.use_multihead = field(model_cfg, 'USE_MULTIHEAD', False)
-        if self.use_multihead:
-            raise NotImplementedError("USE_MULTIHEAD (AnchorHeadMulti)")
+        if bool(self.use_multihead) != self.MULTIHEAD:
+            raise NotImplementedError("USE_MULTIHEAD: %s on %s (AnchorHeadMulti is the head of USE_MULTIHEAD: True)"
+                                      % (self.use_multihead, type(self).__name__))
         target_cfg = model_cfg['TARGET_ASSIGNER_CONFIG']
         coder = target_cfg['BOX_CODER']
         if coder != 'ResidualCoder':
@@ -272,7 +284,7 @@ class AnchorHeadTemplate(nn.Module):
         if self.box_coder.encode_angle_by_sincos or self.box_coder.code_size != 7:
             raise NotImplementedError("encode_angle_by_sincos / boxes with more than 7 columns")
         generator_cfg = model_cfg['ANCHOR_GENERATOR_CONFIG']
-        if len({c['feature_map_stride'] for c in generator_cfg}) != 1:
+        if not self.MULTIHEAD and len({c['feature_map_stride'] for c in generator_cfg}) != 1:
             raise NotImplementedError("anchor classes with different feature_map_stride (the reference's torch.cat fails there)")
         anchors, self.num_anchors_per_location = self.generate_anchors(
             generator_cfg, grid_size=grid_size, point_cloud_range=point_cloud_range, anchor_ndim=self.box_coder.code_size)

@@ -6,11 +6,16 @@
 // matrix, takes two argmaxes and several nonzero() compactions and writes through boolean masks; get_loss materialises
 // one-hot tensors and a dozen temporaries and reads four scalars back.
 //
-// Here: anchor_assign_kernel<false> (column maxima through an integer atomicMax on the float's bits, reduced inside the
-// wave first) and anchor_assign_kernel<true> (the same IoUs recomputed by the same code, labels, targets, weights, the
+// Here: anchor_assign_kernel<false, ..> (column maxima through an integer atomicMax on the float's bits, reduced inside the
+// wave first) and anchor_assign_kernel<true, ..> (the same IoUs recomputed by the same code, labels, targets, weights, the
 // positives counted with an integer atomic): no anchors x gts matrix is stored.  anchor_loss_kernel + anchor_loss_finish_kernel:
 // one pass over the anchors for the three terms and their gradients, per-workgroup float64 partials summed in a fixed order
 // (loss_sums.h).  anchor_decode_kernel is one launch.  No float atomics anywhere.
+//
+// AnchorHeadMulti (dense_heads/anchor_head_multi.py) lays its anchors out class after class (anchors.permute(3, 4, 0, 1, 2, 5),
+// concatenated): anchor_assign_kernel<.., true> takes an anchor's class from the row segment that holds it, and
+// anchor_multi_loss_kernel runs the same per-anchor terms (anchor_loss_row) over heads whose logits have different column
+// counts, the per-head tensors described by value.
 #include "loss_sums.h"
 
 #include <math.h>
@@ -21,7 +26,7 @@ namespace {
 constexpr int AH_THREADS = 256;
 constexpr int AH_TILE = 64;           // gt rows staged in LDS at a time
 constexpr int AH_MAX_SLOTS = 64;      // anchors per location, all classes
-constexpr int AH_MAX_CLASSES = 32;    // anchor classes; also num_class of the loss
+constexpr int AH_MAX_CLASSES = 32;    // anchor classes; also num_class of the loss and the heads of a multihead
 constexpr int AH_MAX_BINS = 8;        // NUM_DIR_BINS
 
 struct AnchorAssignCfg {
@@ -29,7 +34,9 @@ struct AnchorAssignCfg {
     int label[AH_MAX_CLASSES];          // the 1-based gt label of each anchor class
     float matched[AH_MAX_CLASSES];
     float unmatched[AH_MAX_CLASSES];
-    int first_slot[AH_MAX_CLASSES + 1]; // class c owns the slots [first_slot[c], first_slot[c + 1])
+    // location-major: class c owns the slots [first[c], first[c + 1]) of every location; class-major (SEGMENTED): the rows
+    // [first[c], first[c + 1]) of the table
+    int first[AH_MAX_CLASSES + 1];
 };
 
 // box_utils.boxes3d_lidar_to_aligned_bev_boxes, every operation a separate float32 one (the file is built with
@@ -59,8 +66,9 @@ __device__ __forceinline__ float iou_normal(float ax1, float ay1, float ax2, flo
 
 // SECOND == false: col_max[s, j] = max over the anchors of j's class of iou(a, j), through the bit pattern (values >= 0).
 // SECOND == true: the same IoUs again; labels, targets, weights and the scene's positives.
-// grid (ceil(n_anchors / 256), b); anchor n of a scene is row n of `anchors`, its class the owner of slot n % slots.
-template <bool SECOND>
+// grid (ceil(n_anchors / 256), b); anchor n of a scene is row n of `anchors`, its class the owner of slot n % slots, or with
+// SEGMENTED the owner of row n; `slot` then is the class itself.
+template <bool SECOND, bool SEGMENTED>
 __global__ __launch_bounds__(AH_THREADS) void anchor_assign_kernel(const float* __restrict__ anchors,
                                                                    const float* __restrict__ gt, AnchorAssignCfg g,
                                                                    uint32_t* __restrict__ col_max,
@@ -71,17 +79,22 @@ __global__ __launch_bounds__(AH_THREADS) void anchor_assign_kernel(const float* 
     __shared__ uint32_t t_col[AH_TILE];
     __shared__ int slot_label[AH_MAX_SLOTS];
     __shared__ float slot_matched[AH_MAX_SLOTS], slot_unmatched[AH_MAX_SLOTS];
+    __shared__ int seg_first[AH_MAX_CLASSES + 1];
     const int s = blockIdx.y;
     const int n = blockIdx.x * AH_THREADS + (int)threadIdx.x;
     const int lane = (int)(threadIdx.x & 63);
     const bool live = n < g.n_anchors;
-    if ((int)threadIdx.x < g.slots) {
-        int c = 0;
-        while (c + 1 < g.n_cls && (int)threadIdx.x >= g.first_slot[c + 1]) ++c;
+    if ((int)threadIdx.x < (SEGMENTED ? g.n_cls : g.slots)) {
+        int c = (int)threadIdx.x;
+        if (!SEGMENTED) {
+            c = 0;
+            while (c + 1 < g.n_cls && (int)threadIdx.x >= g.first[c + 1]) ++c;
+        }
         slot_label[threadIdx.x] = g.label[c];
         slot_matched[threadIdx.x] = g.matched[c];
         slot_unmatched[threadIdx.x] = g.unmatched[c];
     }
+    if (SEGMENTED && (int)threadIdx.x <= g.n_cls) seg_first[threadIdx.x] = g.first[threadIdx.x];
     float a[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (live) {
 #pragma unroll
@@ -91,7 +104,13 @@ __global__ __launch_bounds__(AH_THREADS) void anchor_assign_kernel(const float* 
     aligned_bev(a[0], a[1], a[3], a[4], a[6], ax1, ay1, ax2, ay2);
     const float area_a = (ax2 - ax1) * (ay2 - ay1);
     __syncthreads();
-    const int slot = live ? n % g.slots : 0;
+    int slot = 0;
+    if (SEGMENTED) {
+        if (live)
+            while (slot + 1 < g.n_cls && n >= seg_first[slot + 1]) ++slot;
+    } else if (live) {
+        slot = n % g.slots;
+    }
     const int my_label = live ? slot_label[slot] : -1;      // a dead lane takes part in nothing
     const float* sgt = gt + (size_t)s * g.m * g.cols;
 
@@ -183,11 +202,88 @@ struct AnchorLossCfg {
     double cls_scale, loc_scale, dir_scale;   // weight / b
 };
 
-// One anchor per thread and step.  Per anchor, with norm = max(num_pos[scene], 1):
-//   cls: SigmoidFocalClassificationLoss(alpha 0.25, gamma 2) on the one-hot of the label, weight (label >= 0) / norm;
-//   loc: WeightedSmoothL1Loss(beta 1/9) after add_sin_difference on column 6, weight (label > 0) / norm, a NaN target 0;
-//   dir: softmax cross-entropy against the direction bin, weight (label > 0) / norm.
-// The gradients hold d(rpn_loss) / d(prediction) for an incoming gradient of 1; partials (3, blocks) the unscaled sums.
+// The terms of one anchor, with w = 1 / max(num_pos[scene], 1):
+//   cls: SigmoidFocalClassificationLoss(alpha 0.25, gamma 2) over the row's n_cols logits, the one-hot at column hot_col
+//        (-1: none), weight w_cls (0 for an ignored anchor);
+//   loc: WeightedSmoothL1Loss(beta 1/9), after add_sin_difference on column 6 when sin_diff, weight (label > 0) * w, a NaN
+//        target 0;
+//   dir: softmax cross-entropy against the direction bin, weight (label > 0) * w; dp == nullptr: no direction classifier.
+// Every pointer is the anchor's own row.  The gradients hold d(rpn_loss) / d(prediction) for an incoming gradient of 1 and
+// are written whole; s_cls, s_loc, s_dir gather the unscaled sums.
+__device__ __forceinline__ void anchor_loss_row(const AnchorLossCfg& g, int label, double w_cls, double w, int hot_col, int n_cols,
+                                                bool sin_diff, const float* __restrict__ cls, const float* __restrict__ pr,
+                                                const float* __restrict__ tg, const float* __restrict__ anchor,
+                                                const float* __restrict__ dp, float* __restrict__ grad_cls,
+                                                float* __restrict__ grad_box, float* __restrict__ grad_dir, double& s_cls,
+                                                double& s_loc, double& s_dir) {
+    const double beta = 1.0 / 9.0;
+    for (int k = 0; k < n_cols; ++k) {
+        float gr = 0.f;
+        if (label >= 0) {
+            const double x = (double)cls[k];
+            const bool t = hot_col == k;
+            const double p = 1.0 / (1.0 + exp(-x));
+            const double alpha = t ? 0.25 : 0.75;
+            const double pt = t ? 1.0 - p : p;
+            const double bce = fmax(x, 0.0) - (t ? x : 0.0) + log1p(exp(-fabs(x)));
+            s_cls += alpha * pt * pt * bce * w_cls;
+            const double dpt = t ? -p * (1.0 - p) : p * (1.0 - p);
+            const double dbce = p - (t ? 1.0 : 0.0);
+            gr = (float)(alpha * (2.0 * pt * dpt * bce + pt * pt * dbce) * w_cls * g.cls_scale);
+        }
+        grad_cls[k] = gr;
+    }
+    // regression and direction: positives only
+    float gb[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float gd[AH_MAX_BINS];
+#pragma unroll
+    for (int k = 0; k < AH_MAX_BINS; ++k) gd[k] = 0.f;
+    if (label > 0) {
+#pragma unroll
+        for (int c = 0; c < 7; ++c) {
+            const float tf = tg[c];
+            if (is_nan_bits(tf)) continue;
+            double p = (double)pr[c], t = (double)tf, chain = 1.0;
+            if (c == 6 && sin_diff) {      // sin(a - b) = sin a cos b - cos a sin b, both halves differentiated in the prediction
+                const double a0 = p, b0 = t;
+                p = sin(a0) * cos(b0);
+                t = cos(a0) * sin(b0);
+                chain = cos(a0) * cos(b0) + sin(a0) * sin(b0);
+            }
+            const double diff = (p - t) * (double)g.code_weight[c];
+            const double ad = fabs(diff);
+            s_loc += (ad < beta ? 0.5 * ad * ad / beta : ad - 0.5 * beta) * w;
+            const double dl = ad < beta ? diff / beta : (diff > 0.0 ? 1.0 : (diff < 0.0 ? -1.0 : 0.0));
+            gb[c] = (float)(dl * (double)g.code_weight[c] * chain * w * g.loc_scale);
+        }
+        if (dp) {
+            // get_direction_target in float32, as the reference evaluates it
+            const float rot_gt = tg[6] + anchor[6];
+            const float val = rot_gt - g.dir_offset;
+            const float offset_rot = val - floorf(val / g.two_pi + 0.f) * g.two_pi;
+            int bin = (int)floorf(offset_rot / g.bin_width);
+            bin = bin < 0 ? 0 : (bin > g.bins - 1 ? g.bins - 1 : bin);
+            double mx = -INFINITY;
+            for (int k = 0; k < g.bins; ++k) mx = fmax(mx, (double)dp[k]);
+            double z = 0.0;
+            for (int k = 0; k < g.bins; ++k) z += exp((double)dp[k] - mx);
+            const double lse = mx + log(z);
+            s_dir += (lse - (double)dp[bin]) * w;
+#pragma unroll
+            for (int k = 0; k < AH_MAX_BINS; ++k)
+                if (k < g.bins) gd[k] = (float)((exp((double)dp[k] - lse) - (k == bin ? 1.0 : 0.0)) * w * g.dir_scale);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 7; ++c) grad_box[c] = gb[c];
+    if (dp) {
+#pragma unroll
+        for (int k = 0; k < AH_MAX_BINS; ++k)
+            if (k < g.bins) grad_dir[k] = gd[k];
+    }
+}
+
+// One anchor per thread and step over (b, n_anchors), every prediction one tensor; partials (3, blocks) the unscaled sums.
 __global__ __launch_bounds__(AL_THREADS) void anchor_loss_kernel(
         const float* __restrict__ cls_preds, const float* __restrict__ box_preds, const float* __restrict__ dir_preds,
         const int32_t* __restrict__ labels, const float* __restrict__ targets, const int32_t* __restrict__ num_pos,
@@ -196,83 +292,87 @@ __global__ __launch_bounds__(AL_THREADS) void anchor_loss_kernel(
     double s_cls = 0.0, s_loc = 0.0, s_dir = 0.0;
     const long long total = (long long)g.b * g.n_anchors;
     const long long stride = (long long)gridDim.x * AL_THREADS;
-    const double beta = 1.0 / 9.0;
     for (long long e = (long long)blockIdx.x * AL_THREADS + threadIdx.x; e < total; e += stride) {
         const int s = (int)(e / g.n_anchors);
         const int n = (int)(e % g.n_anchors);
         const int label = labels[e];
-        const double norm = (double)max(num_pos[s], 1);
-        const double w = 1.0 / norm;
-        // classification
-        const int hot = label > 0 ? (g.num_class == 1 ? 1 : label) : 0;      // class-agnostic: every positive is class 1
-        for (int k = 0; k < g.num_class; ++k) {
-            const size_t at = (size_t)e * g.num_class + k;
-            float gr = 0.f;
-            if (label >= 0) {
-                const double x = (double)cls_preds[at];
-                const bool t = hot == k + 1;
-                const double p = 1.0 / (1.0 + exp(-x));
-                const double alpha = t ? 0.25 : 0.75;
-                const double pt = t ? 1.0 - p : p;
-                const double bce = fmax(x, 0.0) - (t ? x : 0.0) + log1p(exp(-fabs(x)));
-                s_cls += alpha * pt * pt * bce * w;
-                const double dpt = t ? -p * (1.0 - p) : p * (1.0 - p);
-                const double dbce = p - (t ? 1.0 : 0.0);
-                gr = (float)(alpha * (2.0 * pt * dpt * bce + pt * pt * dbce) * w * g.cls_scale);
-            }
-            grad_cls[at] = gr;
-        }
-        // regression and direction: positives only
-        float gb[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        float gd[AH_MAX_BINS];
-#pragma unroll
-        for (int k = 0; k < AH_MAX_BINS; ++k) gd[k] = 0.f;
-        if (label > 0) {
-            const float* pr = box_preds + (size_t)e * 7;
-            const float* tg = targets + (size_t)e * 7;
-#pragma unroll
-            for (int c = 0; c < 7; ++c) {
-                const float tf = tg[c];
-                if (is_nan_bits(tf)) continue;
-                double p = (double)pr[c], t = (double)tf, chain = 1.0;
-                if (c == 6) {      // sin(a - b) = sin a cos b - cos a sin b, both halves differentiated in the prediction
-                    const double a0 = p, b0 = t;
-                    p = sin(a0) * cos(b0);
-                    t = cos(a0) * sin(b0);
-                    chain = cos(a0) * cos(b0) + sin(a0) * sin(b0);
-                }
-                const double diff = (p - t) * (double)g.code_weight[c];
-                const double ad = fabs(diff);
-                s_loc += (ad < beta ? 0.5 * ad * ad / beta : ad - 0.5 * beta) * w;
-                const double dl = ad < beta ? diff / beta : (diff > 0.0 ? 1.0 : (diff < 0.0 ? -1.0 : 0.0));
-                gb[c] = (float)(dl * (double)g.code_weight[c] * chain * w * g.loc_scale);
-            }
-            if (dir_preds) {
-                // get_direction_target in float32, as the reference evaluates it
-                const float rot_gt = tg[6] + anchors[(size_t)n * 7 + 6];
-                const float val = rot_gt - g.dir_offset;
-                const float offset_rot = val - floorf(val / g.two_pi + 0.f) * g.two_pi;
-                int bin = (int)floorf(offset_rot / g.bin_width);
-                bin = bin < 0 ? 0 : (bin > g.bins - 1 ? g.bins - 1 : bin);
-                const float* dp = dir_preds + (size_t)e * g.bins;
-                double mx = -INFINITY;
-                for (int k = 0; k < g.bins; ++k) mx = fmax(mx, (double)dp[k]);
-                double z = 0.0;
-                for (int k = 0; k < g.bins; ++k) z += exp((double)dp[k] - mx);
-                const double lse = mx + log(z);
-                s_dir += (lse - (double)dp[bin]) * w;
-#pragma unroll
-                for (int k = 0; k < AH_MAX_BINS; ++k)
-                    if (k < g.bins) gd[k] = (float)((exp((double)dp[k] - lse) - (k == bin ? 1.0 : 0.0)) * w * g.dir_scale);
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 7; ++c) grad_box[(size_t)e * 7 + c] = gb[c];
-        if (dir_preds) {
-#pragma unroll
-            for (int k = 0; k < AH_MAX_BINS; ++k)
-                if (k < g.bins) grad_dir[(size_t)e * g.bins + k] = gd[k];
-        }
+        const double w = 1.0 / (double)max(num_pos[s], 1);
+        const int hot_col = label > 0 ? (g.num_class == 1 ? 0 : label - 1) : -1;      // class-agnostic: every positive is class 1
+        anchor_loss_row(g, label, w, w, hot_col, g.num_class, true, cls_preds + (size_t)e * g.num_class, box_preds + (size_t)e * 7,
+                        targets + (size_t)e * 7, anchors + (size_t)n * 7,
+                        dir_preds ? dir_preds + (size_t)e * g.bins : nullptr, grad_cls + (size_t)e * g.num_class,
+                        grad_box + (size_t)e * 7, dir_preds ? grad_dir + (size_t)e * g.bins : nullptr, s_cls, s_loc, s_dir);
+    }
+    const double sums[3] = {s_cls, s_loc, s_dir};
+    block_sums_to_partials<3, AL_THREADS>(sums, partials);
+}
+
+// AnchorHeadMulti: head h owns the rows [row0[h], row0[h + 1]) of the class-major table and predicts them in tensors of its own,
+// cls (b, rows_h, cols[h]), box (b, rows_h, 7), dir (b, rows_h, bins); labels, targets and anchors stay (b, n_anchors, ..).
+struct AnchorMultiLossCfg {
+    AnchorLossCfg t;                    // t.num_class: the detector's (1 = class-agnostic)
+    int n_heads, sin_diff;
+    double pos_w, neg_w;                // pos_cls_weight, neg_cls_weight
+    int row0[AH_MAX_CLASSES + 1];
+    int cols[AH_MAX_CLASSES];
+    int col_base[AH_MAX_CLASSES];       // a positive of label l is hot at column l - 1 - col_base[h]
+    const float* cls[AH_MAX_CLASSES];
+    const float* box[AH_MAX_CLASSES];
+    const float* dir[AH_MAX_CLASSES];
+    float* grad_cls[AH_MAX_CLASSES];
+    float* grad_box[AH_MAX_CLASSES];
+    float* grad_dir[AH_MAX_CLASSES];
+};
+
+// The elements run head after head, (scene, row) inside a head, so that neighbouring threads read neighbouring rows of one
+// head's tensors; the per-head descriptors are staged in LDS, where a per-thread head index costs nothing.
+__global__ __launch_bounds__(AL_THREADS) void anchor_multi_loss_kernel(const int32_t* __restrict__ labels,
+                                                                        const float* __restrict__ targets,
+                                                                        const int32_t* __restrict__ num_pos,
+                                                                        const float* __restrict__ anchors, AnchorMultiLossCfg g,
+                                                                        double* __restrict__ partials) {
+    __shared__ int h_row0[AH_MAX_CLASSES + 1], h_cols[AH_MAX_CLASSES], h_base[AH_MAX_CLASSES];
+    __shared__ const float* h_cls[AH_MAX_CLASSES];
+    __shared__ const float* h_box[AH_MAX_CLASSES];
+    __shared__ const float* h_dir[AH_MAX_CLASSES];
+    __shared__ float* h_gcls[AH_MAX_CLASSES];
+    __shared__ float* h_gbox[AH_MAX_CLASSES];
+    __shared__ float* h_gdir[AH_MAX_CLASSES];
+    if ((int)threadIdx.x < g.n_heads) {
+        const int h = (int)threadIdx.x;
+        h_cols[h] = g.cols[h];
+        h_base[h] = g.col_base[h];
+        h_cls[h] = g.cls[h];
+        h_box[h] = g.box[h];
+        h_dir[h] = g.dir[h];
+        h_gcls[h] = g.grad_cls[h];
+        h_gbox[h] = g.grad_box[h];
+        h_gdir[h] = g.grad_dir[h];
+    }
+    if ((int)threadIdx.x <= g.n_heads) h_row0[threadIdx.x] = g.row0[threadIdx.x];
+    __syncthreads();
+    double s_cls = 0.0, s_loc = 0.0, s_dir = 0.0;
+    const long long total = (long long)g.t.b * g.t.n_anchors;
+    const long long stride = (long long)gridDim.x * AL_THREADS;
+    for (long long e = (long long)blockIdx.x * AL_THREADS + threadIdx.x; e < total; e += stride) {
+        int h = 0;      // head h holds the elements [b * row0[h], b * row0[h + 1])
+        while (h + 1 < g.n_heads && e >= (long long)g.t.b * h_row0[h + 1]) ++h;
+        const int rows = h_row0[h + 1] - h_row0[h];
+        const long long local = e - (long long)g.t.b * h_row0[h];
+        const int s = (int)(local / rows);
+        const int r = (int)(local % rows);
+        const int n = h_row0[h] + r;
+        const size_t at = (size_t)s * g.t.n_anchors + n;      // in labels and targets
+        const size_t hr = (size_t)s * rows + r;               // in the head's tensors
+        const int label = labels[at];
+        const double w = 1.0 / (double)max(num_pos[s], 1);
+        const double w_cls = (label > 0 ? g.pos_w : g.neg_w) * w;
+        const int c = h_cols[h];
+        const int hot_col = label > 0 ? (g.t.num_class == 1 ? 0 : label - 1 - h_base[h]) : -1;
+        const float* dir = h_dir[h];
+        anchor_loss_row(g.t, label, w_cls, w, hot_col, c, g.sin_diff != 0, h_cls[h] + hr * c, h_box[h] + hr * 7, targets + at * 7,
+                        anchors + (size_t)n * 7, dir ? dir + hr * g.t.bins : nullptr, h_gcls[h] + hr * c,
+                        h_gbox[h] + hr * 7, dir ? h_gdir[h] + hr * g.t.bins : nullptr, s_cls, s_loc, s_dir);
     }
     const double sums[3] = {s_cls, s_loc, s_dir};
     block_sums_to_partials<3, AL_THREADS>(sums, partials);
@@ -338,61 +438,91 @@ __global__ __launch_bounds__(256) void anchor_decode_kernel(const float* __restr
 }  // namespace pda
 
 // ---- C entry points --------------------------------------------------------------------------------------------------------------
-PDA_API int pda_anchor_assign_targets(const float* gt_boxes, int gt_cols, int b, int m, const float* anchors, int n_anchors,
-                                      int n_cls, const int32_t* class_label, const float* matched, const float* unmatched,
-                                      const int32_t* class_count, uint32_t* col_max, int32_t* box_cls_labels,
-                                      float* box_reg_targets, float* reg_weights, int32_t* num_pos, pda_stream_t stream) {
-    PDA_REQUIRE(b >= 0 && m >= 0 && n_anchors >= 0, "pda_anchor_assign_targets: b=%d m=%d n_anchors=%d", b, m, n_anchors);
-    PDA_REQUIRE(gt_cols == 8, "pda_anchor_assign_targets: gt_cols=%d, boxes must have 7 + 1 columns", gt_cols);
-    PDA_REQUIRE(n_cls >= 1 && n_cls <= pda::AH_MAX_CLASSES, "pda_anchor_assign_targets: n_cls=%d outside 1..%d", n_cls,
-                pda::AH_MAX_CLASSES);
-    PDA_REQUIRE(b <= 65535, "pda_anchor_assign_targets: batch %d > 65535", b);
-    PDA_REQUIRE((int64_t)b * n_anchors < ((int64_t)1 << 31) / 8, "pda_anchor_assign_targets: b=%d n_anchors=%d too large", b,
-                n_anchors);
-    PDA_REQUIRE((int64_t)b * m < ((int64_t)1 << 28), "pda_anchor_assign_targets: b=%d m=%d too large", b, m);
+namespace pda {
+namespace {
+
+// Both layouts of the anchor table.  class_count: the slots a class owns at every location (location-major), or with
+// `segmented` the contiguous rows it owns (class-major).
+int assign_targets(const char* what, bool segmented, const float* gt_boxes, int gt_cols, int b, int m, const float* anchors,
+                   int n_anchors, int n_cls, const int32_t* class_label, const float* matched, const float* unmatched,
+                   const int32_t* class_count, uint32_t* col_max, int32_t* box_cls_labels, float* box_reg_targets,
+                   float* reg_weights, int32_t* num_pos, pda_stream_t stream) {
+    PDA_REQUIRE(b >= 0 && m >= 0 && n_anchors >= 0, "%s: b=%d m=%d n_anchors=%d", what, b, m, n_anchors);
+    PDA_REQUIRE(gt_cols == 8, "%s: gt_cols=%d, boxes must have 7 + 1 columns", what, gt_cols);
+    PDA_REQUIRE(n_cls >= 1 && n_cls <= AH_MAX_CLASSES, "%s: n_cls=%d outside 1..%d", what, n_cls, AH_MAX_CLASSES);
+    PDA_REQUIRE(b <= 65535, "%s: batch %d > 65535", what, b);
+    PDA_REQUIRE((int64_t)b * n_anchors < ((int64_t)1 << 31) / 8, "%s: b=%d n_anchors=%d too large", what, b, n_anchors);
+    PDA_REQUIRE((int64_t)b * m < ((int64_t)1 << 28), "%s: b=%d m=%d too large", what, b, m);
     if (b == 0 || n_anchors == 0) return PDA_OK;
-    PDA_REQUIRE(class_label && matched && unmatched && class_count, "pda_anchor_assign_targets: null class array");
-    pda::AnchorAssignCfg g{};
+    PDA_REQUIRE(class_label && matched && unmatched && class_count, "%s: null class array", what);
+    AnchorAssignCfg g{};
     g.b = b;
     g.m = m;
     g.cols = gt_cols;
     g.n_anchors = n_anchors;
     g.n_cls = n_cls;
-    int slots = 0;
+    int64_t total = 0;
     for (int c = 0; c < n_cls; ++c) {
-        PDA_REQUIRE(class_label[c] >= 1 && class_label[c] <= 1048576, "pda_anchor_assign_targets: class_label[%d]=%d", c,
-                    class_label[c]);
+        PDA_REQUIRE(class_label[c] >= 1 && class_label[c] <= 1048576, "%s: class_label[%d]=%d", what, c, class_label[c]);
         for (int d = 0; d < c; ++d)
-            PDA_REQUIRE(class_label[d] != class_label[c], "pda_anchor_assign_targets: anchor classes %d and %d share label %d",
-                        d, c, class_label[c]);
-        PDA_REQUIRE(class_count[c] >= 1 && class_count[c] <= pda::AH_MAX_SLOTS, "pda_anchor_assign_targets: class_count[%d]=%d",
-                    c, class_count[c]);
+            PDA_REQUIRE(class_label[d] != class_label[c], "%s: anchor classes %d and %d share label %d", what, d, c,
+                        class_label[c]);
+        PDA_REQUIRE(class_count[c] >= 1 && (segmented || class_count[c] <= AH_MAX_SLOTS), "%s: class_count[%d]=%d", what, c,
+                    class_count[c]);
         g.label[c] = class_label[c];
         g.matched[c] = matched[c];
         g.unmatched[c] = unmatched[c];
-        g.first_slot[c] = slots;
-        slots += class_count[c];
-        PDA_REQUIRE(slots <= pda::AH_MAX_SLOTS, "pda_anchor_assign_targets: more than %d anchors per location", pda::AH_MAX_SLOTS);
+        g.first[c] = (int)total;
+        total += class_count[c];
+        PDA_REQUIRE(segmented || total <= AH_MAX_SLOTS, "%s: more than %d anchors per location", what, AH_MAX_SLOTS);
+        PDA_REQUIRE(total <= n_anchors || !segmented, "%s: the classes own more than the n_anchors=%d rows of the table", what,
+                    n_anchors);
     }
-    g.first_slot[n_cls] = slots;
-    g.slots = slots;
-    PDA_REQUIRE(n_anchors % slots == 0, "pda_anchor_assign_targets: n_anchors=%d is no multiple of %d anchors per location",
-                n_anchors, slots);
-    PDA_REQUIRE(anchors && box_cls_labels && box_reg_targets && reg_weights && num_pos, "pda_anchor_assign_targets: null pointer");
-    PDA_REQUIRE(m == 0 || (gt_boxes && col_max), "pda_anchor_assign_targets: null gt_boxes or col_max");
+    g.first[n_cls] = (int)total;
+    g.slots = segmented ? 0 : (int)total;
+    if (segmented)
+        PDA_REQUIRE(total == n_anchors, "%s: the classes own %d rows of a table of n_anchors=%d", what, (int)total, n_anchors);
+    else
+        PDA_REQUIRE(n_anchors % g.slots == 0, "%s: n_anchors=%d is no multiple of %d anchors per location", what, n_anchors,
+                    g.slots);
+    PDA_REQUIRE(anchors && box_cls_labels && box_reg_targets && reg_weights && num_pos, "%s: null pointer", what);
+    PDA_REQUIRE(m == 0 || (gt_boxes && col_max), "%s: null gt_boxes or col_max", what);
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(num_pos, 0, (size_t)b * 4, st) != hipSuccess ||
         (m > 0 && hipMemsetAsync(col_max, 0, (size_t)b * m * 4, st) != hipSuccess)) {
-        pda::set_error("pda_anchor_assign_targets: hipMemsetAsync failed");
+        set_error("%s: hipMemsetAsync failed", what);
         return PDA_ERR_LAUNCH;
     }
-    const dim3 grid(pda::divup(n_anchors, pda::AH_THREADS), b);
+    const dim3 grid(divup(n_anchors, AH_THREADS), b);
+    auto first = segmented ? anchor_assign_kernel<false, true> : anchor_assign_kernel<false, false>;
+    auto second = segmented ? anchor_assign_kernel<true, true> : anchor_assign_kernel<true, false>;
     if (m > 0)
-        hipLaunchKernelGGL(pda::anchor_assign_kernel<false>, grid, dim3(pda::AH_THREADS), 0, st, anchors, gt_boxes, g, col_max,
-                           (int32_t*)nullptr, (float*)nullptr, (float*)nullptr, (int32_t*)nullptr);
-    hipLaunchKernelGGL(pda::anchor_assign_kernel<true>, grid, dim3(pda::AH_THREADS), 0, st, anchors, gt_boxes, g, col_max,
-                       box_cls_labels, box_reg_targets, reg_weights, num_pos);
-    return pda::check_launch("pda_anchor_assign_targets");
+        hipLaunchKernelGGL(first, grid, dim3(AH_THREADS), 0, st, anchors, gt_boxes, g, col_max, (int32_t*)nullptr,
+                           (float*)nullptr, (float*)nullptr, (int32_t*)nullptr);
+    hipLaunchKernelGGL(second, grid, dim3(AH_THREADS), 0, st, anchors, gt_boxes, g, col_max, box_cls_labels, box_reg_targets,
+                       reg_weights, num_pos);
+    return check_launch(what);
+}
+
+}  // namespace
+}  // namespace pda
+
+PDA_API int pda_anchor_assign_targets(const float* gt_boxes, int gt_cols, int b, int m, const float* anchors, int n_anchors,
+                                      int n_cls, const int32_t* class_label, const float* matched, const float* unmatched,
+                                      const int32_t* class_count, uint32_t* col_max, int32_t* box_cls_labels,
+                                      float* box_reg_targets, float* reg_weights, int32_t* num_pos, pda_stream_t stream) {
+    return pda::assign_targets("pda_anchor_assign_targets", false, gt_boxes, gt_cols, b, m, anchors, n_anchors, n_cls, class_label,
+                               matched, unmatched, class_count, col_max, box_cls_labels, box_reg_targets, reg_weights, num_pos,
+                               stream);
+}
+
+PDA_API int pda_anchor_multi_assign_targets(const float* gt_boxes, int gt_cols, int b, int m, const float* anchors, int n_anchors,
+                                            int n_cls, const int32_t* class_label, const float* matched, const float* unmatched,
+                                            const int32_t* class_rows, uint32_t* col_max, int32_t* box_cls_labels,
+                                            float* box_reg_targets, float* reg_weights, int32_t* num_pos, pda_stream_t stream) {
+    return pda::assign_targets("pda_anchor_multi_assign_targets", true, gt_boxes, gt_cols, b, m, anchors, n_anchors, n_cls,
+                               class_label, matched, unmatched, class_rows, col_max, box_cls_labels, box_reg_targets, reg_weights,
+                               num_pos, stream);
 }
 
 PDA_API int64_t pda_anchor_loss_blocks(int64_t n) {
@@ -433,6 +563,76 @@ PDA_API int pda_anchor_loss(const float* cls_preds, const float* box_preds, cons
     hipLaunchKernelGGL(pda::anchor_loss_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partials, blocks, g.cls_scale,
                        g.loc_scale, g.dir_scale, out);
     return pda::check_launch("pda_anchor_loss");
+}
+
+PDA_API int64_t pda_anchor_multi_loss_blocks(int64_t n) {
+    return pda::partial_blocks(n, (int64_t)pda::AL_THREADS * pda::AL_PER_THREAD, pda::AL_MAX_BLOCKS);
+}
+
+PDA_API int pda_anchor_multi_loss(const float* const* cls_preds, const float* const* box_preds, const float* const* dir_cls_preds,
+                                  int n_heads, const int32_t* head_rows, const int32_t* head_cols, const int32_t* head_col_base,
+                                  const int32_t* box_cls_labels, const float* box_reg_targets, const int32_t* num_pos,
+                                  const float* anchors, int b, int n_anchors, int num_class, int bins, const float* code_weights,
+                                  double cls_weight, double loc_weight, double dir_weight, double dir_offset, double pos_cls_weight,
+                                  double neg_cls_weight, float* const* grad_cls, float* const* grad_box, float* const* grad_dir,
+                                  double* partials, float* out, pda_stream_t stream) {
+    PDA_REQUIRE(b >= 1 && n_anchors >= 1, "pda_anchor_multi_loss: b=%d n_anchors=%d", b, n_anchors);
+    PDA_REQUIRE((int64_t)b * n_anchors < ((int64_t)1 << 31) / 32, "pda_anchor_multi_loss: b=%d n_anchors=%d too large", b, n_anchors);
+    PDA_REQUIRE(n_heads >= 1 && n_heads <= pda::AH_MAX_CLASSES, "pda_anchor_multi_loss: n_heads=%d outside 1..%d", n_heads,
+                pda::AH_MAX_CLASSES);
+    PDA_REQUIRE(num_class >= 1 && num_class <= pda::AH_MAX_CLASSES, "pda_anchor_multi_loss: num_class=%d outside 1..%d", num_class,
+                pda::AH_MAX_CLASSES);
+    PDA_REQUIRE(!dir_cls_preds || (bins >= 1 && bins <= pda::AH_MAX_BINS), "pda_anchor_multi_loss: bins=%d outside 1..%d", bins,
+                pda::AH_MAX_BINS);
+    PDA_REQUIRE(cls_preds && box_preds && head_rows && head_cols && head_col_base && grad_cls && grad_box,
+                "pda_anchor_multi_loss: null head array");
+    PDA_REQUIRE(!dir_cls_preds || grad_dir, "pda_anchor_multi_loss: null grad_dir");
+    pda::AnchorMultiLossCfg g{};
+    int64_t rows = 0;
+    for (int h = 0; h < n_heads; ++h) {
+        PDA_REQUIRE(head_rows[h] >= 1, "pda_anchor_multi_loss: head_rows[%d]=%d", h, head_rows[h]);
+        PDA_REQUIRE(head_cols[h] >= 1 && head_col_base[h] >= 0 && head_cols[h] + head_col_base[h] <= num_class,
+                    "pda_anchor_multi_loss: head %d has columns %d..%d of num_class=%d", h, head_col_base[h],
+                    head_col_base[h] + head_cols[h], num_class);
+        g.row0[h] = (int)rows;
+        rows += head_rows[h];
+        PDA_REQUIRE(rows <= n_anchors, "pda_anchor_multi_loss: the heads own more than the n_anchors=%d rows", n_anchors);
+        g.cols[h] = head_cols[h];
+        g.col_base[h] = head_col_base[h];
+        PDA_REQUIRE(cls_preds[h] && box_preds[h] && grad_cls[h] && grad_box[h] && (!dir_cls_preds || (dir_cls_preds[h] && grad_dir[h])),
+                    "pda_anchor_multi_loss: null pointer of head %d", h);
+        g.cls[h] = cls_preds[h];
+        g.box[h] = box_preds[h];
+        g.dir[h] = dir_cls_preds ? dir_cls_preds[h] : nullptr;
+        g.grad_cls[h] = grad_cls[h];
+        g.grad_box[h] = grad_box[h];
+        g.grad_dir[h] = dir_cls_preds ? grad_dir[h] : nullptr;
+    }
+    g.row0[n_heads] = (int)rows;
+    PDA_REQUIRE(rows == n_anchors, "pda_anchor_multi_loss: the heads own %d rows of n_anchors=%d", (int)rows, n_anchors);
+    PDA_REQUIRE(box_cls_labels && box_reg_targets && num_pos && anchors && code_weights && partials && out,
+                "pda_anchor_multi_loss: null pointer");
+    g.n_heads = n_heads;
+    g.sin_diff = dir_cls_preds ? 1 : 0;      // anchor_head_multi.py adds the sin difference only behind a direction classifier
+    g.pos_w = pos_cls_weight;
+    g.neg_w = neg_cls_weight;
+    g.t.b = b;
+    g.t.n_anchors = n_anchors;
+    g.t.num_class = num_class;
+    g.t.bins = dir_cls_preds ? bins : 0;
+    for (int c = 0; c < 7; ++c) g.t.code_weight[c] = code_weights[c];
+    g.t.dir_offset = (float)dir_offset;
+    g.t.two_pi = (float)(2.0 * M_PI);
+    g.t.bin_width = (float)(2.0 * M_PI / (dir_cls_preds ? bins : 1));
+    g.t.cls_scale = cls_weight / b;
+    g.t.loc_scale = loc_weight / b;
+    g.t.dir_scale = dir_cls_preds ? dir_weight / b : 0.0;
+    const int blocks = (int)pda_anchor_multi_loss_blocks((int64_t)b * n_anchors);
+    hipLaunchKernelGGL(pda::anchor_multi_loss_kernel, dim3(blocks), dim3(pda::AL_THREADS), 0, (hipStream_t)stream, box_cls_labels,
+                       box_reg_targets, num_pos, anchors, g, partials);
+    hipLaunchKernelGGL(pda::anchor_loss_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partials, blocks, g.t.cls_scale,
+                       g.t.loc_scale, g.t.dir_scale, out);
+    return pda::check_launch("pda_anchor_multi_loss");
 }
 
 PDA_API int pda_anchor_decode(const float* box_preds, const float* dir_cls_preds, const float* anchors, int b, int n_anchors,

@@ -113,6 +113,55 @@ __global__ __launch_bounds__(64) void nms_scan_kernel(const unsigned long long* 
     if (lane == 0) num_keep[scene] = num;
 }
 
+// multi_classes_nms' result for one scene per workgroup: the scene's c problems (head after head, class column after class
+// column) each contribute their first min(num_keep, cap) kept boxes, in score order; the rows behind them are zero.
+constexpr int MN_THREADS = 256;
+constexpr int MN_MAX_PROBLEMS = 256;
+
+__global__ __launch_bounds__(MN_THREADS) void multi_nms_compact_kernel(
+        const float* __restrict__ boxes, const float* __restrict__ scores, const long long* __restrict__ keep,
+        const int* __restrict__ num_keep, const int* __restrict__ label_map, int c, int k, int cap,
+        float* __restrict__ pred_boxes, float* __restrict__ pred_scores, long long* __restrict__ pred_labels,
+        int* __restrict__ num_pred) {
+    __shared__ int first[MN_MAX_PROBLEMS + 1];
+    const int scene = blockIdx.x;
+    if (threadIdx.x == 0) {
+        int at = 0;
+        for (int p = 0; p < c; ++p) {
+            first[p] = at;
+            at += max(0, min(num_keep[scene * c + p], cap));
+        }
+        first[c] = at;
+        num_pred[scene] = at;
+    }
+    __syncthreads();
+    const int total = first[c], rows = c * cap;
+    float* ob = pred_boxes + (size_t)scene * rows * 7;
+    float* os = pred_scores + (size_t)scene * rows;
+    long long* ol = pred_labels + (size_t)scene * rows;
+    for (int j = threadIdx.x; j < rows; j += MN_THREADS) {
+        const int p = j / cap, r = j % cap;
+        if (r < first[p + 1] - first[p]) {
+            const size_t problem = (size_t)scene * c + p;
+            const long long i = keep[problem * k + r];
+            if (i >= 0 && i < k) {      // what pda_nms_bev wrote for r < num_keep
+                const int o = first[p] + r;
+                const float* src = boxes + (problem * k + (size_t)i) * 7;
+#pragma unroll
+                for (int q = 0; q < 7; ++q) ob[(size_t)o * 7 + q] = src[q];
+                os[o] = scores[problem * k + (size_t)i];
+                ol[o] = label_map[p];
+            }
+        }
+        if (j >= total) {
+#pragma unroll
+            for (int q = 0; q < 7; ++q) ob[(size_t)j * 7 + q] = 0.f;
+            os[j] = 0.f;
+            ol[j] = 0;
+        }
+    }
+}
+
 template <bool IOU>
 static int launch_boxes_bev(const float* a, const float* b, float* out, int na, int nb, hipStream_t stream, const char* what) {
     PDA_REQUIRE(na >= 0 && nb >= 0, "%s: na=%d nb=%d", what, na, nb);
@@ -158,4 +207,22 @@ PDA_API int pda_nms_bev(const float* boxes, const int32_t* num_valid, int64_t* k
     hipLaunchKernelGGL(pda::nms_scan_kernel, dim3(b), dim3(64), 0, (hipStream_t)stream, (const unsigned long long*)mask_scratch,
                        num_valid, (long long*)keep, num_keep, n, cb);
     return pda::check_launch("pda_nms_bev");
+}
+
+PDA_API int pda_multi_nms_compact(const float* boxes, const float* scores, const int64_t* keep, const int32_t* num_keep,
+                                  const int32_t* label_map, int b, int c, int k, int post_max, float* pred_boxes,
+                                  float* pred_scores, int64_t* pred_labels, int32_t* num_pred, pda_stream_t stream) {
+    PDA_REQUIRE(b >= 0 && k >= 0 && post_max >= 0, "pda_multi_nms_compact: b=%d k=%d post_max=%d", b, k, post_max);
+    PDA_REQUIRE(c >= 1 && c <= pda::MN_MAX_PROBLEMS, "pda_multi_nms_compact: c=%d problems a scene outside 1..%d", c,
+                pda::MN_MAX_PROBLEMS);
+    PDA_REQUIRE(b <= 65535 && (int64_t)b * c * k < ((int64_t)1 << 31) / 8, "pda_multi_nms_compact: b=%d c=%d k=%d too large", b, c, k);
+    if (b == 0) return PDA_OK;
+    PDA_REQUIRE(num_keep && num_pred, "pda_multi_nms_compact: null counts");
+    const int cap = post_max < k ? post_max : k;      // the rows a problem can contribute
+    PDA_REQUIRE(cap == 0 || (boxes && scores && keep && label_map && pred_boxes && pred_scores && pred_labels),
+                "pda_multi_nms_compact: null pointer");
+    hipLaunchKernelGGL(pda::multi_nms_compact_kernel, dim3(b), dim3(pda::MN_THREADS), 0, (hipStream_t)stream, boxes, scores,
+                       (const long long*)keep, num_keep, label_map, c, k, cap, pred_boxes, pred_scores, (long long*)pred_labels,
+                       num_pred);
+    return pda::check_launch("pda_multi_nms_compact");
 }

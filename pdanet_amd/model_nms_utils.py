@@ -47,12 +47,16 @@ def class_agnostic_nms_batched(box_scores, box_preds, nms_config, score_thresh=N
 
 
 def post_processing(batch_dict, post_process_cfg, num_class):
-    """detector3d_template.py:179-290 for point heads (`batch_index` layout, equal points per scene).
+    """detector3d_template.py:179-290 for point heads (`batch_index` layout, equal points per scene); with
+    NMS_CONFIG.MULTI_CLASSES_NMS and a list batch_cls_preds (a separate multihead) multi_classes_nms_batched.
     Returns padded device tensors: pred_boxes (B, K, 7+C), pred_scores (B, K), pred_labels (B, K) int64
     (0 = padding) and num_pred (B) int32; with RECALL_MODE 'normal' (the default) and gt_boxes in batch_dict also
     recall (1 + len(RECALL_THRESH_LIST)) int64 [gt, rcnn_<t>...], this batch's recall counts."""
     if post_process_cfg["NMS_CONFIG"]["MULTI_CLASSES_NMS"]:
-        raise NotImplementedError("MULTI_CLASSES_NMS (not used by PDA-SSD.yaml)")
+        if not isinstance(batch_dict['batch_cls_preds'], list):
+            raise NotImplementedError("MULTI_CLASSES_NMS with one batch_cls_preds tensor (the reference's arange(1, num_class) "
+                                      "label mapping fails its own assertion there); a separate multihead passes a list")
+        return _post_processing_multi_classes(batch_dict, post_process_cfg)
     B = batch_dict['batch_size']
     box_preds = batch_dict['batch_box_preds'].view(B, -1, batch_dict['batch_box_preds'].shape[-1])
     cls_preds = batch_dict['batch_cls_preds'].view(B, box_preds.shape[1], -1)
@@ -78,6 +82,75 @@ def post_processing(batch_dict, post_process_cfg, num_class):
     padded = {'pred_boxes': pred_boxes, 'pred_scores': sel_scores, 'pred_labels': pred_labels, 'num_pred': num}
     if post_process_cfg.get('RECALL_MODE', 'normal') == 'normal' and 'gt_boxes' in batch_dict:
         # (1 + n) int64 [gt, rcnn_<t>...] of this batch, on the device
+        padded['recall'] = recall_record(pred_boxes, num, batch_dict['gt_boxes'], post_process_cfg['RECALL_THRESH_LIST'])
+    return padded
+
+
+def multi_classes_nms_batched(cls_preds, box_preds, label_mapping, nms_config, score_thresh=None, normalized=False):
+    """model_nms_utils.multi_classes_nms under detector3d_template.post_processing's loop over heads, for all scenes at once.
+    cls_preds: a list of per-head (B, N_h, C_h) logits (scores when `normalized`); box_preds (B, sum N_h, >= 7), head h owning
+    the N_h rows behind those of the heads before it; label_mapping: per head the (C_h) 1-based labels of its columns.
+    Every (scene, head, class column) is one NMS problem: its scores >= score_thresh, sorted, the first
+    min(N_h, NMS_PRE_MAXSIZE) of them gathered -- only those rows, so a head may have more rows than pda_nms_bev takes --
+    and all problems go through one pda_nms_bev and one pda_multi_nms_compact.  Returns pred_boxes (B, K, 7), pred_scores
+    (B, K), pred_labels (B, K) int64 (0 = padding) and num_pred (B) int32, K = sum C_h * min(NMS_POST_MAXSIZE, max_h
+    min(N_h, NMS_PRE_MAXSIZE)); a scene's rows run head after head, class column after class column, by descending score, as
+    the reference concatenates them.  No host read.  Equal scores within a column are outside the parity claim: the
+    reference leaves their order to topk, this to sort."""
+    if nms_config["NMS_TYPE"] not in ("nms_gpu", "nms_normal_gpu"):
+        raise NotImplementedError(nms_config["NMS_TYPE"])
+    if len(cls_preds) != len(label_mapping) or not cls_preds:
+        raise ValueError("one label mapping per head")
+    B = box_preds.shape[0]
+    pre, post = int(nms_config["NMS_PRE_MAXSIZE"]), int(nms_config["NMS_POST_MAXSIZE"])
+    if sum(x.shape[1] for x in cls_preds) != box_preds.shape[1]:
+        raise ValueError("the heads score %d rows, box_preds has %d" % (sum(x.shape[1] for x in cls_preds), box_preds.shape[1]))
+    K = max(min(x.shape[1], pre) for x in cls_preds)
+    boxes, scores, num_valid = [], [], []
+    start = 0
+    for x, mapping in zip(cls_preds, label_mapping):
+        n, c = x.shape[1], x.shape[2]
+        assert c == len(mapping)
+        k = min(n, pre)
+        s = (x if normalized else torch.sigmoid(x)).transpose(1, 2)                                  # (B, c, n)
+        ok = s >= score_thresh if score_thresh is not None else torch.ones_like(s, dtype=torch.bool)
+        sorted_scores, order = torch.where(ok, s, torch.full_like(s, float("-inf"))).sort(dim=2, descending=True)
+        sorted_scores, order = sorted_scores[..., :k], order[..., :k]          # before the gather: k rows a problem, not n
+        rows = box_preds[:, start:start + n, 0:7].unsqueeze(1).expand(B, c, n, 7)
+        picked = torch.gather(rows, 2, order.unsqueeze(-1).expand(B, c, k, 7))
+        boxes.append(torch.nn.functional.pad(picked, (0, 0, 0, K - k)))
+        scores.append(torch.nn.functional.pad(sorted_scores, (0, K - k)))
+        num_valid.append(ok.sum(dim=2).clamp(max=k).to(torch.int32))
+        start += n
+    boxes = torch.cat(boxes, dim=1).to(F32).contiguous()                                             # (B, C, K, 7)
+    scores = torch.cat(scores, dim=1).to(F32).contiguous()
+    num_valid = torch.cat(num_valid, dim=1).contiguous()
+    C = boxes.shape[1]
+    labels = torch.cat([m.reshape(-1) for m in label_mapping]).to(device=boxes.device, dtype=torch.int32).contiguous()
+    keep, num_keep = iou3d_nms_utils.nms_batched(boxes.view(B * C, K, 7), nms_config["NMS_THRESH"], num_valid=num_valid.view(-1),
+                                                 normal=nms_config["NMS_TYPE"] == "nms_normal_gpu")
+    rows = C * min(post, K)
+    dev = boxes.device
+    pred_boxes = torch.empty((B, rows, 7), dtype=F32, device=dev)
+    pred_scores = torch.empty((B, rows), dtype=F32, device=dev)
+    pred_labels = torch.empty((B, rows), dtype=torch.int64, device=dev)
+    num_pred = torch.empty((B,), dtype=torch.int32, device=dev)
+    if B:
+        _call("pda_multi_nms_compact", boxes, _chk(boxes, "boxes", F32), _chk(scores, "scores", F32), _chk(keep, "keep", torch.int64),
+              _chk(num_keep, "num_keep", I32), _chk(labels, "label_mapping", I32), B, C, K, post, pred_boxes.data_ptr(),
+              pred_scores.data_ptr(), pred_labels.data_ptr(), num_pred.data_ptr())
+    return pred_boxes, pred_scores, pred_labels, num_pred
+
+
+def _post_processing_multi_classes(batch_dict, post_process_cfg):
+    """post_processing with NMS_CONFIG.MULTI_CLASSES_NMS and a list batch_cls_preds (detector3d_template.py:225-250)."""
+    B = batch_dict['batch_size']
+    box_preds = batch_dict['batch_box_preds'].view(B, -1, batch_dict['batch_box_preds'].shape[-1])
+    pred_boxes, pred_scores, pred_labels, num = multi_classes_nms_batched(
+        batch_dict['batch_cls_preds'], box_preds, batch_dict['multihead_label_mapping'], post_process_cfg["NMS_CONFIG"],
+        score_thresh=post_process_cfg["SCORE_THRESH"], normalized=batch_dict['cls_preds_normalized'])
+    padded = {'pred_boxes': pred_boxes, 'pred_scores': pred_scores, 'pred_labels': pred_labels, 'num_pred': num}
+    if post_process_cfg.get('RECALL_MODE', 'normal') == 'normal' and 'gt_boxes' in batch_dict:
         padded['recall'] = recall_record(pred_boxes, num, batch_dict['gt_boxes'], post_process_cfg['RECALL_THRESH_LIST'])
     return padded
 

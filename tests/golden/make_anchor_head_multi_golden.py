@@ -1,0 +1,398 @@
+#!/usr/bin/env python
+"""Generates tests/golden/anchor_head_multi.npz: the REFERENCE's own AnchorHeadMulti, AxisAlignedTargetAssigner (use_multihead)
+and Detector3DTemplate.post_processing over model_nms_utils.multi_classes_nms, imported from where they lie and run on CPU
+tensors.  The extension modules are stubs, those of make_second_iou_golden.py (whose loader this uses): iou3d_nms_cuda.nms_gpu
+and boxes_overlap_bev_gpu are the repository's C oracle (oracle/).  Nothing of the reference is copied; what is committed is
+data.
+
+    python tests/golden/make_anchor_head_multi_golden.py <checkout of the reference>
+
+Range [0, -3.6, -3, 8.8, 3.6, 1], voxels of 0.4 m, stride 2: an 11 x 9 map, so that neither a head's rows nor N is a multiple of
+64.  B = 2, M = 12.  Three configurations:
+  a  the head of kitti_models/second_multihead.yaml: three one-class heads, SEPARATE_MULTIHEAD, SHARED_CONV_NUM_FILTER, the
+     direction classifier: 3 x 198 = 594 anchors a scene;
+  b  heads [Car] and [Pedestrian, Cyclist], separate (1 and 2 logit columns, the second head's column base 1); Pedestrian has
+     two anchor sizes and Cyclist three rotations: 198 + 396 + 297 = 891 anchors;
+  c  the heads of b with SEPARATE_MULTIHEAD False (every prediction one tensor, num_class columns), no direction classifier
+     (anchor_head_multi.py then takes no sin difference), non-uniform code_weights, and one head with LAYER_NUMS and a
+     SEPARATE_REG_CONFIG for the state-dict keys.
+Batches as in make_anchor_head_golden.py: x = [rich scene, one class only], y = [empty, one class only], z = [empty, empty].
+The rich scene holds two identical boxes, a square box centred on an anchor location (both rotations tie for its column
+maximum), a small box whose best anchor lies below unmatched_threshold (a forced positive), a box that overlaps no anchor, a
+heading past pi / 4, an interior zero row and trailing zero rows; in the second scene every head but Car's is pure background.
+Per batch: the targets, the four loss terms and the gradient of every prediction; per configuration the decoded boxes.
+
+post_a, post_b: post_processing with MULTI_CLASSES_NMS on logits that are, column by column, a permutation of an even grid
+(about 70 % of it above the threshold), and the decoded boxes of random codes, SCORE_THRESH
+0.1, NMS_THRESH 0.1, NMS_PRE_MAXSIZE 96 (below every head's rows, and below the rows above the threshold of some column),
+NMS_POST_MAXSIZE 8 (below the survivors of some column); one column of scene 1 has nothing above the threshold.  The maker
+asserts these cases, that the scores of a column are pairwise 1e-5 apart and 1e-4 away from the threshold, and on the
+targets' inputs what make_anchor_head_golden.py asserts.
+"""
+import json
+import os
+import sys
+import types
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+sys.path.insert(0, ROOT)
+import make_second_iou_golden as loader  # noqa: E402
+import oracle  # noqa: E402
+from pdanet_amd.config import to_attr  # noqa: E402
+
+OUT = os.path.join(HERE, "anchor_head_multi.npz")
+B, M = 2, 12
+PCR, VOXEL = [0, -3.6, -3, 8.8, 3.6, 1], [0.4, 0.4, 4]
+CLASS_NAMES = ['Car', 'Pedestrian', 'Cyclist']
+TARGET = {'NAME': 'AxisAlignedTargetAssigner', 'POS_FRACTION': -1.0, 'SAMPLE_SIZE': 512, 'NORM_BY_NUM_EXAMPLES': False,
+          'MATCH_HEIGHT': False, 'BOX_CODER': 'ResidualCoder'}
+
+
+def generator(ped_sizes, cyc_rotations):
+    base = {'anchor_bottom_heights': [-1.6], 'align_center': False, 'feature_map_stride': 2}
+    return [dict(base, class_name='Car', anchor_sizes=[[3.9, 1.6, 1.56]], anchor_rotations=[0, 1.57], matched_threshold=0.6,
+                 unmatched_threshold=0.45),
+            dict(base, class_name='Pedestrian', anchor_sizes=ped_sizes, anchor_rotations=[0, 1.57], matched_threshold=0.5,
+                 unmatched_threshold=0.35),
+            dict(base, class_name='Cyclist', anchor_sizes=[[1.76, 0.6, 1.73]], anchor_rotations=cyc_rotations,
+                 matched_threshold=0.5, unmatched_threshold=0.35)]
+
+
+def head_cfg(separate, heads, gen, direction, code_weights, **more):
+    cfg = {'CLASS_AGNOSTIC': False, 'USE_MULTIHEAD': True, 'SEPARATE_MULTIHEAD': separate, 'ANCHOR_GENERATOR_CONFIG': gen,
+           'RPN_HEAD_CFGS': heads, 'TARGET_ASSIGNER_CONFIG': TARGET,
+           'LOSS_CONFIG': {'LOSS_WEIGHTS': {'cls_weight': 1.0, 'loc_weight': 2.0, 'dir_weight': 0.2, 'code_weights': code_weights}}}
+    if direction:
+        cfg.update({'USE_DIRECTION_CLASSIFIER': True, 'DIR_OFFSET': 0.78539, 'DIR_LIMIT_OFFSET': 0.0, 'NUM_DIR_BINS': 2})
+    cfg.update(more)
+    return cfg
+
+
+TWO_HEADS = [{'HEAD_CLS_NAME': ['Car']}, {'HEAD_CLS_NAME': ['Pedestrian', 'Cyclist']}]
+CONFIGS = {
+    'a': head_cfg(True, [{'HEAD_CLS_NAME': [n]} for n in CLASS_NAMES], generator([[0.8, 0.6, 1.73]], [0, 1.57]), True, [1.0] * 7,
+                  SHARED_CONV_NUM_FILTER=8),
+    'b': head_cfg(True, TWO_HEADS, generator([[0.8, 0.6, 1.73], [0.6, 0.9, 1.5]], [0, 1.57, 0.5]), True, [1.0] * 7),
+    'c': head_cfg(False, [TWO_HEADS[0], dict(TWO_HEADS[1], LAYER_NUMS=[1], LAYER_STRIDES=[1], NUM_FILTERS=[16],
+                                             UPSAMPLE_STRIDES=[1], NUM_UPSAMPLE_FILTERS=[16])],
+                  generator([[0.8, 0.6, 1.73], [0.6, 0.9, 1.5]], [0, 1.57, 0.5]), False, [1.0, 1.0, 0.5, 1.0, 1.0, 2.0, 0.75],
+                  SEPARATE_REG_CONFIG={'NUM_MIDDLE_CONV': 1, 'NUM_MIDDLE_FILTER': 8, 'REG_LIST': ['reg:2', 'height:1', 'size:3',
+                                                                                                  'angle:1']}),
+}
+POST = {'RECALL_THRESH_LIST': [0.3, 0.5, 0.7], 'SCORE_THRESH': 0.1, 'OUTPUT_RAW_SCORE': False,
+        'NMS_CONFIG': {'MULTI_CLASSES_NMS': True, 'NMS_TYPE': 'nms_gpu', 'NMS_THRESH': 0.1, 'NMS_PRE_MAXSIZE': 96,
+                       'NMS_POST_MAXSIZE': 8}}
+# the square box and the small box: their class (1-based label) and where to look for them, as in make_anchor_head_golden.py
+RICH = {'square': (2, 0.7, (3, 4)), 'small': (2, (0.3, 0.3, 1.6), (6, 2)), 'turned': 3, 'last': 3}
+
+
+def load_reference(root):
+    """-> (anchor_head_multi, detector3d_template, box_utils) of the reference, as pcdet_ref.*"""
+    loader.load_reference(root)
+    pcdet = os.path.join(root, "pcdet")
+    bev = loader._module("pcdet_ref.models.backbones_2d.base_bev_backbone",
+                         os.path.join(pcdet, "models", "backbones_2d", "base_bev_backbone.py"))
+    sys.modules["pcdet_ref.models.backbones_2d"].BaseBEVBackbone = bev.BaseBEVBackbone
+    loader._package("pcdet_ref.models.dense_heads.target_assigner", None)
+    ta = os.path.join(pcdet, "models", "dense_heads", "target_assigner")
+    for name in ("anchor_generator", "atss_target_assigner", "axis_aligned_target_assigner"):
+        loader._module("pcdet_ref.models.dense_heads.target_assigner." + name, os.path.join(ta, name + ".py"))
+    heads = os.path.join(pcdet, "models", "dense_heads")
+    loader._module("pcdet_ref.models.dense_heads.anchor_head_template", os.path.join(heads, "anchor_head_template.py"))
+    multi = loader._module("pcdet_ref.models.dense_heads.anchor_head_multi", os.path.join(heads, "anchor_head_multi.py"))
+    return multi, sys.modules["pcdet_ref.models.detectors.detector3d_template"], sys.modules["pcdet_ref.utils.box_utils"]
+
+
+def make_head(mod, cfg):
+    pcr, vs = np.array(PCR, np.float64), np.array(VOXEL, np.float64)
+    grid = np.round((pcr[3:] - pcr[:3]) / vs).astype(np.int64)
+    return mod.AnchorHeadMulti(model_cfg=to_attr(cfg), input_channels=16, num_class=3, class_names=CLASS_NAMES, grid_size=grid,
+                               point_cloud_range=pcr, predict_boxes_when_training=False)
+
+
+def table_of(head):
+    flat = [a.permute(3, 4, 0, 1, 2, 5).contiguous().view(-1, 7) for a in head.anchors]
+    return torch.cat(flat, dim=0).numpy().copy(), [f.shape[0] for f in flat]
+
+
+def scenes(cfg, head, box_utils):
+    pcr = PCR
+    sizes = {c['class_name']: c['anchor_sizes'][0] for c in cfg['ANCHOR_GENERATOR_CONFIG']}
+    size_of = lambda label: np.array(sizes[CLASS_NAMES[label - 1]])
+    car = size_of(1)
+    rich = np.zeros((M, 8), np.float64)
+    rich[0] = rich[1] = [pcr[0] + 5.03, pcr[1] + 5.02, -1.0, car[0] * 1.05, car[1] * 0.95, car[2], 0.1, 1]
+    label, side, (iy, ix) = RICH['square']
+    anc = head.anchors[label - 1]
+    found = None      # a location at which the float32 IoUs of the two rotations are bit-equal
+    for cell in range(iy * anc.shape[2] + ix, anc.shape[1] * anc.shape[2]):
+        cy, cx = divmod(cell, anc.shape[2])
+        loc = anc[0, cy, cx, 0, 0].numpy().astype(np.float64)
+        row = np.array([[loc[0], loc[1], loc[2], side, side, size_of(label)[2], 0.0]], np.float32)
+        pair = box_utils.boxes3d_nearest_bev_iou(anc[0, cy, cx, 0].reshape(-1, 7), torch.from_numpy(row)).numpy()[:, 0]
+        if pair[0] == pair[1] and pair[0] > 0:
+            found = row[0]
+            break
+    assert found is not None, "no location where both rotations tie"
+    rich[2, :7], rich[2, 7] = found, label
+    label, dims, (iy, ix) = RICH['small']
+    loc = head.anchors[label - 1][0, iy, ix, 0, 0].numpy().astype(np.float64)
+    rich[3] = [loc[0] + 0.13, loc[1] + 0.17, loc[2], dims[0], dims[1], dims[2], 0.2, label]
+    rich[4] = [pcr[3] + 27.0, 0.5, -1.0, 1.8, 0.6, 1.7, 0.3, RICH['last']]                  # overlaps no anchor
+    t = size_of(RICH['turned'])
+    rich[5] = [pcr[0] + 6.1, pcr[1] + 2.3, -0.8, t[0] * 0.97, t[1] * 1.1, t[2], 1.3, RICH['turned']]      # a heading past pi / 4
+    # row 6 stays zero
+    rich[7] = [pcr[0] + 2.4, pcr[1] + 1.9, -1.1, car[0] * 0.9, car[1] * 1.02, car[2] * 1.1, -2.0, 1]
+    t = size_of(RICH['last'])
+    rich[8] = [pcr[0] + 7.7, pcr[4] - 1.3, -0.7, t[0] * 1.08, t[1] * 0.93, t[2] * 0.95, 0.35, RICH['last']]
+    only = np.zeros((M, 8), np.float64)
+    only[0] = [pcr[0] + 3.3, pcr[1] + 3.1, -0.9, car[0], car[1] * 1.1, car[2], 0.05, 1]
+    only[2] = [pcr[0] + 6.6, pcr[1] + 4.4, -1.2, car[0] * 0.92, car[1], car[2] * 0.9, 1.5, 1]
+    only[3] = [pcr[0] + 5.2, pcr[4] - 1.1, -1.0, car[0] * 1.1, car[1] * 0.9, car[2], -0.4, 1]
+    return rich.astype(np.float32), only.astype(np.float32)
+
+
+def check_inputs(cfg, head, gt, box_utils):
+    """The conditions on the inputs, with the reference alone.  Returns the per-class IoU matrices of scene 0."""
+    def away(boxes):
+        ry = boxes[:, 6].astype(np.float64)
+        rr = np.abs(ry - np.floor(ry / np.pi + 0.5) * np.pi)
+        assert (np.abs(rr - np.pi / 4) >= 1e-4).all(), "a heading next to pi / 4"
+    ious = []
+    for s in range(gt.shape[0]):
+        away(gt[s][np.abs(gt[s]).sum(-1) > 0])
+        for c, (anchors, acfg) in enumerate(zip(head.anchors, cfg['ANCHOR_GENERATOR_CONFIG'])):
+            a = anchors.permute(3, 4, 0, 1, 2, 5).contiguous().view(-1, 7)
+            away(a.numpy())
+            iou = box_utils.boxes3d_nearest_bev_iou(a, torch.from_numpy(gt[s, :, :7].copy())).numpy()
+            if s == 0:
+                ious.append(iou)
+            mine = iou[:, gt[s, :, 7] == c + 1]
+            if mine.shape[1]:
+                row_max = mine.max(axis=1).astype(np.float64)
+                for thr in (acfg['matched_threshold'], acfg['unmatched_threshold']):
+                    assert (np.abs(row_max - thr) >= 1e-6).all(), "a row maximum next to a threshold"
+    return ious
+
+
+def head_layout(cfg, class_rows):
+    """Per prediction tensor of the loss: its rows and logit columns (one tensor when not separate)."""
+    if not cfg['SEPARATE_MULTIHEAD']:
+        return [sum(class_rows)], [3]
+    rows, cols, at = [], [], 0
+    for h in cfg['RPN_HEAD_CFGS']:
+        k = len(h['HEAD_CLS_NAME'])
+        rows.append(sum(class_rows[at:at + k]))
+        cols.append(k)
+        at += k
+    return rows, cols
+
+
+def predictions(rng, cfg, N, positives):
+    """As make_anchor_head_golden.py: few distinct values, every one a float16."""
+    cls = np.clip(np.round((rng.standard_normal((B, N, 3)) - 6.0) * 4) / 4, -9, -2.5).astype(np.float32)
+    cls[positives[0][:4], positives[1][:4], :] = np.array([2.5, -6.0, 0.25, -1.5], np.float32)[:, None]
+    box = np.round(rng.standard_normal((B, N, 7)) * 0.3 * 64) / 64
+    keep = rng.random((B, N)) < 0.2
+    keep[positives] = True
+    box = (box * keep[..., None]).astype(np.float32)
+    d = None
+    if cfg.get('USE_DIRECTION_CLASSIFIER'):
+        d = np.round(rng.standard_normal((B, N, 2)) * 8) / 8
+        d[..., 1] = d[..., 0] + rng.choice([-1.5, -0.5, -0.125, 0.125, 0.75, 2.0], size=(B, N))
+        d = d.astype(np.float32)
+    return cls, box, d
+
+
+def split(x, rows, cols=None, bases=None):
+    """(B, N, C) -> the per-tensor list; with cols the head's own logit columns."""
+    out, at = [], 0
+    for h, n in enumerate(rows):
+        part = x[:, at:at + n]
+        if cols is not None and len(rows) > 1:
+            part = part[..., bases[h]:bases[h] + cols[h]]
+        out.append(np.ascontiguousarray(part))
+        at += n
+    return out
+
+
+def run_batch(out, p, cfg, head, gt, preds, table, rows, cols):
+    targets = head.assign_targets(torch.from_numpy(gt.copy()))
+    labels = targets['box_cls_labels'].numpy().copy()
+    out[p + 'gt_boxes'] = gt
+    out[p + 'box_cls_labels'] = labels.astype(np.int32)
+    out[p + 'box_reg_targets'] = targets['box_reg_targets'].numpy().copy()
+    out[p + 'reg_weights'] = targets['reg_weights'].numpy().copy()
+    if preds is None:
+        return targets
+    bases = [sum(cols[:h]) for h in range(len(cols))]
+    leaf = lambda parts: [torch.from_numpy(v.copy()).requires_grad_(True) for v in parts]
+    cls, box = leaf(split(preds[0], rows, cols, bases)), leaf(split(preds[1], rows))
+    d = None if preds[2] is None else leaf(split(preds[2], rows))
+    one = lambda v: v if cfg['SEPARATE_MULTIHEAD'] else v[0]
+    head.forward_ret_dict = {'cls_preds': one(cls), 'box_preds': one(box), 'box_cls_labels': targets['box_cls_labels'].clone(),
+                             'box_reg_targets': targets['box_reg_targets'].clone(), 'reg_weights': targets['reg_weights'].clone()}
+    if d is not None:
+        head.forward_ret_dict['dir_cls_preds'] = one(d)
+    loss, tb = head.get_loss()
+    loss.backward()
+    out[p + 'losses'] = np.array([tb['rpn_loss_cls'], tb['rpn_loss_loc'], tb.get('rpn_loss_dir', 0.0), tb['rpn_loss']], np.float64)
+    for name, parts in (('cls', cls), ('box', box), ('dir', d)):
+        for h, v in enumerate(parts or []):
+            out['%sg_%s_%d' % (p, name, h)] = v.grad.numpy().copy()
+    if d is not None:      # the direction offsets of the positives against the bin edges
+        rot = (targets['box_reg_targets'].numpy()[..., 6].astype(np.float64) + table[None, :, 6])[labels > 0] - cfg['DIR_OFFSET']
+        q = (rot - np.floor(rot / (2 * np.pi)) * 2 * np.pi) / (2 * np.pi / cfg['NUM_DIR_BINS'])
+        assert (np.abs(q - np.round(q)) >= 1e-4).all(), "a direction offset next to a bin edge"
+    return targets
+
+
+def decode_case(out, name, cfg, head, preds, table, rows):
+    one = lambda v: v if cfg['SEPARATE_MULTIHEAD'] else v[0]
+    t = lambda parts: one([torch.from_numpy(v.copy()) for v in parts])
+    with torch.no_grad():
+        _, bb = head.generate_predicted_boxes(B, t(split(preds[0], rows)), t(split(preds[1], rows)),
+                                              None if preds[2] is None else t(split(preds[2], rows)))
+    out[name + '_batch_box_preds'] = bb.numpy().copy()
+    if preds[2] is not None:
+        period = 2 * np.pi / cfg['NUM_DIR_BINS']
+        q = (preds[1][..., 6].astype(np.float64) + table[None, :, 6] - cfg['DIR_OFFSET']) / period + cfg['DIR_LIMIT_OFFSET']
+        assert (np.abs(q - np.round(q)) >= 1e-4).all(), "a decoded heading next to a bin edge"
+
+
+def post_case(out, name, cfg, head, template, table, rows, cols, gt, rng):
+    """post_processing with MULTI_CLASSES_NMS on the list of per-head logits of a separate multihead."""
+    N = table.shape[0]
+    thr = POST['SCORE_THRESH']
+    logit_thr = np.log(thr / (1 - thr))
+    # every column a permutation of an even grid of logits, about 70 % of it above the threshold: distinct, well-separated scores
+    cls = [np.stack([np.stack([rng.permutation(np.linspace(-4.0, 2.0, n)) + rng.uniform(0, 0.01) for _ in range(c)], axis=1)
+                     for _ in range(B)]).astype(np.float32) for n, c in zip(rows, cols)]
+    for x in cls:
+        x[np.abs(x - logit_thr) < 0.01] += 0.02
+    cls[-1][1, :, -1] -= 5.0                                                           # a column with nothing above the threshold
+    codes = (rng.standard_normal((B, N, 7)) * 0.2).astype(np.float32)
+    dirs = rng.standard_normal((B, N, 2)).astype(np.float32)
+    with torch.no_grad():
+        _, boxes = head.generate_predicted_boxes(B, [torch.from_numpy(v) for v in cls], [torch.from_numpy(v) for v in split(codes, rows)],
+                                                 [torch.from_numpy(v) for v in split(dirs, rows)])
+    boxes = boxes.numpy().copy()
+    for x in cls:
+        s = 1 / (1 + np.exp(-x.astype(np.float64)))
+        assert np.abs(s - thr).min() >= 1e-4, "a score next to the threshold"
+        for b in range(B):
+            for k in range(x.shape[2]):
+                live = np.sort(s[b, :, k][s[b, :, k] >= thr])
+                assert len(live) < 2 or np.diff(live).min() >= 1e-5, "two scores of a column closer than 1e-5"
+    batch = {'batch_size': B, 'batch_cls_preds': [torch.from_numpy(v.copy()) for v in cls],
+             'batch_box_preds': torch.from_numpy(boxes.copy()), 'cls_preds_normalized': False,
+             'multihead_label_mapping': [h.head_label_indices for h in head.rpn_heads], 'gt_boxes': torch.from_numpy(gt.copy())}
+    fake = types.SimpleNamespace(model_cfg=to_attr({'POST_PROCESSING': POST}), num_class=3,
+                                 generate_recall_record=template.Detector3DTemplate.generate_recall_record)
+    with torch.no_grad():
+        pred_dicts, recall = template.Detector3DTemplate.post_processing(fake, batch)
+    pre, post = POST['NMS_CONFIG']['NMS_PRE_MAXSIZE'], POST['NMS_CONFIG']['NMS_POST_MAXSIZE']
+    K = sum(cols) * post
+    pb, ps, pl = np.zeros((B, K, 7), np.float32), np.zeros((B, K), np.float32), np.zeros((B, K), np.int64)
+    counts = np.zeros(B, np.int32)
+    for b, d in enumerate(pred_dicts):
+        n = counts[b] = len(d['pred_scores'])
+        pb[b, :n], ps[b, :n], pl[b, :n] = d['pred_boxes'].numpy(), d['pred_scores'].numpy(), d['pred_labels'].numpy()
+    p = 'post_%s_' % name
+    for h, x in enumerate(cls):
+        out['%scls_%d' % (p, h)] = x
+    out[p + 'boxes'], out[p + 'gt_boxes'] = boxes, gt
+    out[p + 'pred_boxes'], out[p + 'pred_scores'], out[p + 'pred_labels'], out[p + 'num_pred'] = pb, ps, pl, counts
+    out[p + 'recall'] = np.array(json.dumps({k: int(v) for k, v in recall.items()}))
+    # the cases: a head with more rows above the threshold than NMS_PRE_MAXSIZE, a column with more survivors than
+    # NMS_POST_MAXSIZE (its label then fills exactly `post` rows), a column with none
+    above = max(int((1 / (1 + np.exp(-x.astype(np.float64))) >= thr).sum(axis=1).max()) for x in cls)
+    per_label = [np.bincount(pl[b, :counts[b]], minlength=4) for b in range(B)]
+    assert min(rows) > pre and above > pre, "no column is truncated by NMS_PRE_MAXSIZE"
+    assert max(v.max() for v in per_label) == post, "no column reaches NMS_POST_MAXSIZE"
+    assert per_label[1][3] == 0 and per_label[0][3] > 0, "the empty column"
+    print(name, 'post: counts', counts, 'per label', per_label, 'recall', recall)
+
+
+def main():
+    root = sys.argv[1] if len(sys.argv) > 1 else os.environ.get("PDA_REFERENCE_ROOT")
+    if not root:
+        sys.exit(__doc__)
+    oracle.build()
+    multi, template, box_utils = load_reference(root)
+    rng = np.random.default_rng(20261020)
+    torch.manual_seed(17)
+    out = {'configs': np.array(json.dumps({'point_cloud_range': PCR, 'voxel_size': VOXEL, 'class_names': CLASS_NAMES,
+                                           'heads': CONFIGS, 'post': POST}))}
+    for name, cfg in CONFIGS.items():
+        head = make_head(multi, cfg)
+        out['keys_' + name] = np.array(list(head.state_dict().keys()), dtype='<U80')
+        out['shapes_' + name] = np.array(json.dumps([list(v.shape) for v in head.state_dict().values()]))
+        for c, a in enumerate(head.anchors):
+            out['%s_anchors_%d' % (name, c)] = a.numpy().copy()
+        table, class_rows = table_of(head)
+        out[name + '_table'], out[name + '_class_rows'] = table, np.array(class_rows, np.int64)
+        rows, cols = head_layout(cfg, class_rows)
+        N = table.shape[0]
+        assert N % 64 and all(r % 64 for r in class_rows)
+        rich, only = scenes(cfg, head, box_utils)
+        empty = np.zeros_like(rich)
+        batches = (('x', np.stack([rich, only])), ('y', np.stack([empty, only])), ('z', np.stack([empty, empty])))
+        ious = check_inputs(cfg, head, batches[0][1], box_utils)
+        for c, iou in enumerate(ious):
+            out['%sx_iou_%d' % (name, c)] = iou
+        first = run_batch({}, 'tmp_', cfg, head, batches[0][1], None, table, rows, cols)
+        positives = np.nonzero(first['box_cls_labels'].numpy() > 0)
+        preds = predictions(rng, cfg, N, positives)
+        for key, v in zip(('cls', 'box', 'dir'), preds):
+            if v is not None:
+                out['%s_%s_preds' % (name, key)] = v.astype(np.float16)
+                assert np.array_equal(v.astype(np.float16).astype(np.float32), v)
+        for tag, gt in batches:
+            check_inputs(cfg, head, gt, box_utils)
+            run_batch(out, name + tag + '_', cfg, head, gt, preds, table, rows, cols)
+            lab = out[name + tag + '_box_cls_labels']
+            print(name, tag, 'positives', (lab > 0).sum(axis=1), 'ignored', (lab < 0).sum(axis=1), 'losses', out[name + tag + '_losses'])
+        decode_case(out, name, cfg, head, preds, table, rows)
+        # the cases the rich scene is there for
+        lab = out[name + 'x_box_cls_labels'][0]
+        first_row = np.concatenate([[0], np.cumsum(class_rows)])
+        iou_all = np.zeros((N, M), np.float32)
+        for c, iou in enumerate(ious):
+            iou_all[first_row[c]:first_row[c + 1]] = iou
+        row_label = np.repeat(np.arange(1, 4), class_rows)
+        sq = iou_all[:, 2] * (row_label == RICH['square'][0])
+        assert (sq == sq.max()).sum() >= 2 and sq.max() > 0 and (lab[sq == sq.max()] > 0).all(), "a tie on the square box"
+        assert iou_all[:, 4].max() == 0, "a box that overlaps no anchor"
+        small = iou_all[:, 3] * (row_label == RICH['small'][0])
+        thr = cfg['ANCHOR_GENERATOR_CONFIG'][RICH['small'][0] - 1]['unmatched_threshold']
+        assert 0 < small.max() < thr and (lab[small == small.max()] > 0).all(), "a forced positive below the unmatched threshold"
+        assert (out[name + 'z_box_cls_labels'] == 0).all() and (lab < 0).any()
+        only_lab = out[name + 'x_box_cls_labels'][1]
+        assert (only_lab[:class_rows[0]] > 0).any() and (only_lab[class_rows[0]:] == 0).all(), "the other heads are background"
+        if cfg['SEPARATE_MULTIHEAD']:
+            post_case(out, name, cfg, head, template, table, rows, cols, batches[0][1], rng)
+    # kitti_models/second_multihead.yaml: its MODEL block (settings only) and the state dict of its dense head on KITTI's grid
+    import yaml
+    with open(os.path.join(root, "tools", "cfgs", "kitti_models", "second_multihead.yaml")) as f:
+        model = yaml.safe_load(f)['MODEL']
+    kitti = {'point_cloud_range': [0, -40, -3, 70.4, 40, 1], 'voxel_size': [0.05, 0.05, 0.1]}
+    grid = np.round((np.array(kitti['point_cloud_range'][3:]) - np.array(kitti['point_cloud_range'][:3])) / np.array(kitti['voxel_size']))
+    head = multi.AnchorHeadMulti(model_cfg=to_attr(model['DENSE_HEAD']), input_channels=512, num_class=3, class_names=CLASS_NAMES,
+                                 grid_size=grid.astype(np.int64), point_cloud_range=np.array(kitti['point_cloud_range'], np.float64),
+                                 predict_boxes_when_training=False)
+    out['yaml'] = np.array(json.dumps({'MODEL': model, 'dataset': kitti, 'head_state_dict': [[k, list(v.shape)] for k, v in
+                                                                                              head.state_dict().items()]}))
+    np.savez_compressed(OUT, **out)
+    size = os.path.getsize(OUT)
+    print(OUT, size, "bytes")
+    assert size < 1 << 20
+
+
+if __name__ == "__main__":
+    main()
