@@ -35,6 +35,15 @@ def field(cfg, key, default=_REQUIRED):
     return cfg.get(key, default) if isinstance(cfg, dict) else getattr(cfg, key, default)
 
 
+def fused_or_composed(env):
+    """The value of the environment variable `env`, 'fused' when it is unset: which of a module's two paths runs.  Read at
+    every call, because tests and benchmarks set the variable after the import."""
+    v = os.environ.get(env, "fused")
+    if v not in ("fused", "composed"):
+        raise ValueError("%s must be 'fused' or 'composed', got %r" % (env, v))
+    return v
+
+
 def to_attr(obj):
     if isinstance(obj, dict):
         return AttrDict({k: to_attr(v) for k, v in obj.items()})

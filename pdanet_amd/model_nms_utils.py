@@ -46,6 +46,32 @@ def class_agnostic_nms_batched(box_scores, box_preds, nms_config, score_thresh=N
     return selected, scores, num_keep.clamp(max=K)
 
 
+def _selected_rows(nms, box_preds, **rows):
+    """The padded tensors of class_agnostic_nms_batched's result `nms`: box_preds (B, N, 7+C) and each (B, N) tensor of `rows`
+    at selected (B, K), zero where selected is -1.  The boxes are multiplied by the mask, the others go through torch.where;
+    the two differ for non-finite rows.  A `pred_scores` among the rows takes the place of the scores the NMS ranked by."""
+    selected, sel_scores, num = nms
+    ok = selected >= 0
+    safe = selected.clamp(min=0)
+    padded = {'pred_boxes': torch.gather(box_preds, 1, safe.unsqueeze(-1).expand(-1, -1, box_preds.shape[-1])) * ok.unsqueeze(-1),
+              'pred_scores': sel_scores, 'num_pred': num}
+    for k, x in rows.items():
+        padded[k] = torch.where(ok, torch.gather(x, 1, safe), torch.zeros_like(x[:, :safe.shape[1]]))
+    return padded
+
+
+def _with_recall(padded, batch_dict, post_process_cfg, rois=None):
+    """padded with 'recall', (1 + n) int64 [gt, rcnn_<t>...] of this batch on the device, when RECALL_MODE is 'normal' (the
+    default) and the batch carries gt_boxes: counted on padded's boxes, or on all rows of rois (B, N, 7) when given."""
+    if post_process_cfg.get('RECALL_MODE', 'normal') == 'normal' and 'gt_boxes' in batch_dict:
+        boxes, num = padded['pred_boxes'], padded['num_pred']
+        if rois is not None:
+            boxes, num = rois.contiguous(), torch.full_like(num, rois.shape[1])
+            padded['recall_on_rois'] = True
+        padded['recall'] = recall_record(boxes, num, batch_dict['gt_boxes'], post_process_cfg['RECALL_THRESH_LIST'])
+    return padded
+
+
 def post_processing(batch_dict, post_process_cfg, num_class):
     """detector3d_template.py:179-290 for point heads (`batch_index` layout, equal points per scene); with
     NMS_CONFIG.MULTI_CLASSES_NMS and a list batch_cls_preds (a separate multihead) multi_classes_nms_batched.
@@ -70,20 +96,11 @@ def post_processing(batch_dict, post_process_cfg, num_class):
         labels = batch_dict['roi_labels' if 'roi_labels' in batch_dict else 'batch_pred_labels'].view(B, -1)
     else:
         labels = labels + 1
-    selected, sel_scores, num = class_agnostic_nms_batched(scores, box_preds, post_process_cfg["NMS_CONFIG"],
-                                                           score_thresh=post_process_cfg["SCORE_THRESH"])
-    ok = selected >= 0
-    safe = selected.clamp(min=0)
+    nms = class_agnostic_nms_batched(scores, box_preds, post_process_cfg["NMS_CONFIG"], score_thresh=post_process_cfg["SCORE_THRESH"])
+    rows = {'pred_labels': labels}
     if post_process_cfg.get("OUTPUT_RAW_SCORE", False):
-        raw, _ = torch.max(src_cls_preds, dim=-1)
-        sel_scores = torch.where(ok, torch.gather(raw, 1, safe), torch.zeros_like(sel_scores))
-    pred_labels = torch.where(ok, torch.gather(labels, 1, safe), torch.zeros_like(safe))
-    pred_boxes = torch.gather(box_preds, 1, safe.unsqueeze(-1).expand(-1, -1, box_preds.shape[-1])) * ok.unsqueeze(-1)
-    padded = {'pred_boxes': pred_boxes, 'pred_scores': sel_scores, 'pred_labels': pred_labels, 'num_pred': num}
-    if post_process_cfg.get('RECALL_MODE', 'normal') == 'normal' and 'gt_boxes' in batch_dict:
-        # (1 + n) int64 [gt, rcnn_<t>...] of this batch, on the device
-        padded['recall'] = recall_record(pred_boxes, num, batch_dict['gt_boxes'], post_process_cfg['RECALL_THRESH_LIST'])
-    return padded
+        rows['pred_scores'] = torch.max(src_cls_preds, dim=-1)[0]
+    return _with_recall(_selected_rows(nms, box_preds, **rows), batch_dict, post_process_cfg)
 
 
 def multi_classes_nms_batched(cls_preds, box_preds, label_mapping, nms_config, score_thresh=None, normalized=False):
@@ -150,9 +167,11 @@ def _post_processing_multi_classes(batch_dict, post_process_cfg):
         batch_dict['batch_cls_preds'], box_preds, batch_dict['multihead_label_mapping'], post_process_cfg["NMS_CONFIG"],
         score_thresh=post_process_cfg["SCORE_THRESH"], normalized=batch_dict['cls_preds_normalized'])
     padded = {'pred_boxes': pred_boxes, 'pred_scores': pred_scores, 'pred_labels': pred_labels, 'num_pred': num}
-    if post_process_cfg.get('RECALL_MODE', 'normal') == 'normal' and 'gt_boxes' in batch_dict:
-        padded['recall'] = recall_record(pred_boxes, num, batch_dict['gt_boxes'], post_process_cfg['RECALL_THRESH_LIST'])
-    return padded
+    return _with_recall(padded, batch_dict, post_process_cfg)
+
+
+PRED_KEYS = ('pred_boxes', 'pred_scores', 'pred_labels')
+IOU_PRED_KEYS = PRED_KEYS + ('pred_cls_scores', 'pred_iou_scores')
 
 
 def to_pred_dicts(padded):
@@ -161,23 +180,34 @@ def to_pred_dicts(padded):
     return _split(padded, padded['num_pred'].tolist())
 
 
-def _split(padded, counts):
-    return [{k: padded[k][s, :n] for k in ('pred_boxes', 'pred_scores', 'pred_labels')} for s, n in enumerate(counts)]
+def _split(padded, counts, keys=PRED_KEYS):
+    return [{k: padded[k][s, :n] for k in keys} for s, n in enumerate(counts)]
 
 
-def to_pred_and_recall_dicts(padded, thresh_list):
-    """Detector3DTemplate.post_processing's return value (pred_dicts, recall_dict): the recall dict holds 'gt' and
-    'roi_<t>' / 'rcnn_<t>' for every t of thresh_list (the RECALL_THRESH_LIST post_processing used) when padded carries
-    the batch's recall counters, and is {} otherwise.  The counters come back in the one host read of to_pred_dicts."""
-    if 'recall' not in padded:
-        return to_pred_dicts(padded), {}
+def to_pred_and_recall_dicts(padded, thresh_list, keys=PRED_KEYS):
+    """Detector3DTemplate.post_processing's return value (pred_dicts, recall_dict): the pred dicts hold `keys`; the recall dict
+    holds 'gt' and 'roi_<t>' / 'rcnn_<t>' for every t of thresh_list (the RECALL_THRESH_LIST post_processing used) when padded
+    carries the batch's recall counters, and is {} otherwise; roi_<t> equals rcnn_<t> when the recall was counted on the RoIs
+    (SECONDHead's boxes ARE its RoIs).  The counters come back in the one host read that the counts need anyway."""
     B = padded['num_pred'].shape[0]
-    h = torch.cat([padded['num_pred'].to(torch.int64), padded['recall']]).tolist()
-    return _split(padded, h[:B]), (recall_dict(h[B:], thresh_list) if B > 0 else {})
+    has_recall = 'recall' in padded
+    h = (torch.cat([padded['num_pred'].to(torch.int64), padded['recall']]) if has_recall else padded['num_pred']).tolist()
+    preds = _split(padded, h[:B], keys)
+    if not has_recall or B == 0:
+        return preds, {}
+    ret = recall_dict(h[B:], thresh_list)
+    if padded.get('recall_on_rois', False):
+        for t in thresh_list:
+            ret['roi_%s' % str(t)] = ret['rcnn_%s' % str(t)]
+    return preds, ret
+
+
+def to_iou_pred_and_recall_dicts(padded, thresh_list):
+    """SECONDNetIoU.post_processing's return value from post_processing_iou's tensors: the pred dicts hold IOU_PRED_KEYS."""
+    return to_pred_and_recall_dicts(padded, thresh_list, IOU_PRED_KEYS)
 
 
 IOU_SCORE_TYPES = ('iou', 'cls', 'weighted_iou_cls', 'num_pts_iou_cls', 'score_by_class')
-IOU_PRED_KEYS = ('pred_boxes', 'pred_scores', 'pred_labels', 'pred_cls_scores', 'pred_iou_scores')
 
 
 def scores_by_npoints(cls_scores, iou_scores, num_points, cls_thresh=10, iou_thresh=100):
@@ -253,36 +283,10 @@ def post_processing_iou(batch_dict, post_process_cfg, num_class, class_names):
     else:
         raise NotImplementedError("NMS_CONFIG.SCORE_TYPE %r (%s)" % (score_type, ", ".join(IOU_SCORE_TYPES)))
 
-    selected, sel_scores, num = class_agnostic_nms_batched(nms_scores, box_preds, nms_cfg, score_thresh=post_process_cfg["SCORE_THRESH"])
-    ok = selected >= 0
-    safe = selected.clamp(min=0)
-    pick = lambda x: torch.where(ok, torch.gather(x, 1, safe), torch.zeros_like(x[:, :safe.shape[1]]))
-    pred_boxes = torch.gather(box_preds, 1, safe.unsqueeze(-1).expand(-1, -1, box_preds.shape[-1])) * ok.unsqueeze(-1)
-    padded = {'pred_boxes': pred_boxes, 'pred_scores': sel_scores, 'pred_labels': pick(label_preds), 'num_pred': num,
-              'pred_cls_scores': pick(cls_preds), 'pred_iou_scores': pick(iou_preds), 'nms_scores': nms_scores}
-    if post_process_cfg.get('RECALL_MODE', 'normal') == 'normal' and 'gt_boxes' in batch_dict:
-        on_rois = 'rois' in batch_dict
-        boxes, rows = (box_preds, torch.full_like(num, N)) if on_rois else (pred_boxes, num)
-        padded['recall'] = recall_record(boxes.contiguous(), rows, batch_dict['gt_boxes'], post_process_cfg['RECALL_THRESH_LIST'])
-        padded['recall_on_rois'] = on_rois
-    return padded
-
-
-def to_iou_pred_and_recall_dicts(padded, thresh_list):
-    """SECONDNetIoU.post_processing's return value from post_processing_iou's tensors: pred dicts with the five keys of
-    IOU_PRED_KEYS, and the recall dict, in which roi_<t> equals rcnn_<t> when the recall was counted on the RoIs (the head's
-    boxes ARE its RoIs).  One host read for the batch."""
-    B = padded['num_pred'].shape[0]
-    has_recall = 'recall' in padded
-    h = (torch.cat([padded['num_pred'].to(torch.int64), padded['recall']]) if has_recall else padded['num_pred']).tolist()
-    preds = [{k: padded[k][s, :n] for k in IOU_PRED_KEYS} for s, n in enumerate(h[:B])]
-    if not has_recall or B == 0:
-        return preds, {}
-    ret = recall_dict(h[B:], thresh_list)
-    if padded.get('recall_on_rois', False):
-        for t in thresh_list:
-            ret['roi_%s' % str(t)] = ret['rcnn_%s' % str(t)]
-    return preds, ret
+    nms = class_agnostic_nms_batched(nms_scores, box_preds, nms_cfg, score_thresh=post_process_cfg["SCORE_THRESH"])
+    padded = _selected_rows(nms, box_preds, pred_labels=label_preds, pred_cls_scores=cls_preds, pred_iou_scores=iou_preds)
+    padded['nms_scores'] = nms_scores
+    return _with_recall(padded, batch_dict, post_process_cfg, rois=box_preds if 'rois' in batch_dict else None)
 
 
 def recall_dict(counts, thresh_list):

@@ -5,7 +5,6 @@ many rows per scene, and `gt_boxes` (B, M, 8) in training.  Training returns ({'
 point_* and rcnn_* entries, disp_dict); eval returns (pred_dicts, recall_dict) with the labels of the first stage's RoIs.
 
 Out of scope: PointIntraPartOffsetHead, PointNet2Backbone (the reference asserts it off)."""
-from . import model_nms_utils
 from .detector3d_template import PointDetector
 from .point_head import PointHeadBox
 from .pointnet2_backbone import PointNet2MSG
@@ -16,9 +15,3 @@ class PointRCNN(PointDetector):
     BACKBONE_3D = {'PointNet2MSG': PointNet2MSG}
     POINT_HEAD = {'PointHeadBox': PointHeadBox}
     ROI_HEAD = {'PointRCNNHead': PointRCNNHead}
-
-    def post_processing(self, batch_dict):
-        """(pred_dicts, recall_dict), as PVRCNN.post_processing; the scores are the second stage's."""
-        cfg = self.model_cfg['POST_PROCESSING']
-        padded = model_nms_utils.post_processing(batch_dict, cfg, self.num_class)
-        return model_nms_utils.to_pred_and_recall_dicts(padded, cfg.get('RECALL_THRESH_LIST', ()))

@@ -26,7 +26,7 @@ detached RoIs.  (The composed path differentiates rel as the reference does.)  d
 the feature columns of the first conv's weight gradient, which autograd derives from it, are not bit-reproducible.
 
 Out of scope: VectorPoolAggregationModuleMSG (PV-RCNN++), StackPointnetFPModule."""
-import os
+from functools import partial
 
 import torch
 import torch.nn as nn
@@ -35,20 +35,15 @@ import torch.nn.functional as F
 from . import pointnet2_stack_cuda as pointnet2
 from . import pointnet2_stack_utils as pointnet2_utils
 from ._lib import load as _load
+from .config import fused_or_composed
 from .pointnet2_batch_cuda import F32, I32, _call, _chk
 
 # 'fused' (default) or 'composed', read when a layer runs
 ENV = "PDA_STACK_SA"
+sa_path = partial(fused_or_composed, ENV)
 FUSED_CHANNELS = (16, 32, 64)
 FUSED_MAX_NSAMPLE = 255
 U8, F64 = torch.uint8, torch.float64
-
-
-def sa_path():
-    v = os.environ.get(ENV, "fused")
-    if v not in ("fused", "composed"):
-        raise ValueError("%s must be 'fused' or 'composed', got %r" % (ENV, v))
-    return v
 
 
 # ---- the float64 finish: plain torch, any device --------------------------------------------------------------------------

@@ -15,23 +15,18 @@ USE_BN: False, only xyz_up_layer and merge_down_layer follow the key.  The losse
 Target sampling: batch_dict may carry 'roi_target_seed' or 'roi_target_draws' (ProposalTargetLayer.forward's seed / draws).
 
 Out of scope: boxes with velocities, a backward for the pooling, graph capture of the head."""
-import os
+from functools import partial
 
 import torch
 import torch.nn as nn
 
 from . import pointnet2_modules, roipoint_pool3d_utils
+from .config import fused_or_composed
 from .roi_head_template import RoIHeadTemplate
 
 # 'fused' (default) or 'composed', read when the head pools
 ENV = "PDA_ROIPOINT_POOL"
-
-
-def pool_path():
-    v = os.environ.get(ENV, "fused")
-    if v not in ("fused", "composed"):
-        raise ValueError("%s must be 'fused' or 'composed', got %r" % (ENV, v))
-    return v
+pool_path = partial(fused_or_composed, ENV)
 
 
 class PointRCNNHead(RoIHeadTemplate):
@@ -71,25 +66,6 @@ class PointRCNNHead(RoIHeadTemplate):
                                                                           pool_extra_width=pool_cfg['POOL_EXTRA_WIDTH'])
         self.init_weights(weight_init='xavier')
 
-    def init_weights(self, weight_init='xavier'):
-        if weight_init == 'kaiming':
-            init_func = nn.init.kaiming_normal_
-        elif weight_init == 'xavier':
-            init_func = nn.init.xavier_normal_
-        elif weight_init == 'normal':
-            init_func = nn.init.normal_
-        else:
-            raise NotImplementedError
-        for m in self.modules():
-            if isinstance(m, (nn.Conv2d, nn.Conv1d)):
-                if weight_init == 'normal':
-                    init_func(m.weight, mean=0, std=0.001)
-                else:
-                    init_func(m.weight)
-                if m.bias is not None:
-                    nn.init.constant_(m.bias, 0)
-        nn.init.normal_(self.reg_layers[-1].weight, mean=0, std=0.001)
-
     def roipool3d_gpu(self, batch_dict):
         """rois (B, num_rois, 7), point_coords (B * N, 4) [bs_idx, x, y, z], point_features (B * N, C), point_cls_scores (B * N)
         -> (B * num_rois, NUM_SAMPLED_POINTS, 5 + C): [canonical xyz | score | depth | features], zero for an empty RoI."""
@@ -113,12 +89,7 @@ class PointRCNNHead(RoIHeadTemplate):
         return pooled_features.view(-1, pooled_features.shape[-2], pooled_features.shape[-1])
 
     def forward(self, batch_dict):
-        targets_dict = self.proposal_layer(batch_dict, nms_config=self.model_cfg['NMS_CONFIG']['TRAIN' if self.training else 'TEST'])
-        if self.training:
-            targets_dict = self.assign_targets(batch_dict, seed=batch_dict.get('roi_target_seed'),
-                                               draws=batch_dict.get('roi_target_draws'))
-            batch_dict['rois'] = targets_dict['rois']
-            batch_dict['roi_labels'] = targets_dict['roi_labels']
+        targets_dict = self.proposals_and_targets(batch_dict)
 
         pooled_features = self.roipool3d_gpu(batch_dict)                    # (total_rois, num_sampled_points, 5 + C)
 
@@ -137,14 +108,4 @@ class PointRCNNHead(RoIHeadTemplate):
         rcnn_cls = self.cls_layers(shared_features).transpose(1, 2).contiguous().squeeze(dim=1)   # (B, 1 or 2)
         rcnn_reg = self.reg_layers(shared_features).transpose(1, 2).contiguous().squeeze(dim=1)   # (B, C)
 
-        if not self.training:
-            batch_cls_preds, batch_box_preds = self.generate_predicted_boxes(
-                batch_size=batch_dict['batch_size'], rois=batch_dict['rois'], cls_preds=rcnn_cls, box_preds=rcnn_reg)
-            batch_dict['batch_cls_preds'] = batch_cls_preds
-            batch_dict['batch_box_preds'] = batch_box_preds
-            batch_dict['cls_preds_normalized'] = False
-        else:
-            targets_dict['rcnn_cls'] = rcnn_cls
-            targets_dict['rcnn_reg'] = rcnn_reg
-            self.forward_ret_dict = targets_dict
-        return batch_dict
+        return self.keep_predictions(batch_dict, targets_dict, rcnn_cls, rcnn_reg)

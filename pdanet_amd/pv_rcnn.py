@@ -6,7 +6,6 @@ the voxels.  Training returns ({'loss': loss_rpn + loss_point + loss_rcnn}, tb_d
 entries, disp_dict); eval returns (pred_dicts, recall_dict) with the labels of the first stage's RoIs.
 
 Out of scope: PV-RCNN++ (SPC sampling, VectorPoolAggregationModuleMSG), PointIntraPartOffsetHead."""
-from . import model_nms_utils
 from .anchor_head import AnchorHeadSingle
 from .detector3d_template import VoxelDetector
 from .mean_vfe import MeanVFE
@@ -23,15 +22,4 @@ class PVRCNN(VoxelDetector):
     PFE = {'VoxelSetAbstraction': VoxelSetAbstraction}
     POINT_HEAD = {'PointHeadSimple': PointHeadSimple}
     ROI_HEAD = {'PVRCNNHead': PVRCNNHead}
-
-    def __init__(self, model_cfg, num_class, dataset):
-        for key in ('PFE', 'POINT_HEAD', 'ROI_HEAD'):
-            if model_cfg.get(key, None) is None:
-                raise ValueError("PVRCNN needs MODEL.%s" % key)
-        super().__init__(model_cfg, num_class, dataset)
-
-    def post_processing(self, batch_dict):
-        """(pred_dicts, recall_dict), as VoxelRCNN.post_processing; the scores are the second stage's."""
-        cfg = self.model_cfg['POST_PROCESSING']
-        padded = model_nms_utils.post_processing(batch_dict, cfg, self.num_class)
-        return model_nms_utils.to_pred_and_recall_dicts(padded, cfg.get('RECALL_THRESH_LIST', ()))
+    REQUIRED = ('PFE', 'POINT_HEAD', 'ROI_HEAD')

@@ -1,7 +1,9 @@
 """RoIHeadTemplate (pcdet/models/roi_heads/roi_head_template.py): what every two-stage head of the reference shares --
 `proposal_layer` (first-stage predictions -> rois / roi_scores / roi_labels through per-scene NMS), `assign_targets`
 (ProposalTargetLayer and the canonical transformation), the fc stacks, the box decoding and the rcnn losses -- for the
-whole batch at once and without a host read anywhere on the training path.
+whole batch at once and without a host read anywhere on the training path.  It also holds, once, what the reference's heads
+each repeat: the two ends of forward() (`proposals_and_targets`, `keep_predictions`), the RoI grid points, the Conv1d shared
+stack and `init_weights`.
 
 Where the reference loops over scenes (proposal_layer) this uses model_nms_utils.class_agnostic_nms_batched; where it
 loops over scenes and classes and draws on the host (assign_targets) this uses proposal_target_layer (csrc/roi_targets.hip),
@@ -48,6 +50,39 @@ class RoIHeadTemplate(nn.Module):
         fc_layers.append(nn.Conv1d(pre_channel, output_channels, kernel_size=1, bias=True))
         return nn.Sequential(*fc_layers)
 
+    def make_shared_fc_layers(self, input_channels, fc_list):
+        """The Conv1d-BN-ReLU stack in front of the prediction stacks (pvrcnn_head.py:33-43, second_head.py:33-43), a Dropout
+        between its blocks.  Returns the stack and its output width."""
+        fc_layers = []
+        pre_channel = input_channels
+        for k in range(len(fc_list)):
+            fc_layers.extend([nn.Conv1d(pre_channel, fc_list[k], kernel_size=1, bias=False), nn.BatchNorm1d(fc_list[k]),
+                              nn.ReLU()])
+            pre_channel = fc_list[k]
+            if k != len(fc_list) - 1 and self.model_cfg['DP_RATIO'] > 0:
+                fc_layers.append(nn.Dropout(self.model_cfg['DP_RATIO']))
+        return nn.Sequential(*fc_layers), pre_channel
+
+    def init_weights(self, weight_init='xavier'):
+        """pvrcnn_head.py:48-65 / pointrcnn_head.py:74-91: every Conv of the head, then reg_layers' last one again."""
+        if weight_init == 'kaiming':
+            init_func = nn.init.kaiming_normal_
+        elif weight_init == 'xavier':
+            init_func = nn.init.xavier_normal_
+        elif weight_init == 'normal':
+            init_func = nn.init.normal_
+        else:
+            raise NotImplementedError
+        for m in self.modules():
+            if isinstance(m, (nn.Conv2d, nn.Conv1d)):
+                if weight_init == 'normal':
+                    init_func(m.weight, mean=0, std=0.001)
+                else:
+                    init_func(m.weight)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+        nn.init.normal_(self.reg_layers[-1].weight, mean=0, std=0.001)
+
     @torch.no_grad()
     def proposal_layer(self, batch_dict, nms_config):
         """:45-102 for the whole batch.  batch_cls_preds (B, N, num_class | 1) with batch_box_preds (B, N, 7), or both with
@@ -93,6 +128,56 @@ class RoIHeadTemplate(nn.Module):
         """:104-134: the targets dict with gt_of_rois in each RoI's canonical frame and gt_of_rois_src the sampled GT rows.
         seed / draws / check: see ProposalTargetLayer.forward."""
         return self.proposal_target_layer.forward(batch_dict, seed=seed, draws=draws, check=check)
+
+    def proposals_and_targets(self, batch_dict):
+        """What every head's forward() opens with: the proposals of the current mode and, in training, the sampled targets
+        (batch_dict's 'roi_target_seed' / 'roi_target_draws' are ProposalTargetLayer.forward's seed / draws), whose rois and
+        roi_labels replace the proposals in the batch.  Returns the targets dict (the batch itself in eval)."""
+        targets_dict = self.proposal_layer(batch_dict, nms_config=self.model_cfg['NMS_CONFIG']['TRAIN' if self.training else 'TEST'])
+        if self.training:
+            targets_dict = self.assign_targets(batch_dict, seed=batch_dict.get('roi_target_seed'),
+                                               draws=batch_dict.get('roi_target_draws'))
+            batch_dict['rois'] = targets_dict['rois']
+            batch_dict['roi_labels'] = targets_dict['roi_labels']
+        return targets_dict
+
+    def keep_predictions(self, batch_dict, targets_dict, rcnn_cls, rcnn_reg):
+        """What a head with a class and a box branch closes forward() with: the decoded boxes into the batch in eval, the raw
+        predictions next to their targets into forward_ret_dict in training."""
+        if not self.training:
+            batch_cls_preds, batch_box_preds = self.generate_predicted_boxes(
+                batch_size=batch_dict['batch_size'], rois=batch_dict['rois'], cls_preds=rcnn_cls, box_preds=rcnn_reg)
+            batch_dict['batch_cls_preds'] = batch_cls_preds
+            batch_dict['batch_box_preds'] = batch_box_preds
+            batch_dict['cls_preds_normalized'] = False
+        else:
+            targets_dict['rcnn_cls'] = rcnn_cls
+            targets_dict['rcnn_reg'] = rcnn_reg
+            self.forward_ret_dict = targets_dict
+        return batch_dict
+
+    def get_global_grid_points_of_roi(self, rois, grid_size):
+        """voxelrcnn_head.py / pvrcnn_head.py: rois (..., 7 + C) -> the GRID_SIZE^3 grid points of each RoI in the lidar frame
+        and in the RoI's own, (BxN, 6x6x6, 3) each."""
+        rois = rois.view(-1, rois.shape[-1])
+        batch_size_rcnn = rois.shape[0]
+        local_roi_grid_points = self.get_dense_grid_points(rois, batch_size_rcnn, grid_size)    # (B, 6x6x6, 3)
+        global_roi_grid_points = box_utils.rotate_points_along_z(local_roi_grid_points.clone(), rois[:, 6]).squeeze(dim=1)
+        global_center = rois[:, 0:3].clone()
+        global_roi_grid_points += global_center.unsqueeze(dim=1)
+        return global_roi_grid_points, local_roi_grid_points
+
+    @staticmethod
+    def get_dense_grid_points(rois, batch_size_rcnn, grid_size):
+        """The reference's `faked_features.nonzero()` of an all-ones cube is the index grid in row-major order; built here
+        without the host read nonzero() makes."""
+        axis = torch.arange(grid_size, device=rois.device)
+        dense_idx = torch.stack(torch.meshgrid(axis, axis, axis, indexing='ij'), dim=-1).view(-1, 3)
+        dense_idx = dense_idx.repeat(batch_size_rcnn, 1, 1).to(rois.dtype)                       # (B, 6x6x6, 3)
+        local_roi_size = rois.view(batch_size_rcnn, -1)[:, 3:6]
+        roi_grid_points = (dense_idx + 0.5) / grid_size * local_roi_size.unsqueeze(dim=1) \
+            - (local_roi_size.unsqueeze(dim=1) / 2)
+        return roi_grid_points
 
     def get_box_reg_layer_loss(self, forward_ret_dict):
         loss_cfgs = self.model_cfg['LOSS_CONFIG']

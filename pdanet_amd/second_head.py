@@ -17,26 +17,21 @@ Target sampling: batch_dict may carry 'roi_target_seed' or 'roi_target_draws' (P
 
 Out of scope: boxes with velocities, IOU_LOSS 'focalbce' (the reference calls loss_utils.sigmoid_focal_cls_loss, which it
 does not have), MULTI_CLASSES_NMS."""
-import os
+from functools import partial
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import loss_utils
+from .config import fused_or_composed
 from .pointnet2_batch_cuda import F32, _call, _chk
 from .roi_head_template import RoIHeadTemplate
 
 # 'fused' (default) or 'composed', read when the head pools
 ENV = "PDA_BEV_ROI_POOL"
+pool_path = partial(fused_or_composed, ENV)
 IOU_LOSSES = ('BinaryCrossEntropy', 'L2', 'smoothL1')
-
-
-def pool_path():
-    v = os.environ.get(ENV, "fused")
-    if v not in ("fused", "composed"):
-        raise ValueError("%s must be 'fused' or 'composed', got %r" % (ENV, v))
-    return v
 
 
 def bev_roi_grid_pool(bev, rois, grid_size, min_x, min_y, cell_x, cell_y):
@@ -91,16 +86,7 @@ class SECONDHead(RoIHeadTemplate):
         self.cell_x, self.cell_y = float(voxel_size[0]) * ratio, float(voxel_size[1]) * ratio
 
         grid = self.pool_cfg['GRID_SIZE']
-        pre_channel = self.pool_cfg['IN_CHANNEL'] * grid * grid
-        shared_fc, dp = model_cfg['SHARED_FC'], model_cfg['DP_RATIO']
-        shared_fc_list = []
-        for k in range(len(shared_fc)):
-            shared_fc_list.extend([nn.Conv1d(pre_channel, shared_fc[k], kernel_size=1, bias=False), nn.BatchNorm1d(shared_fc[k]),
-                                   nn.ReLU()])
-            pre_channel = shared_fc[k]
-            if k != len(shared_fc) - 1 and dp > 0:
-                shared_fc_list.append(nn.Dropout(dp))
-        self.shared_fc_layer = nn.Sequential(*shared_fc_list)
+        self.shared_fc_layer, pre_channel = self.make_shared_fc_layers(self.pool_cfg['IN_CHANNEL'] * grid * grid, model_cfg['SHARED_FC'])
         self.iou_layers = self.make_fc_layers(input_channels=pre_channel, output_channels=1, fc_list=model_cfg['IOU_FC'])
         self.init_weights()
 
@@ -122,12 +108,7 @@ class SECONDHead(RoIHeadTemplate):
                     self.cell_x, self.cell_y)
 
     def forward(self, batch_dict):
-        targets_dict = self.proposal_layer(batch_dict, nms_config=self.model_cfg['NMS_CONFIG']['TRAIN' if self.training else 'TEST'])
-        if self.training:
-            targets_dict = self.assign_targets(batch_dict, seed=batch_dict.get('roi_target_seed'),
-                                               draws=batch_dict.get('roi_target_draws'))
-            batch_dict['rois'] = targets_dict['rois']
-            batch_dict['roi_labels'] = targets_dict['roi_labels']
+        targets_dict = self.proposals_and_targets(batch_dict)
 
         pooled_features = self.roi_grid_pool(batch_dict)                                         # (BxN, C, 7, 7)
         batch_size_rcnn = pooled_features.shape[0]

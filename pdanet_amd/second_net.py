@@ -4,7 +4,6 @@ AnchorHeadSingle / AnchorHeadMulti (whose list of per-head scores takes MULTI_CL
 module names (vfe, backbone_3d, map_to_bev_module, backbone_2d, dense_head), so a reference checkpoint (spconv 2.x) loads
 with strict=True.  The batch carries the collated hard voxels (voxel_utils.VoxelGenerator.generate_batch + collate_voxels).
 Training returns ({'loss': loss}, tb_dict, disp_dict); eval returns what PointPillar returns."""
-from . import model_nms_utils
 from .anchor_head import AnchorHeadSingle
 from .anchor_head_multi import AnchorHeadMulti
 from .detector3d_template import VoxelDetector
@@ -16,9 +15,3 @@ class SECONDNet(VoxelDetector):
     VFE = {'MeanVFE': MeanVFE}
     BACKBONE_3D = {'VoxelBackBone8x': VoxelBackBone8x, 'VoxelResBackBone8x': VoxelResBackBone8x}
     DENSE_HEAD = {'AnchorHeadSingle': AnchorHeadSingle, 'AnchorHeadMulti': AnchorHeadMulti}
-
-    def post_processing(self, batch_dict):
-        """(pred_dicts, recall_dict), as PointPillar.post_processing."""
-        cfg = self.model_cfg['POST_PROCESSING']
-        padded = model_nms_utils.post_processing(batch_dict, cfg, self.num_class)
-        return model_nms_utils.to_pred_and_recall_dicts(padded, cfg.get('RECALL_THRESH_LIST', ()))

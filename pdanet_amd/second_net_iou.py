@@ -20,10 +20,9 @@ class SECONDNetIoU(VoxelDetector):
     BACKBONE_3D = {'VoxelBackBone8x': VoxelBackBone8x, 'VoxelResBackBone8x': VoxelResBackBone8x}
     DENSE_HEAD = {'AnchorHeadSingle': AnchorHeadSingle}
     ROI_HEAD = {'SECONDHead': SECONDHead}
+    REQUIRED = ('ROI_HEAD',)
 
     def __init__(self, model_cfg, num_class, dataset):
-        if model_cfg.get('ROI_HEAD', None) is None:
-            raise ValueError("SECONDNetIoU needs MODEL.ROI_HEAD")
         if model_cfg['POST_PROCESSING']['NMS_CONFIG']['MULTI_CLASSES_NMS']:
             raise NotImplementedError("POST_PROCESSING.NMS_CONFIG.MULTI_CLASSES_NMS")
         super().__init__(model_cfg, num_class, dataset)

@@ -16,7 +16,7 @@ statistics.  The backward is closed form too: with g the incoming gradient where
     dbeta_c = sum g,   dgamma_c = (sum g (w_c . x*) - mean_c dbeta_c) / sigma_c
     dW_c = (gamma_c / sigma_c) (sum g x*^T - dbeta_c / n S1^T - dgamma_c / n (w_c^T S2 - mean_c S1^T) / sigma_c)
 finished here in float64 from the kernel's per-channel sums (`moment_finish`, `moment_backward`: plain torch, any device)."""
-import os
+from functools import partial
 
 import torch
 import torch.nn as nn
@@ -25,18 +25,13 @@ import torch.nn.functional as F
 from . import pointnet2_stack_cuda as pointnet2
 from . import pointnet2_stack_utils as voxel_query_utils
 from ._lib import load as _load
+from .config import fused_or_composed
 from .pointnet2_batch_cuda import F32, I32, _call, _chk
 
 # 'fused' (default) or 'composed', read when a layer runs
 ENV = "PDA_VOXEL_POOL"
+pool_path = partial(fused_or_composed, ENV)
 FUSED_CHANNELS = (32, 64)
-
-
-def pool_path():
-    v = os.environ.get(ENV, "fused")
-    if v not in ("fused", "composed"):
-        raise ValueError("%s must be 'fused' or 'composed', got %r" % (ENV, v))
-    return v
 
 
 def _sym(s2):

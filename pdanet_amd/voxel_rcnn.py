@@ -5,7 +5,6 @@ Training returns ({'loss': loss_rpn + loss_rcnn}, tb_dict with the rpn_* and rcn
 (pred_dicts, recall_dict) with the labels of the first stage's RoIs.
 
 Out of scope: the Waymo variant's wiring (CenterHead and DynMeanVFE in front of the same head)."""
-from . import model_nms_utils
 from .anchor_head import AnchorHeadSingle
 from .detector3d_template import VoxelDetector
 from .mean_vfe import MeanVFE
@@ -18,14 +17,4 @@ class VoxelRCNN(VoxelDetector):
     BACKBONE_3D = {'VoxelBackBone8x': VoxelBackBone8x}
     DENSE_HEAD = {'AnchorHeadSingle': AnchorHeadSingle}
     ROI_HEAD = {'VoxelRCNNHead': VoxelRCNNHead}
-
-    def __init__(self, model_cfg, num_class, dataset):
-        if model_cfg.get('ROI_HEAD', None) is None:
-            raise ValueError("VoxelRCNN needs MODEL.ROI_HEAD")
-        super().__init__(model_cfg, num_class, dataset)
-
-    def post_processing(self, batch_dict):
-        """(pred_dicts, recall_dict), as SECONDNet.post_processing; the scores are the second stage's."""
-        cfg = self.model_cfg['POST_PROCESSING']
-        padded = model_nms_utils.post_processing(batch_dict, cfg, self.num_class)
-        return model_nms_utils.to_pred_and_recall_dicts(padded, cfg.get('RECALL_THRESH_LIST', ()))
+    REQUIRED = ('ROI_HEAD',)

@@ -13,7 +13,6 @@ Out of scope: GRID_3D_IOU_LOSS, graph capture of the head."""
 import torch
 import torch.nn as nn
 
-from . import box_utils
 from .roi_head_template import RoIHeadTemplate
 from .voxel_pool_modules import NeighborVoxelSAModuleMSG
 from .voxel_utils import generate_voxel2pinds, get_voxel_centers
@@ -114,34 +113,8 @@ class VoxelRCNNHead(RoIHeadTemplate):
             pooled_features_list.append(pooled_features.view(-1, grid_size ** 3, pooled_features.shape[-1]))
         return torch.cat(pooled_features_list, dim=-1)
 
-    def get_global_grid_points_of_roi(self, rois, grid_size):
-        rois = rois.view(-1, rois.shape[-1])
-        batch_size_rcnn = rois.shape[0]
-        local_roi_grid_points = self.get_dense_grid_points(rois, batch_size_rcnn, grid_size)    # (B, 6x6x6, 3)
-        global_roi_grid_points = box_utils.rotate_points_along_z(local_roi_grid_points.clone(), rois[:, 6]).squeeze(dim=1)
-        global_center = rois[:, 0:3].clone()
-        global_roi_grid_points += global_center.unsqueeze(dim=1)
-        return global_roi_grid_points, local_roi_grid_points
-
-    @staticmethod
-    def get_dense_grid_points(rois, batch_size_rcnn, grid_size):
-        """The reference's `faked_features.nonzero()` of an all-ones cube is the index grid in row-major order; built here
-        without the host read nonzero() makes."""
-        axis = torch.arange(grid_size, device=rois.device)
-        dense_idx = torch.stack(torch.meshgrid(axis, axis, axis, indexing='ij'), dim=-1).view(-1, 3)
-        dense_idx = dense_idx.repeat(batch_size_rcnn, 1, 1).float()                              # (B, 6x6x6, 3)
-        local_roi_size = rois.view(batch_size_rcnn, -1)[:, 3:6]
-        roi_grid_points = (dense_idx + 0.5) / grid_size * local_roi_size.unsqueeze(dim=1) \
-            - (local_roi_size.unsqueeze(dim=1) / 2)
-        return roi_grid_points
-
     def forward(self, batch_dict):
-        targets_dict = self.proposal_layer(batch_dict, nms_config=self.model_cfg['NMS_CONFIG']['TRAIN' if self.training else 'TEST'])
-        if self.training:
-            targets_dict = self.assign_targets(batch_dict, seed=batch_dict.get('roi_target_seed'),
-                                               draws=batch_dict.get('roi_target_draws'))
-            batch_dict['rois'] = targets_dict['rois']
-            batch_dict['roi_labels'] = targets_dict['roi_labels']
+        targets_dict = self.proposals_and_targets(batch_dict)
 
         pooled_features = self.roi_grid_pool(batch_dict)                                         # (BxN, 6x6x6, C)
         pooled_features = pooled_features.view(pooled_features.size(0), -1)
@@ -149,14 +122,4 @@ class VoxelRCNNHead(RoIHeadTemplate):
         rcnn_cls = self.cls_pred_layer(self.cls_fc_layers(shared_features))
         rcnn_reg = self.reg_pred_layer(self.reg_fc_layers(shared_features))
 
-        if not self.training:
-            batch_cls_preds, batch_box_preds = self.generate_predicted_boxes(
-                batch_size=batch_dict['batch_size'], rois=batch_dict['rois'], cls_preds=rcnn_cls, box_preds=rcnn_reg)
-            batch_dict['batch_cls_preds'] = batch_cls_preds
-            batch_dict['batch_box_preds'] = batch_box_preds
-            batch_dict['cls_preds_normalized'] = False
-        else:
-            targets_dict['rcnn_cls'] = rcnn_cls
-            targets_dict['rcnn_reg'] = rcnn_reg
-            self.forward_ret_dict = targets_dict
-        return batch_dict
+        return self.keep_predictions(batch_dict, targets_dict, rcnn_cls, rcnn_reg)

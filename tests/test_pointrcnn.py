@@ -179,17 +179,6 @@ def test_wrapper_has_no_cpu_path():
         roipoint_pool3d_canonical(torch.zeros(1, 4, 3), torch.zeros(1, 4), torch.zeros(1, 4, 2), torch.zeros(2, 2, 7), (0, 0, 0), 8, 70.0)
 
 
-def test_pool_path_switch(monkeypatch):
-    from pdanet_amd import pointrcnn_head
-    monkeypatch.delenv(pointrcnn_head.ENV, raising=False)
-    assert pointrcnn_head.pool_path() == "fused"
-    monkeypatch.setenv(pointrcnn_head.ENV, "composed")
-    assert pointrcnn_head.pool_path() == "composed"
-    monkeypatch.setenv(pointrcnn_head.ENV, "neither")
-    with pytest.raises(ValueError):
-        pointrcnn_head.pool_path()
-
-
 @pytest.mark.parametrize("tag,kw", [("mean", {'use_mean_size': True, 'mean_size': [[3.9, 1.6, 1.56], [0.8, 0.6, 1.73], [1.76, 0.6, 1.73]]}),
                                     ("plain", {'use_mean_size': False})])
 def test_point_residual_coder_matches_reference(npz, tag, kw):
