@@ -6,7 +6,7 @@ state-dict keys of AnchorHeadSingle and PillarVFE.
 
 The reference's own anchor_head_template.py, anchor_head_single.py, anchor_generator.py, axis_aligned_target_assigner.py,
 pillar_vfe.py, loss_utils.py, box_coder_utils.py, box_utils.py and common_utils.py are loaded as pcdet_ref.* with their
-package imports stubbed and .cuda() the identity.
+package imports stubbed (reference_loader.py).
 
 Two configurations, B = 2, M = 12:
   a  range [0, -8, -3, 12.8, 8, 1], voxels of 0.2 m, stride 2: a 32 x 40 map; the three KITTI anchor classes with the yaml's
@@ -28,76 +28,31 @@ decoding); no row_max within 1e-6 of a threshold; no two top direction logits eq
 
 Run with the reference checkout:  python tests/golden/make_anchor_head_golden.py /path/to/reference
 """
-import importlib.util
 import json
 import os
 import sys
-import types
 
 import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = sys.argv[1] if len(sys.argv) > 1 else os.environ["PDA_REFERENCE"]
-PCDET = os.path.join(REF, "pcdet")
-OUT = os.path.join(HERE, "anchor_head.npz")
-sys.path.insert(0, ROOT)
+sys.path.insert(0, HERE)
+from reference_loader import ANCHOR_HEAD, MODEL_UTILS, cpu_torch, extension_stubs, load, reference_root  # noqa: E402
 from pdanet_amd.config import to_attr  # noqa: E402
 
+OUT = os.path.join(HERE, "anchor_head.npz")
 B, M = 2, 12
+AHS = PVFE = BOX_UTILS = None       # the reference's anchor_head_single, pillar_vfe and box_utils, once load_reference has run
 
 
-def _package(name, path=None, **attrs):
-    pkg = types.ModuleType(name)
-    pkg.__path__ = [path] if path else []
-    pkg.__dict__.update(attrs)
-    sys.modules[name] = pkg
-    parent, _, leaf = name.rpartition(".")
-    if parent in sys.modules:
-        setattr(sys.modules[parent], leaf, pkg)
-    return pkg
+def load_reference(root):
+    global AHS, PVFE, BOX_UTILS
+    cpu_torch()
+    needed = load(root, "pcdet_ref", MODEL_UTILS + ANCHOR_HEAD + ["models.backbones_3d.vfe.vfe_template"],
+                  stubs=extension_stubs())
+    BOX_UTILS = needed[MODEL_UTILS.index("utils.box_utils")]
+    AHS, PVFE = load(root, "pcdet_ref", ["models.dense_heads.anchor_head_single", "models.backbones_3d.vfe.pillar_vfe"])
 
-
-def _module(name, path):
-    spec = importlib.util.spec_from_file_location(name, path)
-    m = importlib.util.module_from_spec(spec)
-    sys.modules[name] = m
-    parent, _, leaf = name.rpartition(".")
-    setattr(sys.modules[parent], leaf, m)
-    spec.loader.exec_module(m)
-    return m
-
-
-def _load_reference():
-    torch.Tensor.cuda = lambda self, *a, **k: self
-    sys.modules["SharedArray"] = types.ModuleType("SharedArray")
-    _package("pcdet_ref", PCDET)
-    _package("pcdet_ref.utils", None)
-    _package("pcdet_ref.ops", None)
-    _package("pcdet_ref.ops.roiaware_pool3d", None, roiaware_pool3d_utils=types.ModuleType("roiaware_pool3d_utils"))
-    _package("pcdet_ref.ops.iou3d_nms", None)
-    _package("pcdet_ref.ops.iou3d_nms.iou3d_nms_cuda", None)
-    for name in ("common_utils", "box_utils", "loss_utils", "box_coder_utils"):
-        _module("pcdet_ref.utils." + name, os.path.join(PCDET, "utils", name + ".py"))
-    _module("pcdet_ref.ops.iou3d_nms.iou3d_nms_utils", os.path.join(PCDET, "ops", "iou3d_nms", "iou3d_nms_utils.py"))
-    _package("pcdet_ref.models", None)
-    _package("pcdet_ref.models.dense_heads", None)
-    _package("pcdet_ref.models.dense_heads.target_assigner", None)
-    ta = os.path.join(PCDET, "models", "dense_heads", "target_assigner")
-    for name in ("anchor_generator", "atss_target_assigner", "axis_aligned_target_assigner"):
-        _module("pcdet_ref.models.dense_heads.target_assigner." + name, os.path.join(ta, name + ".py"))
-    _module("pcdet_ref.models.dense_heads.anchor_head_template", os.path.join(PCDET, "models", "dense_heads", "anchor_head_template.py"))
-    single = _module("pcdet_ref.models.dense_heads.anchor_head_single", os.path.join(PCDET, "models", "dense_heads", "anchor_head_single.py"))
-    _package("pcdet_ref.models.backbones_3d", None)
-    _package("pcdet_ref.models.backbones_3d.vfe", None)
-    vfe = os.path.join(PCDET, "models", "backbones_3d", "vfe")
-    _module("pcdet_ref.models.backbones_3d.vfe.vfe_template", os.path.join(vfe, "vfe_template.py"))
-    pvfe = _module("pcdet_ref.models.backbones_3d.vfe.pillar_vfe", os.path.join(vfe, "pillar_vfe.py"))
-    return single, pvfe, sys.modules["pcdet_ref.utils.box_utils"]
-
-
-AHS, PVFE, BOX_UTILS = _load_reference()
 
 TARGET = {'NAME': 'AxisAlignedTargetAssigner', 'POS_FRACTION': -1.0, 'SAMPLE_SIZE': 512, 'NORM_BY_NUM_EXAMPLES': False,
           'MATCH_HEIGHT': False, 'BOX_CODER': 'ResidualCoder'}
@@ -340,6 +295,7 @@ def vfe_case(out, rng):
 
 
 def main():
+    load_reference(reference_root())
     rng = np.random.default_rng(20261019)
     torch.manual_seed(13)
     out = {'configs': np.array(json.dumps(CONFIGS))}

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Generates tests/golden/anchor_head_multi.npz: the REFERENCE's own AnchorHeadMulti, AxisAlignedTargetAssigner (use_multihead)
 and Detector3DTemplate.post_processing over model_nms_utils.multi_classes_nms, imported from where they lie and run on CPU
-tensors.  The extension modules are stubs, those of make_second_iou_golden.py (whose loader this uses): iou3d_nms_cuda.nms_gpu
-and boxes_overlap_bev_gpu are the repository's C oracle (oracle/).  Nothing of the reference is copied; what is committed is
+tensors.  The extension modules are the stubs of reference_loader.py: iou3d_nms_cuda.nms_gpu and boxes_overlap_bev_gpu are the
+repository's C oracle (oracle/).  Nothing of the reference is copied; what is committed is
 data.
 
     python tests/golden/make_anchor_head_multi_golden.py <checkout of the reference>
@@ -38,10 +38,9 @@ import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, HERE)
-sys.path.insert(0, ROOT)
-import make_second_iou_golden as loader  # noqa: E402
+from reference_loader import (ANCHOR_HEAD, DETECTOR_STUBS, MODEL_UTILS, cpu_torch, extension_stubs, load,  # noqa: E402
+                              reference_root)
 import oracle  # noqa: E402
 from pdanet_amd.config import to_attr  # noqa: E402
 
@@ -93,19 +92,14 @@ RICH = {'square': (2, 0.7, (3, 4)), 'small': (2, (0.3, 0.3, 1.6), (6, 2)), 'turn
 
 def load_reference(root):
     """-> (anchor_head_multi, detector3d_template, box_utils) of the reference, as pcdet_ref.*"""
-    loader.load_reference(root)
-    pcdet = os.path.join(root, "pcdet")
-    bev = loader._module("pcdet_ref.models.backbones_2d.base_bev_backbone",
-                         os.path.join(pcdet, "models", "backbones_2d", "base_bev_backbone.py"))
-    sys.modules["pcdet_ref.models.backbones_2d"].BaseBEVBackbone = bev.BaseBEVBackbone
-    loader._package("pcdet_ref.models.dense_heads.target_assigner", None)
-    ta = os.path.join(pcdet, "models", "dense_heads", "target_assigner")
-    for name in ("anchor_generator", "atss_target_assigner", "axis_aligned_target_assigner"):
-        loader._module("pcdet_ref.models.dense_heads.target_assigner." + name, os.path.join(ta, name + ".py"))
-    heads = os.path.join(pcdet, "models", "dense_heads")
-    loader._module("pcdet_ref.models.dense_heads.anchor_head_template", os.path.join(heads, "anchor_head_template.py"))
-    multi = loader._module("pcdet_ref.models.dense_heads.anchor_head_multi", os.path.join(heads, "anchor_head_multi.py"))
-    return multi, sys.modules["pcdet_ref.models.detectors.detector3d_template"], sys.modules["pcdet_ref.utils.box_utils"]
+    cpu_torch()
+    mods = load(root, "pcdet_ref", MODEL_UTILS + ["models.model_utils.model_nms_utils", "models.detectors.detector3d_template",
+                                                  "models.backbones_2d.base_bev_backbone"],
+                stubs=extension_stubs(dict(DETECTOR_STUBS, **{"models.roi_heads": {}})))
+    det, bev = mods[-2:]
+    sys.modules["pcdet_ref.models.backbones_2d"].BaseBEVBackbone = bev.BaseBEVBackbone      # where anchor_head_multi.py looks
+    multi = load(root, "pcdet_ref", ANCHOR_HEAD + ["models.dense_heads.anchor_head_multi"])[-1]
+    return multi, det, mods[MODEL_UTILS.index("utils.box_utils")]
 
 
 def make_head(mod, cfg):
@@ -320,9 +314,7 @@ def post_case(out, name, cfg, head, template, table, rows, cols, gt, rng):
 
 
 def main():
-    root = sys.argv[1] if len(sys.argv) > 1 else os.environ.get("PDA_REFERENCE_ROOT")
-    if not root:
-        sys.exit(__doc__)
+    root = reference_root()
     oracle.build()
     multi, template, box_utils = load_reference(root)
     rng = np.random.default_rng(20261020)

@@ -11,17 +11,16 @@ and per-object .bin files written to a temporary directory), with every draw it 
 The augmented scenes then go through the reference DataProcessor (mask_points_and_boxes_outside_range -> sample_points
 -> shuffle_points) and collate_batch with their draws recorded as make_input_golden.py records them (end-to-end case).
 
-The compiled modules are stubbed.  points_in_boxes_cpu is a numpy statement of roiaware_pool3d.cpp:121-170 (the CPU
-test, margin 1e-2) and boxes_bev_iou_cpu is the repository's C oracle of the BEV overlap (oracle/, the
+The compiled modules are stubbed (through reference_loader.py).  points_in_boxes_cpu is a numpy statement of
+roiaware_pool3d.cpp:121-170 (the CPU test, margin 1e-2) and boxes_bev_iou_cpu is the repository's C oracle of the BEV overlap (oracle/, the
 iou3d_nms_kernel.cu statement): like the other fixtures, this pins the reference's Python composition, not its C++
 arithmetic.  Inputs are kept away from knife edges so that either arithmetic decides alike: box pairs overlap clearly or
 stay 1e-3 apart, scene points stay 1e-4 or more from every enlarged database box face, final coordinates stay 1e-4 or
 more from the range planes and the 40 m sphere, final headings 1e-4 or more from +-pi.  Only inputs and outputs are
 stored.
 
-Run here only:  python tests/golden/make_augment_golden.py
+Run with the reference checkout:  python tests/golden/make_augment_golden.py /path/to/reference
 """
-import importlib
 import os
 import pickle
 import sys
@@ -31,8 +30,11 @@ import types
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = "/root/reference"
+sys.path.insert(0, HERE)
+from reference_loader import cpu_torch, load, points_in_boxes_cpu_np, q as _q, reference_root  # noqa: E402
+import oracle  # noqa: E402
+from pdanet_amd.config import AttrDict as AD, to_attr as _ad  # noqa: E402
+
 OUT = os.path.join(HERE, "augment.npz")
 K = 2048
 ONCE_CLASSES = ["Car", "Bus", "Truck", "Pedestrian", "Cyclist"]
@@ -69,54 +71,10 @@ def kitti_calib():
     return Calib(v2c, r0)
 
 
-class AD(dict):
-    def __getattr__(self, k):
-        try:
-            return self[k]
-        except KeyError:
-            raise AttributeError(k)
-
-
-def _ad(x):
-    if isinstance(x, dict):
-        return AD({k: _ad(v) for k, v in x.items()})
-    if isinstance(x, list):
-        return [_ad(v) for v in x]
-    return x
-
-
-def _mod(name, path=None, **attrs):
-    m = types.ModuleType(name)
-    if path is not None:
-        m.__path__ = [path]
-    m.__dict__.update(attrs)
-    sys.modules[name] = m
-    return m
-
-
-# ---- the CPU statements the stubs stand for ------------------------------------------------------------------------------
-def points_in_boxes_cpu_np(points, boxes):
-    """roiaware_pool3d.cpp check_pt_in_box3d_cpu for every (box, point): (N, num_points) int."""
-    pts = np.asarray(points, np.float32)
-    out = np.zeros((boxes.shape[0], pts.shape[0]), np.int32)
-    for i, b in enumerate(np.asarray(boxes, np.float32)):
-        cx, cy, cz, dx, dy, dz, rz = b[:7]
-        zin = np.abs(pts[:, 2] - cz).astype(np.float64) <= np.float64(dz) / 2.0
-        cosa, sina = np.float32(np.cos(-np.float64(rz))), np.float32(np.sin(-np.float64(rz)))
-        sx, sy = pts[:, 0] - cx, pts[:, 1] - cy
-        lx = sx * cosa + sy * (-sina)
-        ly = sx * sina + sy * cosa
-        m = np.float64(np.float32(1e-2))
-        inx = np.abs(lx).astype(np.float64) < np.float64(dx) / 2.0 + m
-        iny = np.abs(ly).astype(np.float64) < np.float64(dy) / 2.0 + m
-        out[i] = (zin & inx & iny).astype(np.int32)
-    return out
-
-
-def import_reference():
+def import_reference(root):
+    """-> (DataAugmentor, DataBaseSampler, DataProcessor, DatasetTemplate) of the reference, loaded as pcdet.*"""
     import torch
-    sys.path.insert(0, ROOT)
-    import oracle
+    cpu_torch()
     oracle.build()
 
     def boxes_bev_iou_cpu(a, b):
@@ -132,28 +90,15 @@ def import_reference():
         bx = boxes.numpy() if isinstance(boxes, torch.Tensor) else boxes
         return torch.from_numpy(points_in_boxes_cpu_np(pts, bx))
 
-    _mod("skimage", transform=None)
-    _mod("skimage.transform")
-    _mod("SharedArray")
-    _mod("cumm")
-    for pkg in ("pcdet", "pcdet.utils", "pcdet.ops", "pcdet.ops.roiaware_pool3d", "pcdet.ops.iou3d_nms", "pcdet.datasets",
-                "pcdet.datasets.processor", "pcdet.datasets.augmentor"):
-        _mod(pkg, REF + "/" + pkg.replace(".", "/"))
-    _mod("pcdet.ops.roiaware_pool3d.roiaware_pool3d_utils", points_in_boxes_cpu=points_in_boxes_cpu)
-    _mod("pcdet.ops.iou3d_nms.iou3d_nms_utils", boxes_bev_iou_cpu=boxes_bev_iou_cpu)
-    _mod("pcdet.datasets.processor.point_feature_encoder", PointFeatureEncoder=None)
-    da = importlib.import_module("pcdet.datasets.augmentor.data_augmentor")
-    dbs = importlib.import_module("pcdet.datasets.augmentor.database_sampler")
-    dp = importlib.import_module("pcdet.datasets.processor.data_processor")
-    ds = importlib.import_module("pcdet.datasets.dataset")
+    stubs = {"ops.roiaware_pool3d.roiaware_pool3d_utils": {"points_in_boxes_cpu": points_in_boxes_cpu},
+             "ops.iou3d_nms.iou3d_nms_utils": {"boxes_bev_iou_cpu": boxes_bev_iou_cpu},
+             "datasets.processor.point_feature_encoder": {"PointFeatureEncoder": None}}
+    da, dbs, dp, ds = load(root, "pcdet", ["datasets.augmentor.data_augmentor", "datasets.augmentor.database_sampler",
+                                           "datasets.processor.data_processor", "datasets.dataset"], stubs=stubs, real_paths=True)
     return da.DataAugmentor, dbs.DataBaseSampler, dp.DataProcessor, ds.DatasetTemplate
 
 
 # ---- synthetic database and scenes --------------------------------------------------------------------------------------
-def _q(x):
-    return (np.round(np.asarray(x, np.float64) * 256.0) / 256.0).astype(np.float32)
-
-
 def _rot(x, y, h):
     c, s = np.cos(h), np.sin(h)
     return x * c - y * s, x * s + y * c
@@ -439,9 +384,7 @@ def build_case(refs, maker, seed0, iou_fn, need):
 
 
 def main():
-    refs = import_reference()
-    sys.path.insert(0, ROOT)
-    import oracle
+    refs = import_reference(reference_root())
 
     def iou_fn(a, b):
         a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)

@@ -26,7 +26,7 @@ reference's draws depend on box counts only.  Box centres within 1e-4 of a world
 within 1e-4 of +-pi, reject the attempt.  Only inputs, draws and outputs are stored, plus per output row the number of
 rotations it went through and a few coverage counts that tests/test_augment_steps.py asserts.
 
-Run here only:  python tests/golden/make_augment_steps_golden.py
+Run with the reference checkout:  python tests/golden/make_augment_steps_golden.py /path/to/reference
 """
 import os
 import pathlib
@@ -37,10 +37,11 @@ import tempfile
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
 OUT = os.path.join(HERE, "augment_steps.npz")
 sys.path.insert(0, HERE)
 import make_augment_golden as mag  # noqa: E402
+from reference_loader import q, reference_root  # noqa: E402
+from pdanet_amd.config import to_attr  # noqa: E402
 
 CLASSES = ["Car", "Pedestrian", "Cyclist"]
 C = 5
@@ -193,8 +194,8 @@ def make_scene(rng, n_bg, region, zc, names, extra=()):
     p = np.concatenate(pts)
     p = p[rng.permutation(len(p))]
     out = np.zeros((len(p), 4), np.float32)
-    out[:, :3] = mag._q(p)
-    out[:, 3] = mag._q(rng.uniform(0, 1, len(p)))
+    out[:, :3] = q(p)
+    out[:, 3] = q(rng.uniform(0, 1, len(p)))
     return out, np.array(boxes, np.float32).reshape(-1, 7), np.array(list(names) + ["Car"] * len(extra), dtype="<U10")
 
 
@@ -264,7 +265,7 @@ def run_case(refs, cfg, infos, bins5, scenes5, seed):
         pickle.dump(infos, f)
     for path, p in bins5.items():
         p.tofile(os.path.join(tmp, path))
-    aug = DataAugmentor(pathlib.Path(tmp), mag._ad(cfg), CLASSES, logger=None)
+    aug = DataAugmentor(pathlib.Path(tmp), to_attr(cfg), CLASSES, logger=None)
     steps = [c for c in cfg["AUG_CONFIG_LIST"] if c["NAME"] not in cfg["DISABLE_AUG_LIST"]]
     tried = []
     if steps[0]["NAME"] == "gt_sampling":
@@ -400,7 +401,7 @@ def pad_rows(rows_per_scene, n_sub):
 
 
 def main():
-    refs = mag.import_reference()
+    refs = mag.import_reference(reference_root())
     import oracle
     import pcdet.datasets.augmentor.augmentor_utils as au
     instrument(au)

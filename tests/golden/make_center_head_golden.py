@@ -5,8 +5,8 @@ results of _topk, decode_bbox_from_heatmap and class_agnostic_nms, and the state
 BaseBEVBackbone.
 
 The reference's own center_head.py, centernet_utils.py, loss_utils.py, model_nms_utils.py, pointpillar_scatter.py and
-base_bev_backbone.py are loaded as pcdet_ref.* with their package imports stubbed: .cuda() is the identity, numba (not
-installed) is a stub whose jit is an identity decorator, iou3d_nms_cuda is bound to the repository's C oracle.  gt_boxes is
+base_bev_backbone.py are loaded as pcdet_ref.* through reference_loader.py: numba (not installed) is a stub whose jit is an
+identity decorator, iou3d_nms_cuda is bound to the repository's C oracle.  gt_boxes is
 cloned before each call, because assign_targets writes the head-local class index back into its argument.
 
 Two configurations on a map of W = 48, H = 40, B = 2 (not square, so that an x / y swap shows):
@@ -29,86 +29,34 @@ pair of boxes that enter the NMS has a BEV IoU within 1e-4 of NMS_THRESH.
 
 Run with the reference checkout:  python tests/golden/make_center_head_golden.py /path/to/reference
 """
-import importlib.util
 import json
 import os
 import sys
-import types
 
 import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = sys.argv[1] if len(sys.argv) > 1 else os.environ["PDA_REFERENCE"]
-PCDET = os.path.join(REF, "pcdet")
-OUT = os.path.join(HERE, "center_head.npz")
-sys.path.insert(0, ROOT)
+sys.path.insert(0, HERE)
+from reference_loader import MODEL_UTILS, cpu_torch, extension_stubs, load, reference_root, stub_numba  # noqa: E402
 import oracle  # noqa: E402
 from pdanet_amd.config import to_attr  # noqa: E402
 
+OUT = os.path.join(HERE, "center_head.npz")
 W, H, B = 48, 40, 2
+# the reference's center_head, centernet_utils, model_nms_utils, base_bev_backbone and pointpillar_scatter, once loaded
+CH = CU = NMS = BEV = PPS = None
 
 
-def _package(name, path=None, **attrs):
-    pkg = types.ModuleType(name)
-    pkg.__path__ = [path] if path else []
-    pkg.__dict__.update(attrs)
-    sys.modules[name] = pkg
-    parent, _, leaf = name.rpartition(".")
-    if parent in sys.modules:
-        setattr(sys.modules[parent], leaf, pkg)
-    return pkg
+def load_reference(root):
+    global CH, CU, NMS, BEV, PPS
+    cpu_torch()
+    stub_numba()
+    load(root, "pcdet_ref", MODEL_UTILS, stubs=extension_stubs())
+    NMS, CU, CH, BEV, PPS = load(root, "pcdet_ref", [
+        "models.model_utils.model_nms_utils", "models.model_utils.centernet_utils", "models.dense_heads.center_head",
+        "models.backbones_2d.base_bev_backbone", "models.backbones_2d.map_to_bev.pointpillar_scatter"])
 
-
-def _module(name, path):
-    spec = importlib.util.spec_from_file_location(name, path)
-    m = importlib.util.module_from_spec(spec)
-    sys.modules[name] = m
-    parent, _, leaf = name.rpartition(".")
-    setattr(sys.modules[parent], leaf, m)
-    spec.loader.exec_module(m)
-    return m
-
-
-def _overlap_bev(boxes_a, boxes_b, ans):
-    oracle.boxes_overlap_bev_gpu(boxes_a.numpy(), boxes_b.numpy(), ans.numpy())
-
-
-def _nms_gpu(boxes, keep, thresh):
-    return oracle.nms_gpu(boxes.numpy(), keep.numpy(), thresh)
-
-
-def _load_reference():
-    torch.Tensor.cuda = lambda self, *a, **k: self
-    sys.modules["SharedArray"] = types.ModuleType("SharedArray")
-    numba = types.ModuleType("numba")
-    numba.jit = lambda *a, **k: (lambda f: f)
-    sys.modules["numba"] = numba
-    _package("pcdet_ref", PCDET)
-    _package("pcdet_ref.utils", None)
-    _package("pcdet_ref.ops", None)
-    _package("pcdet_ref.ops.roiaware_pool3d", None, roiaware_pool3d_utils=types.ModuleType("roiaware_pool3d_utils"))
-    _package("pcdet_ref.ops.iou3d_nms", None)
-    _package("pcdet_ref.ops.iou3d_nms.iou3d_nms_cuda", None, boxes_overlap_bev_gpu=_overlap_bev, nms_gpu=_nms_gpu)
-    for name in ("common_utils", "box_utils", "loss_utils"):
-        _module("pcdet_ref.utils." + name, os.path.join(PCDET, "utils", name + ".py"))
-    _module("pcdet_ref.ops.iou3d_nms.iou3d_nms_utils", os.path.join(PCDET, "ops", "iou3d_nms", "iou3d_nms_utils.py"))
-    _package("pcdet_ref.models", None)
-    _package("pcdet_ref.models.model_utils", None)
-    nms = _module("pcdet_ref.models.model_utils.model_nms_utils", os.path.join(PCDET, "models", "model_utils", "model_nms_utils.py"))
-    cu = _module("pcdet_ref.models.model_utils.centernet_utils", os.path.join(PCDET, "models", "model_utils", "centernet_utils.py"))
-    _package("pcdet_ref.models.dense_heads", None)
-    ch = _module("pcdet_ref.models.dense_heads.center_head", os.path.join(PCDET, "models", "dense_heads", "center_head.py"))
-    _package("pcdet_ref.models.backbones_2d", None)
-    bev = _module("pcdet_ref.models.backbones_2d.base_bev_backbone", os.path.join(PCDET, "models", "backbones_2d", "base_bev_backbone.py"))
-    _package("pcdet_ref.models.backbones_2d.map_to_bev", None)
-    pps = _module("pcdet_ref.models.backbones_2d.map_to_bev.pointpillar_scatter",
-                  os.path.join(PCDET, "models", "backbones_2d", "map_to_bev", "pointpillar_scatter.py"))
-    return ch, cu, nms, bev, pps
-
-
-CH, CU, NMS, BEV, PPS = _load_reference()
 
 CLASS_NAMES = ['A', 'B', 'C']
 HEAD_DICT = {'center': {'out_channels': 2, 'num_conv': 2}, 'center_z': {'out_channels': 1, 'num_conv': 2},
@@ -366,6 +314,7 @@ def scatter_case(out, rng):
 
 
 def main():
+    load_reference(reference_root())
     rng = np.random.default_rng(20261018)
     torch.manual_seed(11)
     out = {'configs': np.array(json.dumps(CONFIGS)), 'class_names': np.array(CLASS_NAMES), 'map_hw': np.array([H, W], np.int64)}

@@ -1,11 +1,11 @@
 #!/usr/bin/env python
 """Generates tests/golden/dyn_voxel.npz: the REFERENCE's dynamic encoders
-(/root/reference/pcdet/models/backbones_3d/vfe/dynamic_mean_vfe.py DynamicMeanVFE and dynamic_pillar_vfe.py
+(pcdet/models/backbones_3d/vfe/dynamic_mean_vfe.py DynamicMeanVFE and dynamic_pillar_vfe.py
 DynamicPillarVFE / PFNLayerV2) run on the CPU over one synthetic collated batch, in the two settings of the Waymo recipes
 centerpoint_dyn_pillar_1x.yaml and voxel_rcnn_with_centerhead_dyn_voxel.yaml.
 
-The two files are loaded the way make_input_golden.py loads the processor: stub packages for the absent ones, nothing
-copied.  Tensor.cuda() is a no-op while the constructors run (they move three tensors).  torch_scatter is not installed
+The two files are loaded the way make_input_golden.py loads the processor (reference_loader.py): stub packages for the absent
+ones, nothing copied; Tensor.cuda() is a no-op (the constructors move three tensors).  torch_scatter is not installed
 and WAS NOT RUN: sys.modules holds the stand-in defined below, which states the contract of the two functions the
 encoders call:
   scatter_mean(src, index, dim=0): the sum over the rows of a segment in ascending row order (np.add.at, in src's dtype)
@@ -25,9 +25,8 @@ float32 difference (`*_d64`): float64 value = float64(f32) + float64(d64), far b
 The feature rows the first PFN layer sees are stored as their computed columns only (`pillar_fcols`: f_cluster, f_center,
 dist); the leading columns are columns of `points`.
 
-Run here only:  python tests/golden/make_dyn_voxel_golden.py
+Run with the reference checkout:  python tests/golden/make_dyn_voxel_golden.py /path/to/reference
 """
-import importlib
 import os
 import sys
 import types
@@ -36,21 +35,16 @@ import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference"
+sys.path.insert(0, HERE)
+from reference_loader import cpu_torch, load, q as _q, reference_root  # noqa: E402
+from pdanet_amd.config import AttrDict as AD  # noqa: E402
+
 OUT = os.path.join(HERE, "dyn_voxel.npz")
 BATCH, C = 3, 5
 VOXEL = dict(voxel_size=[0.1, 0.1, 0.15], range=[-75.2, -75.2, -2, 75.2, 75.2, 4])
 PILLAR = dict(voxel_size=[0.32, 0.32, 6], range=[-74.88, -74.88, -2, 74.88, 74.88, 4])
 PILLAR_CASES = (("abs_dist", True, True), ("rel", False, False))      # tag, USE_ABSLOTE_XYZ, WITH_DISTANCE
 NUM_FILTERS = [64, 64]
-
-
-class AD(dict):
-    def __getattr__(self, k):
-        try:
-            return self[k]
-        except KeyError:
-            raise AttributeError(k)
 
 
 # ---- the stand-in torch_scatter --------------------------------------------------------------------------------------------
@@ -107,26 +101,11 @@ def install_torch_scatter():
     return m
 
 
-def import_reference():
+def import_reference(root):
     install_torch_scatter()
-    for pkg in ("pcdet", "pcdet.models", "pcdet.models.backbones_3d", "pcdet.models.backbones_3d.vfe"):
-        m = types.ModuleType(pkg)
-        m.__path__ = [REF + "/" + pkg.replace(".", "/")]
-        sys.modules[pkg] = m
-    mean = importlib.import_module("pcdet.models.backbones_3d.vfe.dynamic_mean_vfe")
-    pillar = importlib.import_module("pcdet.models.backbones_3d.vfe.dynamic_pillar_vfe")
-    return mean, pillar
-
-
-class no_cuda:
-    """Tensor.cuda() returns the tensor itself while a constructor runs."""
-
-    def __enter__(self):
-        self.cuda = torch.Tensor.cuda
-        torch.Tensor.cuda = lambda t, *a, **k: t
-
-    def __exit__(self, *a):
-        torch.Tensor.cuda = self.cuda
+    cpu_torch()                        # the constructors move three tensors with .cuda()
+    vfe = "models.backbones_3d.vfe."
+    return load(root, "pcdet", [vfe + "dynamic_mean_vfe", vfe + "dynamic_pillar_vfe"], real_paths=True)
 
 
 class FloorLookup:
@@ -149,10 +128,6 @@ def grid_of(setting):
 
 
 # ---- the scenes ------------------------------------------------------------------------------------------------------------
-def _q(x):
-    return (np.round(np.asarray(x, np.float64) * 256.0) / 256.0).astype(np.float32)      # compressible values
-
-
 def make_points(rng):
     f = np.float32
     vlo, vvs = np.array(VOXEL["range"][:3]), np.array(VOXEL["voxel_size"])
@@ -253,8 +228,7 @@ def projection(rows, cols):
 
 def run_pillar(pillar_mod, points, use_abs, with_dist, dtype, state, cells):
     cfg = AD(USE_NORM=True, WITH_DISTANCE=with_dist, USE_ABSLOTE_XYZ=use_abs, NUM_FILTERS=NUM_FILTERS)
-    with no_cuda():
-        vfe = pillar_mod.DynamicPillarVFE(cfg, C, PILLAR["voxel_size"], grid_of(PILLAR).tolist(), PILLAR["range"])
+    vfe = pillar_mod.DynamicPillarVFE(cfg, C, PILLAR["voxel_size"], grid_of(PILLAR).tolist(), PILLAR["range"])
     if state is None:
         torch.manual_seed(20261018)
         for p in vfe.parameters():                      # seeded weights; BatchNorm away from its identity start
@@ -284,7 +258,7 @@ def run_pillar(pillar_mod, points, use_abs, with_dist, dtype, state, cells):
 
 
 def main():
-    mean_mod, pillar_mod = import_reference()
+    mean_mod, pillar_mod = import_reference(reference_root())
     rng = np.random.default_rng(20261018)
     points = make_points(rng)
     n = len(points)
@@ -292,8 +266,7 @@ def main():
     seen, real_unique = capture_unique()
     try:
         # ---- DynamicMeanVFE, the voxel setting -------------------------------------------------------------------------
-        with no_cuda():
-            vfe = mean_mod.DynamicMeanVFE(AD(), C, VOXEL["voxel_size"], grid_of(VOXEL).tolist(), VOXEL["range"])
+        vfe = mean_mod.DynamicMeanVFE(AD(), C, VOXEL["voxel_size"], grid_of(VOXEL).tolist(), VOXEL["range"])
         out = vfe({"points": torch.from_numpy(points), "batch_size": BATCH})
         mask, _ = index_outputs(points, VOXEL, False)
         data.update(voxel_range=np.array(VOXEL["range"], np.float64), voxel_size=np.array(VOXEL["voxel_size"], np.float64),

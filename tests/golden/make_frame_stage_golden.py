@@ -16,10 +16,8 @@ for the fixture it writes that the restatement's flags equal the reference's on 
 evaluation draws (1e-2 px around the image limits, 1e-3 m around depth 0), that the band holds at most 0.1 % of any scene,
 and that the deliberately placed near-edge points are outside the band.  Only inputs and outputs are stored.
 
-Run here only:  python tests/golden/make_frame_stage_golden.py
+Run with the reference checkout:  python tests/golden/make_frame_stage_golden.py /path/to/reference
 """
-import importlib
-import importlib.util
 import os
 import pathlib
 import pickle
@@ -30,8 +28,10 @@ import types
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = "/root/reference"
+sys.path.insert(0, HERE)
+import make_augment_golden as mag  # noqa: E402
+from reference_loader import ROOT, load, module, points_in_boxes_cpu_np, q as _q, reference_root  # noqa: E402
+
 OUT = os.path.join(HERE, "frame_stage.npz")
 
 CALIBS = [
@@ -50,28 +50,11 @@ DIMS = {"Car": (3.9, 1.6, 1.56), "Pedestrian": (0.8, 0.6, 1.73), "Cyclist": (1.7
 KITTI_USED = ["Car", "Pedestrian", "Cyclist"]
 
 
-def _load(name, path):
-    spec = importlib.util.spec_from_file_location(name, path)
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
-
-
-def _q(x, step=256.0):
-    return (np.round(np.asarray(x, np.float64) * step) / step).astype(np.float32)
-
-
-def import_reference(mag):
-    mag.import_reference()          # the stubs of make_augment_golden.py (points_in_boxes_cpu, the BEV IoU, SharedArray ...)
-    sys.modules["skimage"].io = None
-    mag._mod("skimage.io")
-    for pkg in ("pcdet.datasets.kitti", "pcdet.datasets.once"):
-        mag._mod(pkg, REF + "/" + pkg.replace(".", "/"))
-    mag._mod("pcdet.datasets.once.once_toolkits", Octopus=None)
-    calibration = importlib.import_module("pcdet.utils.calibration_kitti")
-    box_utils = importlib.import_module("pcdet.utils.box_utils")
-    kitti = importlib.import_module("pcdet.datasets.kitti.kitti_dataset")
-    once = importlib.import_module("pcdet.datasets.once.once_dataset")
+def import_reference(root):
+    mag.import_reference(root)      # the stubs of make_augment_golden.py (points_in_boxes_cpu, the BEV IoU, SharedArray ...)
+    calibration, box_utils, kitti, once = load(root, "pcdet", ["utils.calibration_kitti", "utils.box_utils",
+                                                               "datasets.kitti.kitti_dataset", "datasets.once.once_dataset"],
+                                               stubs={"datasets.once.once_toolkits": {"Octopus": None}}, real_paths=True)
     for m in (kitti, once):                 # the reference imports Path only under __main__
         if not hasattr(m, "Path"):
             m.Path = pathlib.Path
@@ -153,9 +136,8 @@ def edge_points(calib, shape, rng):
 
 
 def main():
-    mag = _load("make_augment_golden", os.path.join(HERE, "make_augment_golden.py"))
-    tfs = _load("test_frame_stage", os.path.join(ROOT, "tests", "test_frame_stage.py"))
-    calibration, ref_box_utils, KittiDataset, ONCEDataset = import_reference(mag)
+    tfs = module("test_frame_stage", os.path.join(ROOT, "tests", "test_frame_stage.py"))
+    calibration, ref_box_utils, KittiDataset, ONCEDataset = import_reference(reference_root())
     rng = np.random.default_rng(20260117)
     calibs = [ref_calib(calibration, c) for c in CALIBS]
     data = {}
@@ -240,7 +222,7 @@ def main():
     bins = [np.fromfile(tmp / "gt_database" / name, dtype=np.float32).reshape(-1, 4) for name in order]
     assert "Van" not in dbinfos and "Truck" not in dbinfos and set(dbinfos) == set(KITTI_USED)
     owner = np.zeros(len(frames[1][0]), np.int32)
-    for row in mag.points_in_boxes_cpu_np(frames[1][0][:, :3], frames[1][1]):
+    for row in points_in_boxes_cpu_np(frames[1][0][:, :3], frames[1][1]):
         owner += row
     assert (owner >= 2).sum() >= 5, "no points in two overlapping boxes"
     data["kitti_frame_ids"] = np.array(ids)

@@ -1,109 +1,38 @@
 #!/usr/bin/env python
-"""Generates tests/golden/*.npz|json by running the REFERENCE's own Python composition
-(/root/reference/pcdet/ops/pointnet2/pointnet2_batch/{pointnet2_utils,pointnet2_modules,
-PointFormer}.py and pcdet/models/backbones_3d/IASSD_backbone.py) on CPU, with its CUDA
-extension module replaced by a stub backed by this repo's CPU oracle.
+"""Generates tests/golden/reference_composition.npz, reference_composition_meta.json and backbone_state_dict_schema.json by
+running the REFERENCE's own Python composition (pcdet/ops/pointnet2/pointnet2_batch/{pointnet2_utils,pointnet2_modules,
+PointFormer}.py and pcdet/models/backbones_3d/IASSD_backbone.py) on CPU, with its CUDA extension module replaced by a stub
+backed by this repo's CPU oracle (reference_loader.pointnet2_batch_stub).
 
-Run here only (the GPU box has no /root/reference):  python tests/golden/make_golden.py
+Run with the reference checkout:  python tests/golden/make_golden.py /path/to/reference
 The reference sources are imported from where they lie; nothing of them is copied.  What is
 committed is data: seeds, small inputs, and the reference composition's outputs.
 """
-import importlib.util
 import json
 import os
 import sys
-import types
 
 import numpy as np
 import torch
 import yaml
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = "/root/reference"
-sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
-
-import oracle  # noqa: E402
+from reference_loader import cpu_torch, load, pointnet2_batch_stub, reference_root  # noqa: E402
 from detweights import fill_deterministic  # noqa: E402
+from pdanet_amd.config import to_attr  # noqa: E402
 
-torch.set_num_threads(8)
-
-
-# ---- stub extension: reference-named entry points on CPU tensors, backed by the oracle ----
-def _np(t):
-    assert t.device.type == "cpu" and t.is_contiguous()
-    return t.numpy()
+BATCH = "ops.pointnet2.pointnet2_batch."
 
 
-stub = types.ModuleType("pointnet2_batch_cuda")
-for _name in ["ball_query_wrapper", "ball_query_dilated_wrapper", "group_points_wrapper",
-              "group_points_grad_wrapper", "gather_points_wrapper", "gather_points_grad_wrapper",
-              "farthest_point_sampling_wrapper", "furthest_point_sampling_with_dist_wrapper",
-              "three_nn_wrapper", "three_interpolate_wrapper", "three_interpolate_grad_wrapper"]:
-    def _mk(name):
-        fn = getattr(oracle, name)
-
-        def call(*args):
-            return fn(*[_np(a) if isinstance(a, torch.Tensor) else a for a in args])
-        return call
-    setattr(stub, _name, _mk(_name))
-
-
-def _pkg(name, path=None):
-    m = types.ModuleType(name)
-    m.__path__ = [path] if path else []
-    sys.modules[name] = m
-    return m
-
-
-def import_reference():
-    # the reference allocates with torch.cuda.IntTensor/FloatTensor (pointnet2_utils.py:25-26...)
-    torch.cuda.IntTensor = torch.IntTensor
-    torch.cuda.FloatTensor = torch.FloatTensor
-    sys.modules["open3d"] = types.ModuleType("open3d")  # semantic_view.py:1 (visualisation only)
-    base = REF + "/pcdet/ops/pointnet2/pointnet2_batch"
-    _pkg("pcdet", REF + "/pcdet")
-    _pkg("pcdet.ops", REF + "/pcdet/ops")
-    _pkg("pcdet.ops.pointnet2", REF + "/pcdet/ops/pointnet2")
-    _pkg("pcdet.ops.pointnet2.pointnet2_batch", base)
-    sys.modules["pcdet.ops.pointnet2.pointnet2_batch.pointnet2_batch_cuda"] = stub
-    sys.modules["pcdet.ops.pointnet2.pointnet2_batch"].pointnet2_batch_cuda = stub
-
-    def load(modname, path):
-        spec = importlib.util.spec_from_file_location(modname, path)
-        mod = importlib.util.module_from_spec(spec)
-        sys.modules[modname] = mod
-        spec.loader.exec_module(mod)
-        return mod
-    pu = load("pcdet.ops.pointnet2.pointnet2_batch.pointnet2_utils", base + "/pointnet2_utils.py")
-    load("pcdet.ops.pointnet2.pointnet2_batch.PointFormer", base + "/PointFormer.py")
-    load("pcdet.ops.pointnet2.pointnet2_batch.semantic_view", base + "/semantic_view.py") \
-        if False else sys.modules.setdefault("pcdet.ops.pointnet2.pointnet2_batch.semantic_view",
-                                             types.ModuleType("semantic_view"))
-    pm = load("pcdet.ops.pointnet2.pointnet2_batch.pointnet2_modules", base + "/pointnet2_modules.py")
-    # backbone: parents + the unused torchsparse import (IASSD_backbone.py:7)
-    _pkg("pcdet.models", REF + "/pcdet/models")
-    _pkg("pcdet.models.backbones_3d", REF + "/pcdet/models/backbones_3d")
-    _pkg("pcdet.models.backbones_3d.cluster")
-    sp = types.ModuleType("pcdet.models.backbones_3d.cluster.spvnas_cluster")
-    sp.SPVNAS = object
-    sys.modules["pcdet.models.backbones_3d.cluster.spvnas_cluster"] = sp
-    bb = load("pcdet.models.backbones_3d.IASSD_backbone", REF + "/pcdet/models/backbones_3d/IASSD_backbone.py")
-    return pu, pm, bb
-
-
-class AD(dict):
-    def __getattr__(self, k):
-        return self[k]
-
-
-def to_ad(o):
-    if isinstance(o, dict):
-        return AD({k: to_ad(v) for k, v in o.items()})
-    if isinstance(o, list):
-        return [to_ad(v) for v in o]
-    return o
+def import_reference(root):
+    """-> (pointnet2_utils, PointFormer, pointnet2_modules, IASSD_backbone) of the reference, as pcdet.*"""
+    cpu_torch()              # the reference allocates with torch.cuda.IntTensor/FloatTensor (pointnet2_utils.py:25-26...)
+    # semantic_view.py is visualisation only; spvnas_cluster is the unused torchsparse import (IASSD_backbone.py:7)
+    stubs = {BATCH + "pointnet2_batch_cuda": pointnet2_batch_stub(), BATCH + "semantic_view": {},
+             "models.backbones_3d.cluster.spvnas_cluster": {"SPVNAS": object}}
+    return load(root, "pcdet", [BATCH + "pointnet2_utils", BATCH + "PointFormer", BATCH + "pointnet2_modules",
+                                "models.backbones_3d.IASSD_backbone"], stubs=stubs, real_paths=True)
 
 
 def scene_points(b, n, seed):
@@ -116,16 +45,18 @@ def t2n(x):
 
 
 def main():
-    pu, pm, bb = import_reference()
+    torch.set_num_threads(8)
+    root = reference_root()
+    pu, PF, pm, bb = import_reference(root)
     out = {}
-    meta = {"generator": "tests/golden/make_golden.py", "reference": "Geo3DSmart/PDANet @ /root/reference",
+    meta = {"generator": "tests/golden/make_golden.py", "reference": "Geo3DSmart/PDANet @ " + root,
             "torch": torch.__version__}
 
     # 1. state-dict schema of the reference backbone for both yamls
     schema = {}
-    for tag, path in [("once", REF + "/tools/cfgs/once_models/PDA-SSD.yaml"),
-                      ("kitti", REF + "/tools/cfgs/kitti_models/PDA-SSD.yaml")]:
-        cfg = to_ad(yaml.safe_load(open(path)))
+    for tag, path in [("once", root + "/tools/cfgs/once_models/PDA-SSD.yaml"),
+                      ("kitti", root + "/tools/cfgs/kitti_models/PDA-SSD.yaml")]:
+        cfg = to_attr(yaml.safe_load(open(path)))
         model = bb.IASSD_Backbone(cfg.MODEL.BACKBONE_3D, num_class=len(cfg.CLASS_NAMES), input_channels=4)
         schema[tag] = [[k, list(v.shape)] for k, v in model.state_dict().items()]
         meta[tag + "_params"] = sum(p.numel() for p in model.parameters())
@@ -133,7 +64,6 @@ def main():
 
     # 2. pure-torch sub-blocks
     torch.manual_seed(0)
-    PF = sys.modules["pcdet.ops.pointnet2.pointnet2_batch.PointFormer"]
     tr = fill_deterministic(PF.TransformerEncoderLayerPreNorm(d_model=32, nhead=4, dim_feedforward=16, dropout=0.0)).eval()
     x = torch.randn(8, 6, 32)
     out["transformer_in"] = t2n(x); out["transformer_out"] = t2n(tr(x))
@@ -205,7 +135,7 @@ def main():
     out["fp_known_feats"], out["fp_unknown_feats"] = t2n(kf), t2n(uf)
 
     # 6. the whole backbone, scaled-down point counts (real channel widths), eval + train BN
-    cfg = to_ad(yaml.safe_load(open(REF + "/tools/cfgs/once_models/PDA-SSD.yaml")))
+    cfg = to_attr(yaml.safe_load(open(root + "/tools/cfgs/once_models/PDA-SSD.yaml")))
     sa = cfg.MODEL.BACKBONE_3D.SA_CONFIG
     sa["NPOINT_LIST"] = [[2048], [512], [256], [128], [-1], [128]]
     meta["backbone_npoint_list"] = sa["NPOINT_LIST"]

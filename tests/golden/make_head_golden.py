@@ -1,11 +1,11 @@
 #!/usr/bin/env python
 """Generates tests/golden/head_{once,kitti}.npz: the REFERENCE's IASSD_Head
-(/root/reference/pcdet/models/dense_heads/IASSD_head.py, built from the POINT_HEAD section of the
+(pcdet/models/dense_heads/IASSD_head.py, built from the POINT_HEAD section of the
 reference's own PDA-SSD.yaml) run on CPU in training mode on seeded synthetic backbone outputs:
 forward -> assign_targets -> get_loss -> backward.  The CUDA extensions it reaches are stubbed with
-this repo's CPU oracle (points_in_boxes, chamfer); absent third-party imports (SharedArray,
-torch_scatter, open3d) are empty stub modules; `.cuda()` is made the identity.  Only inputs and
-outputs are stored.  Run here only:  python tests/golden/make_head_golden.py
+this repo's CPU oracle (points_in_boxes, chamfer, the pointnet2_batch entries); absent third-party imports and `.cuda()`
+are handled by reference_loader.py, torch_scatter is an empty stub.  Only inputs and
+outputs are stored.  Run with the reference checkout:  python tests/golden/make_head_golden.py /path/to/reference
 """
 import os
 import sys
@@ -17,41 +17,33 @@ import yaml
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-import make_golden as mg  # noqa: E402  (stub infrastructure: oracle-backed pointnet2_batch_cuda, _pkg, to_ad)
+from reference_loader import as_np, cpu_torch, load, np_args, pointnet2_batch_stub, reference_root  # noqa: E402
 from detweights import fill_deterministic  # noqa: E402
 from head_inputs import synth_inputs  # noqa: E402
-
 import oracle  # noqa: E402
+from pdanet_amd.config import to_attr  # noqa: E402
 
-REF = mg.REF
 
-
-def import_head():
-    mg.import_reference()
-    torch.Tensor.cuda = lambda self, *a, **k: self
+def import_head(root):
+    cpu_torch()
     torch.cuda.set_device = lambda d: None
-    for name in ("SharedArray", "torch_scatter"):
-        sys.modules[name] = types.ModuleType(name)
+    sys.modules["torch_scatter"] = types.ModuleType("torch_scatter")
     sys.modules["torch_scatter"].scatter_mean = sys.modules["torch_scatter"].scatter_max = None
     # chamfer entry points of pointnet2_batch_cuda (chamfer_cuda.cpp:22-31)
     # (only reached by the logged-only CD metric; its inputs are non-contiguous slices there)
-    mg.stub.chamfer_forward = lambda x1, x2, *a: oracle.chamfer_forward(mg._np(x1.contiguous()), mg._np(x2.contiguous()), *[mg._np(x) for x in a])
-    mg.stub.chamfer_backward = lambda x1, x2, *a: oracle.chamfer_backward(mg._np(x1.contiguous()), mg._np(x2.contiguous()), *[mg._np(x) for x in a])
-    roi = types.ModuleType("roiaware_pool3d_cuda")
-    roi.points_in_boxes_gpu = lambda boxes, pts, out: oracle.points_in_boxes_gpu(mg._np(boxes), mg._np(pts), mg._np(out))
-    mg._pkg("pcdet.utils", REF + "/pcdet/utils")
-    mg._pkg("pcdet.ops.roiaware_pool3d", REF + "/pcdet/ops/roiaware_pool3d")
-    sys.modules["pcdet.ops.roiaware_pool3d.roiaware_pool3d_cuda"] = roi
-    sys.modules["pcdet.ops.roiaware_pool3d"].roiaware_pool3d_cuda = roi
-    mg._pkg("pcdet.models.dense_heads", REF + "/pcdet/models/dense_heads")
-    import importlib
-    return importlib.import_module("pcdet.models.dense_heads.IASSD_head")
+    stub = pointnet2_batch_stub()
+    stub.chamfer_forward = lambda x1, x2, *a: oracle.chamfer_forward(as_np(x1.contiguous()), as_np(x2.contiguous()), *np_args(a))
+    stub.chamfer_backward = lambda x1, x2, *a: oracle.chamfer_backward(as_np(x1.contiguous()), as_np(x2.contiguous()), *np_args(a))
+    roi = {"points_in_boxes_gpu": lambda boxes, pts, out: oracle.points_in_boxes_gpu(as_np(boxes), as_np(pts), as_np(out))}
+    batch = "ops.pointnet2.pointnet2_batch."
+    stubs = {batch + "pointnet2_batch_cuda": stub, batch + "semantic_view": {}, "ops.roiaware_pool3d.roiaware_pool3d_cuda": roi}
+    return load(root, "pcdet", ["models.dense_heads.IASSD_head"], stubs=stubs, real_paths=True)[0]
 
 
 def run(head_mod, yaml_path, tag, seed):
     cfg = yaml.safe_load(open(yaml_path))
     num_class = len(cfg["CLASS_NAMES"])
-    head_cfg = mg.to_ad(cfg["MODEL"]["POINT_HEAD"])
+    head_cfg = to_attr(cfg["MODEL"]["POINT_HEAD"])
     torch.manual_seed(0)
     head = head_mod.IASSD_Head(num_class=num_class, input_channels=512, model_cfg=head_cfg)
     fill_deterministic(head, salt="head.")
@@ -100,7 +92,13 @@ def run(head_mod, yaml_path, tag, seed):
           "sa fg:", [int((l > 0).sum()) for l in r["sa_ins_labels"]])
 
 
+def main():
+    torch.set_num_threads(8)
+    root = reference_root()
+    hm = import_head(root)
+    run(hm, root + "/tools/cfgs/once_models/PDA-SSD.yaml", "once", seed=11)
+    run(hm, root + "/tools/cfgs/kitti_models/PDA-SSD.yaml", "kitti", seed=12)
+
+
 if __name__ == "__main__":
-    hm = import_head()
-    run(hm, REF + "/tools/cfgs/once_models/PDA-SSD.yaml", "once", seed=11)
-    run(hm, REF + "/tools/cfgs/kitti_models/PDA-SSD.yaml", "kitti", seed=12)
+    main()

@@ -1,66 +1,42 @@
 #!/usr/bin/env python
 """Generates tests/golden/input_stage.npz: the REFERENCE's input stage
-(/root/reference/pcdet/datasets/processor/data_processor.py DataProcessor: mask_points_and_boxes_outside_range ->
+(pcdet/datasets/processor/data_processor.py DataProcessor: mask_points_and_boxes_outside_range ->
 sample_points -> shuffle_points, then pcdet/datasets/dataset.py DatasetTemplate.collate_batch) run on synthetic ragged
 scenes, with every draw it makes recorded:
   * np.random.choice -> `pick`, stored as RANKS into the array it picks from (near_idxs / arange(n), both ascending);
   * np.random.shuffle (sample_points) -> `perm1`: the permutation the shuffle applied (shuffled[t] = before[perm1[t]]),
     obtained by shuffling arange(len) with the same generator state -- Fisher-Yates swaps depend on the length only;
   * np.random.permutation (shuffle_points) -> `perm2`.
-Absent modules are stubbed: skimage, SharedArray, cumm, roiaware_pool3d_cuda (box_utils imports it, the range mask does
-not reach it), and dataset.py's augmentor / point-feature-encoder imports.  Only inputs and outputs are stored.
+Absent modules are stubbed (reference_loader.py): skimage, SharedArray, cumm, roiaware_pool3d_cuda (box_utils imports it, the
+range mask does not reach it), and dataset.py's augmentor / point-feature-encoder imports.  Only inputs and outputs are stored.
 
 Box corners are kept 1e-4 or more away from every range plane: the reference rotates them through torch's CPU matmul,
 whose rounding (summation order, FMA use) is not specified, so a corner closer to a plane than that could fall on
 either side of it.
 
-Run here only:  python tests/golden/make_input_golden.py
+Run with the reference checkout:  python tests/golden/make_input_golden.py /path/to/reference
 """
-import importlib
 import os
 import sys
-import types
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference"
+sys.path.insert(0, HERE)
+from reference_loader import cpu_torch, load, q as _q, reference_root  # noqa: E402
+from pdanet_amd.config import AttrDict as AD  # noqa: E402
+
 OUT = os.path.join(HERE, "input_stage.npz")
 K = 4096
 ONCE_RANGE = [-75.2, -75.2, -5.0, 75.2, 75.2, 3.0]
 KITTI_RANGE = [0.0, -40.0, -3.0, 70.4, 40.0, 1.0]
 
 
-class AD(dict):
-    def __getattr__(self, k):
-        try:
-            return self[k]
-        except KeyError:
-            raise AttributeError(k)
-
-
-def _mod(name, path=None, **attrs):
-    m = types.ModuleType(name)
-    if path is not None:
-        m.__path__ = [path]
-    m.__dict__.update(attrs)
-    sys.modules[name] = m
-    return m
-
-
-def import_reference():
-    _mod("skimage", transform=None)
-    _mod("skimage.transform")
-    _mod("SharedArray")
-    _mod("cumm")
-    for pkg in ("pcdet", "pcdet.utils", "pcdet.ops", "pcdet.ops.roiaware_pool3d", "pcdet.datasets", "pcdet.datasets.processor",
-                "pcdet.datasets.augmentor"):
-        _mod(pkg, REF + "/" + pkg.replace(".", "/"))
-    _mod("pcdet.ops.roiaware_pool3d.roiaware_pool3d_cuda")
-    _mod("pcdet.datasets.augmentor.data_augmentor", DataAugmentor=None)
-    _mod("pcdet.datasets.processor.point_feature_encoder", PointFeatureEncoder=None)
-    dp = importlib.import_module("pcdet.datasets.processor.data_processor")
-    ds = importlib.import_module("pcdet.datasets.dataset")
+def import_reference(root):
+    cpu_torch()
+    stubs = {"ops.roiaware_pool3d.roiaware_pool3d_cuda": {}, "datasets.augmentor.data_augmentor": {"DataAugmentor": None},
+             "datasets.processor.point_feature_encoder": {"PointFeatureEncoder": None}}
+    dp, ds = load(root, "pcdet", ["datasets.processor.data_processor", "datasets.dataset"], stubs=stubs, real_paths=True)
     return dp.DataProcessor, ds.DatasetTemplate.collate_batch
 
 
@@ -103,10 +79,6 @@ class Recorder:
 
 
 # ---- synthetic scenes ----------------------------------------------------------------------------------------------------
-def _q(x):
-    return (np.round(np.asarray(x, np.float64) * 256.0) / 256.0).astype(np.float32)   # compressible coordinates
-
-
 def _cloud(rng, n, rmin, rmax, rng_xy, c, z=(-2.0, 0.5)):
     """n points at horizontal distance [rmin, rmax) from the origin inside the xy box rng_xy (x0, y0, x1, y1)."""
     out = np.zeros((0, c), np.float32)
@@ -262,7 +234,7 @@ def run(DataProcessor, collate, c, pr, scenes, boxes, training, seed):
 
 
 def main():
-    DataProcessor, collate = import_reference()
+    DataProcessor, collate = import_reference(reference_root())
     rng = np.random.default_rng(20261016)
     data, cases = {}, []
     for tag, maker, training, seed in (("once", scenes_once, True, 11), ("kitti", scenes_kitti, False, 12)):

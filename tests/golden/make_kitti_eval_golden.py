@@ -3,9 +3,8 @@
 (pcdet/datasets/kitti/kitti_object_eval_python/eval.py, rotate_iou.py) run on ~30 synthetic KITTI-like frames, and its
 generate_prediction_dicts geometry (pcdet/utils/calibration_kitti.py, box_utils.py) on a few synthetic calibrations.
 
-numba is stubbed: jit / cuda.jit are identity decorators, cuda.local.array is np.zeros(..., float32), and
-rotate_iou_gpu_eval is a loop over the reference's own devRotateIoUEval(query_k, box_n, criterion) with the same
-float32 casts and return dtype.  clean_data, get_thresholds and fused_compute_statistics are wrapped to record the
+numba is stubbed (reference_loader.stub_numba), and rotate_iou_gpu_eval is a loop over the reference's own
+devRotateIoUEval(query_k, box_n, criterion) with the same float32 casts and return dtype.  clean_data, get_thresholds and fused_compute_statistics are wrapped to record the
 flags, num_valid_gt, thresholds and pr table of every (metric, class, difficulty, overlap setting); the per-frame
 overlap blocks come from the reference's calculate_iou_partly(dt_annos, gt_annos, metric).
 
@@ -19,17 +18,14 @@ float64 template of generate_prediction_dicts.
 
 Run with the reference checkout:  python tests/golden/make_kitti_eval_golden.py /path/to/reference
 """
-import importlib.util
 import os
 import sys
-import types
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = sys.argv[1] if len(sys.argv) > 1 else os.environ["PDA_REFERENCE"]
-PCDET = os.path.join(REF, "pcdet")
-EVAL_DIR = os.path.join(PCDET, "datasets", "kitti", "kitti_object_eval_python")
+sys.path.insert(0, HERE)
+from reference_loader import extension_stubs, load, reference_root, stub_numba  # noqa: E402
 
 NAMES = ['Car', 'Pedestrian', 'Cyclist', 'Van', 'Person_sitting', 'Truck', 'Misc', 'DontCare']
 CLASSES = ['Car', 'Pedestrian', 'Cyclist', 'Truck']
@@ -40,55 +36,17 @@ THRS = (0.25, 0.5, 0.7)
 IMG_W, IMG_H = 1242, 375
 
 
-def _stub_numba():
-    ident = lambda *a, **k: (lambda f: f) if not (len(a) == 1 and callable(a[0]) and not k) else a[0]
-    cuda = types.ModuleType("numba.cuda")
-    cuda.jit = ident
-    cuda.local = types.SimpleNamespace(array=lambda shape, dtype=None: np.zeros(shape, np.float32))
-    cuda.shared = cuda.local
-    numba = types.ModuleType("numba")
-    numba.jit = ident
-    numba.njit = ident
-    numba.float32 = np.float32
-    numba.cuda = cuda
-    sys.modules["numba"] = numba
-    sys.modules["numba.cuda"] = cuda
+ROT = EV = BOX = CAL = None      # the reference's rotate_iou, eval, box_utils and calibration_kitti, once load_reference has run
 
 
-def _package(name, path):
-    pkg = types.ModuleType(name)
-    pkg.__path__ = [path] if path else []
-    sys.modules[name] = pkg
-    return pkg
-
-
-def _module(name, path):
-    spec = importlib.util.spec_from_file_location(name, path)
-    m = importlib.util.module_from_spec(spec)
-    sys.modules[name] = m
-    spec.loader.exec_module(m)
-    return m
-
-
-def _load_reference():
-    _stub_numba()
-    _package("kitti_ref", EVAL_DIR)
-    rot = _module("kitti_ref.rotate_iou", os.path.join(EVAL_DIR, "rotate_iou.py"))
-    ev = _module("kitti_ref.eval", os.path.join(EVAL_DIR, "eval.py"))
-    # box_utils without the compiled ops it imports but these functions do not use
-    _package("pcdet_ref", PCDET)
-    _package("pcdet_ref.ops", None)
-    ops = _package("pcdet_ref.ops.roiaware_pool3d", None)
-    ops.roiaware_pool3d_utils = None
-    _package("pcdet_ref.utils", os.path.join(PCDET, "utils"))
-    sys.modules["pcdet_ref.utils.common_utils"] = types.ModuleType("pcdet_ref.utils.common_utils")
-    sys.modules["pcdet_ref.utils"].common_utils = sys.modules["pcdet_ref.utils.common_utils"]
-    box = _module("pcdet_ref.utils.box_utils", os.path.join(PCDET, "utils", "box_utils.py"))
-    cal = _module("pcdet_ref.utils.calibration_kitti", os.path.join(PCDET, "utils", "calibration_kitti.py"))
-    return rot, ev, box, cal
-
-
-ROT, EV, BOX, CAL = _load_reference()
+def load_reference(root):
+    global ROT, EV, BOX, CAL
+    stub_numba()
+    kitti_eval = "datasets.kitti.kitti_object_eval_python."
+    # box_utils without common_utils and the compiled ops, which it imports but these functions do not use
+    ROT, EV, BOX, CAL = load(root, "pcdet_ref", [kitti_eval + "rotate_iou", kitti_eval + "eval", "utils.box_utils",
+                                                 "utils.calibration_kitti"], stubs=extension_stubs({"utils.common_utils": {}}))
+    EV.rotate_iou_gpu_eval = rotate_iou_loop
 
 
 def rotate_iou_loop(boxes, query_boxes, criterion=-1, device_id=0):
@@ -99,9 +57,6 @@ def rotate_iou_loop(boxes, query_boxes, criterion=-1, device_id=0):
         for k in range(q32.shape[0]):
             iou[n, k] = ROT.devRotateIoUEval(np.ascontiguousarray(q32[k]), np.ascontiguousarray(b32[n]), criterion)
     return iou.astype(b32.dtype)
-
-
-EV.rotate_iou_gpu_eval = rotate_iou_loop
 
 
 # ---- scenes ------------------------------------------------------------------------------------------------------------
@@ -383,6 +338,7 @@ def pack(frames, prefix, aos, out):
 
 
 def main():
+    load_reference(reference_root())
     frames = build_scenes()
     out = {'names': np.array(NAMES), 'classes': np.array(CLASSES)}
     gt_annos, dt_annos = pack(frames, 'aos/', True, out)

@@ -2,9 +2,8 @@
 """Generates tests/golden/once_eval.npz: the REFERENCE's ONCE evaluation (pcdet/datasets/once/once_eval/evaluation.py,
 eval_utils.py, iou_utils.py) run on ~30 synthetic ONCE-like frames.
 
-numba is stubbed: jit / cuda.jit are identity decorators, cuda.local.array is np.zeros(..., float32), and
-rotate_iou_gpu_eval is a loop over the reference's own devRotateIoUEval(pred, gt, 2) with the same float32 casts and
-return dtype.  num_parts = the number of frames, so only per-frame blocks are computed (as the reference uses them).
+numba is stubbed (reference_loader.stub_numba), and rotate_iou_gpu_eval is a loop over the reference's own
+devRotateIoUEval(pred, gt, 2) with the same float32 casts and return dtype.  num_parts = the number of frames, so only per-frame blocks are computed (as the reference uses them).
 get_thresholds and compute_statistics are wrapped to record the thresholds, num_valid_gt and summed tp / fp / fn of
 every (class, difficulty).
 
@@ -14,18 +13,16 @@ frame without GT, a class without GT (Bus) and one frame with more than 64 GT an
 redrawn: |iou - thr| < 1e-3 for 0.3 / 0.5 / 0.7, distances within 1e-3 of 30 or 50, folded heading differences within
 1e-3 of pi / 2 or pi, and any pair for which the stubbed reference overflows its 16-float point buffer.
 
-Run here only:  python tests/golden/make_once_eval_golden.py [/path/to/reference]
+Run with the reference checkout:  python tests/golden/make_once_eval_golden.py /path/to/reference
 """
-import importlib.util
 import os
 import sys
-import types
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = sys.argv[1] if len(sys.argv) > 1 else os.environ.get("PDA_REFERENCE", "/root/reference")
-EVAL_DIR = os.path.join(REF, "pcdet", "datasets", "once", "once_eval")
+sys.path.insert(0, HERE)
+from reference_loader import load, reference_root, stub_numba  # noqa: E402
 
 NAMES = ['Car', 'Bus', 'Truck', 'Pedestrian', 'Cyclist', 'Tricycle']
 CLASSES = ['Car', 'Bus', 'Truck', 'Pedestrian', 'Cyclist']
@@ -42,38 +39,16 @@ CONFIGS = [
 ]
 
 
-def _stub_numba():
-    ident = lambda *a, **k: (lambda f: f) if not (len(a) == 1 and callable(a[0]) and not k) else a[0]
-    cuda = types.ModuleType("numba.cuda")
-    cuda.jit = ident
-    cuda.local = types.SimpleNamespace(array=lambda shape, dtype=None: np.zeros(shape, np.float32))
-    cuda.shared = cuda.local
-    numba = types.ModuleType("numba")
-    numba.jit = ident
-    numba.njit = ident
-    numba.float32 = np.float32
-    numba.cuda = cuda
-    sys.modules["numba"] = numba
-    sys.modules["numba.cuda"] = cuda
-
-
-def _load_reference():
-    _stub_numba()
-    pkg = types.ModuleType("once_eval")
-    pkg.__path__ = [EVAL_DIR]
-    sys.modules["once_eval"] = pkg
-    mods = {}
-    for name in ("iou_utils", "eval_utils", "evaluation"):
-        spec = importlib.util.spec_from_file_location("once_eval." + name, os.path.join(EVAL_DIR, name + ".py"))
-        m = importlib.util.module_from_spec(spec)
-        sys.modules["once_eval." + name] = m
-        spec.loader.exec_module(m)
-        mods[name] = m
-    return mods
-
-
-REFM = _load_reference()
+REFM = {}                        # the reference's iou_utils, eval_utils and evaluation by name, once load_reference has run
 _INTER = {}
+
+
+def load_reference(root):
+    stub_numba()
+    names = ("iou_utils", "eval_utils", "evaluation")
+    REFM.update(zip(names, load(root, "pcdet_ref", ["datasets.once.once_eval." + name for name in names])))
+    REFM["evaluation"].rotate_iou_gpu_eval = rotate_iou_loop
+    return REFM
 
 
 def _pair_area(p5, g5):
@@ -92,9 +67,6 @@ def rotate_iou_loop(boxes, query_boxes, criterion=-1, device_id=0):
         for k in range(q32.shape[0]):
             iou[n, k] = _pair_area(np.ascontiguousarray(q32[k]), np.ascontiguousarray(b32[n]))
     return iou.astype(boxes.dtype)
-
-
-REFM["evaluation"].rotate_iou_gpu_eval = rotate_iou_loop
 
 
 def ref_ious(gt_boxes, pred_boxes, heading):
@@ -238,6 +210,7 @@ def run_reference(gt_annos, pred_annos, kwargs):
 
 
 def main():
+    load_reference(reference_root())
     gt_annos, pred_annos = build_scenes()
     n_gt = np.array([len(a['name']) for a in gt_annos])
     n_pred = np.array([len(a['name']) for a in pred_annos])

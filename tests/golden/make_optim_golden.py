@@ -1,7 +1,9 @@
 """Generates tests/golden/optim_onecycle.npz by running the REFERENCE's optimizer code
-(/root/reference/tools/train_utils/optimization: build_optimizer / build_scheduler with
+(tools/train_utils/optimization: build_optimizer / build_scheduler with
 OPTIMIZER=adam_onecycle, plus clip_grad_norm_ as in train_utils.py:56) on CPU for 12 iterations of a
-small model with seeded parameters and gradients.  Only inputs and outputs are stored."""
+small model with seeded parameters and gradients.  Only inputs and outputs are stored.
+
+Run with the reference checkout:  python tests/golden/make_optim_golden.py /path/to/reference"""
 import os
 import sys
 import types
@@ -11,10 +13,9 @@ import torch
 from torch import nn
 from torch.nn.utils import clip_grad_norm_
 
-sys.path.insert(0, "/root/reference/tools/train_utils")
-from optimization import build_optimizer, build_scheduler  # noqa: E402
-
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+from reference_loader import reference_root  # noqa: E402
 
 
 class Net(nn.Module):
@@ -28,6 +29,8 @@ class Net(nn.Module):
 
 
 def main():
+    sys.path.insert(0, os.path.join(reference_root(), "tools", "train_utils"))
+    from optimization import build_optimizer, build_scheduler    # the reference's package, importable as it lies
     torch.manual_seed(20240)
     model = Net()
     names = [n for n, _ in model.named_parameters()]

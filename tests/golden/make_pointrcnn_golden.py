@@ -9,8 +9,9 @@ Stubs: `pointnet2_batch_cuda` over the repository's C oracle (ball query, farthe
 gathering and interpolation entries are numpy gathers in the dtype of the run), `roipoint_pool3d_cuda` over
 roi_pool_restatement.py, `points_in_boxes_gpu` over stack_sa_restatement.py, the NMS and the RoI sampling by what
 make_roi_targets_golden.py uses (its run_targets, which records the reference's draws).  Nothing of the reference is copied;
-what is committed is data.  The float64 run points torch.cuda.FloatTensor at the double constructor and lets .float() return
-a double, so that the reference's own allocations and casts follow the run's precision; every input of it is a float32 value.
+what is committed is data.  The float64 run (reference_loader.precision) points the reference's float allocator at the double
+constructor and lets .float() return a double, so that the reference's own allocations and casts follow the run's precision;
+every input of it is a float32 value.
 
 pointrcnn.npz -- every float output as <key> (float32 run) and <key>_f64:
   sa_*   one PointnetSAModuleMSG (npoint 32, two scales) and one PointnetSAModule(npoint=None) on 2 x 128 points: train and
@@ -45,7 +46,6 @@ Coordinates lie on the 1/8 lattice.  The generator fails (a part then tries its 
 pointrcnn_state_dict.json: keys and shapes, in order, of the reference's PointNet2MSG, PointHeadBox and PointRCNNHead for
 kitti_models/pointrcnn.yaml (3 classes, 4 point features), of the whole PointRCNN in the reference's module order, and the
 config used."""
-import contextlib
 import copy
 import json
 import os
@@ -55,17 +55,13 @@ import types
 import numpy as np
 import torch
 import torch.nn as nn
-import yaml
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, HERE)
-sys.path.insert(0, ROOT)
-import make_roi_targets_golden as rt  # noqa: E402  (loads the reference's utils, NMS and roi_head_template as pcdet_ref.*)
+from reference_loader import load, model_yaml, precision, randomise, reference_root, shapes, state, write_state_dict  # noqa: E402
+import make_roi_targets_golden as rt  # noqa: E402  (the scenes and run_targets, which records the reference's draws)
 import oracle  # noqa: E402
 import roi_pool_restatement as rp  # noqa: E402
-import stack_sa_restatement as rs  # noqa: E402
-from make_voxel_rcnn_golden import randomise, shapes, state  # noqa: E402
 from pdanet_amd.config import to_attr  # noqa: E402
 
 F32, I32, F64 = np.float32, np.int32, np.float64
@@ -73,7 +69,6 @@ WIN_MARGIN = 2e-5
 t = torch.from_numpy
 QUERIES = []                     # (radius, new_xyz (B, M, 3), xyz (B, N, 3)) of every ball query made, for condition (b)
 SAMPLINGS = []                   # (xyz (B, N, 3), npoint) of every farthest-point sampling made, for condition (d)
-PCDET = rt.PCDET
 
 
 def _c32(x):
@@ -154,54 +149,21 @@ def _roipoint_forward(xyz, boxes3d, pts_feature, pooled_features, pooled_empty_f
                                       pooled_empty_flag.numpy())
 
 
-def load_reference():
+def load_reference(root):
     """-> (pointnet2_modules, pointnet2_backbone, box_coder_utils, point_head_box, pointrcnn_head) of the reference, beside what
-    make_roi_targets_golden has loaded as pcdet_ref.*"""
-    torch.cuda.IntTensor, torch.cuda.FloatTensor = torch.IntTensor, torch.FloatTensor
-    pib = sys.modules["pcdet_ref.ops.roiaware_pool3d"].roiaware_pool3d_utils
-    pib.points_in_boxes_gpu = lambda points, boxes: t(rs.points_in_boxes_gpu(_c32(points), _c32(boxes)))
-    sys.modules["pcdet_ref.ops.roiaware_pool3d.roiaware_pool3d_utils"] = pib
-    ops = os.path.join(PCDET, "ops")
-    rt._package("pcdet_ref.ops.pointnet2", None)
-    stub = Stub()
-    rt._package("pcdet_ref.ops.pointnet2.pointnet2_batch", None, pointnet2_batch_cuda=stub,
-                semantic_view=types.ModuleType("semantic_view"))
-    sys.modules["pcdet_ref.ops.pointnet2.pointnet2_batch.pointnet2_batch_cuda"] = stub
-    batch = os.path.join(ops, "pointnet2", "pointnet2_batch")
-    for name in ("pointnet2_utils", "PointFormer", "pointnet2_modules"):
-        rt._module("pcdet_ref.ops.pointnet2.pointnet2_batch." + name, os.path.join(batch, name + ".py"))
+    make_roi_targets_golden loads as pcdet_ref.*"""
+    rt.load_reference(root)
+    batch = "ops.pointnet2.pointnet2_batch."
     # pointnet2_backbone.py imports the stack package for PointNet2Backbone, which nothing here builds
-    rt._package("pcdet_ref.ops.pointnet2.pointnet2_stack", None, pointnet2_modules=types.ModuleType("pointnet2_modules"),
-                pointnet2_utils=types.ModuleType("pointnet2_utils"))
-    rt._package("pcdet_ref.ops.roipoint_pool3d", None, roipoint_pool3d_cuda=types.SimpleNamespace(forward=_roipoint_forward))
-    rt._module("pcdet_ref.ops.roipoint_pool3d.roipoint_pool3d_utils", os.path.join(ops, "roipoint_pool3d", "roipoint_pool3d_utils.py"))
-    models = os.path.join(PCDET, "models")
-    rt._package("pcdet_ref.models.backbones_3d", None)
-    bb = rt._module("pcdet_ref.models.backbones_3d.pointnet2_backbone", os.path.join(models, "backbones_3d", "pointnet2_backbone.py"))
-    rt._package("pcdet_ref.models.dense_heads", None)
-    rt._module("pcdet_ref.models.dense_heads.point_head_template", os.path.join(models, "dense_heads", "point_head_template.py"))
-    ph = rt._module("pcdet_ref.models.dense_heads.point_head_box", os.path.join(models, "dense_heads", "point_head_box.py"))
-    rh = rt._module("pcdet_ref.models.roi_heads.pointrcnn_head", os.path.join(models, "roi_heads", "pointrcnn_head.py"))
-    return sys.modules["pcdet_ref.ops.pointnet2.pointnet2_batch.pointnet2_modules"], bb, rt.CODER, ph, rh
-
-
-@contextlib.contextmanager
-def precision(dtype):
-    """float64: the reference's torch.cuda.FloatTensor allocations and .float() casts give doubles."""
-    if dtype == torch.float32:
-        yield
-        return
-    alloc, own = torch.cuda.FloatTensor, torch.Tensor.__dict__.get('float')
-    torch.cuda.FloatTensor = torch.DoubleTensor
-    torch.Tensor.float = lambda self, *a, **k: self.double()
-    try:
-        yield
-    finally:
-        torch.cuda.FloatTensor = alloc
-        if own is None:
-            del torch.Tensor.float
-        else:
-            torch.Tensor.float = own
+    stubs = {batch + "pointnet2_batch_cuda": Stub(), batch + "semantic_view": {},
+             "ops.pointnet2.pointnet2_stack": {"pointnet2_modules": types.ModuleType("pointnet2_modules"),
+                                               "pointnet2_utils": types.ModuleType("pointnet2_utils")},
+             "ops.roipoint_pool3d.roipoint_pool3d_cuda": {"forward": _roipoint_forward}}
+    load(root, "pcdet_ref", [batch + "pointnet2_utils", batch + "PointFormer", "ops.roipoint_pool3d.roipoint_pool3d_utils",
+                             "models.dense_heads.point_head_template"], stubs=stubs)
+    pm, bb, ph, rh = load(root, "pcdet_ref", [batch + "pointnet2_modules", "models.backbones_3d.pointnet2_backbone",
+                                              "models.dense_heads.point_head_box", "models.roi_heads.pointrcnn_head"])
+    return pm, bb, rt.CODER, ph, rh
 
 
 RUNS = ((torch.float32, ""), (torch.float64, "_f64"))
@@ -727,8 +689,7 @@ def rh_part(rh, out):
 
 
 def state_dict_part(root, bb, ph, rh):
-    with open(os.path.join(root, "tools", "cfgs", "kitti_models", "pointrcnn.yaml")) as f:
-        y = yaml.safe_load(f)
+    y = model_yaml(root, "kitti_models/pointrcnn.yaml")
     model, names = y["MODEL"], y["CLASS_NAMES"]
     backbone = bb.PointNet2MSG(to_attr(copy.deepcopy(model["BACKBONE_3D"])), input_channels=4)
     point = ph.PointHeadBox(num_class=3, input_channels=backbone.num_point_features, model_cfg=to_attr(copy.deepcopy(model["POINT_HEAD"])),
@@ -738,15 +699,12 @@ def state_dict_part(root, bb, ph, rh):
     # the whole detector: the reference's module_topology keeps backbone_3d, point_head, roi_head of this config, in that order
     out["PointRCNN"] = shapes(backbone, "backbone_3d.") + shapes(point, "point_head.") + shapes(head, "roi_head.")
     out["config"] = {"MODEL": model, "dataset": {"class_names": names, "num_point_features": 4}}
-    path = os.path.join(HERE, "pointrcnn_state_dict.json")
-    with open(path, "w") as f:
-        json.dump(out, f, indent=0)
-    print(path, {k: len(v) for k, v in out.items()})
+    write_state_dict("pointrcnn_state_dict.json", out)
 
 
 def main():
-    root = rt.REF
-    pm, bb, coder_mod, ph, rh = load_reference()
+    root = reference_root()
+    pm, bb, coder_mod, ph, rh = load_reference(root)
     out = {}
     sa_part(pm, out)
     fp_part(pm, out)

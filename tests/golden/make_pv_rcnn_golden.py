@@ -6,10 +6,9 @@ they lie and run on the CPU in float32.
     python tests/golden/make_pv_rcnn_golden.py <checkout of the reference>
 
 The `pointnet2_stack_cuda` extension is a stub over numpy restatements (stack_sa_restatement.py: ball query, farthest-point
-sampling; the grouping entries are gathers), roiaware_pool3d_utils.points_in_boxes_gpu likewise.  torch.cuda.IntTensor /
-FloatTensor, which the reference's autograd functions allocate with, are pointed at the CPU constructors.  Nothing of the
-reference is copied; what is committed is data.  The grouping backward adds in float32, as the reference's kernel does with
-its float atomicAdd (in an order the hardware picks; the stub takes the ascending one): a float64 accumulation there would
+sampling; the grouping entries are gathers), roiaware_pool3d_utils.points_in_boxes_gpu likewise; the loading and the CPU
+patches are reference_loader.py's.  Nothing of the reference is copied; what is committed is data.  The grouping backward
+adds in float32, as the reference's kernel does with its float atomicAdd (in an order the hardware picks; the stub takes the ascending one): a float64 accumulation there would
 make the fixture's feature gradient more accurate than any float32 run of the reference, and the tests measure the device
 against the error of such a run.
 
@@ -53,14 +52,13 @@ import types
 
 import numpy as np
 import torch
-import yaml
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, HERE)
-sys.path.insert(0, ROOT)
 import stack_sa_restatement as rs  # noqa: E402
-from make_voxel_rcnn_golden import GRID_XYZ, PCR, VOXEL, _module, _np, _package, randomise, shapes, sparse_level, state  # noqa: E402
+from make_voxel_rcnn_golden import PCR, VOXEL, sparse_level  # noqa: E402
+from reference_loader import (MODEL_UTILS, ROI_HEAD, as_np as _np, cpu_torch, extension_stubs, load, model_yaml,  # noqa: E402
+                              randomise, reference_root, second_settings, shapes, state, write_state_dict)
 from pdanet_amd.config import to_attr  # noqa: E402
 
 F32, I32 = np.float32, np.int32
@@ -102,47 +100,12 @@ class Stub(types.ModuleType):
 
 def load_reference(root):
     """-> the reference's modules as pcdet_ref.*"""
-    pcdet = os.path.join(root, "pcdet")
-    torch.cuda.IntTensor, torch.cuda.FloatTensor = torch.IntTensor, torch.FloatTensor
-    torch.Tensor.cuda = lambda self, *a, **k: self
-    sys.modules["SharedArray"] = types.ModuleType("SharedArray")
-    pib = types.ModuleType("roiaware_pool3d_utils")
-    pib.points_in_boxes_gpu = lambda points, boxes: t(rs.points_in_boxes_gpu(_np(points.contiguous()), _np(boxes.contiguous())))
-    _package("pcdet_ref", pcdet)
-    _package("pcdet_ref.utils", None)
-    _package("pcdet_ref.ops", None)
-    _package("pcdet_ref.ops.roiaware_pool3d", None, roiaware_pool3d_utils=pib)
-    sys.modules["pcdet_ref.ops.roiaware_pool3d.roiaware_pool3d_utils"] = pib
-    _package("pcdet_ref.ops.iou3d_nms", None)
-    _package("pcdet_ref.ops.iou3d_nms.iou3d_nms_cuda", None)
-    for name in ("common_utils", "box_utils", "loss_utils", "box_coder_utils"):
-        _module("pcdet_ref.utils." + name, os.path.join(pcdet, "utils", name + ".py"))
-    _module("pcdet_ref.ops.iou3d_nms.iou3d_nms_utils", os.path.join(pcdet, "ops", "iou3d_nms", "iou3d_nms_utils.py"))
-    stack = os.path.join(pcdet, "ops", "pointnet2", "pointnet2_stack")
-    _package("pcdet_ref.ops.pointnet2", None)
-    _package("pcdet_ref.ops.pointnet2.pointnet2_stack", None, pointnet2_stack_cuda=Stub())
-    sys.modules["pcdet_ref.ops.pointnet2.pointnet2_stack.pointnet2_stack_cuda"] = sys.modules[
-        "pcdet_ref.ops.pointnet2.pointnet2_stack"].pointnet2_stack_cuda
-    for name in ("pointnet2_utils", "pointnet2_modules"):
-        _module("pcdet_ref.ops.pointnet2.pointnet2_stack." + name, os.path.join(stack, name + ".py"))
-    _package("pcdet_ref.models", None)
-    _package("pcdet_ref.models.model_utils", None)
-    _module("pcdet_ref.models.model_utils.model_nms_utils", os.path.join(pcdet, "models", "model_utils", "model_nms_utils.py"))
-    _package("pcdet_ref.models.backbones_3d", None)
-    _package("pcdet_ref.models.backbones_3d.pfe", None)
-    vsa = _module("pcdet_ref.models.backbones_3d.pfe.voxel_set_abstraction",
-                  os.path.join(pcdet, "models", "backbones_3d", "pfe", "voxel_set_abstraction.py"))
-    _package("pcdet_ref.models.dense_heads", None)
-    _module("pcdet_ref.models.dense_heads.point_head_template", os.path.join(pcdet, "models", "dense_heads", "point_head_template.py"))
-    point = _module("pcdet_ref.models.dense_heads.point_head_simple", os.path.join(pcdet, "models", "dense_heads", "point_head_simple.py"))
-    heads = os.path.join(pcdet, "models", "roi_heads")
-    _package("pcdet_ref.models.roi_heads", None)
-    _package("pcdet_ref.models.roi_heads.target_assigner", None)
-    _module("pcdet_ref.models.roi_heads.target_assigner.proposal_target_layer",
-            os.path.join(heads, "target_assigner", "proposal_target_layer.py"))
-    _module("pcdet_ref.models.roi_heads.roi_head_template", os.path.join(heads, "roi_head_template.py"))
-    head = _module("pcdet_ref.models.roi_heads.pvrcnn_head", os.path.join(heads, "pvrcnn_head.py"))
-    return sys.modules["pcdet_ref.ops.pointnet2.pointnet2_stack.pointnet2_modules"], vsa, point, head
+    cpu_torch()
+    stack = "ops.pointnet2.pointnet2_stack."
+    load(root, "pcdet_ref", MODEL_UTILS + ROI_HEAD + [stack + "pointnet2_utils", "models.dense_heads.point_head_template"],
+         stubs=extension_stubs({stack + "pointnet2_stack_cuda": Stub()}))
+    return load(root, "pcdet_ref", [stack + "pointnet2_modules", "models.backbones_3d.pfe.voxel_set_abstraction",
+                                    "models.dense_heads.point_head_simple", "models.roi_heads.pvrcnn_head"])
 
 
 def check_radii(what):
@@ -455,10 +418,8 @@ def point_part(point_mod, rng, out):
 
 
 def state_dict_part(root, vsa_mod, point_mod, head_mod):
-    with open(os.path.join(root, "tools", "cfgs", "kitti_models", "pv_rcnn.yaml")) as f:
-        model = yaml.safe_load(f)["MODEL"]
-    with open(os.path.join(HERE, "second_state_dict.json")) as f:
-        second = json.load(f)
+    model = model_yaml(root, "kitti_models/pv_rcnn.yaml")["MODEL"]
+    second = second_settings()
     ds = second["config"]["dataset"]
     pfe_cfg, point_cfg, roi_cfg = model["PFE"], model["POINT_HEAD"], model["ROI_HEAD"]
     n_feat = ds.get("num_point_features", 4)
@@ -484,16 +445,11 @@ def state_dict_part(root, vsa_mod, point_mod, head_mod):
     out["config"] = {"MODEL": model_cfg, "dataset": ds, "grid_size": second["config"]["grid_size"],
                      "yaml": {"PFE": pfe_cfg, "POINT_HEAD": point_cfg, "ROI_HEAD": roi_cfg,
                               "NUM_BEV_FEATURES": model["MAP_TO_BEV"]["NUM_BEV_FEATURES"]}}
-    path = os.path.join(HERE, "pv_rcnn_state_dict.json")
-    with open(path, "w") as f:
-        json.dump(out, f, indent=0)
-    print(path, {k: len(v) for k, v in out.items()})
+    write_state_dict("pv_rcnn_state_dict.json", out)
 
 
 def main():
-    root = sys.argv[1] if len(sys.argv) > 1 else os.environ.get("PDA_REFERENCE_ROOT")
-    if not root:
-        sys.exit(__doc__)
+    root = reference_root()
     pm, vsa_mod, point_mod, head_mod = load_reference(root)
     out = {}
     sa_part(pm, out)

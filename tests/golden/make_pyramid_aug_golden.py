@@ -30,9 +30,8 @@ pasted scene (the input of the step, stored under the keys of the other cases) a
 is taken only when a pasted box is dropped or thinned and a pasted box is in a real swap.  Box pairs are robust against the
 collision test (make_augment_golden._robust_pairs) and no raw point lies near a face of a database box.
 
-Run here only:  python tests/golden/make_pyramid_aug_golden.py
+Run with the reference checkout:  python tests/golden/make_pyramid_aug_golden.py /path/to/reference
 """
-import importlib
 import os
 import pathlib
 import pickle
@@ -45,6 +44,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import make_augment_golden as mag  # noqa: E402
 from make_augment_golden import import_reference  # noqa: E402
+from reference_loader import reference_root  # noqa: E402
+from pdanet_amd.config import to_attr  # noqa: E402
 
 OUT = os.path.join(HERE, "pyramid_aug.npz")
 CFG = dict(DROP_PROB=0.5, SPARSIFY_PROB=0.5, SPARSIFY_MAX_NUM=8, SWAP_PROB=0.5, SWAP_MAX_NUM=8)
@@ -282,7 +283,7 @@ def paste_case(refs, au, iou_fn):
         for path, q in bins.items():
             q.tofile(os.path.join(tmp, path))
         cfg = {"DISABLE_AUG_LIST": ["placeholder"], "AUG_CONFIG_LIST": [GT_SAMPLING, dict(CFG, NAME="random_local_pyramid_aug")]}
-        aug = DataAugmentor(pathlib.Path(tmp), mag._ad(cfg), CLASSES, logger=None)
+        aug = DataAugmentor(pathlib.Path(tmp), to_attr(cfg), CLASSES, logger=None)
         sampler = aug.data_augmentor_queue[0]
         gid, start, tried = {}, 0, []
         for n in CLASSES:
@@ -332,7 +333,7 @@ def paste_case(refs, au, iou_fn):
 
 
 def main():
-    refs = import_reference()
+    refs = import_reference(reference_root())
     import oracle
 
     def iou_fn(a, b):
@@ -341,7 +342,7 @@ def main():
         oracle.boxes_overlap_bev_gpu(a, b, ans)
         return ans
 
-    au = importlib.import_module("pcdet.datasets.augmentor.augmentor_utils")
+    au = sys.modules["pcdet.datasets.augmentor.augmentor_utils"]
     rng = np.random.default_rng(20260321)
     cases = {}
     c = lambda r: r["cover"]

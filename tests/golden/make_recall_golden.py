@@ -4,11 +4,9 @@ Detector3DTemplate.generate_recall_record) run on synthetic eval batches, called
 calls it: box_preds = the scene's final boxes (the first num_pred rows of the padded boxes), the dict threaded through the
 scenes of the batch.
 
-detector3d_template.py is loaded with its package imports stubbed.  Its IoU is the reference's own
-iou3d_nms_utils.boxes_iou3d_gpu on CPU tensors, with torch.cuda.FloatTensor as a CPU float32 tensor and
-iou3d_nms_cuda.boxes_overlap_bev_gpu bound to the repository's C oracle of the BEV overlap (oracle/, the
-iou3d_nms_kernel.cu statement).  boxes_iou3d_gpu is wrapped to record the matrix of each scene, whose max over the
-predictions is each kept GT row's max IoU (0 for a scene without predictions, NaN for a trimmed row).
+detector3d_template.py is loaded with its package imports stubbed (reference_loader.py).  Its IoU is the reference's own
+iou3d_nms_utils.boxes_iou3d_gpu on CPU tensors over the C oracle of the BEV overlap.  boxes_iou3d_gpu is wrapped to record
+the matrix of each scene, whose max over the predictions is each kept GT row's max IoU (0 for a scene without predictions, NaN for a trimmed row).
 
 Batches (pred (B, K, 7) float32 zero-padded, num_pred (B), gt (B, T, 8) or none, the threshold list):
   kitti16 / kitti64   B = 4, max_gt 16 / 64, up to 100 predictions: jittered from GT across IoU 0.1-0.95, false
@@ -23,92 +21,37 @@ Batches (pred (B, K, 7) float32 zero-padded, num_pred (B), gt (B, T, 8) or none,
 
 Run with the reference checkout:  python tests/golden/make_recall_golden.py /path/to/reference
 """
-import importlib.util
 import os
 import sys
-import types
 
 import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = sys.argv[1] if len(sys.argv) > 1 else os.environ["PDA_REFERENCE"]
-PCDET = os.path.join(REF, "pcdet")
+sys.path.insert(0, HERE)
+from reference_loader import DETECTOR_STUBS, cpu_torch, extension_stubs, load, reference_root  # noqa: E402
+
 OUT = os.path.join(HERE, "recall.npz")
 THRESH = [0.3, 0.5, 0.7]
-sys.path.insert(0, ROOT)
-import oracle  # noqa: E402
+DET = None                       # the reference's Detector3DTemplate, once load_reference has run
+_LAST = []                       # the matrices its boxes_iou3d_gpu returned since the list was emptied
 
 
-def _package(name, path=None, **attrs):
-    pkg = types.ModuleType(name)
-    pkg.__path__ = [path] if path else []
-    pkg.__dict__.update(attrs)
-    sys.modules[name] = pkg
-    parent, _, leaf = name.rpartition(".")
-    if parent in sys.modules:
-        setattr(sys.modules[parent], leaf, pkg)
-    return pkg
+def load_reference(root):
+    global DET
+    cpu_torch()
+    stubs = dict(DETECTOR_STUBS, **{"utils.common_utils": {}, "models.roi_heads": {}, "models.model_utils.model_nms_utils": {}})
+    iou, det = load(root, "pcdet_ref", ["ops.iou3d_nms.iou3d_nms_utils", "models.detectors.detector3d_template"],
+                    stubs=extension_stubs(stubs))
+    real = iou.boxes_iou3d_gpu
 
+    def recording_iou3d(a, b):
+        r = real(a, b)
+        _LAST.append(r)
+        return r
 
-def _module(name, path):
-    spec = importlib.util.spec_from_file_location(name, path)
-    m = importlib.util.module_from_spec(spec)
-    sys.modules[name] = m
-    parent, _, leaf = name.rpartition(".")
-    setattr(sys.modules[parent], leaf, m)
-    spec.loader.exec_module(m)
-    return m
-
-
-class _CpuTorch(types.ModuleType):
-    """torch, with torch.cuda.FloatTensor(size) a CPU float32 tensor (boxes_iou3d_gpu allocates its BEV plane so)."""
-
-    def __getattr__(self, name):
-        return getattr(torch, name)
-
-
-def _overlap_bev(boxes_a, boxes_b, ans):
-    oracle.boxes_overlap_bev_gpu(boxes_a.numpy(), boxes_b.numpy(), ans.numpy())   # writes through to the tensor
-
-
-def _load_reference():
-    _package("pcdet_ref", PCDET)
-    _package("pcdet_ref.utils", None, common_utils=types.ModuleType("pcdet_ref.utils.common_utils"))
-    _package("pcdet_ref.utils.spconv_utils", None, find_all_spconv_keys=None)
-    _package("pcdet_ref.ops", None)
-    _package("pcdet_ref.ops.iou3d_nms", None)
-    _package("pcdet_ref.ops.iou3d_nms.iou3d_nms_cuda", None, boxes_overlap_bev_gpu=_overlap_bev)
-    iou = _module("pcdet_ref.ops.iou3d_nms.iou3d_nms_utils", os.path.join(PCDET, "ops", "iou3d_nms", "iou3d_nms_utils.py"))
-    ct = _CpuTorch("torch")
-    ct.cuda = types.SimpleNamespace(FloatTensor=lambda size: torch.empty(size, dtype=torch.float32))
-    iou.torch = ct
-    _package("pcdet_ref.models", None)
-    for sub in ("backbones_2d", "backbones_3d", "dense_heads", "roi_heads", "model_utils"):
-        _package("pcdet_ref.models." + sub, None)
-    _package("pcdet_ref.models.backbones_2d.map_to_bev", None)
-    _package("pcdet_ref.models.backbones_3d.pfe", None)
-    _package("pcdet_ref.models.backbones_3d.vfe", None)
-    _package("pcdet_ref.models.model_utils.model_nms_utils", None)
-    _package("pcdet_ref.models.detectors", None)
-    det = _module("pcdet_ref.models.detectors.detector3d_template",
-                  os.path.join(PCDET, "models", "detectors", "detector3d_template.py"))
-    return iou, det.Detector3DTemplate
-
-
-IOU, DET = _load_reference()
-_REAL_IOU3D = IOU.boxes_iou3d_gpu
-_LAST = []
-
-
-def _recording_iou3d(a, b):
-    r = _REAL_IOU3D(a, b)
-    _LAST.append(r)
-    return r
-
-
-IOU.boxes_iou3d_gpu = _recording_iou3d
+    iou.boxes_iou3d_gpu = recording_iou3d
+    DET = det.Detector3DTemplate
 
 
 def run_reference(pred, num, gt, thresh):
@@ -259,6 +202,7 @@ def _thresh_cases(max_iou):
 
 
 def main():
+    load_reference(reference_root())
     rng = np.random.default_rng(20261016)
     batches = []
     for i in range(3):

@@ -13,10 +13,8 @@ The reference sources are imported from where they lie; nothing of them is copie
 and the composition's outputs.  Inputs are the `exact` scenes of roi_pool_inputs.py (1/8 lattice, heading 0), so the file
 does not depend on the contraction mode.
 """
-import importlib.util
 import os
 import sys
-import types
 
 import numpy as np
 import torch
@@ -25,24 +23,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import roi_pool_inputs as gen  # noqa: E402
 import roi_pool_restatement as ref  # noqa: E402
+from reference_loader import load, np_args as _args, reference_root  # noqa: E402
 
 F32, I32 = np.float32, np.int32
-
-
-def _np(t):
-    assert t.device.type == "cpu" and t.is_contiguous()
-    return t.detach().numpy()                      # shares memory: the restatement writes the caller's buffers in place
-
-
-def _args(args):
-    return [_np(a) if isinstance(a, torch.Tensor) else a for a in args]
-
-
-def _stub(name, **functions):
-    m = types.ModuleType(name)
-    for k, f in functions.items():
-        setattr(m, k, f)
-    return m
 
 
 def _check_numpy_to_torch(x):
@@ -59,42 +42,21 @@ def _enlarge_box3d(boxes3d, extra_width=(0, 0, 0)):
 
 
 def import_reference(root):
-    ops = os.path.join(root, "pcdet", "ops")
-    for name, path in [("pcdet", os.path.join(root, "pcdet")), ("pcdet.ops", ops), ("pcdet.utils", os.path.join(root, "pcdet", "utils")),
-                       ("pcdet.ops.roiaware_pool3d", os.path.join(ops, "roiaware_pool3d")),
-                       ("pcdet.ops.roipoint_pool3d", os.path.join(ops, "roipoint_pool3d"))]:
-        m = types.ModuleType(name)
-        m.__path__ = [path]
-        sys.modules[name] = m
     stubs = {
-        "pcdet.utils.common_utils": _stub("common_utils", check_numpy_to_torch=_check_numpy_to_torch),
-        "pcdet.utils.box_utils": _stub("box_utils", enlarge_box3d=_enlarge_box3d),
-        "pcdet.ops.roiaware_pool3d.roiaware_pool3d_cuda": _stub(
-            "roiaware_pool3d_cuda", forward=lambda *a: ref.roiaware_pool3d_forward(*_args(a)),
-            backward=lambda *a: ref.roiaware_pool3d_backward(*_args(a)),
-            points_in_boxes_cpu=lambda *a: ref.points_in_boxes_cpu(*_args(a))),
-        "pcdet.ops.roipoint_pool3d.roipoint_pool3d_cuda": _stub(
-            "roipoint_pool3d_cuda", forward=lambda *a: ref.roipoint_pool3d_forward(*_args(a))),
+        "utils.common_utils": {"check_numpy_to_torch": _check_numpy_to_torch},
+        "utils.box_utils": {"enlarge_box3d": _enlarge_box3d},
+        "ops.roiaware_pool3d.roiaware_pool3d_cuda": {
+            "forward": lambda *a: ref.roiaware_pool3d_forward(*_args(a)),
+            "backward": lambda *a: ref.roiaware_pool3d_backward(*_args(a)),
+            "points_in_boxes_cpu": lambda *a: ref.points_in_boxes_cpu(*_args(a))},
+        "ops.roipoint_pool3d.roipoint_pool3d_cuda": {"forward": lambda *a: ref.roipoint_pool3d_forward(*_args(a))},
     }
-    for name, m in stubs.items():
-        sys.modules[name] = m
-        setattr(sys.modules[name.rsplit(".", 1)[0]], name.rsplit(".", 1)[1], m)
-    mods = []
-    for pkg, fname in [("roiaware_pool3d", "roiaware_pool3d_utils"), ("roipoint_pool3d", "roipoint_pool3d_utils")]:
-        name = "pcdet.ops.%s.%s" % (pkg, fname)
-        spec = importlib.util.spec_from_file_location(name, os.path.join(ops, pkg, fname + ".py"))
-        mod = importlib.util.module_from_spec(spec)
-        sys.modules[name] = mod
-        spec.loader.exec_module(mod)
-        mods.append(mod)
-    return mods
+    return load(root, "pcdet", ["ops.roiaware_pool3d.roiaware_pool3d_utils", "ops.roipoint_pool3d.roipoint_pool3d_utils"],
+                stubs=stubs, real_paths=True)
 
 
 def main():
-    root = sys.argv[1] if len(sys.argv) > 1 else os.environ.get("PDA_REFERENCE_ROOT")
-    if not root:
-        sys.exit(__doc__)
-    aware, point = import_reference(root)
+    aware, point = import_reference(reference_root())
     t = torch.from_numpy
     a, b = gen.roiaware_inputs("exact"), gen.roipoint_inputs("exact")
     rng = np.random.default_rng(5)

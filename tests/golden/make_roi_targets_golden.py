@@ -5,11 +5,10 @@ generate_predicted_boxes and get_loss (pcdet/models/roi_heads/roi_head_template.
 roi_heads/target_assigner/proposal_target_layer.py), ResidualCoder (pcdet/utils/box_coder_utils.py) and the state-dict keys
 of make_fc_layers.
 
-The two modules are loaded with their package imports stubbed; pcdet/utils/{common_utils, box_utils, box_coder_utils,
-loss_utils}.py, model_nms_utils.py and iou3d_nms_utils.py are the reference's own files.  iou3d_nms_cuda is bound to the
-repository's C oracle (oracle/: boxes_overlap_bev_gpu, nms_gpu), torch.cuda.FloatTensor is a CPU float32 tensor and .cuda()
-the identity; in proposal_target_layer.py torch.cat reads the `[]` of the fg-only branch as an empty index tensor (this torch
-refuses a list there).  np.random.permutation, np.random.rand and torch.randint are wrapped to record each scene's draws, which the
+The two modules are loaded through reference_loader.py; pcdet/utils/{common_utils, box_utils, box_coder_utils,
+loss_utils}.py, model_nms_utils.py and iou3d_nms_utils.py are the reference's own files, iou3d_nms_cuda is the repository's C
+oracle (oracle/: boxes_overlap_bev_gpu, nms_gpu); in proposal_target_layer.py torch.cat reads the `[]` of the fg-only branch
+as an empty index tensor (this torch refuses a list there).  np.random.permutation, np.random.rand and torch.randint are wrapped to record each scene's draws, which the
 fixture stores padded per scene so that the explicit mode of pda_roi_sample_targets can repeat them.
 
 Stored per target batch b<i>_: case, cfg (json of TARGET_CONFIG), rois, roi_scores, roi_labels, gt_boxes, the draws
@@ -21,7 +20,6 @@ roi_labels.  Coverage is asserted with roi_targets_cover.py.
 Run with the reference checkout:  python tests/golden/make_roi_targets_golden.py /path/to/reference
 """
 import contextlib
-import importlib.util
 import json
 import os
 import sys
@@ -31,86 +29,39 @@ import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = sys.argv[1] if len(sys.argv) > 1 else os.environ["PDA_REFERENCE"]
-PCDET = os.path.join(REF, "pcdet")
-OUT = os.path.join(HERE, "roi_targets.npz")
-sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
-import oracle  # noqa: E402
+from reference_loader import MODEL_UTILS, ROI_HEAD, cpu_torch, extension_stubs, load, reference_root  # noqa: E402
 from pdanet_amd.config import to_attr  # noqa: E402
 import roi_targets_cover as cover  # noqa: E402
 
-
-def _package(name, path=None, **attrs):
-    pkg = types.ModuleType(name)
-    pkg.__path__ = [path] if path else []
-    pkg.__dict__.update(attrs)
-    sys.modules[name] = pkg
-    parent, _, leaf = name.rpartition(".")
-    if parent in sys.modules:
-        setattr(sys.modules[parent], leaf, pkg)
-    return pkg
-
-
-def _module(name, path):
-    spec = importlib.util.spec_from_file_location(name, path)
-    m = importlib.util.module_from_spec(spec)
-    sys.modules[name] = m
-    parent, _, leaf = name.rpartition(".")
-    setattr(sys.modules[parent], leaf, m)
-    spec.loader.exec_module(m)
-    return m
+OUT = os.path.join(HERE, "roi_targets.npz")
+IOU = PTL = RHT = CODER = None   # the reference's iou3d_nms_utils, proposal_target_layer, roi_head_template and box_coder_utils
 
 
 class _CpuTorch(types.ModuleType):
-    """torch, with torch.cuda.FloatTensor(size) a CPU float32 tensor (boxes_iou3d_gpu allocates its BEV plane so)."""
+    """torch, with cuda.FloatTensor(size) a CPU float32 tensor (boxes_iou3d_gpu allocates its BEV plane so)."""
 
     def __getattr__(self, name):
         return getattr(torch, name)
 
 
-def _overlap_bev(boxes_a, boxes_b, ans):
-    oracle.boxes_overlap_bev_gpu(boxes_a.numpy(), boxes_b.numpy(), ans.numpy())   # writes through to the tensor
-
-
-def _nms_gpu(boxes, keep, thresh):
-    return oracle.nms_gpu(boxes.numpy(), keep.numpy(), thresh)
-
-
-def _load_reference():
-    torch.Tensor.cuda = lambda self, *a, **k: self
-    sys.modules["SharedArray"] = types.ModuleType("SharedArray")
-    _package("pcdet_ref", PCDET)
-    _package("pcdet_ref.utils", None)
-    _package("pcdet_ref.ops", None)
-    _package("pcdet_ref.ops.roiaware_pool3d", None, roiaware_pool3d_utils=types.ModuleType("roiaware_pool3d_utils"))
-    _package("pcdet_ref.ops.iou3d_nms", None)
-    _package("pcdet_ref.ops.iou3d_nms.iou3d_nms_cuda", None, boxes_overlap_bev_gpu=_overlap_bev, nms_gpu=_nms_gpu)
-    for name in ("common_utils", "box_utils", "box_coder_utils", "loss_utils"):
-        _module("pcdet_ref.utils." + name, os.path.join(PCDET, "utils", name + ".py"))
-    iou = _module("pcdet_ref.ops.iou3d_nms.iou3d_nms_utils", os.path.join(PCDET, "ops", "iou3d_nms", "iou3d_nms_utils.py"))
+def load_reference(root):
+    """Loads the reference's utils, NMS, proposal_target_layer and roi_head_template as pcdet_ref.* and binds IOU, PTL, RHT and
+    CODER to them."""
+    global IOU, PTL, RHT, CODER
+    cpu_torch()
+    utils = dict(zip(MODEL_UTILS, load(root, "pcdet_ref", MODEL_UTILS, stubs=extension_stubs())))
+    IOU, CODER = utils["ops.iou3d_nms.iou3d_nms_utils"], utils["utils.box_coder_utils"]
     ct = _CpuTorch("torch")
     ct.cuda = types.SimpleNamespace(FloatTensor=lambda size: torch.empty(size, dtype=torch.float32))
-    iou.torch = ct
-    _package("pcdet_ref.models", None)
-    _package("pcdet_ref.models.model_utils", None)
-    _module("pcdet_ref.models.model_utils.model_nms_utils", os.path.join(PCDET, "models", "model_utils", "model_nms_utils.py"))
-    _package("pcdet_ref.models.roi_heads", None)
-    _package("pcdet_ref.models.roi_heads.target_assigner", None)
-    ptl = _module("pcdet_ref.models.roi_heads.target_assigner.proposal_target_layer",
-                  os.path.join(PCDET, "models", "roi_heads", "target_assigner", "proposal_target_layer.py"))
+    IOU.torch = ct
+    PTL = load(root, "pcdet_ref", ROI_HEAD[:2])[1]
     # subsample_rois' fg-only branch ends in torch.cat((fg_inds, [])), which this torch refuses; an empty list element is
     # read as the empty index tensor it stands for, so that the branch yields the fg picks it computed
     pt = _CpuTorch("torch")
     pt.cat = lambda ts, dim=0: torch.cat([t if isinstance(t, torch.Tensor) else torch.zeros(0, dtype=torch.long) for t in ts], dim=dim)
-    ptl.torch = pt
-    rht = _module("pcdet_ref.models.roi_heads.roi_head_template",
-                  os.path.join(PCDET, "models", "roi_heads", "roi_head_template.py"))
-    return iou, ptl, rht, sys.modules["pcdet_ref.utils.box_coder_utils"]
-
-
-IOU, PTL, RHT, CODER = _load_reference()
+    PTL.torch = pt
+    RHT, = load(root, "pcdet_ref", ROI_HEAD[2:])
 
 
 @contextlib.contextmanager
@@ -356,6 +307,7 @@ def proposal_inputs(rng, B, N, T):
 
 
 def main():
+    load_reference(reference_root())
     rng = np.random.default_rng(20261018)
     np.random.seed(7)
     torch.manual_seed(7)

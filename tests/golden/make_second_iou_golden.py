@@ -4,10 +4,9 @@ and second_net_iou.py, imported from where they lie and run on the CPU.
 
     python tests/golden/make_second_iou_golden.py <checkout of the reference>
 
-The extension modules are stubs: iou3d_nms_cuda.nms_gpu and boxes_overlap_bev_gpu are the repository's C oracle of the BEV
-overlap (oracle/), roiaware_pool3d_utils.points_in_boxes_cpu is roi_pool_restatement.points_in_boxes_cpu.
-torch.cuda.FloatTensor is pointed at the CPU constructor and Tensor.cuda() stays where it is.  Nothing of the reference is
-copied; what is committed is data.
+The extension modules are the stubs of reference_loader.py: iou3d_nms_cuda.nms_gpu and boxes_overlap_bev_gpu are the
+repository's C oracle of the BEV overlap (oracle/), roiaware_pool3d_utils.points_in_boxes_cpu is
+roi_pool_restatement.points_in_boxes_cpu.  Nothing of the reference is copied; what is committed is data.
 
 second_iou.npz
   lat_*    roi_grid_pool on the lattice: B = 2, C = 5, H = 17, W = 9, G = 4, cell 1.0, heading 0, centres on multiples of 1/8,
@@ -25,97 +24,31 @@ second_iou_state_dict.json: keys and shapes, in order, of the reference's SECOND
 the whole SECONDNetIoU on the settings of second_state_dict.json with the yaml's ROI_HEAD block.
 """
 import copy
-import importlib.util
 import json
 import os
 import sys
-import types
 
 import numpy as np
 import torch
-import yaml
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, HERE)
-sys.path.insert(0, ROOT)
 import bev_roi_pool_restatement as bev_rs  # noqa: E402
 import roi_pool_restatement as roi_rs  # noqa: E402
+from reference_loader import (DETECTOR_STUBS, MODEL_UTILS, ROI_HEAD, cpu_torch, extension_stubs, load, model_yaml,  # noqa: E402
+                              randomise, reference_root, second_settings, shapes, write_state_dict)
 import oracle  # noqa: E402
 from pdanet_amd.config import to_attr  # noqa: E402
 
 F32, I32 = np.float32, np.int32
 
 
-def _package(name, path=None, **attrs):
-    pkg = types.ModuleType(name)
-    pkg.__path__ = [path] if path else []
-    pkg.__dict__.update(attrs)
-    sys.modules[name] = pkg
-    parent, _, leaf = name.rpartition(".")
-    if parent in sys.modules:
-        setattr(sys.modules[parent], leaf, pkg)
-    return pkg
-
-
-def _module(name, path):
-    spec = importlib.util.spec_from_file_location(name, path)
-    m = importlib.util.module_from_spec(spec)
-    sys.modules[name] = m
-    parent, _, leaf = name.rpartition(".")
-    setattr(sys.modules[parent], leaf, m)
-    spec.loader.exec_module(m)
-    return m
-
-
-def _overlap_bev(boxes_a, boxes_b, ans):
-    oracle.boxes_overlap_bev_gpu(boxes_a.numpy(), boxes_b.numpy(), ans.numpy())   # writes through to the tensor
-
-
-def _nms_gpu(boxes, keep, thresh):
-    return oracle.nms_gpu(np.ascontiguousarray(boxes.numpy()), keep.numpy(), float(thresh))
-
-
-def _points_in_boxes_cpu(points, boxes):
-    out = np.zeros((boxes.shape[0], points.shape[0]), I32)
-    roi_rs.points_in_boxes_cpu(boxes.numpy().astype(F32), points.numpy().astype(F32), out)
-    return torch.from_numpy(out)
-
-
 def load_reference(root):
     """-> (second_head, second_net_iou) of the reference, as pcdet_ref.*"""
-    pcdet = os.path.join(root, "pcdet")
-    torch.cuda.FloatTensor = torch.FloatTensor
-    torch.Tensor.cuda = lambda self, *a, **k: self
-    sys.modules["SharedArray"] = types.ModuleType("SharedArray")
-    _package("pcdet_ref", pcdet)
-    _package("pcdet_ref.utils", None)
-    _package("pcdet_ref.utils.spconv_utils", None, find_all_spconv_keys=None)
-    _package("pcdet_ref.ops", None)
-    pib = types.ModuleType("roiaware_pool3d_utils")
-    pib.points_in_boxes_cpu = _points_in_boxes_cpu
-    _package("pcdet_ref.ops.roiaware_pool3d", None, roiaware_pool3d_utils=pib)
-    _package("pcdet_ref.ops.iou3d_nms", None)
-    _package("pcdet_ref.ops.iou3d_nms.iou3d_nms_cuda", None, boxes_overlap_bev_gpu=_overlap_bev, nms_gpu=_nms_gpu)
-    for name in ("common_utils", "box_utils", "loss_utils", "box_coder_utils"):
-        _module("pcdet_ref.utils." + name, os.path.join(pcdet, "utils", name + ".py"))
-    _module("pcdet_ref.ops.iou3d_nms.iou3d_nms_utils", os.path.join(pcdet, "ops", "iou3d_nms", "iou3d_nms_utils.py"))
-    _package("pcdet_ref.models", None)
-    for sub in ("backbones_2d", "backbones_3d", "dense_heads", "roi_heads", "model_utils", "detectors"):
-        _package("pcdet_ref.models." + sub, None)
-    _package("pcdet_ref.models.backbones_2d.map_to_bev", None)
-    _package("pcdet_ref.models.backbones_3d.pfe", None)
-    _package("pcdet_ref.models.backbones_3d.vfe", None)
-    _module("pcdet_ref.models.model_utils.model_nms_utils", os.path.join(pcdet, "models", "model_utils", "model_nms_utils.py"))
-    heads = os.path.join(pcdet, "models", "roi_heads")
-    _package("pcdet_ref.models.roi_heads.target_assigner", None)
-    _module("pcdet_ref.models.roi_heads.target_assigner.proposal_target_layer",
-            os.path.join(heads, "target_assigner", "proposal_target_layer.py"))
-    _module("pcdet_ref.models.roi_heads.roi_head_template", os.path.join(heads, "roi_head_template.py"))
-    head = _module("pcdet_ref.models.roi_heads.second_head", os.path.join(heads, "second_head.py"))
-    dets = os.path.join(pcdet, "models", "detectors")
-    _module("pcdet_ref.models.detectors.detector3d_template", os.path.join(dets, "detector3d_template.py"))
-    net = _module("pcdet_ref.models.detectors.second_net_iou", os.path.join(dets, "second_net_iou.py"))
+    cpu_torch()
+    load(root, "pcdet_ref", MODEL_UTILS + ROI_HEAD, stubs=extension_stubs(DETECTOR_STUBS))
+    head, _, net = load(root, "pcdet_ref", ["models.roi_heads.second_head", "models.detectors.detector3d_template",
+                                            "models.detectors.second_net_iou"])
     return head, net
 
 
@@ -223,18 +156,6 @@ def general_part(head_mod, rng, out):
 
 # ---- the head -----------------------------------------------------------------------------------------------------------------
 HEAD = dict(B=2, R=8, C=8, H=12, W=10, G=4, pcr=[0.0, -2.4, -3.0, 4.0, 2.4, 1.0], voxel=[0.05, 0.05, 0.1], ratio=8)
-
-
-def randomise(module, rng):
-    """BatchNorm weights, biases and running statistics away from their initial values, so that each of them matters."""
-    g = torch.Generator().manual_seed(int(rng.integers(1 << 30)))
-    for m in module.modules():
-        if isinstance(m, torch.nn.BatchNorm1d):
-            with torch.no_grad():
-                m.weight.copy_(torch.rand(m.weight.shape, generator=g) + 0.5)
-                m.bias.copy_(torch.randn(m.bias.shape, generator=g) * 0.2)
-                m.running_mean.copy_(torch.randn(m.bias.shape, generator=g) * 0.1)
-                m.running_var.copy_(torch.rand(m.bias.shape, generator=g) + 0.5)
 
 
 def head_part(head_mod, rng, out):
@@ -411,30 +332,18 @@ def post_part(net_mod, rng, out):
     net_mod.class_agnostic_nms = real_nms
 
 
-def shapes(module, prefix=""):
-    return [[prefix + k, list(v.shape)] for k, v in module.state_dict().items()]
-
-
 def state_dict_part(root, head_mod):
-    with open(os.path.join(root, "tools", "cfgs", "kitti_models", "second_iou.yaml")) as f:
-        model_yaml = yaml.safe_load(f)["MODEL"]
-    with open(os.path.join(HERE, "second_state_dict.json")) as f:
-        second = json.load(f)
-    roi_cfg = model_yaml["ROI_HEAD"]
+    roi_cfg = model_yaml(root, "kitti_models/second_iou.yaml")["MODEL"]["ROI_HEAD"]
+    second = second_settings()
     head = head_mod.SECONDHead(input_channels=roi_cfg['ROI_GRID_POOL']['IN_CHANNEL'], model_cfg=to_attr(copy.deepcopy(roi_cfg)), num_class=1)
     model_cfg = dict(second["config"]["MODEL"], NAME="SECONDNetIoU", ROI_HEAD=roi_cfg)
-    out = {"config": {"MODEL": model_cfg, "dataset": second["config"]["dataset"], "grid_size": second["config"]["grid_size"]},
-           "SECONDHead": shapes(head), "SECONDNetIoU": second["SECONDNet"] + shapes(head, "roi_head.")}
-    path = os.path.join(HERE, "second_iou_state_dict.json")
-    with open(path, "w") as f:
-        json.dump(out, f, indent=0)
-    print(path, {k: len(v) for k, v in out.items()})
+    config = {"MODEL": model_cfg, "dataset": second["config"]["dataset"], "grid_size": second["config"]["grid_size"]}
+    write_state_dict("second_iou_state_dict.json", {"config": config, "SECONDHead": shapes(head),
+                                                    "SECONDNetIoU": second["SECONDNet"] + shapes(head, "roi_head.")})
 
 
 def main():
-    root = sys.argv[1] if len(sys.argv) > 1 else os.environ.get("PDA_REFERENCE_ROOT")
-    if not root:
-        sys.exit(__doc__)
+    root = reference_root()
     oracle.build()
     head_mod, net_mod = load_reference(root)
     rng = np.random.default_rng(2026)

@@ -5,7 +5,7 @@ VoxelBackBone8x, VoxelResBackBone8x and SECONDNet, instantiated on the CPU, plus
 spconv is not a dependency, so this file defines a minimal stand-in for it: modules that hold parameters of spconv 2.x's
 shapes (weight (C_out, kD, kH, kW, C_in), bias (C_out)) and a SparseSequential with nn.Sequential's child naming; nothing
 in it computes.  The reference's own spconv_backbone.py, base_bev_backbone.py, anchor_head_single.py (with its template,
-anchor generator, target assigner and utilities) are loaded as pcdet_ref.* with their package imports stubbed.  SECONDNet's
+anchor generator, target assigner and utilities) are loaded as pcdet_ref.* through reference_loader.py.  SECONDNet's
 keys are those modules under the names Detector3DTemplate.build_networks registers them with (vfe -- MeanVFE, no
 parameters --, backbone_3d, map_to_bev_module -- HeightCompression, no parameters --, backbone_2d, dense_head).
 
@@ -14,7 +14,6 @@ The SECONDNet settings: kitti_models/second.yaml's MODEL block with the 2D backb
 
 Run with the reference checkout:  python tests/golden/make_second_state_dict.py /path/to/reference
 """
-import importlib.util
 import json
 import os
 import sys
@@ -23,15 +22,14 @@ import types
 import numpy as np
 import torch
 import torch.nn as nn
-import yaml
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = sys.argv[1] if len(sys.argv) > 1 else os.environ["PDA_REFERENCE"]
-PCDET = os.path.join(REF, "pcdet")
-OUT = os.path.join(HERE, "second_state_dict.json")
-sys.path.insert(0, ROOT)
+sys.path.insert(0, HERE)
+from reference_loader import (ANCHOR_HEAD, MODEL_UTILS, cpu_torch, extension_stubs, load, model_yaml,  # noqa: E402
+                              reference_root, shapes)
 from pdanet_amd.config import to_attr  # noqa: E402
+
+OUT = os.path.join(HERE, "second_state_dict.json")
 
 
 def _triple(v):
@@ -62,63 +60,18 @@ def _spconv_stand_in():
     sys.modules.update({"spconv": sp, "spconv.pytorch": pt, "spconv.conv": conv})
 
 
-def _package(name, path=None, **attrs):
-    pkg = types.ModuleType(name)
-    pkg.__path__ = [path] if path else []
-    pkg.__dict__.update(attrs)
-    sys.modules[name] = pkg
-    parent, _, leaf = name.rpartition(".")
-    if parent in sys.modules:
-        setattr(sys.modules[parent], leaf, pkg)
-    return pkg
-
-
-def _module(name, path):
-    spec = importlib.util.spec_from_file_location(name, path)
-    m = importlib.util.module_from_spec(spec)
-    sys.modules[name] = m
-    parent, _, leaf = name.rpartition(".")
-    setattr(sys.modules[parent], leaf, m)
-    spec.loader.exec_module(m)
-    return m
-
-
-def _load_reference():
+def load_reference(root):
     _spconv_stand_in()
-    torch.Tensor.cuda = lambda self, *a, **k: self
-    sys.modules["SharedArray"] = types.ModuleType("SharedArray")
-    _package("pcdet_ref", PCDET)
-    _package("pcdet_ref.utils", None)
-    _package("pcdet_ref.ops", None)
-    _package("pcdet_ref.ops.roiaware_pool3d", None, roiaware_pool3d_utils=types.ModuleType("roiaware_pool3d_utils"))
-    _package("pcdet_ref.ops.iou3d_nms", None)
-    _package("pcdet_ref.ops.iou3d_nms.iou3d_nms_cuda", None)
-    for name in ("common_utils", "box_utils", "loss_utils", "box_coder_utils", "spconv_utils"):
-        _module("pcdet_ref.utils." + name, os.path.join(PCDET, "utils", name + ".py"))
-    _module("pcdet_ref.ops.iou3d_nms.iou3d_nms_utils", os.path.join(PCDET, "ops", "iou3d_nms", "iou3d_nms_utils.py"))
-    _package("pcdet_ref.models", None)
-    _package("pcdet_ref.models.dense_heads", None)
-    _package("pcdet_ref.models.dense_heads.target_assigner", None)
-    ta = os.path.join(PCDET, "models", "dense_heads", "target_assigner")
-    for name in ("anchor_generator", "atss_target_assigner", "axis_aligned_target_assigner"):
-        _module("pcdet_ref.models.dense_heads.target_assigner." + name, os.path.join(ta, name + ".py"))
-    _module("pcdet_ref.models.dense_heads.anchor_head_template", os.path.join(PCDET, "models", "dense_heads", "anchor_head_template.py"))
-    head = _module("pcdet_ref.models.dense_heads.anchor_head_single", os.path.join(PCDET, "models", "dense_heads", "anchor_head_single.py"))
-    _package("pcdet_ref.models.backbones_3d", None)
-    b3d = _module("pcdet_ref.models.backbones_3d.spconv_backbone", os.path.join(PCDET, "models", "backbones_3d", "spconv_backbone.py"))
-    _package("pcdet_ref.models.backbones_2d", None)
-    b2d = _module("pcdet_ref.models.backbones_2d.base_bev_backbone", os.path.join(PCDET, "models", "backbones_2d", "base_bev_backbone.py"))
-    return b3d, b2d, head
-
-
-def shapes(module, prefix=""):
-    return [[prefix + k, list(v.shape)] for k, v in module.state_dict().items()]
+    cpu_torch()
+    load(root, "pcdet_ref", MODEL_UTILS + ["utils.spconv_utils"] + ANCHOR_HEAD, stubs=extension_stubs())
+    return load(root, "pcdet_ref", ["models.backbones_3d.spconv_backbone", "models.backbones_2d.base_bev_backbone",
+                                    "models.dense_heads.anchor_head_single"])
 
 
 def main():
-    b3d, b2d, head = _load_reference()
-    with open(os.path.join(REF, "tools", "cfgs", "kitti_models", "second.yaml")) as f:
-        model_cfg = yaml.safe_load(f)["MODEL"]
+    root = reference_root()
+    b3d, b2d, head = load_reference(root)
+    model_cfg = model_yaml(root, "kitti_models/second.yaml")["MODEL"]
     model_cfg["BACKBONE_2D"]["LAYER_NUMS"] = [1, 1]
     dataset = {"class_names": ["Car", "Pedestrian", "Cyclist"], "point_cloud_range": [0, -0.4, -3, 0.8, 0.4, 1],
                "voxel_size": [0.05, 0.05, 0.1], "num_point_features": 4}

@@ -10,7 +10,6 @@ The reference sources are imported from where they lie; nothing of them is copie
 and the composition's outputs.  Inputs lie on the 1/8 lattice, so every distance and cell index is exact in float32 and the
 file does not depend on the contraction mode of the squared distance.
 """
-import importlib.util
 import os
 import sys
 import types
@@ -21,13 +20,9 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import stack_pool_restatement as ref  # noqa: E402
+from reference_loader import as_np as _np, load, np_args, reference_root  # noqa: E402
 
 F32, I32 = np.float32, np.int32
-
-
-def _np(t):
-    assert t.device.type == "cpu" and t.is_contiguous()
-    return t.detach().numpy()                      # shares memory: the restatement writes the caller's buffers in place
 
 
 class Stub(types.ModuleType):
@@ -38,17 +33,17 @@ class Stub(types.ModuleType):
 
     @staticmethod
     def query_stacked_local_neighbor_idxs_wrapper_stack(*args):
-        ref.query_stacked_local_neighbor_idxs(*[_np(a) if isinstance(a, torch.Tensor) else a for a in args])
+        ref.query_stacked_local_neighbor_idxs(*np_args(args))
         return 0
 
     @staticmethod
     def query_three_nn_by_stacked_local_idxs_wrapper_stack(*args):
-        ref.query_three_nn_by_stacked_local_idxs(*[_np(a) if isinstance(a, torch.Tensor) else a for a in args])
+        ref.query_three_nn_by_stacked_local_idxs(*np_args(args))
         return 0
 
     @staticmethod
     def vector_pool_wrapper(*args):
-        return ref.vector_pool(*[_np(a) if isinstance(a, torch.Tensor) else a for a in args])
+        return ref.vector_pool(*np_args(args))
 
     def vector_pool_grad_wrapper(self, grad_new_features, point_cnt_of_grid, grouped_idxs, grad_support_features):
         self.rows = _np(grouped_idxs).copy()
@@ -57,29 +52,13 @@ class Stub(types.ModuleType):
 
 
 def import_reference(root, stub):
-    base = os.path.join(root, "pcdet", "ops", "pointnet2", "pointnet2_stack")
-    for name, path in [("pcdet", os.path.join(root, "pcdet")), ("pcdet.ops", os.path.join(root, "pcdet", "ops")),
-                       ("pcdet.ops.pointnet2", os.path.join(root, "pcdet", "ops", "pointnet2")),
-                       ("pcdet.ops.pointnet2.pointnet2_stack", base)]:
-        m = types.ModuleType(name)
-        m.__path__ = [path]
-        sys.modules[name] = m
-    sys.modules["pcdet.ops.pointnet2.pointnet2_stack.pointnet2_stack_cuda"] = stub
-    sys.modules["pcdet.ops.pointnet2.pointnet2_stack"].pointnet2_stack_cuda = stub
-    name = "pcdet.ops.pointnet2.pointnet2_stack.pointnet2_utils"
-    spec = importlib.util.spec_from_file_location(name, os.path.join(base, "pointnet2_utils.py"))
-    mod = importlib.util.module_from_spec(spec)
-    sys.modules[name] = mod
-    spec.loader.exec_module(mod)
-    return mod
+    stack = "ops.pointnet2.pointnet2_stack."
+    return load(root, "pcdet", [stack + "pointnet2_utils"], stubs={stack + "pointnet2_stack_cuda": stub}, real_paths=True)[0]
 
 
 def main():
-    root = sys.argv[1] if len(sys.argv) > 1 else os.environ.get("PDA_REFERENCE_ROOT")
-    if not root:
-        sys.exit(__doc__)
     stub = Stub()
-    pu = import_reference(root, stub)
+    pu = import_reference(reference_root(), stub)
     rng = np.random.default_rng(2024)
     xyz_cnt, new_cnt = np.array([170, 130], I32), np.array([70, 50], I32)
     N, M, c_in, ce = int(xyz_cnt.sum()), int(new_cnt.sum()), 8, 4

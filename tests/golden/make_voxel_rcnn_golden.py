@@ -5,9 +5,8 @@ voxel_pool_modules.py, voxel_query_utils.py and voxelrcnn_head.py, imported from
     python tests/golden/make_voxel_rcnn_golden.py <checkout of the reference>
 
 The `pointnet2_stack_cuda` extension is a stub: voxel_query_wrapper is stack_pool_restatement.voxel_query, the two grouping
-entry points are numpy gathers.  torch.cuda.IntTensor / FloatTensor, which the reference's autograd functions allocate with,
-are pointed at the CPU constructors, and Tensor.cuda() stays where it is.  Nothing of the reference is copied; what is
-committed is data.
+entry points are numpy gathers.  The loading and the CPU patches are reference_loader.py's.  Nothing of the reference is
+copied; what is committed is data.
 
 voxel_rcnn.npz
   pool_*   NeighborVoxelSAModuleMSG with two scales (C = 32 and 64, nsample 16 and 4): inputs, every parameter and buffer,
@@ -23,7 +22,6 @@ voxel_rcnn_state_dict.json: keys and shapes, in order, of the reference's VoxelR
 grid and cut 2D backbone, three classes) with the yaml's ROI_HEAD block.
 """
 import copy
-import importlib.util
 import json
 import os
 import sys
@@ -31,22 +29,16 @@ import types
 
 import numpy as np
 import torch
-import yaml
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, HERE)
-sys.path.insert(0, ROOT)
 import stack_pool_restatement as rs  # noqa: E402
+from reference_loader import (MODEL_UTILS, ROI_HEAD, as_np as _np, cpu_torch, extension_stubs, load, model_yaml,  # noqa: E402
+                              randomise, reference_root, second_settings, shapes, state, write_state_dict)
 from pdanet_amd.config import to_attr  # noqa: E402
 
 F32, I32 = np.float32, np.int32
 BACKBONE_CHANNELS = {'x_conv1': 16, 'x_conv2': 32, 'x_conv3': 64, 'x_conv4': 64}
-
-
-def _np(t):
-    assert t.device.type == "cpu" and t.is_contiguous()
-    return t.detach().numpy()
 
 
 def _starts(cnt, rows_cnt):
@@ -80,78 +72,14 @@ class Stub(types.ModuleType):
         return 1
 
 
-def _package(name, path=None, **attrs):
-    pkg = types.ModuleType(name)
-    pkg.__path__ = [path] if path else []
-    pkg.__dict__.update(attrs)
-    sys.modules[name] = pkg
-    parent, _, leaf = name.rpartition(".")
-    if parent in sys.modules:
-        setattr(sys.modules[parent], leaf, pkg)
-    return pkg
-
-
-def _module(name, path):
-    spec = importlib.util.spec_from_file_location(name, path)
-    m = importlib.util.module_from_spec(spec)
-    sys.modules[name] = m
-    parent, _, leaf = name.rpartition(".")
-    setattr(sys.modules[parent], leaf, m)
-    spec.loader.exec_module(m)
-    return m
-
-
 def load_reference(root):
     """-> (voxel_pool_modules, voxelrcnn_head, common_utils) of the reference, as pcdet_ref.*"""
-    pcdet = os.path.join(root, "pcdet")
-    torch.cuda.IntTensor, torch.cuda.FloatTensor = torch.IntTensor, torch.FloatTensor
-    torch.Tensor.cuda = lambda self, *a, **k: self
-    sys.modules["SharedArray"] = types.ModuleType("SharedArray")
-    _package("pcdet_ref", pcdet)
-    _package("pcdet_ref.utils", None)
-    _package("pcdet_ref.ops", None)
-    _package("pcdet_ref.ops.roiaware_pool3d", None, roiaware_pool3d_utils=types.ModuleType("roiaware_pool3d_utils"))
-    _package("pcdet_ref.ops.iou3d_nms", None)
-    _package("pcdet_ref.ops.iou3d_nms.iou3d_nms_cuda", None)
-    for name in ("common_utils", "box_utils", "loss_utils", "box_coder_utils"):
-        _module("pcdet_ref.utils." + name, os.path.join(pcdet, "utils", name + ".py"))
-    _module("pcdet_ref.ops.iou3d_nms.iou3d_nms_utils", os.path.join(pcdet, "ops", "iou3d_nms", "iou3d_nms_utils.py"))
-    stack = os.path.join(pcdet, "ops", "pointnet2", "pointnet2_stack")
-    _package("pcdet_ref.ops.pointnet2", None)
-    _package("pcdet_ref.ops.pointnet2.pointnet2_stack", None, pointnet2_stack_cuda=Stub())
-    sys.modules["pcdet_ref.ops.pointnet2.pointnet2_stack.pointnet2_stack_cuda"] = sys.modules[
-        "pcdet_ref.ops.pointnet2.pointnet2_stack"].pointnet2_stack_cuda
-    for name in ("pointnet2_utils", "voxel_query_utils", "voxel_pool_modules"):
-        _module("pcdet_ref.ops.pointnet2.pointnet2_stack." + name, os.path.join(stack, name + ".py"))
-    _package("pcdet_ref.models", None)
-    _package("pcdet_ref.models.model_utils", None)
-    _module("pcdet_ref.models.model_utils.model_nms_utils", os.path.join(pcdet, "models", "model_utils", "model_nms_utils.py"))
-    heads = os.path.join(pcdet, "models", "roi_heads")
-    _package("pcdet_ref.models.roi_heads", None)
-    _package("pcdet_ref.models.roi_heads.target_assigner", None)
-    _module("pcdet_ref.models.roi_heads.target_assigner.proposal_target_layer",
-            os.path.join(heads, "target_assigner", "proposal_target_layer.py"))
-    _module("pcdet_ref.models.roi_heads.roi_head_template", os.path.join(heads, "roi_head_template.py"))
-    head = _module("pcdet_ref.models.roi_heads.voxelrcnn_head", os.path.join(heads, "voxelrcnn_head.py"))
-    return (sys.modules["pcdet_ref.ops.pointnet2.pointnet2_stack.voxel_pool_modules"], head,
-            sys.modules["pcdet_ref.utils.common_utils"])
-
-
-def randomise(module, rng):
-    """BatchNorm weights, biases and running statistics away from their initial values, so that each of them matters."""
-    g = torch.Generator().manual_seed(int(rng.integers(1 << 30)))
-    for m in module.modules():
-        if isinstance(m, (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d)):
-            with torch.no_grad():
-                m.weight.copy_(torch.rand(m.weight.shape, generator=g) + 0.5)
-                m.bias.copy_(torch.randn(m.bias.shape, generator=g) * 0.2)
-                m.running_mean.copy_(torch.randn(m.bias.shape, generator=g) * 0.1)
-                m.running_var.copy_(torch.rand(m.bias.shape, generator=g) + 0.5)
-
-
-def state(module, prefix, out):
-    for k, v in module.state_dict().items():
-        out[prefix + "sd." + k] = v.detach().numpy().copy()
+    cpu_torch()
+    stack = "ops.pointnet2.pointnet2_stack."
+    needed = load(root, "pcdet_ref", MODEL_UTILS + ROI_HEAD + [stack + "pointnet2_utils", stack + "voxel_query_utils"],
+                  stubs=extension_stubs({stack + "pointnet2_stack_cuda": Stub()}))
+    vpm, head = load(root, "pcdet_ref", [stack + "voxel_pool_modules", "models.roi_heads.voxelrcnn_head"])
+    return vpm, head, needed[MODEL_UTILS.index("utils.common_utils")]
 
 
 # ---- geometry shared by the two parts: voxel size 1/4 on [0, 8) x [-4, 4) x [-2, 2) --------------------------------------
@@ -284,31 +212,20 @@ def head_part(head_mod, rng, out):
     print("head: pooled", out["head_pooled_train"].shape, "nonzero share", float((out["head_pooled_train"] != 0).mean()))
 
 
-def shapes(module, prefix=""):
-    return [[prefix + k, list(v.shape)] for k, v in module.state_dict().items()]
-
-
 def state_dict_part(root, head_mod):
-    with open(os.path.join(root, "tools", "cfgs", "kitti_models", "voxel_rcnn_car.yaml")) as f:
-        roi_cfg = yaml.safe_load(f)["MODEL"]["ROI_HEAD"]
-    with open(os.path.join(HERE, "second_state_dict.json")) as f:
-        second = json.load(f)
+    roi_cfg = model_yaml(root, "kitti_models/voxel_rcnn_car.yaml")["MODEL"]["ROI_HEAD"]
+    second = second_settings()
     ds = second["config"]["dataset"]
     head = head_mod.VoxelRCNNHead(backbone_channels=BACKBONE_CHANNELS, model_cfg=to_attr(copy.deepcopy(roi_cfg)),
                                   point_cloud_range=np.array(ds["point_cloud_range"]), voxel_size=ds["voxel_size"], num_class=1)
     model_cfg = dict(second["config"]["MODEL"], NAME="VoxelRCNN", ROI_HEAD=roi_cfg)
-    out = {"config": {"MODEL": model_cfg, "dataset": ds, "grid_size": second["config"]["grid_size"]},
-           "VoxelRCNNHead": shapes(head), "VoxelRCNN": second["SECONDNet"] + shapes(head, "roi_head.")}
-    path = os.path.join(HERE, "voxel_rcnn_state_dict.json")
-    with open(path, "w") as f:
-        json.dump(out, f, indent=0)
-    print(path, {k: len(v) for k, v in out.items()})
+    write_state_dict("voxel_rcnn_state_dict.json",
+                     {"config": {"MODEL": model_cfg, "dataset": ds, "grid_size": second["config"]["grid_size"]},
+                      "VoxelRCNNHead": shapes(head), "VoxelRCNN": second["SECONDNet"] + shapes(head, "roi_head.")})
 
 
 def main():
-    root = sys.argv[1] if len(sys.argv) > 1 else os.environ.get("PDA_REFERENCE_ROOT")
-    if not root:
-        sys.exit(__doc__)
+    root = reference_root()
     vpm, head_mod, cu = load_reference(root)
     rng = np.random.default_rng(2025)
     out = {}

@@ -14,7 +14,7 @@ Two sets of scenes: `raw` holds points within 2e-5 m of the 40 m sphere that sam
 generator asserts that no voxel mean lies within 1e-4 m of the sphere (the reference tests the float64 means in float64, the
 device the float32 rows in float32).
 
-Run here only:  python tests/golden/make_voxel_sample_golden.py
+Run with the reference checkout:  python tests/golden/make_voxel_sample_golden.py /path/to/reference
 """
 import os
 import sys
@@ -23,7 +23,9 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-import make_input_golden as mig   # noqa: E402  (the module stubs, the scene helpers)
+import make_input_golden as mig   # noqa: E402  (the scene helpers, the draw recorder, its loading of the processor)
+from reference_loader import q, reference_root  # noqa: E402
+from pdanet_amd.config import AttrDict as AD  # noqa: E402
 
 OUT = os.path.join(HERE, "voxel_sample.npz")
 K = 2048
@@ -32,7 +34,6 @@ RANGE = [-51.2, -51.2, -3.0, 51.2, 51.2, 2.0]
 VOXEL_SIZE = [0.4, 0.4, 0.5]
 MAX_POINTS = 5
 MAX_VOXELS = {"train": 3000, "test": 3200}
-AD = mig.AD
 COUNTS = []          # per generate() call: [n_points, n_in_grid, n_voxels_before_cap]
 
 
@@ -98,8 +99,8 @@ def _cells(rng, n_cells, rmin, rmax, per_cell):
         seen.add(cell)
         m = per_cell(rng)
         p = np.zeros((m, C), np.float32)
-        p[:, :3] = mig._q(lo + (np.array(cell) + rng.uniform(0.1, 0.9, (m, 3))) * vs)
-        p[:, 3:] = mig._q(rng.uniform(0, 1, (m, C - 3)))
+        p[:, :3] = q(lo + (np.array(cell) + rng.uniform(0.1, 0.9, (m, 3))) * vs)
+        p[:, 3:] = q(rng.uniform(0, 1, (m, C - 3)))
         rows.append(p)
     return np.concatenate(rows)
 
@@ -183,7 +184,7 @@ def voxel_rows(points, training, perm0, sample_type):
 
 
 def main():
-    DataProcessor, collate = mig.import_reference()
+    DataProcessor, collate = mig.import_reference(reference_root())
     sys.modules["pcdet.datasets.processor.data_processor"].VoxelGeneratorWrapper = PyVoxelGenerator
     rng = np.random.default_rng(20261017)
     data = {"num_points": np.array(K), "range": np.array(RANGE, np.float32), "voxel_size": np.array(VOXEL_SIZE, np.float64),
