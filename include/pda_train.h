@@ -44,6 +44,18 @@ int pda_bn_relu_fwd(const float *x, const float *gamma, const float *beta, float
 int pda_bn_relu_bwd(const float *x, const float *grad_y, const float *gamma, const float *beta,
                     const float *mean_invstd, float *grad_x, float *grad_gamma, float *grad_beta,
                     void *scratch, int64_t rows, int c, pda_stream_t stream);
+/* The counted form, for padded sparse tensors: `rows` is a capacity that sizes every grid, and the rows
+ * that count are [0, *count), a device word clipped to [0, rows].  The same arithmetic as above over the live rows.  Dead rows
+ * of x and grad_y are never read; dead rows of y and grad_x are written as exact zeros.  relu == 0: BatchNorm alone.
+ * training == 0: normalise with the running statistics (required then), which are not updated.  In training mode *count < 2
+ * ORs 8 into *status (torch would have raised): one row gives variance 0, no row leaves the running statistics alone.
+ * rows == 0 is PDA_OK.  The same (live rows, capacity) gives the same bits from run to run. */
+int pda_bn_relu_fwd_counted(const float *x, const float *gamma, const float *beta, float *running_mean, float *running_var,
+                            float *y, float *mean_invstd, void *scratch, int64_t rows, int c, float eps, float momentum,
+                            const int32_t *count, int32_t *status, int relu, int training, pda_stream_t stream);
+int pda_bn_relu_bwd_counted(const float *x, const float *grad_y, const float *gamma, const float *beta,
+                            const float *mean_invstd, float *grad_x, float *grad_gamma, float *grad_beta, void *scratch,
+                            int64_t rows, int c, const int32_t *count, int relu, int training, pda_stream_t stream);
 /* The reduction half of pda_bn_relu_bwd alone: grad_gamma, grad_beta and sums (2, C) = the per-channel means of the masked
  * gradient and of its product with the normalised input, for a consumer that forms grad_x itself (pda_sa_point_grad_bn). */
 int pda_bn_relu_bwd_reduce(const float *x, const float *grad_y, const float *gamma, const float *beta,
@@ -1104,6 +1116,21 @@ int pda_spconv_index_subm(const int32_t *indices, int64_t n, int batch, int d, i
 int pda_spconv_index_strided(const int32_t *indices, int64_t n, int batch, int d, int h, int w, int kd, int kh, int kw, int sd,
                              int sh, int sw, int pd, int ph, int pw, int64_t cap, int32_t *out_indices, int32_t *nbr_out,
                              int32_t *nbr_in, int32_t *stat, void *workspace, pda_stream_t stream);
+/* The counted builds, for padded tensors: n is the CAPACITY of the input and *count_in, a device word, the
+ * number of live rows, clipped to [0, n].  Rows from *count_in on take part in nothing and raise no flag, whatever they hold.
+ * status is one device word that the build ORs its flags into and never clears: 1 and 2 as above, 4 = more output sites than
+ * cap (the cap smallest keys are kept, so the result is still determined).  The strided form writes *count_out = min(found,
+ * cap), out_indices (cap, 4) and nbr_out (cap, T) with -1 in the rows from *count_out on, nbr_in (n, T) with -1 in the rows from
+ * *count_in on; its first *count_out rows are what pda_spconv_index_strided returns for the live rows alone.  The submanifold
+ * form writes nbr_out (n, T), -1 in the rows from *count_in on.  Every grid and the workspace (the same query) depend on n and
+ * cap only; nothing is read back. */
+int pda_spconv_index_subm_counted(const int32_t *indices, int64_t n, const int32_t *count_in, int batch, int d, int h, int w,
+                                  int kd, int kh, int kw, int32_t *nbr_out, int32_t *status, void *workspace,
+                                  pda_stream_t stream);
+int pda_spconv_index_strided_counted(const int32_t *indices, int64_t n, const int32_t *count_in, int batch, int d, int h, int w,
+                                     int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph, int pw, int64_t cap,
+                                     int32_t *out_indices, int32_t *nbr_out, int32_t *nbr_in, int32_t *count_out,
+                                     int32_t *status, void *workspace, pda_stream_t stream);
 /* The feature kernels: float32 in, float32 accumulate with the exact f32-input MFMA, no float atomics, fixed summation
  * orders.  cin in [1, 128], cout a multiple of 16 up to 128; anything else is refused with a message.
  * pda_spconv_gemm: out[i] = sum_t in[nbr[i][t']] . plane[t] (+ bias), t' = flip ? T - 1 - t : t, a tap with nbr < 0 (or

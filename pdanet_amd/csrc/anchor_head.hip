@@ -64,6 +64,14 @@ __device__ __forceinline__ float iou_normal(float ax1, float ay1, float ax2, flo
     return inter / fmaxf(area_a + area_b - inter, 1e-6f);
 }
 
+// The accumulators of the two passes below, zeroed: num_pos (n_pos) and col_max (n_col, or nullptr).
+__global__ __launch_bounds__(AH_THREADS) void anchor_clear_kernel(int32_t* __restrict__ num_pos, int64_t n_pos,
+                                                                  uint32_t* __restrict__ col_max, int64_t n_col) {
+    const int64_t i = (int64_t)blockIdx.x * AH_THREADS + threadIdx.x;
+    if (i < n_pos) num_pos[i] = 0;
+    if (col_max != nullptr && i < n_col) col_max[i] = 0u;
+}
+
 // SECOND == false: col_max[s, j] = max over the anchors of j's class of iou(a, j), through the bit pattern (values >= 0).
 // SECOND == true: the same IoUs again; labels, targets, weights and the scene's positives.
 // grid (ceil(n_anchors / 256), b); anchor n of a scene is row n of `anchors`, its class the owner of slot n % slots, or with
@@ -488,11 +496,12 @@ int assign_targets(const char* what, bool segmented, const float* gt_boxes, int 
     PDA_REQUIRE(anchors && box_cls_labels && box_reg_targets && reg_weights && num_pos, "%s: null pointer", what);
     PDA_REQUIRE(m == 0 || (gt_boxes && col_max), "%s: null gt_boxes or col_max", what);
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(num_pos, 0, (size_t)b * 4, st) != hipSuccess ||
-        (m > 0 && hipMemsetAsync(col_max, 0, (size_t)b * m * 4, st) != hipSuccess)) {
-        set_error("%s: hipMemsetAsync failed", what);
-        return PDA_ERR_LAUNCH;
-    }
+    // A kernel and not two memsets: the accumulators of a captured graph must be cleared by every replay, and memset nodes
+    // did not do that reliably (MI355X: from the second replay on num_pos and col_max carried the replay before).
+    const int64_t n_clear = (int64_t)b * (m > 1 ? m : 1);
+    if (n_clear > 0)
+        hipLaunchKernelGGL(anchor_clear_kernel, dim3((unsigned)divup64(n_clear, AH_THREADS)), dim3(AH_THREADS), 0, st, num_pos, (int64_t)b,
+                           m > 0 ? col_max : (uint32_t*)nullptr, (int64_t)b * m);
     const dim3 grid(divup(n_anchors, AH_THREADS), b);
     auto first = segmented ? anchor_assign_kernel<false, true> : anchor_assign_kernel<false, false>;
     auto second = segmented ? anchor_assign_kernel<true, true> : anchor_assign_kernel<true, false>;

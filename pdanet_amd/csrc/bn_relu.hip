@@ -370,6 +370,173 @@ static int launch_bn_relu_pool_bwd(const TX* x, const float* grad_out, const uin
     return check_launch(what);
 }
 
+
+// ---- the counted form: rows is a CAPACITY, the rows that count are [0, *count), read on the device ------------------------------
+// (the padded sparse tensors of spconv_utils.py: DESIGN.md section 7).  The same arithmetic and the same layout of partials
+// as above, so sum_partials is shared; every grid is sized from the capacity, a block without live rows writes zero
+// partials.  Dead rows are never loaded; their y / grad_x are exact zeros by a select.
+constexpr int BN_FLAG_FEW_ROWS = 8;      // spconv_utils.FLAG_FEW_ROWS
+
+__device__ __forceinline__ int64_t bn_live_rows(const int32_t* __restrict__ count, int64_t rows) {
+    const int32_t v = *count;
+    return v < 0 ? 0 : (v > rows ? rows : (int64_t)v);
+}
+
+template <bool BWD>
+__global__ __launch_bounds__(256) void bn_reduce_counted_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                                const float* __restrict__ mean_invstd,
+                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                double* __restrict__ partial, BnShape s,
+                                                                const int32_t* __restrict__ count, int relu) {
+    __shared__ double lds[2 * 256 * 4];
+    const int tid = threadIdx.x;
+    const int64_t n = bn_live_rows(count, s.rows);
+    double a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
+    const int col = tid % s.cg, r0 = tid / s.cg;
+    float4 mu = make_float4(0, 0, 0, 0), is = mu, g = mu, be = mu;
+    if (BWD) {
+        mu = reinterpret_cast<const float4*>(mean_invstd)[col];
+        is = reinterpret_cast<const float4*>(mean_invstd + s.c)[col];
+        g = reinterpret_cast<const float4*>(gamma)[col];
+        be = reinterpret_cast<const float4*>(beta)[col];
+    }
+    const int64_t stride = (int64_t)gridDim.x * s.rpb;
+    auto row = [&](const float4& v, const float4& d) {
+        if (!BWD) {
+            a[0] += v.x; a[1] += v.y; a[2] += v.z; a[3] += v.w;
+            b[0] += (double)v.x * v.x; b[1] += (double)v.y * v.y; b[2] += (double)v.z * v.z; b[3] += (double)v.w * v.w;
+        } else {
+            const float xh[4] = {(v.x - mu.x) * is.x, (v.y - mu.y) * is.y, (v.z - mu.z) * is.z, (v.w - mu.w) * is.w};
+            const float gg[4] = {g.x, g.y, g.z, g.w}, bb[4] = {be.x, be.y, be.z, be.w}, dd[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float dyh = (!relu || xh[k] * gg[k] + bb[k] > 0.f) ? dd[k] : 0.f;
+                a[k] += dyh;
+                b[k] += (double)dyh * xh[k];
+            }
+        }
+    };
+    constexpr int U = BWD ? 1 : 4;          // independent 16-byte loads in flight per thread: see bn_reduce_kernel
+    int64_t r = (int64_t)blockIdx.x * s.rpb + r0;
+    for (; r + (U - 1) * stride < n; r += U * stride) {
+        float4 v[U], d[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            v[u] = load4(x + (r + u * stride) * s.c + 4 * col);
+            d[u] = BWD ? load4(dy + (r + u * stride) * s.c + 4 * col) : make_float4(0, 0, 0, 0);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) row(v[u], d[u]);
+    }
+    for (; r < n; r += stride) row(load4(x + r * s.c + 4 * col), BWD ? load4(dy + r * s.c + 4 * col) : make_float4(0, 0, 0, 0));
+    double* pa = partial + (size_t)blockIdx.x * 2 * s.c;
+    block_reduce_cols(a, b, lds, s.cg, s.rpb, pa, pa + s.c);
+}
+
+// bn_finalize_fwd_kernel with the row count read here.  No live row: the running statistics stay, mean_invstd is (0,
+// 1 / sqrt(eps)) so that the backward stays finite.  Fewer than two: torch would have raised; the flag says so.
+__global__ __launch_bounds__(512) void bn_finalize_fwd_counted_kernel(const double* __restrict__ partial, int nblocks, int c,
+                                                                       int64_t cap, const int32_t* __restrict__ count, float eps,
+                                                                       float momentum, float* __restrict__ mean_invstd,
+                                                                       float* __restrict__ running_mean,
+                                                                       float* __restrict__ running_var, int32_t* __restrict__ status) {
+    double s1, s2;
+    int ch;
+    const int64_t rows = bn_live_rows(count, cap);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && rows < 2) atomicOr(status, BN_FLAG_FEW_ROWS);
+    if (!sum_partials(partial, nblocks, c, s1, s2, ch)) return;
+    if (rows == 0) {
+        mean_invstd[ch] = 0.f;
+        mean_invstd[c + ch] = (float)(1.0 / sqrt((double)eps));
+        return;
+    }
+    const double mean = s1 / (double)rows;
+    double var = s2 / (double)rows - mean * mean;
+    var = var < 0 ? 0 : var;
+    mean_invstd[ch] = (float)mean;
+    mean_invstd[c + ch] = (float)(1.0 / sqrt(var + (double)eps));
+    if (running_mean) {
+        const double unbiased = rows > 1 ? var * ((double)rows / (double)(rows - 1)) : var;
+        running_mean[ch] = (float)((1.0 - momentum) * running_mean[ch] + momentum * mean);
+        running_var[ch] = (float)((1.0 - momentum) * running_var[ch] + momentum * unbiased);
+    }
+}
+
+// eval mode: the statistics are the running ones
+__global__ __launch_bounds__(256) void bn_eval_stats_kernel(const float* __restrict__ running_mean,
+                                                             const float* __restrict__ running_var, int c, float eps,
+                                                             float* __restrict__ mean_invstd) {
+    const int ch = blockIdx.x * 256 + threadIdx.x;
+    if (ch >= c) return;
+    mean_invstd[ch] = running_mean[ch];
+    mean_invstd[c + ch] = (float)(1.0 / sqrt((double)running_var[ch] + (double)eps));
+}
+
+// bn_finalize_bwd_kernel with the row count read here; in eval mode the statistics do not depend on x and the mean terms
+// of grad_x vanish.
+__global__ __launch_bounds__(512) void bn_finalize_bwd_counted_kernel(const double* __restrict__ partial, int nblocks, int c,
+                                                                       int64_t cap, const int32_t* __restrict__ count, int training,
+                                                                       float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                       float* __restrict__ sums) {
+    double s1, s2;
+    int ch;
+    const int64_t rows = bn_live_rows(count, cap);
+    if (!sum_partials(partial, nblocks, c, s1, s2, ch)) return;
+    dbeta[ch] = (float)s1;
+    dgamma[ch] = (float)s2;
+    const bool means = training && rows > 0;
+    sums[ch] = means ? (float)(s1 / (double)rows) : 0.f;
+    sums[c + ch] = means ? (float)(s2 / (double)rows) : 0.f;
+}
+
+template <bool BWD>
+__global__ __launch_bounds__(256) void bn_apply_counted_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                               const float* __restrict__ mean_invstd,
+                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                               const float* __restrict__ sums, float* __restrict__ out, BnShape s,
+                                                               const int32_t* __restrict__ count, int relu) {
+    const int tid = threadIdx.x;
+    const int col = tid % s.cg, r0 = tid / s.cg;
+    const int64_t n = bn_live_rows(count, s.rows);
+    const float4 mu = reinterpret_cast<const float4*>(mean_invstd)[col], is = reinterpret_cast<const float4*>(mean_invstd + s.c)[col];
+    const float4 g = reinterpret_cast<const float4*>(gamma)[col], be = reinterpret_cast<const float4*>(beta)[col];
+    float4 m1 = make_float4(0, 0, 0, 0), m2 = m1;
+    if (BWD) { m1 = reinterpret_cast<const float4*>(sums)[col]; m2 = reinterpret_cast<const float4*>(sums + s.c)[col]; }
+    const float muv[4] = {mu.x, mu.y, mu.z, mu.w}, isv[4] = {is.x, is.y, is.z, is.w}, gv[4] = {g.x, g.y, g.z, g.w},
+                bv[4] = {be.x, be.y, be.z, be.w}, m1v[4] = {m1.x, m1.y, m1.z, m1.w}, m2v[4] = {m2.x, m2.y, m2.z, m2.w};
+    const int64_t stride = (int64_t)gridDim.x * s.rpb;
+    const float4 zero = make_float4(0, 0, 0, 0);
+    for (int64_t r = (int64_t)blockIdx.x * s.rpb + r0; r < s.rows; r += stride) {
+        const bool live = r < n;
+        const float4 v = live ? load4(x + r * s.c + 4 * col) : zero;          // a dead row is not read
+        const float4 d = (BWD && live) ? load4(dy + r * s.c + 4 * col) : zero;
+        const float xv[4] = {v.x, v.y, v.z, v.w}, dv[4] = {d.x, d.y, d.z, d.w};
+        float o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float xh = (xv[k] - muv[k]) * isv[k];
+            const float y = xh * gv[k] + bv[k];
+            float val;
+            if (!BWD) {
+                val = relu ? fmaxf(y, 0.f) : y;
+            } else {
+                const float dyh = (!relu || y > 0.f) ? dv[k] : 0.f;
+                val = gv[k] * isv[k] * (dyh - (m1v[k] + xh * m2v[k]));
+            }
+            o[k] = live ? val : 0.f;                                          // a select, not a product: exact zeros
+        }
+        store4(out + r * s.c + 4 * col, make_float4(o[0], o[1], o[2], o[3]));
+    }
+}
+
+static int bn_counted_shape(int64_t rows, int c, BnShape& s, const char* what) {
+    PDA_REQUIRE(rows >= 0 && rows <= ((int64_t)1 << 31) - 1, "%s: bad size: rows = %lld", what, (long long)rows);
+    PDA_REQUIRE(c >= 4 && c <= 1024 && (c & (c - 1)) == 0, "%s: C = %d is not a power of two in [4, 1024]", what, c);
+    s.rows = rows; s.c = c; s.cg = c / 4; s.rpb = 256 / s.cg; s.ns = 1;
+    s.roww = nullptr; s.count = rows;
+    return PDA_OK;
+}
+
 }  // namespace pda
 
 PDA_API int pda_bn_relu_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
@@ -508,5 +675,62 @@ PDA_API int pda_bn_relu_max_pool_apply(const float* x, const float* gamma, const
                     ((uintptr_t)arg & 3) == 0, "%s: alignment", what);
     hipLaunchKernelGGL(pda::bn_apply_pool_kernel<float>, dim3((unsigned)pda::divup64(groups * s.cg, 256)), dim3(256), 0, (hipStream_t)stream, x,
                        mean_invstd, gamma, beta, out, arg, groups, s);
+    return pda::check_launch(what);
+}
+
+// ---- the counted form (padded sparse tensors): rows = capacity, *count = the rows that count --------------------------------------
+PDA_API int pda_bn_relu_fwd_counted(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                                    float* y, float* mean_invstd, void* scratch, int64_t rows, int c, float eps, float momentum,
+                                    const int32_t* count, int32_t* status, int relu, int training, pda_stream_t stream) {
+    const char* what = "pda_bn_relu_fwd_counted";
+    pda::BnShape s;
+    if (int rc = pda::bn_counted_shape(rows, c, s, what)) return rc;
+    PDA_REQUIRE(x && gamma && beta && y && mean_invstd && scratch && count && status, "%s: null pointer", what);
+    PDA_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "%s: running_mean/var must come together", what);
+    PDA_REQUIRE(training || running_mean, "%s: eval mode normalises with the running statistics", what);
+    PDA_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)mean_invstd) & 15) == 0,
+                "%s: pointers must be 16-byte aligned", what);
+    if (rows == 0) return PDA_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = pda::bn_grid(s);
+    if (training) {
+        hipLaunchKernelGGL(pda::bn_reduce_counted_kernel<false>, dim3(grid), dim3(256), 0, st, x, (const float*)nullptr,
+                           (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (double*)scratch, s, count, relu);
+        hipLaunchKernelGGL(pda::bn_finalize_fwd_counted_kernel, dim3(pda::divup(c, 32)), dim3(512), 0, st, (const double*)scratch, grid, c,
+                           rows, count, eps, momentum, mean_invstd, running_mean, running_var, status);
+    } else {
+        hipLaunchKernelGGL(pda::bn_eval_stats_kernel, dim3(pda::divup(c, 256)), dim3(256), 0, st, (const float*)running_mean,
+                           (const float*)running_var, c, eps, mean_invstd);
+    }
+    hipLaunchKernelGGL(pda::bn_apply_counted_kernel<false>, dim3(grid), dim3(256), 0, st, x, (const float*)nullptr,
+                       (const float*)mean_invstd, gamma, beta, (const float*)nullptr, y, s, count, relu);
+    return pda::check_launch(what);
+}
+
+PDA_API int pda_bn_relu_bwd_counted(const float* x, const float* grad_y, const float* gamma, const float* beta,
+                                    const float* mean_invstd, float* grad_x, float* grad_gamma, float* grad_beta, void* scratch,
+                                    int64_t rows, int c, const int32_t* count, int relu, int training, pda_stream_t stream) {
+    const char* what = "pda_bn_relu_bwd_counted";
+    pda::BnShape s;
+    if (int rc = pda::bn_counted_shape(rows, c, s, what)) return rc;
+    PDA_REQUIRE(x && grad_y && gamma && beta && mean_invstd && grad_x && grad_gamma && grad_beta && scratch && count,
+                "%s: null pointer", what);
+    PDA_REQUIRE((((uintptr_t)x | (uintptr_t)grad_y | (uintptr_t)grad_x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)mean_invstd) & 15) == 0,
+                "%s: pointers must be 16-byte aligned", what);
+    if (rows == 0) {
+        if (hipMemsetAsync(grad_gamma, 0, (size_t)c * 4, (hipStream_t)stream) != hipSuccess ||
+            hipMemsetAsync(grad_beta, 0, (size_t)c * 4, (hipStream_t)stream) != hipSuccess)
+            return pda::check_launch(what);
+        return PDA_OK;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = pda::bn_grid(s);
+    float* sums = reinterpret_cast<float*>(reinterpret_cast<double*>(scratch) + (size_t)pda::BN_BLOCKS * 2 * c);
+    hipLaunchKernelGGL(pda::bn_reduce_counted_kernel<true>, dim3(grid), dim3(256), 0, st, x, grad_y, mean_invstd, gamma, beta,
+                       (double*)scratch, s, count, relu);
+    hipLaunchKernelGGL(pda::bn_finalize_bwd_counted_kernel, dim3(pda::divup(c, 32)), dim3(512), 0, st, (const double*)scratch, grid, c, rows,
+                       count, training, grad_gamma, grad_beta, sums);
+    hipLaunchKernelGGL(pda::bn_apply_counted_kernel<true>, dim3(grid), dim3(256), 0, st, x, grad_y, mean_invstd, gamma, beta,
+                       (const float*)sums, grad_x, s, count, relu);
     return pda::check_launch(what);
 }

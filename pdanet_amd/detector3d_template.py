@@ -160,6 +160,15 @@ class VoxelDetector(PillarDetector):
                 num_class=class_count(roi_cfg, num_class), **point_kwargs)
             self.module_list.append(self.roi_head)
 
+    def forward(self, batch_dict):
+        """A padded batch (voxel_num_active, voxel_utils.collate_voxels_padded) runs the one-stage detectors without a host
+        read; the voxel queries and RoI pools of a second stage are not count-aware and refuse it."""
+        if batch_dict.get('voxel_num_active') is not None and any(
+                getattr(self, name, None) is not None for name in ('pfe', 'point_head', 'roi_head')):
+            raise NotImplementedError("%s: a padded batch (voxel_num_active) is implemented for the one-stage detectors only; "
+                                      "the second stage's voxel queries and RoI pools are not count-aware" % type(self).__name__)
+        return super().forward(batch_dict)
+
     def get_training_loss(self):
         loss, tb_dict, disp_dict = super().get_training_loss()
         if getattr(self, 'point_head', None) is not None:

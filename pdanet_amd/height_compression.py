@@ -12,7 +12,8 @@ class HeightCompression(nn.Module):
         self.num_bev_features = field(model_cfg, 'NUM_BEV_FEATURES')
 
     def forward(self, batch_dict):
-        """encoded_spconv_tensor -> spatial_features (B, C * D, H, W), spatial_features_stride."""
+        """encoded_spconv_tensor -> spatial_features (B, C * D, H, W), spatial_features_stride.  A padded tensor scatters its
+        live rows only (dense() hands num_active to the scatter as its device count); voxel_status stays in the batch."""
         spatial_features = batch_dict['encoded_spconv_tensor'].dense()
         N, C, D, H, W = spatial_features.shape
         batch_dict['spatial_features'] = spatial_features.view(N, C * D, H, W)

@@ -13,7 +13,9 @@ class MeanVFE(nn.Module):
         return self.num_point_features
 
     def forward(self, batch_dict, **kwargs):
-        """voxels (num_voxels, max_points_per_voxel, C), voxel_num_points (num_voxels) -> voxel_features (num_voxels, C)."""
+        """voxels (num_voxels, max_points_per_voxel, C), voxel_num_points (num_voxels) -> voxel_features (num_voxels, C).
+        A padded batch (voxel_num_active, voxel_status: voxel_utils.collate_voxels_padded) passes through as it is: a dead
+        row has zero points and zero voxels, so its mean is 0 / 1 = 0."""
         voxel_features, voxel_num_points = batch_dict['voxels'], batch_dict['voxel_num_points']
         points_mean = voxel_features.sum(dim=1, keepdim=False)
         normalizer = torch.clamp_min(voxel_num_points.view(-1, 1), min=1.0).type_as(voxel_features)

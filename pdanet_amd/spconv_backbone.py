@@ -4,13 +4,15 @@ constructor signatures, sparse_shape (grid_size reversed, + 1 in z), `last_pad` 
 and backbone_channels, and the same module names, so a reference checkpoint (spconv 2.x layout) loads with strict=True.
 BatchNorm1d(eps=1e-3, momentum=0.01) stays a plain module over the active rows.  A forward builds one rulebook
 per indice_key -- subm1, spconv2, subm2, spconv3, subm3, spconv4, subm4, spconv_down2; the Res form res1..res4 in place of
-subm2..subm4 and next to subm1 -- and makes four host reads, one per strided convolution."""
+subm2..subm4 and next to subm1 -- and makes four host reads, one per strided convolution.  A padded batch
+(voxel_num_active) makes none: the rulebooks keep their counts on the device, the BatchNorm1d modules run
+through the counted kernels, and model_cfg PADDED_CAPS says how many rows each strided convolution reserves."""
 from functools import partial
 
 import torch.nn as nn
 
 from . import spconv_utils as spconv
-from .spconv_utils import replace_feature
+from .spconv_utils import counted_batch_norm, replace_feature
 
 
 def post_act_block(in_channels, out_channels, kernel_size, indice_key=None, stride=1, padding=0, conv_type='subm', norm_fn=None):
@@ -44,10 +46,15 @@ class SparseBasicBlock(spconv.SparseModule):
     def forward(self, x):
         identity = x
         out = self.conv1(x)
-        out = replace_feature(out, self.bn1(out.features))
-        out = replace_feature(out, self.relu(out.features))
-        out = self.conv2(out)
-        out = replace_feature(out, self.bn2(out.features))
+        if x.num_active is not None:          # padded: counted BatchNorm, bn1's ReLU folded in; dead rows stay exact zeros
+            out = replace_feature(out, counted_batch_norm(self.bn1, out.features, out.num_active, out.status, relu=True))
+            out = self.conv2(out)
+            out = replace_feature(out, counted_batch_norm(self.bn2, out.features, out.num_active, out.status, relu=False))
+        else:
+            out = replace_feature(out, self.bn1(out.features))
+            out = replace_feature(out, self.relu(out.features))
+            out = self.conv2(out)
+            out = replace_feature(out, self.bn2(out.features))
         if self.downsample is not None:
             identity = self.downsample(x)
         out = replace_feature(out, out.features + identity.features)
@@ -76,10 +83,18 @@ class _VoxelBackBone(nn.Module):
         self.backbone_channels = {'x_conv1': 16, 'x_conv2': 32, 'x_conv3': 64, 'x_conv4': self.LEVEL4}
 
     def forward(self, batch_dict):
-        """batch_dict: batch_size, voxel_features (num_voxels, C), voxel_coords (num_voxels, 4) [batch_idx, z, y, x]."""
+        """batch_dict: batch_size, voxel_features (num_voxels, C), voxel_coords (num_voxels, 4) [batch_idx, z, y, x].
+        With voxel_num_active (a device int32; voxel_utils.collate_voxels_padded) the rows are a capacity and the whole
+        forward reads nothing back: the strided convolutions reserve model_cfg PADDED_CAPS[indice_key] rows (default: the
+        bound that cannot overflow), and voxel_status collects the flags (spconv_utils.padded_report)."""
         voxel_features, voxel_coords = batch_dict['voxel_features'], batch_dict['voxel_coords']
+        num_active = batch_dict.get('voxel_num_active')
         x = spconv.SparseConvTensor(features=voxel_features, indices=voxel_coords.int(), spatial_shape=self.sparse_shape,
-                                    batch_size=batch_dict['batch_size'])
+                                    batch_size=batch_dict['batch_size'], num_active=num_active,
+                                    status=None if num_active is None else batch_dict.get('voxel_status'))
+        if num_active is not None:
+            x.caps = {key: int(rows) for key, rows in (self.model_cfg.get('PADDED_CAPS') or {}).items()}
+            batch_dict['voxel_status'] = x.status
         x = self.conv_input(x)
         x_conv1 = self.conv1(x)
         x_conv2 = self.conv2(x_conv1)

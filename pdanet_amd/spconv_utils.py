@@ -15,7 +15,14 @@ is order-free.  Weights keep spconv 2.x's layout (C_out, kD, kH, kW, C_in), the 
 Host reads: a strided build reads the output count and the flag word in one copy (BatchNorm must see exactly the live rows);
 that read is where duplicate coordinates, coordinates outside the grid and overflow raise.  A submanifold build reads
 nothing unless check=True.  With a rulebook in place forward and backward read nothing back and allocate through torch
-only, so they are graph-capturable."""
+only, so they are graph-capturable.
+
+The padded form reads nothing at all: a SparseConvTensor that carries `num_active` (a device int32)
+holds `cap` rows of which the first *num_active are live; the dead rows have indices -1, rulebook rows -1 and, after every
+counted BatchNorm, features exactly 0.  The index stage takes its input count from the device and leaves the output count
+there (Rulebook.count_out), BatchNorm runs through pda_bn_relu_*_counted, and what would have raised -- duplicate or outside
+coordinates, more output sites than the capacity, a BatchNorm over fewer than two rows -- is ORed into the tensor's `status`
+word instead, which padded_report reads whenever the caller likes."""
 import math
 
 import torch
@@ -24,10 +31,11 @@ import torch.nn.functional as F
 
 from . import param_cache
 from .pointpillar_scatter import pillar_scatter
-from .pointnet2_batch_cuda import F32, I32, _call, _chk
+from .pointnet2_batch_cuda import F32, I32, _buffers_written, _call, _chk, bn_relu_scratch_bytes
 from .stage_common import workspace
 
 FLAG_DUPLICATE, FLAG_OUTSIDE = 1, 2
+FLAG_OVERFLOW, FLAG_FEW_ROWS = 4, 8          # the padded form only: what the compact form raises for
 MAX_CHANNELS = 128
 ROW_TILE = 64              # output rows of a workgroup of the gather-GEMM (csrc/sparse_conv.hip SC_ROWS)
 _KEY_LIMIT = 2 ** 31
@@ -66,7 +74,9 @@ class Rulebook:
     """What the index stage leaves for one (input sites, kernel, stride, padding): out_indices (n_out, 4), spatial shape of
     the output, nbr_out (n_out, T), nbr_in (n_in, T) or None for a submanifold convolution (nbr_out with mirrored taps)."""
 
-    def __init__(self, kind, kernel_size, stride, padding, in_shape, out_shape, n_in, out_indices, nbr_out, nbr_in):
+    def __init__(self, kind, kernel_size, stride, padding, in_shape, out_shape, n_in, out_indices, nbr_out, nbr_in,
+                 count_out=None):
+        self.count_out = count_out          # padded form: device int32 (1), the live output rows; n_out is then the capacity
         self.kind, self.kernel_size, self.stride, self.padding = kind, kernel_size, stride, padding
         self.in_shape, self.out_shape, self.n_in = list(in_shape), list(out_shape), n_in
         self.out_indices, self.nbr_out, self.nbr_in = out_indices, nbr_out, nbr_in
@@ -84,9 +94,25 @@ def _indices_ok(indices):
         raise ValueError("indices must be (N, 4) int32 (b, z, y, x), got %s" % (tuple(indices.shape),))
 
 
-def build_subm_rulebook(indices, spatial_shape, batch_size, kernel_size, check=False):
+def _count_ok(t, name):
+    """A device word of the padded form: one int32."""
+    if not isinstance(t, torch.Tensor) or t.dtype != I32 or t.numel() != 1:
+        raise ValueError("%s must be an int32 tensor of one element, got %s"
+                         % (name, "%s %s" % (t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__))
+    return t
+
+
+def _counted_args(count, status):
+    if status is None:
+        raise ValueError("a count comes with a status word (one device int32 that the kernels OR their flags into)")
+    _chk(_count_ok(count, "count"), "count", I32)
+    _chk(_count_ok(status, "status"), "status", I32)
+
+
+def build_subm_rulebook(indices, spatial_shape, batch_size, kernel_size, check=False, count=None, status=None):
     """The rulebook of a SubMConv3d (odd kernel, stride 1): no host read unless check=True, which reads the flag word and
-    raises for duplicate or out-of-range coordinates."""
+    raises for duplicate or out-of-range coordinates.  count (with status): the padded form -- the rows from *count on are
+    dead, flags go to *status, check is ignored and nothing is read."""
     _indices_ok(indices)
     k = _triple(kernel_size, "kernel_size")
     if any(v % 2 != 1 for v in k):
@@ -95,8 +121,15 @@ def build_subm_rulebook(indices, spatial_shape, batch_size, kernel_size, check=F
     n, T = indices.shape[0], k[0] * k[1] * k[2]
     D, H, W = (int(v) for v in spatial_shape)
     nbr = torch.empty((n, T), dtype=I32, device=indices.device)
-    book = Rulebook('subm', k, (1, 1, 1), tuple(v // 2 for v in k), spatial_shape, spatial_shape, n, indices, nbr, None)
+    book = Rulebook('subm', k, (1, 1, 1), tuple(v // 2 for v in k), spatial_shape, spatial_shape, n, indices, nbr, None,
+                    count_out=count)
     if n == 0:
+        return book
+    if count is not None:
+        _counted_args(count, status)
+        ws = workspace("pda_spconv_index_workspace_bytes", (n, 0, 1), "%d rows are too many for the index stage" % n, indices.device)
+        _call("pda_spconv_index_subm_counted", indices, indices.data_ptr(), n, count.data_ptr(), int(batch_size), D, H, W, k[0], k[1],
+              k[2], nbr.data_ptr(), status.data_ptr(), ws.data_ptr())
         return book
     stat = torch.empty((2,), dtype=I32, device=indices.device)
     ws = workspace("pda_spconv_index_workspace_bytes", (n, 0, 1), "%d rows are too many for the index stage" % n, indices.device)
@@ -107,9 +140,11 @@ def build_subm_rulebook(indices, spatial_shape, batch_size, kernel_size, check=F
     return book
 
 
-def build_strided_rulebook(indices, spatial_shape, batch_size, kernel_size, stride, padding, cap=None):
+def build_strided_rulebook(indices, spatial_shape, batch_size, kernel_size, stride, padding, cap=None, count=None, status=None):
     """The rulebook of a SparseConv3d.  One host read: the output count and the flag word.  cap: the rows reserved for the
-    output (default: an upper bound that cannot overflow); a count above it raises and nothing is written past it."""
+    output (default: an upper bound that cannot overflow); a count above it raises and nothing is written past it.
+    count (with status): the padded form -- no host read; the output keeps all cap rows, Rulebook.count_out says how many are
+    live, and an overflow keeps the cap smallest keys and sets FLAG_OVERFLOW in *status."""
     _indices_ok(indices)
     k, s, p = _triple(kernel_size, "kernel_size"), _triple(stride, "stride"), _triple(padding, "padding")
     D, H, W = (int(v) for v in spatial_shape)
@@ -132,8 +167,15 @@ def build_strided_rulebook(indices, spatial_shape, batch_size, kernel_size, stri
     out_indices = torch.empty((cap, 4), dtype=I32, device=dev)
     nbr_out = torch.empty((cap, T), dtype=I32, device=dev)
     nbr_in = torch.empty((n, T), dtype=I32, device=dev)
-    stat = torch.empty((2,), dtype=I32, device=dev)
     ws = workspace("pda_spconv_index_workspace_bytes", (n, cap, cands), "%d rows are too many for the index stage" % n, dev)
+    if count is not None:
+        _counted_args(count, status)
+        count_out = torch.empty((1,), dtype=I32, device=dev)
+        _call("pda_spconv_index_strided_counted", indices, indices.data_ptr(), n, count.data_ptr(), int(batch_size), D, H, W, k[0],
+              k[1], k[2], s[0], s[1], s[2], p[0], p[1], p[2], cap, out_indices.data_ptr(), nbr_out.data_ptr(), nbr_in.data_ptr(),
+              count_out.data_ptr(), status.data_ptr(), ws.data_ptr())
+        return Rulebook('spconv', k, s, p, spatial_shape, out_shape, n, out_indices, nbr_out, nbr_in, count_out=count_out)
+    stat = torch.empty((2,), dtype=I32, device=dev)
     _call("pda_spconv_index_strided", indices, indices.data_ptr(), n, int(batch_size), D, H, W, k[0], k[1], k[2], s[0], s[1], s[2],
           p[0], p[1], p[2], cap, out_indices.data_ptr(), nbr_out.data_ptr(), nbr_in.data_ptr(), stat.data_ptr(), ws.data_ptr())
     count, flags = stat.tolist()                                  # the one host read
@@ -233,26 +275,103 @@ def sparse_conv(features, weight, bias, book):
 
 
 class SparseConvTensor:
-    def __init__(self, features, indices, spatial_shape, batch_size, indice_dict=None):
-        """features (N, C) float32, indices (N, 4) int32 (b, z, y, x), spatial_shape (D, H, W)."""
+    def __init__(self, features, indices, spatial_shape, batch_size, indice_dict=None, num_active=None, status=None):
+        """features (N, C) float32, indices (N, 4) int32 (b, z, y, x), spatial_shape (D, H, W).
+        num_active: the padded form -- a device int32 of one element; rows [0, *num_active) are live, the rest dead
+        (indices -1).  status: the int32 word all tensors of one forward share (made here when absent)."""
         self.features = features
         self.indices = indices
         self.spatial_shape = [int(v) for v in spatial_shape]
         self.batch_size = int(batch_size)
         self.indice_dict = {} if indice_dict is None else indice_dict
+        self.num_active = self.status = None
+        self.caps = {}          # padded form: indice_key -> rows reserved for that strided convolution's output
+        if num_active is not None:
+            self.num_active = _count_ok(num_active, "num_active")
+            self.status = torch.zeros((1,), dtype=I32, device=num_active.device) if status is None else _count_ok(status, "status")
+        elif status is not None:
+            raise ValueError("status belongs to a padded tensor: pass num_active too")
 
     def replace_feature(self, feature):
         """A tensor with other features on the same sites (spconv 2.x); the rulebooks are shared."""
-        return SparseConvTensor(feature, self.indices, self.spatial_shape, self.batch_size, self.indice_dict)
+        out = SparseConvTensor(feature, self.indices, self.spatial_shape, self.batch_size, self.indice_dict, self.num_active,
+                               self.status)
+        out.caps = self.caps
+        return out
 
     def dense(self, channels_first=True):
         """(B, C, D, H, W), zero at inactive sites: the pillar scatter over the sites flattened to (b, 0, z * H + y, x)."""
         D, H, W = self.spatial_shape
         idx = self.indices
         flat = torch.stack([idx[:, 0], torch.zeros_like(idx[:, 0]), idx[:, 1] * H + idx[:, 2], idx[:, 3]], dim=1).contiguous()
-        out = pillar_scatter(self.features.contiguous(), flat, self.batch_size, D * H, W)
+        out = pillar_scatter(self.features.contiguous(), flat, self.batch_size, D * H, W, count=self.num_active)
         out = out.view(self.batch_size, self.features.shape[1], D, H, W)
         return out if channels_first else out.permute(0, 2, 3, 4, 1).contiguous()
+
+
+class _CountedBatchNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, count, status, eps, momentum, relu, training):
+        cap, c = x.shape
+        y = torch.empty_like(x)
+        stats = torch.empty((2, c), dtype=F32, device=x.device)
+        scratch = torch.empty((bn_relu_scratch_bytes(c),), dtype=torch.uint8, device=x.device)
+        if training and running_mean is not None:
+            _buffers_written(running_mean)
+        _call("pda_bn_relu_fwd_counted", x, x.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+              None if running_mean is None else running_mean.data_ptr(),
+              None if running_var is None else running_var.data_ptr(), y.data_ptr(), stats.data_ptr(), scratch.data_ptr(), cap, c,
+              float(eps), float(momentum), count.data_ptr(), status.data_ptr(), int(relu), int(training))
+        ctx.save_for_backward(x, weight, bias, stats, count)
+        ctx.flags = (int(relu), int(training))
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, weight, bias, stats, count = ctx.saved_tensors
+        cap, c = x.shape
+        grad = grad.contiguous()
+        g_x = torch.empty_like(x)
+        g_w, g_b = torch.empty_like(weight), torch.empty_like(bias)
+        scratch = torch.empty((bn_relu_scratch_bytes(c),), dtype=torch.uint8, device=x.device)
+        _call("pda_bn_relu_bwd_counted", x, x.data_ptr(), grad.data_ptr(), weight.data_ptr(), bias.data_ptr(), stats.data_ptr(),
+              g_x.data_ptr(), g_w.data_ptr(), g_b.data_ptr(), scratch.data_ptr(), cap, c, count.data_ptr(), ctx.flags[0], ctx.flags[1])
+        return (g_x, g_w, g_b) + (None,) * 8
+
+
+def counted_batch_norm(bn, x, count, status, relu=False):
+    """nn.BatchNorm1d `bn` (+ ReLU) over the live rows [0, *count) of x (cap, C) through pda_bn_relu_*_counted, with the
+    module's own parameters and buffers: batch statistics in training mode (running statistics and num_batches_tracked
+    updated on the device), running statistics in eval mode.  Dead rows of the result and of the gradient are exact zeros.
+    Fewer than two live rows in training mode set FLAG_FEW_ROWS in *status where torch would have raised."""
+    _chk(x, "features", F32)
+    _counted_args(count, status)
+    if x.dim() != 2 or x.shape[1] != bn.num_features:
+        raise ValueError("features %s do not fit BatchNorm1d(%d)" % (tuple(x.shape), bn.num_features))
+    if not bn.affine or bn.momentum is None:
+        raise NotImplementedError("the counted BatchNorm takes an affine module with a fixed momentum")
+    training = bn.training or bn.running_mean is None
+    if training and bn.training and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return _CountedBatchNorm.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, count, status, bn.eps, bn.momentum,
+                                   bool(relu), bool(training))
+
+
+def padded_report(batch_dict_or_tensor):
+    """One host read after a forward of the padded form: ({indice_key or 'input': live rows}, {same: capacity}, status word).
+    For choosing PADDED_CAPS and for checking a run at whatever interval the caller likes (status != 0: see the FLAG_*)."""
+    x = batch_dict_or_tensor
+    if isinstance(x, dict):
+        x = x['encoded_spconv_tensor']
+    if x.num_active is None:
+        raise ValueError("not a padded tensor")
+    books = [(key, b) for key, b in x.indice_dict.items() if b.kind == 'spconv' and b.count_out is not None]
+    first = next((b for b in x.indice_dict.values() if b.kind == 'subm' and b.count_out is not None), None)
+    names = (['input'] if first is not None else []) + [key for key, _ in books]
+    words = ([first.count_out] if first is not None else []) + [b.count_out for _, b in books] + [x.status]
+    host = torch.cat([w.reshape(1) for w in words]).tolist()                # the one host read
+    caps = ([first.n_in] if first is not None else []) + [b.n_out for _, b in books]
+    return dict(zip(names, host[:-1])), dict(zip(names, caps)), host[-1]
 
 
 class SparseModule(nn.Module):
@@ -275,6 +394,8 @@ class SparseSequential(SparseModule):
         return len(self._modules)
 
     def forward(self, input):
+        if isinstance(input, SparseConvTensor) and input.num_active is not None:
+            return self._forward_padded(input)
         for module in self._modules.values():
             if isinstance(module, SparseModule):
                 input = module(input)
@@ -283,6 +404,24 @@ class SparseSequential(SparseModule):
                     input = input.replace_feature(module(input.features))
             else:
                 input = module(input)
+        return input
+
+    def _forward_padded(self, input):
+        """A BatchNorm1d child runs through the counted kernels on the module's own parameters and buffers, with a directly
+        following ReLU folded in; every other child as above (a ReLU keeps the zeros of the dead rows)."""
+        mods = list(self._modules.values())
+        i = 0
+        while i < len(mods):
+            module = mods[i]
+            i += 1
+            if isinstance(module, SparseModule):
+                input = module(input)
+            elif isinstance(module, nn.BatchNorm1d):
+                relu = i < len(mods) and isinstance(mods[i], nn.ReLU)
+                input = input.replace_feature(counted_batch_norm(module, input.features, input.num_active, input.status, relu))
+                i += 1 if relu else 0
+            else:
+                input = input.replace_feature(module(input.features))
         return input
 
 
@@ -326,9 +465,12 @@ class SparseConvolution(SparseModule):
         indices = x.indices if x.indices.dtype == I32 else x.indices.to(I32)
         indices = indices.contiguous()
         if self.subm:
-            book = build_subm_rulebook(indices, x.spatial_shape, x.batch_size, self.kernel_size, check=self.check)
+            book = build_subm_rulebook(indices, x.spatial_shape, x.batch_size, self.kernel_size, check=self.check,
+                                       count=x.num_active, status=x.status)
         else:
-            book = build_strided_rulebook(indices, x.spatial_shape, x.batch_size, self.kernel_size, self.stride, self.padding)
+            book = build_strided_rulebook(indices, x.spatial_shape, x.batch_size, self.kernel_size, self.stride, self.padding,
+                                          cap=x.caps.get(self.indice_key) if x.num_active is not None else None,
+                                          count=x.num_active, status=x.status)
         if self.indice_key is not None:
             x.indice_dict[self.indice_key] = book
         return book
@@ -341,7 +483,10 @@ class SparseConvolution(SparseModule):
         book = self._rulebook(input)
         features = sparse_conv(input.features.contiguous(), self.weight, self.bias, book)
         out_indices = input.indices if self.subm else book.out_indices
-        return SparseConvTensor(features, out_indices, book.out_shape, input.batch_size, input.indice_dict)
+        out = SparseConvTensor(features, out_indices, book.out_shape, input.batch_size, input.indice_dict,
+                               None if input.num_active is None else book.count_out, input.status)
+        out.caps = input.caps
+        return out
 
 
 class SubMConv3d(SparseConvolution):

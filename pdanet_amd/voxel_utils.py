@@ -33,6 +33,33 @@ def collate_voxels(voxels, coords, num_points, num_voxels):
     return vox.contiguous(), crd.contiguous(), num.contiguous()
 
 
+def collate_voxels_padded(voxels, coords, num_points, num_voxels):
+    """collate_voxels without the cut and without the host read: the same inputs -> voxels (B * max_voxels, P, C),
+    voxel_coords (B * max_voxels, 4) int32, voxel_num_points (B * max_voxels) int32, num_active (1) int32, status (1) int32.
+    The live rows come first, scene after scene, and equal collate_voxels' rows exactly (the counts clamped the same way);
+    num_active is their number.  Dead rows: voxels 0, coordinates -1, num_points 0.  status is the zeroed flag word of the
+    padded sparse tensors: the batch's voxel_num_active / voxel_status.
+    A stable partition by index arithmetic (two scans and one indexed copy per tensor); nothing is read back."""
+    _chk(voxels, "voxels", F32)
+    _chk(coords, "coords", torch.int32)
+    _chk(num_points, "num_points", torch.int32)
+    _chk(num_voxels, "num_voxels", torch.int32)
+    B, cap = num_points.shape
+    dev = voxels.device
+    rows = B * cap
+    live = (torch.arange(cap, device=dev, dtype=torch.int32)[None, :] < num_voxels.clamp(0, cap)[:, None]).reshape(rows)
+    before = live.cumsum(0)                                               # live rows up to and including this one
+    total = before[-1:] if rows else before.new_zeros((1,))
+    row = torch.arange(rows, device=dev)
+    dest = torch.where(live, before - 1, total + (row - before))         # a permutation: the live rows first, both parts in order
+    batch = torch.arange(B, device=dev, dtype=torch.int32)[:, None, None].expand(B, cap, 1)
+    crd = torch.where(live[:, None], torch.cat([batch, coords], dim=2).reshape(rows, 4), coords.new_full((), -1))
+    vox = torch.where(live[:, None, None], voxels.reshape((rows,) + tuple(voxels.shape[2:])), voxels.new_zeros(()))
+    num = torch.where(live, num_points.reshape(rows), num_points.new_zeros(()))
+    out = [torch.empty_like(t).index_copy_(0, dest, t) for t in (vox, crd, num)]
+    return out[0], out[1], out[2], total.to(torch.int32), torch.zeros((1,), dtype=torch.int32, device=dev)
+
+
 class VoxelSpec:
     """The host-side arguments of the voxel entries: range, voxel size and grid as C arrays."""
 
