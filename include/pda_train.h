@@ -1248,6 +1248,63 @@ int pda_roipoint_pool3d_canonical_fwd(const float *xyz, const float *scores, con
                                       const float *extra, float depth_normalizer, float *pooled, int32_t *empty_flag,
                                       int batch, int points, int boxes, int channels, int sampled, pda_stream_t stream);
 
+/* ---- Part-A2 (csrc/parta2.hip): the point head's targets and part loss.
+ * pda_part_assign_targets: PointHeadTemplate.assign_stack_targets(set_ignore_flag=True, ret_part_labels=True)
+ *   (point_head_template.py:49-129) for a ragged stacked point set in one launch.  points (n_points, 4) [batch, x, y, z], any
+ *   number of rows per scene in any order; gt_boxes (b, t, 8) [x, y, z, dx, dy, dz, heading, class]; extra_width: 3 host floats
+ *   -> labels (n_points) int64 and part_labels (n_points, 3), every entry written.  The box test is pda_points_in_boxes's
+ *   (margin 1e-5, lowest box index first); a point inside a box gets 1 (single_class) or the box's class, and
+ *   part = rotate_z(p - centre, -heading) / (dx, dy, dz) + 0.5 in float32 (cosf / sinf of the negated heading, no FMA); a point
+ *   inside none but inside a box enlarged by extra_width (float32 additions to the extents) gets -1; everything else 0; part
+ *   labels are 0 wherever the label is not positive.  A batch value that is not a number, not an integer or outside [0, b)
+ *   names no scene: label 0.  points and gt_boxes 16-byte aligned.
+ * pda_part_loss: get_part_layer_loss (:157-170).  logits, part_labels (n_points, 3), labels (n_points) int64 ->
+ *   out[0] = weight * sum over rows with label > 0 and their 3 columns of bce / (3 * max(1, #pos)), out[1] = weight / (3 *
+ *   max(1, #pos)), out[2] = #pos; grad (n_points, 3) = d bce / d logit, zeros in the other rows, so that the logit gradient is
+ *   out[1] * grad.  bce = -(t * max(log p, -100) + (1 - t) * max(log(1 - p), -100)), p = sigmoid(logit), evaluated in float64 per
+ *   element; the labels are taken as they are.  partials: 2 * pda_part_loss_blocks(n_points) doubles (-1 for a bad size); sums
+ *   in float64 in one fixed order, no float atomics, nothing read back. */
+int pda_part_assign_targets(const float *points, const float *gt_boxes, const float *extra_width, int64_t *labels,
+                            float *part_labels, int64_t n_points, int b, int t, int single_class, pda_stream_t stream);
+int64_t pda_part_loss_blocks(int64_t n_points);
+int pda_part_loss(const float *logits, const float *part_labels, const int64_t *labels, double weight, float *grad,
+                  double *partials, float *out, int64_t n_points, pda_stream_t stream);
+
+/* The input stage of PartA2FCHead (partA2_head.py:104-197; csrc/parta2.hip) for the whole batch: scene segments, ONE collection
+ * pass, both poolings and the sparse rows of the live voxels.  rois (b * rois_per_scene, 7), point_coords (n_points, 4)
+ * [batch, x, y, z] SCENE-MAJOR, out the pool size (1..16: out^3 voxel counters live in LDS), k_slots MAX_POINTS_PER_VOXEL;
+ * rois_total * out^3 < 2^31.  Integer work decides every position: two runs give the same bits.
+ * pda_parta2_pool_segments: seg (b + 1) int32, seg[s] = the first row whose batch value is not below s.  flag, when given (one
+ *   int32, zeroed by the caller), gets bit 0 set if the batch column is not ascending or holds a value that names no scene.
+ * pda_parta2_pool_collect: table (rois_total, out^3, k_slots) int32, NOT filled by the caller: slot 0 of every voxel is written
+ *   (the number of points kept, at most k_slots - 1) and slots 1..count hold the first points of the RoI's scene that fall into
+ *   the voxel, as GLOBAL rows in ascending order -- the rules of pda_roiaware_pool3d_fwd's collection (csrc/roi_pool_core.h).
+ * pda_parta2_pool_sparsify: part channels of point p: part_src[p * src_stride + src_offset + (0..2)] where scores[p] >= thresh
+ *   (more exactly: not below it) and 0 elsewhere, and scores[p]; a voxel's four values are their float32 sums in slot order over
+ *   (float)count, as pool_method avg gives them.  A voxel is live iff ((v0 + v1) + v2) + v3 in float32 is not +-0.  Writes
+ *   *n_live and, for the live voxels in ascending (roi, x, y, z): coords (.., 4) int32 [roi, x, y, z], part_rows (.., 4),
+ *   live_vox (..) = roi * out^3 + (x * out + y) * out + z.  The three buffers hold rois_total * out^3 rows (the worst case);
+ *   rows from *n_live on are not written.  workspace: pda_parta2_pool_workspace_bytes (-1 for bad sizes), 16-byte aligned.
+ * pda_parta2_pool_features: feat_rows (.., channels) = the largest point_features[p][c] over the slots of live voxel e (ties keep
+ *   the lower slot, NaN never wins, 0 when nothing wins) and arg_rows its row or -1, as pool_method max; *n_live is read on the
+ *   device and the rows from it on are not written.
+ * pda_parta2_pool_bwd: grad_features[arg_rows[e][c]][c] += grad_feat_rows[e][c] and, for ch < 3 and every slot p of live voxel e
+ *   with scores[p] >= thresh, grad_offset[p][ch] += grad_part_rows[e][ch] / count, both with float atomics into buffers the
+ *   caller zero-filled ((n_points, channels) and (n_points, 3)); either gradient may be NULL.  n_live is the host's count. */
+int64_t pda_parta2_pool_workspace_bytes(int64_t rois_total, int out);
+int pda_parta2_pool_segments(const float *point_coords, int64_t n_points, int b, int32_t *seg, int32_t *flag, pda_stream_t stream);
+int pda_parta2_pool_collect(const float *rois, const float *point_coords, const int32_t *seg, int32_t *table, int b,
+                            int rois_per_scene, int64_t n_points, int out, int k_slots, pda_stream_t stream);
+int pda_parta2_pool_sparsify(const int32_t *table, const float *part_src, int src_stride, int src_offset, const float *scores,
+                             float thresh, void *workspace, int32_t *n_live, int32_t *coords, float *part_rows, int32_t *live_vox,
+                             int64_t rois_total, int64_t n_points, int out, int k_slots, pda_stream_t stream);
+int pda_parta2_pool_features(const float *point_features, const int32_t *table, const int32_t *live_vox, const int32_t *n_live,
+                             float *feat_rows, int32_t *arg_rows, int64_t rois_total, int64_t n_points, int channels, int out,
+                             int k_slots, pda_stream_t stream);
+int pda_parta2_pool_bwd(const int32_t *table, const int32_t *live_vox, const int32_t *arg_rows, const float *scores, float thresh,
+                        const float *grad_part_rows, const float *grad_feat_rows, float *grad_offset, float *grad_features,
+                        int64_t n_live, int64_t n_points, int channels, int k_slots, pda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

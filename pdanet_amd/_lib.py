@@ -275,6 +275,15 @@ SIGNATURES = {
     "pda_bev_interpolate_bwd": [_vp] * 5 + [_i] * 5 + [_vp],
     "pda_bev_roi_grid_pool": [_vp] * 3 + [_i] * 6 + [_f] * 4 + [_vp],
     "pda_roipoint_pool3d_canonical_fwd": [_vp] * 4 + [ctypes.POINTER(_f), _f, _vp, _vp] + [_i] * 5 + [_vp],
+    "pda_part_assign_targets": [_vp, _vp, ctypes.POINTER(_f), _vp, _vp, ctypes.c_int64, _i, _i, _i, _vp],
+    "pda_part_loss_blocks": [ctypes.c_int64],
+    "pda_part_loss": [_vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp, ctypes.c_int64, _vp],
+    "pda_parta2_pool_workspace_bytes": [ctypes.c_int64, _i],
+    "pda_parta2_pool_segments": [_vp, ctypes.c_int64, _i, _vp, _vp, _vp],
+    "pda_parta2_pool_collect": [_vp, _vp, _vp, _vp, _i, _i, ctypes.c_int64, _i, _i, _vp],
+    "pda_parta2_pool_sparsify": [_vp, _vp, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, _vp],
+    "pda_parta2_pool_features": [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, _i, _vp],
+    "pda_parta2_pool_bwd": [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, _vp],
     # include/pda_pointnet2_stack.h
     "pda_stack_ball_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     "pda_stack_group_points": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -303,7 +312,7 @@ SIZE_QUERIES = [
     "pda_voxel_workspace_bytes", "pda_dyn_voxel_workspace_bytes", "pda_center_focal_blocks", "pda_anchor_loss_blocks",
     "pda_anchor_multi_loss_blocks",
     "pda_spconv_index_workspace_bytes", "pda_spconv_wgrad_workspace_bytes", "pda_voxel_pool_scratch_doubles",
-    "pda_stack_sa_scratch_doubles"]
+    "pda_stack_sa_scratch_doubles", "pda_part_loss_blocks", "pda_parta2_pool_workspace_bytes"]
 INFO_SYMBOLS = ["pda_abi_version", "pda_last_error", "pda_fp_contract_mode", "pda_opt_n_threads",
                 "pda_fps_coop_timeouts", "pda_debug_fps_spin_limit", "pda_debug_fps_exchange_nonzero"]
 

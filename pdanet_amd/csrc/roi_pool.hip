@@ -15,37 +15,13 @@
 // voxels and puts the channel on the lane axis, so feature rows and output rows are read and written whole.
 #include "pda_common.h"
 #include "box_rec.h"
+#include "roi_pool_core.h"
 
 namespace pda {
 
-constexpr int ROI_TILE = 256;
-constexpr int ROI_LDS_VOX = 4096;                  // 16 KB of counters: up to 16^3 voxels
 constexpr int ROIPOINT_MAX_S = 15360;              // 60 KB of sampled indices
 
-__device__ __forceinline__ uint64_t lanes_below() { return (1ull << lane_id()) - 1ull; }
-
-// the reference's index expression (roiaware_pool3d_kernel.cu:60-70): float32 operations, truncation, UNSIGNED clamp
-// (a negative index lands in the last voxel)
-__device__ __forceinline__ int roi_voxel_axis(float local, float d, int out) {
-    const float res = d / (float)out;
-    const unsigned int idx = (unsigned int)(int)((local + d / 2) / res);
-    return (int)min(idx, (unsigned int)(out - 1));
-}
-
-// exclusive prefix of this wave over the workgroup's four ballot counts, and their total
-__device__ __forceinline__ int roi_wave_prefix(const int* wave_cnt, int wave, int& total) {
-    int off = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < ROI_TILE / 64; ++w) {
-        const int c = wave_cnt[w];
-        off += w < wave ? c : 0;
-        sum += c;
-    }
-    total = sum;
-    return off;
-}
-
-// ---- roiaware_pool3d: collect ------------------------------------------------------------------------------------------
+// ---- roiaware_pool3d: collect (the walk: roi_pool_core.h) ------------------------------------------------------------------
 template <bool LDS_CNT>
 __global__ __launch_bounds__(256) void roiaware_collect_kernel(const float* __restrict__ rois, const float* __restrict__ pts,
                                                                int* __restrict__ pts_idx, int pts_num, int out_x, int out_y,
@@ -53,77 +29,12 @@ __global__ __launch_bounds__(256) void roiaware_collect_kernel(const float* __re
     __shared__ int cnt[LDS_CNT ? ROI_LDS_VOX : 1];
     __shared__ int hit_vox[ROI_TILE];
     __shared__ int wave_cnt[2][ROI_TILE / 64];
-    const int tid = threadIdx.x, lane = lane_id(), wave = wave_id();
-    const float* b = rois + (size_t)blockIdx.x * 7;
-    const float dx = b[3], dy = b[4], dz = b[5];
-    const BoxRec rec = make_box_rec(b[0], b[1], b[2], dx, dy, dz, b[6], (double)1e-5f);
-    const int n_vox = out_x * out_y * out_z, cap = k_slots - 1;
-    int* mine = pts_idx + (size_t)blockIdx.x * n_vox * k_slots;
-    if (LDS_CNT) {
-        for (int v = tid; v < n_vox; v += ROI_TILE) cnt[v] = 0;
-    }
-    __syncthreads();
-    int it = 0;
-    for (int t0 = 0; t0 < pts_num; t0 += ROI_TILE, it ^= 1) {
-        const int pt = t0 + tid;
-        bool hit = false;
-        int vox = 0;
-        if (pt < pts_num) {
-            const float x = pts[(size_t)pt * 3 + 0], y = pts[(size_t)pt * 3 + 1], z = pts[(size_t)pt * 3 + 2];
-            float lx = 0.f, ly = 0.f;
-            hit = in_box_rec_local<PDA_FP_CONTRACT != 0>(rec, x, y, z, lx, ly);
-            if (hit) {
-                const int xi = roi_voxel_axis(lx, dx, out_x), yi = roi_voxel_axis(ly, dy, out_y);
-                const int zi = roi_voxel_axis(z - rec.cz, dz, out_z);
-                vox = (xi * out_y + yi) * out_z + zi;
-            }
-        }
-        const uint64_t mask = __ballot(hit);
-        if (lane == 0) wave_cnt[it][wave] = __popcll(mask);
-        __syncthreads();                           // wave_cnt[it] is next written two tiles on, behind the next barrier
-        int n_hits;
-        const int pos = roi_wave_prefix(wave_cnt[it], wave, n_hits) + __popcll(mask & lanes_below());
-        if (n_hits == 0) continue;                 // workgroup-uniform
-        if (hit) hit_vox[pos] = vox;
-        __syncthreads();
-        int rank = 0, total = 0, base = 0;
-        if (hit) {
-            for (int j = 0; j < n_hits; ++j) {
-                const int same = hit_vox[j] == vox;
-                rank += same & (int)(j < pos);
-                total += same;
-            }
-            base = LDS_CNT ? cnt[vox] : mine[(size_t)vox * k_slots];
-        }
-        __syncthreads();                           // every counter is read before any is moved
-        if (hit) {
-            const int slot = base + rank;
-            if (slot < cap) mine[(size_t)vox * k_slots + 1 + slot] = pt;
-            if (rank == 0) {
-                const int moved = min(base + total, cap);
-                if (LDS_CNT) cnt[vox] = moved;
-                else mine[(size_t)vox * k_slots] = moved;
-            }
-        }
-        // the next tile reads the counters behind its own two barriers; hit_vox is rewritten behind its first
-    }
-    if (LDS_CNT) {
-        __syncthreads();
-        for (int v = tid; v < n_vox; v += ROI_TILE) {
-            const int c = cnt[v];
-            if (c > 0) mine[(size_t)v * k_slots] = c;
-        }
-    }
+    int* mine = pts_idx + (size_t)blockIdx.x * (out_x * out_y * out_z) * k_slots;
+    roi_collect_walk<LDS_CNT, false>(rois + (size_t)blockIdx.x * 7, pts, 3, 0, pts_num, mine, out_x, out_y, out_z, k_slots, cnt,
+                                     hit_vox, wave_cnt);
 }
 
 // ---- roiaware_pool3d: pool -----------------------------------------------------------------------------------------------
-// total order of the non-NaN floats as signed integers, -0 == +0 (the file is built with -fno-honor-nans, so the strict
-// `>` that NaN must lose is not left to a float compare)
-__device__ __forceinline__ int roi_order_key(uint32_t bits) {
-    if (bits == 0x80000000u) bits = 0u;
-    return (int)(bits ^ ((uint32_t)((int)bits >> 31) & 0x7fffffffu));
-}
-
 // A wave takes 64 consecutive voxels of one box: it reads their counters, compacts the non-empty ones, and groups of
 // 2^wlog lanes (the channels of one voxel) pool them.  Shared by the forward (POOL 0 max, 1 avg) and the avg backward (2).
 template <int MODE>
@@ -138,7 +49,7 @@ __global__ __launch_bounds__(256) void roiaware_pool_kernel(const float* __restr
     const size_t box_vox = (size_t)blockIdx.x * n_vox;
     const int v = v_base + lane;
     int c = v < n_vox ? pts_idx[(box_vox + v) * k_slots] : 0;
-    c = min(max(c, 0), k_slots - 1);
+    c = roi_slot_count(c, k_slots);
     s_cnt[wave][lane] = c;
     const uint64_t mask = __ballot(c > 0);
     const int nnz = __popcll(mask);
@@ -159,33 +70,16 @@ __global__ __launch_bounds__(256) void roiaware_pool_kernel(const float* __restr
         const int* idx = pts_idx + vox * k_slots;
         for (int ch = j0; ch < channels; ch += gw) {
             if (MODE == 0) {
-                int best_key = roi_order_key(0xff800000u), arg = -1;      // -inf: strict > never takes -inf itself
-                uint32_t best_bits = 0;
-                for (int k = 1; k <= n; ++k) {
-                    const int p = idx[k];
-                    if (p < 0 || p >= pts_num) continue;
-                    const uint32_t bits = __float_as_uint(feat[(size_t)p * channels + ch]);
-                    const bool is_nan = (bits & 0x7fffffffu) > 0x7f800000u;
-                    const int key = roi_order_key(bits);
-                    if (!is_nan && key > best_key) { best_key = key; best_bits = bits; arg = p; }
-                }
+                uint32_t best_bits;
+                const int arg = roi_slot_max(feat, idx, n, pts_num, channels, ch, best_bits);
                 if (arg != -1) pooled[vox * channels + ch] = __uint_as_float(best_bits);
                 argmax[vox * channels + ch] = arg;
             } else if (MODE == 1) {
-                float sum = 0.f;
-                for (int k = 1; k <= n; ++k) {
-                    const int p = idx[k];
-                    if (p < 0 || p >= pts_num) continue;
-                    sum += feat[(size_t)p * channels + ch];
-                }
+                const float sum = roi_slot_sum(idx, n, pts_num, [&](int p) { return feat[(size_t)p * channels + ch]; });
                 pooled[vox * channels + ch] = sum / (float)n;
             } else {
-                const float g = grad_out[vox * channels + ch] * (1 / fmaxf((float)n, 1.0f));
-                for (int k = 1; k <= n; ++k) {
-                    const int p = idx[k];
-                    if (p < 0 || p >= pts_num) continue;
-                    atomicAdd(grad_in + (size_t)p * channels + ch, g);
-                }
+                roi_slot_avg_grad(idx, n, pts_num, grad_out[vox * channels + ch],
+                                  [&](int p, float g) { atomicAdd(grad_in + (size_t)p * channels + ch, g); });
             }
         }
     }
@@ -196,11 +90,7 @@ __global__ __launch_bounds__(256) void roiaware_max_grad_kernel(const int* __res
                                                                 const float* __restrict__ grad_out,
                                                                 float* __restrict__ grad_in, int pts_num, int channels,
                                                                 size_t total) {
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const int p = argmax[e];
-        if (p < 0 || p >= pts_num) continue;
-        atomicAdd(grad_in + (size_t)p * channels + e % channels, grad_out[e]);
-    }
+    roi_max_grad(argmax, grad_out, grad_in, pts_num, channels, total);
 }
 
 // ---- roipoint_pool3d -------------------------------------------------------------------------------------------------------

@@ -33,11 +33,15 @@ def class_agnostic_nms_batched(box_scores, box_preds, nms_config, score_thresh=N
     valid = ok if valid is None else ok & valid
     masked = torch.where(valid, box_scores, torch.full_like(box_scores, float("-inf")))
     sorted_scores, order = masked.sort(dim=1, descending=True)
-    num_valid = valid.sum(dim=1).clamp(max=int(nms_config["NMS_PRE_MAXSIZE"])).to(torch.int32)
-    boxes = torch.gather(box_preds[..., 0:7], 1, order.unsqueeze(-1).expand(B, N, 7)).contiguous()
+    pre = int(nms_config["NMS_PRE_MAXSIZE"])
+    num_valid = valid.sum(dim=1).clamp(max=pre).to(torch.int32)
+    K = min(N, int(nms_config["NMS_POST_MAXSIZE"]))
+    # the NMS looks at the first num_valid <= NMS_PRE_MAXSIZE rows of the ranking only: the rest is not handed to it (the anchors
+    # of a full KITTI grid, 211 200 a scene, are more than one call takes)
+    width = min(N, max(pre, K))
+    boxes = torch.gather(box_preds[..., 0:7], 1, order[:, :width].unsqueeze(-1).expand(B, width, 7)).contiguous()
     keep, num_keep = iou3d_nms_utils.nms_batched(boxes, nms_config["NMS_THRESH"], num_valid=num_valid,
                                                  normal=nms_config["NMS_TYPE"] == "nms_normal_gpu")
-    K = min(N, int(nms_config["NMS_POST_MAXSIZE"]))
     keep = keep[:, :K]
     ok = keep >= 0
     safe = keep.clamp(min=0)

@@ -14,8 +14,8 @@ The one departure from the reference: tb_dict values (point_loss_cls, point_loss
 where the reference calls .item().  The per-point loss terms are added in float64 (one deterministic torch reduction) and the sum is
 rounded to float32 once, as this project's loss kernels do (csrc/loss_sums.h); the reference adds them in float32.
 
-Out of scope (NotImplementedError): ret_part_labels, use_ball_constraint -- PointIntraPartOffsetHead needs them, PointHeadSimple
-and PointHeadBox do not."""
+Refused here (NotImplementedError): ret_part_labels, use_ball_constraint -- PointHeadSimple and PointHeadBox need neither;
+PointIntraPartOffsetHead (part_head.py) assigns its part labels with a kernel of its own."""
 import torch
 import torch.nn as nn
 

@@ -4,7 +4,7 @@ loads with strict=True.  The batch carries `points` (B * N, 1 + 3 + C) [bs_idx, 
 many rows per scene, and `gt_boxes` (B, M, 8) in training.  Training returns ({'loss': loss_point + loss_rcnn}, tb_dict with the
 point_* and rcnn_* entries, disp_dict); eval returns (pred_dicts, recall_dict) with the labels of the first stage's RoIs.
 
-Out of scope: PointIntraPartOffsetHead, PointNet2Backbone (the reference asserts it off)."""
+Out of scope: PointNet2Backbone (the reference asserts it off); PointIntraPartOffsetHead belongs to PartA2Net (part_a2_net.py)."""
 from .detector3d_template import PointDetector
 from .point_head import PointHeadBox
 from .pointnet2_backbone import PointNet2MSG

@@ -5,7 +5,7 @@ checkpoint loads with strict=True.  The batch carries `points` (N, 1 + 3 + C) [b
 the voxels.  Training returns ({'loss': loss_rpn + loss_point + loss_rcnn}, tb_dict with the rpn_*, point_* and rcnn_*
 entries, disp_dict); eval returns (pred_dicts, recall_dict) with the labels of the first stage's RoIs.
 
-Out of scope: PV-RCNN++ (SPC sampling, VectorPoolAggregationModuleMSG), PointIntraPartOffsetHead."""
+Out of scope: PV-RCNN++ (SPC sampling, VectorPoolAggregationModuleMSG); PointIntraPartOffsetHead belongs to PartA2Net."""
 from .anchor_head import AnchorHeadSingle
 from .detector3d_template import VoxelDetector
 from .mean_vfe import MeanVFE

@@ -1,6 +1,7 @@
 """Sparse 3D convolution on the device under the names the reference uses (pcdet/utils/spconv_utils.py and the part of
 spconv 2.x that pcdet's voxel backbones touch): SparseConvTensor, SparseModule, SparseSequential, SubMConv3d, SparseConv3d,
-replace_feature and find_all_spconv_keys (SparseInverseConv3d and SparseConvTranspose3d exist to refuse).  spconv itself is not a dependency; the contract is DESIGN.md section 7.
+replace_feature and find_all_spconv_keys (SparseConvTranspose3d exists to refuse, and so does SparseInverseConv3d under this
+name: the inverse convolution is spconv_unet.SparseInverseConv3d).  spconv itself is not a dependency; the contract is DESIGN.md section 7.
 
 A convolution is two stages.  The index stage (csrc/sparse_conv_index.hip) reads coordinates only and leaves a Rulebook: the
 output sites and, per (row, tap), the row read (nbr_out) and, for a strided convolution, the row written (nbr_in).  A
@@ -72,11 +73,13 @@ def _raise_on_flags(flags, what):
 
 class Rulebook:
     """What the index stage leaves for one (input sites, kernel, stride, padding): out_indices (n_out, 4), spatial shape of
-    the output, nbr_out (n_out, T), nbr_in (n_in, T) or None for a submanifold convolution (nbr_out with mirrored taps)."""
+    the output, nbr_out (n_out, T), nbr_in (n_in, T) or None for a submanifold convolution (nbr_out with mirrored taps).
+    in_indices: the input sites (n_in, 4) of a strided book built by a layer -- what spconv_unet.SparseInverseConv3d returns to."""
 
     def __init__(self, kind, kernel_size, stride, padding, in_shape, out_shape, n_in, out_indices, nbr_out, nbr_in,
                  count_out=None):
         self.count_out = count_out          # padded form: device int32 (1), the live output rows; n_out is then the capacity
+        self.in_indices = None
         self.kind, self.kernel_size, self.stride, self.padding = kind, kernel_size, stride, padding
         self.in_shape, self.out_shape, self.n_in = list(in_shape), list(out_shape), n_in
         self.out_indices, self.nbr_out, self.nbr_in = out_indices, nbr_out, nbr_in
@@ -471,6 +474,7 @@ class SparseConvolution(SparseModule):
             book = build_strided_rulebook(indices, x.spatial_shape, x.batch_size, self.kernel_size, self.stride, self.padding,
                                           cap=x.caps.get(self.indice_key) if x.num_active is not None else None,
                                           count=x.num_active, status=x.status)
+            book.in_indices = indices
         if self.indice_key is not None:
             x.indice_dict[self.indice_key] = book
         return book
@@ -503,7 +507,8 @@ class SparseConv3d(SparseConvolution):
 
 class SparseInverseConv3d(SparseModule):
     def __init__(self, *args, **kwargs):
-        raise NotImplementedError("SparseInverseConv3d is not implemented (UNetV2 / PartA2 are out of scope)")
+        raise NotImplementedError("spconv_utils.SparseInverseConv3d refuses: the inverse convolution is "
+                                  "pdanet_amd.spconv_unet.SparseInverseConv3d (UNetV2 builds it there)")
 
 
 class SparseConvTranspose3d(SparseModule):
