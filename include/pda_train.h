@@ -126,6 +126,41 @@ int pda_linear_wgrad_bn(const float *x, const float *grad_out, float *grad_weigh
                         int64_t tokens, int in_features, int out_features, const float *x_mean_invstd,
                         const float *x_gamma, const float *x_beta, pda_stream_t stream);
 
+/* ---- parameter gradients finished later: first stages alone, one grouped second stage (MI355X extension) -------
+ * The second stage of pda_linear_wgrad (the fixed-order sum of the split-K partials) and of pda_layer_norm_bwd (the sum
+ * of the per-block dgamma / dbeta partials) is a few workgroups of load latency, and nothing but the optimizer reads what
+ * it writes.  A caller may therefore run the first stages alone and finish many gradients with one launch:
+ * pda_linear_wgrad_partials / pda_linear_wgrad_bn_partials: the first stage of pda_linear_wgrad / pda_linear_wgrad_bn on
+ * the same operands; scratch (pda_linear_wgrad_scratch_bytes) keeps part_w [S][out * in] and, with want_bias, part_b
+ * [S][out] from float offset S * out * in; *slices = S (written on the host).
+ * pda_layer_norm_bwd_partials: pda_layer_norm_bwd[_mixed] without its last launch: grad_x [and grad_x_bf16] are written,
+ * scratch (pda_layer_norm_scratch_bytes) keeps the [nblocks][2][d] partials, *nblocks is written on the host.
+ * pda_param_grad_reduce_grouped: n >= 1 entries (a host array, passed on as kernel arguments: no allocation, no copy, no
+ * synchronisation; capturable; 48 entries per launch, more entries take more launches), each finished by the workgroups
+ * and the order of additions of its per-problem kernel -- the same bits.
+ *   kind 0, weight gradient: part = part_w, part_bias = part_b, count = S, nm = out * in, n = out, cols = in;
+ *     dst (out rows of `cols` floats, `ld` >= cols floats apart: ld > cols writes a column block of a wider matrix),
+ *     dst_bias (out) or NULL;
+ *   kind 1, LayerNorm: part = the partials, count = nblocks, n = d, dst = grad_gamma, dst_bias = grad_beta (both d).
+ * The partials must stay untouched until the grouped launch has run (stream order). */
+typedef struct pda_param_grad_entry {
+    int32_t kind, count;
+    const float *part, *part_bias;
+    float *dst, *dst_bias;
+    int64_t nm;
+    int32_t n, cols;
+    int64_t ld;
+} pda_param_grad_entry_t;
+int pda_linear_wgrad_partials(const float *x, const float *grad_out, void *scratch, int want_bias, int64_t tokens,
+                              int in_features, int out_features, int *slices, pda_stream_t stream);
+int pda_linear_wgrad_bn_partials(const float *x, const float *grad_out, void *scratch, int64_t tokens, int in_features,
+                                 int out_features, const float *x_mean_invstd, const float *x_gamma,
+                                 const float *x_beta, int *slices, pda_stream_t stream);
+int pda_layer_norm_bwd_partials(const float *x, const float *grad_y, const void *grad_y2, int grad_y2_is_bf16,
+                                const float *gamma, const float *mean_rstd, float *grad_x, uint16_t *grad_x_bf16,
+                                void *scratch, int64_t rows, int d, int *nblocks, pda_stream_t stream);
+int pda_param_grad_reduce_grouped(const pda_param_grad_entry_t *entries, int n, pda_stream_t stream);
+
 /* ---- a [conv1x1 -> BatchNorm(batch statistics) -> ReLU] chain with the BatchNorm passes folded into the contractions
  * (MI355X extension; the group MLP of pointnet2_modules.py:1657-1662 in training).
  * pda_gemm_split_bn: y (tokens, n_out) = X' W^T on the 256 x 256 tile split-bf16 kernel (wf = pda_linear_split_pack planes,

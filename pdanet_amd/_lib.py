@@ -39,6 +39,13 @@ class KittiFrames(ctypes.Structure):
                 ("n_frames", ctypes.c_int), ("max_gt", ctypes.c_int), ("max_det", ctypes.c_int)]
 
 
+class ParamGradEntry(ctypes.Structure):
+    """pda_param_grad_entry_t (include/pda_train.h)."""
+    _fields_ = [("kind", ctypes.c_int32), ("count", ctypes.c_int32), ("part", ctypes.c_void_p), ("part_bias", ctypes.c_void_p),
+                ("dst", ctypes.c_void_p), ("dst_bias", ctypes.c_void_p), ("nm", ctypes.c_int64), ("n", ctypes.c_int32),
+                ("cols", ctypes.c_int32), ("ld", ctypes.c_int64)]
+
+
 # The two epochs of param_cache.py (which explains them and owns every read and write inside the package).
 PARAM_EPOCH = [0]
 WEIGHT_EPOCH = [0]
@@ -105,6 +112,10 @@ SIGNATURES = {
     "pda_linear_wgrad_form": [ctypes.c_int64, _i, _i],
     "pda_linear_wgrad": [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _i, _i, _vp],
     "pda_linear_wgrad_bn": [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _i, _i, _vp, _vp, _vp, _vp],
+    "pda_linear_wgrad_partials": [_vp, _vp, _vp, _i, ctypes.c_int64, _i, _i, ctypes.POINTER(_i), _vp],
+    "pda_linear_wgrad_bn_partials": [_vp, _vp, _vp, ctypes.c_int64, _i, _i, _vp, _vp, _vp, ctypes.POINTER(_i), _vp],
+    "pda_layer_norm_bwd_partials": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _i, ctypes.POINTER(_i), _vp],
+    "pda_param_grad_reduce_grouped": [ctypes.POINTER(ParamGradEntry), _i, _vp],
     "pda_gemm_split_bn_tiles": [ctypes.c_int64],
     "pda_gemm_split_bn": [_vp, _vp, _vp, ctypes.c_int64, _i, _i, _vp, _vp, _vp, _i, _vp, _vp],
     "pda_gemm_split_maxpool": [_vp, _vp, _vp, _vp, ctypes.c_int64, _i, _i, _i, _i, _vp],

@@ -7,6 +7,7 @@
 // every lane keeps running sums of dy and dy*xhat for its own columns, reduced over the block in LDS and
 // written as per-block partials that a small second kernel adds in fixed order (deterministic).
 #include "pda_common.h"
+#include "param_grad_reduce.h"
 
 namespace pda {
 
@@ -128,34 +129,12 @@ __global__ __launch_bounds__(256) void layer_norm_bwd_kernel(const float* __rest
     }
 }
 
-// dbeta / dgamma = sum of the per-block partials; 64 columns x 16 slices per block of 1024 threads
+// dbeta / dgamma = sum of the per-block partials; 64 columns x 16 slices per block of 1024 threads (csrc/param_grad_reduce.h:
+// the body is shared with the grouped kernel)
 __global__ __launch_bounds__(1024) void layer_norm_finalize_kernel(const float* __restrict__ partial, int nblocks, int d,
                                                                    float* __restrict__ dgamma, float* __restrict__ dbeta) {
     __shared__ float red[2][16][64];
-    const int cl = threadIdx.x & 63, part = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cl;
-    float a = 0.f, b = 0.f;
-    if (c < d) {
-        float va[8], vb[8];
-        for (int k0 = part; k0 < nblocks; k0 += 16 * 8) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int k = k0 + 16 * u;
-                va[u] = k < nblocks ? partial[((size_t)k * 2 + 0) * d + c] : 0.f;
-                vb[u] = k < nblocks ? partial[((size_t)k * 2 + 1) * d + c] : 0.f;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { a += va[u]; b += vb[u]; }
-        }
-    }
-    red[0][part][cl] = a; red[1][part][cl] = b;
-    __syncthreads();
-    if (part != 0 || c >= d) return;
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int p = 0; p < 16; ++p) { s1 += red[0][p][cl]; s2 += red[1][p][cl]; }
-    dbeta[c] = s1;
-    dgamma[c] = s2;
+    layer_norm_finalize_block(partial, nblocks, d, dgamma, dbeta, (int)blockIdx.x, red);
 }
 
 static int ln_grid(int64_t rows) {
@@ -192,10 +171,11 @@ static int launch_layer_norm_fwd(const TX* x, const float* residual, const float
 template <typename T2>
 static int launch_layer_norm_bwd(const float* x, const float* grad_y, const T2* grad_y2, const float* gamma, const float* mean_rstd,
                                  float* grad_x, bf16_t* grad_x_b, float* grad_gamma, float* grad_beta, void* scratch, int64_t rows, int d,
-                                 hipStream_t st, const char* what) {
+                                 hipStream_t st, const char* what, int* nblocks_out = nullptr) {
     PDA_REQUIRE(rows >= 1, "%s: rows = %lld", what, (long long)rows);
     PDA_REQUIRE(d == 256 || d == 512 || d == 1024, "%s: D = %d (256, 512 or 1024)", what, d);
-    PDA_REQUIRE(x && grad_y && gamma && mean_rstd && grad_x && grad_gamma && grad_beta && scratch, "%s: null pointer", what);
+    // nblocks_out: the first stage alone -- the partials stay in scratch for pda_param_grad_reduce_grouped
+    PDA_REQUIRE(x && grad_y && gamma && mean_rstd && grad_x && ((grad_gamma && grad_beta) || nblocks_out) && scratch, "%s: null pointer", what);
     PDA_REQUIRE((((uintptr_t)x | (uintptr_t)grad_y | (uintptr_t)grad_x | (uintptr_t)gamma) & 15) == 0 &&
                     ((uintptr_t)grad_y2 & (4 * sizeof(T2) - 1)) == 0 && ((uintptr_t)grad_x_b & 7) == 0,
                 "%s: pointers must be 16-byte aligned (8 for bf16 tensors)", what);
@@ -207,7 +187,8 @@ static int launch_layer_norm_bwd(const float* x, const float* grad_y, const T2* 
     else hipLaunchKernelGGL((layer_norm_bwd_kernel<V, false, T2>), grid, block, 0, st, x, grad_y, grad_y2, gamma, mean_rstd, grad_x, grad_x_b, partial, rows)
     if (d == 256) { PDA_LN_BWD(1); } else if (d == 512) { PDA_LN_BWD(2); } else { PDA_LN_BWD(4); }
 #undef PDA_LN_BWD
-    hipLaunchKernelGGL(layer_norm_finalize_kernel, dim3(divup(d, 64)), dim3(1024), 0, st, partial, nblocks, d, grad_gamma, grad_beta);
+    if (nblocks_out) *nblocks_out = nblocks;
+    else hipLaunchKernelGGL(layer_norm_finalize_kernel, dim3(divup(d, 64)), dim3(1024), 0, st, partial, nblocks, d, grad_gamma, grad_beta);
     return check_launch(what);
 }
 
@@ -245,6 +226,19 @@ PDA_API int pda_layer_norm_bwd_mixed(const float* x, const float* grad_y, const 
                                                        grad_gamma, grad_beta, scratch, rows, d, (hipStream_t)stream, "pda_layer_norm_bwd_mixed");
     return pda::launch_layer_norm_bwd<float>(x, grad_y, (const float*)grad_y2, gamma, mean_rstd, grad_x, grad_x_bf16, grad_gamma, grad_beta,
                                              scratch, rows, d, (hipStream_t)stream, "pda_layer_norm_bwd_mixed");
+}
+
+PDA_API int pda_layer_norm_bwd_partials(const float* x, const float* grad_y, const void* grad_y2, int grad_y2_is_bf16, const float* gamma,
+                                        const float* mean_rstd, float* grad_x, uint16_t* grad_x_bf16, void* scratch, int64_t rows, int d,
+                                        int* nblocks, pda_stream_t stream) {
+    PDA_REQUIRE(rows >= 1 && (d == 256 || d == 512 || d == 1024), "pda_layer_norm_bwd_partials: bad size: rows=%lld D=%d (256, 512 or 1024)",
+                (long long)rows, d);
+    PDA_REQUIRE(nblocks, "pda_layer_norm_bwd_partials: null pointer");
+    if (grad_y2_is_bf16)
+        return pda::launch_layer_norm_bwd<pda::bf16_t>(x, grad_y, (const pda::bf16_t*)grad_y2, gamma, mean_rstd, grad_x, grad_x_bf16, nullptr,
+                                                       nullptr, scratch, rows, d, (hipStream_t)stream, "pda_layer_norm_bwd_partials", nblocks);
+    return pda::launch_layer_norm_bwd<float>(x, grad_y, (const float*)grad_y2, gamma, mean_rstd, grad_x, grad_x_bf16, nullptr, nullptr, scratch,
+                                             rows, d, (hipStream_t)stream, "pda_layer_norm_bwd_partials", nblocks);
 }
 
 // ---- residual add + max-pool over the tokens of a group -------------------------------------------------

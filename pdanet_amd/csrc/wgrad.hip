@@ -14,6 +14,7 @@
 // reader of a G / X chunk hits that XCD's L2.
 #include "pda_common.h"
 #include "split_bf16.h"
+#include "param_grad_reduce.h"
 
 #include <stdlib.h>
 
@@ -392,44 +393,20 @@ void wgrad_split_kernel(const float* __restrict__ X, const float* __restrict__ G
     }
 }
 
-// second stage: out[e] = sum_s part[s][e], fixed order.  Block = 64 elements x 16 slices of S (independent loads
-// in groups of 8: a thread walking all S partials alone would serialise S load latencies).
-__device__ __forceinline__ float sum_slices(const float* __restrict__ part, int S, int64_t stride, int64_t e, bool live, int slice,
-                                            float (*red)[64], int el) {
-    float a = 0.f;
-    if (live) {
-        float v[8];
-        for (int s0 = slice; s0 < S; s0 += 16 * 8) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int sidx = s0 + 16 * u;
-                v[u] = sidx < S ? part[(size_t)sidx * stride + e] : 0.f;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) a += v[u];
-        }
-    }
-    red[slice][el] = a;
-    __syncthreads();
-    float r = 0.f;
-    if (slice == 0)
-#pragma unroll
-        for (int p = 0; p < 16; ++p) r += red[p][el];
-    __syncthreads();
-    return r;
-}
-
+// second stage: out[e] = sum_s part[s][e], fixed order (csrc/param_grad_reduce.h: the bodies are shared with the grouped
+// kernel).  VEC: 256 elements per block through 16-byte loads, else 64 through 4-byte loads; the same bits.
+template <bool VEC>
 __global__ __launch_bounds__(1024) void wgrad_reduce_kernel(const float* __restrict__ part_w, const float* __restrict__ part_b,
                                                             float* __restrict__ dw, float* __restrict__ db, int S, int64_t nm, int N) {
-    __shared__ float red[16][64];
-    const int el = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const int64_t e = (int64_t)blockIdx.x * 64 + el;
-    const float w = sum_slices(part_w, S, nm, e, e < nm, slice, red, el);
-    if (slice == 0 && e < nm) dw[e] = w;
-    if (db && (int64_t)blockIdx.x * 64 < N) {          // block-uniform
-        const float bsum = sum_slices(part_b, S, N, e, e < N, slice, red, el);
-        if (slice == 0 && e < N) db[e] = bsum;
-    }
+    __shared__ __attribute__((aligned(16))) float red[VEC ? 16 * 256 : 16 * 64];
+    if constexpr (VEC) wgrad_reduce_block4(part_w, part_b, dw, db, S, nm, N, 1, 1, (int)blockIdx.x, reinterpret_cast<float (*)[256]>(red));
+    else wgrad_reduce_block(part_w, part_b, dw, db, S, nm, N, 1, 1, (int)blockIdx.x, reinterpret_cast<float (*)[64]>(red));
+}
+
+// PDA_WGRAD_REDUCE_VEC=0: the 4-byte-load form everywhere (A/B timing; the results do not depend on it)
+static bool wgrad_reduce_vec(const float* part_w, const float* part_b, int64_t nm, int N) {
+    static const bool on = [] { const char* e = getenv("PDA_WGRAD_REDUCE_VEC"); return !e || atoi(e) != 0; }();
+    return on && wgrad_reduce_vec_ok(part_w, part_b, nm, N);
 }
 
 // ---- narrow layers (M, N <= 64): an HBM-bound streaming reduction --------------------------------------------------
@@ -580,13 +557,41 @@ PDA_API int pda_linear_wgrad_form(int64_t tokens, int in_features, int out_featu
 }
 
 namespace pda {
+// slices == nullptr: both stages.  Otherwise the first stage alone: the partials stay in scratch (part_w [S][N*M], part_b from
+// S*N*M when want_bias), *slices = S, grad_weight / grad_bias are not used.
 static int linear_wgrad(const float* x, const float* grad_out, float* grad_weight, float* grad_bias, void* scratch, int64_t tokens,
-                        int in_features, int out_features, pda_stream_t stream, const float* x_mi, const float* x_g, const float* x_b);
+                        int in_features, int out_features, pda_stream_t stream, const float* x_mi, const float* x_g, const float* x_b,
+                        int* slices = nullptr, bool want_bias = false);
 }
 
 PDA_API int pda_linear_wgrad(const float* x, const float* grad_out, float* grad_weight, float* grad_bias, void* scratch,
                              int64_t tokens, int in_features, int out_features, pda_stream_t stream) {
     return pda::linear_wgrad(x, grad_out, grad_weight, grad_bias, scratch, tokens, in_features, out_features, stream, nullptr, nullptr, nullptr);
+}
+
+PDA_API int pda_linear_wgrad_partials(const float* x, const float* grad_out, void* scratch, int want_bias, int64_t tokens,
+                                      int in_features, int out_features, int* slices, pda_stream_t stream) {
+    PDA_REQUIRE(tokens >= 1 && in_features >= 4 && out_features >= 4 && (in_features & 3) == 0 && (out_features & 3) == 0,
+                "pda_linear_wgrad_partials: bad size: tokens=%lld in=%d out=%d (features must be multiples of 4)", (long long)tokens,
+                in_features, out_features);
+    PDA_REQUIRE(slices, "pda_linear_wgrad_partials: null pointer");
+    return pda::linear_wgrad(x, grad_out, nullptr, nullptr, scratch, tokens, in_features, out_features, stream, nullptr, nullptr, nullptr,
+                             slices, want_bias != 0);
+}
+
+PDA_API int pda_linear_wgrad_bn_partials(const float* x, const float* grad_out, void* scratch, int64_t tokens, int in_features,
+                                         int out_features, const float* x_mean_invstd, const float* x_gamma, const float* x_beta,
+                                         int* slices, pda_stream_t stream) {
+    PDA_REQUIRE(tokens >= 1 && in_features >= 4 && out_features >= 4 && (in_features & 3) == 0 && (out_features & 3) == 0,
+                "pda_linear_wgrad_bn_partials: bad size: tokens=%lld in=%d out=%d (features must be multiples of 4)", (long long)tokens,
+                in_features, out_features);
+    if (pda_linear_wgrad_form(tokens, in_features, out_features) != 2) {
+        pda::set_error("pda_linear_wgrad_bn_partials: tokens=%lld in=%d out=%d does not run on the split form", (long long)tokens, in_features, out_features);
+        return PDA_ERR_UNSUPPORTED;
+    }
+    PDA_REQUIRE(x_mean_invstd && x_gamma && x_beta && slices, "pda_linear_wgrad_bn_partials: null pointer");
+    return pda::linear_wgrad(x, grad_out, nullptr, nullptr, scratch, tokens, in_features, out_features, stream, x_mean_invstd, x_gamma, x_beta,
+                             slices, false);
 }
 
 // dW = dY^T relu(bn(x)): x is the PRE-BatchNorm tensor, (x_mean_invstd, x_gamma, x_beta) the layer's batch statistics and
@@ -603,19 +608,33 @@ PDA_API int pda_linear_wgrad_bn(const float* x, const float* grad_out, float* gr
 }
 
 int pda::linear_wgrad(const float* x, const float* grad_out, float* grad_weight, float* grad_bias, void* scratch, int64_t tokens,
-                             int in_features, int out_features, pda_stream_t stream, const float* x_mi, const float* x_g, const float* x_b) {
+                             int in_features, int out_features, pda_stream_t stream, const float* x_mi, const float* x_g, const float* x_b,
+                             int* slices, bool want_bias) {
     const int M = in_features, N = out_features;
     PDA_REQUIRE(tokens >= 1 && M >= 4 && N >= 4 && (M & 3) == 0 && (N & 3) == 0,
                 "pda_linear_wgrad: tokens=%lld in=%d out=%d (features must be multiples of 4)", (long long)tokens, M, N);
-    PDA_REQUIRE(x && grad_out && grad_weight && scratch, "pda_linear_wgrad: null pointer");
+    PDA_REQUIRE(x && grad_out && (grad_weight || slices) && scratch, "pda_linear_wgrad: null pointer");
     PDA_REQUIRE((((uintptr_t)x | (uintptr_t)grad_out) & 15) == 0, "pda_linear_wgrad: x / grad_out must be 16-byte aligned");
+    const bool bias = slices ? want_bias : grad_bias != nullptr;
     int tm, tn, S;
     int64_t KS;
     hipStream_t st = (hipStream_t)stream;
+    const int64_t nm = (int64_t)N * M;
+    // the second stage right behind the first, or (first stage alone) the slice count for the caller's grouped second stage
+    auto finish = [&](const float* part_w, const float* part_b) {
+        if (slices) *slices = S;
+        else if (pda::wgrad_reduce_vec(part_w, part_b, nm, N))
+            hipLaunchKernelGGL(pda::wgrad_reduce_kernel<true>, dim3((unsigned)pda::divup64(nm, 256)), dim3(1024), 0, st, part_w, part_b,
+                               grad_weight, grad_bias, S, nm, N);
+        else
+            hipLaunchKernelGGL(pda::wgrad_reduce_kernel<false>, dim3((unsigned)pda::divup64(nm, 64)), dim3(1024), 0, st, part_w, part_b,
+                               grad_weight, grad_bias, S, nm, N);
+        return pda::check_launch("pda_linear_wgrad");
+    };
     if (pda::wgrad_is_skinny(M, N)) {
         pda::wgrad_skinny_plan(tokens, S, KS);
         float* pw = (float*)scratch;
-        float* pb = grad_bias ? pw + (size_t)S * N * M : (float*)nullptr;
+        float* pb = bias ? pw + (size_t)S * N * M : (float*)nullptr;
         const int nt = N > 32 ? 2 : 1, mt = M > 32 ? 2 : 1;
 #define PDA_WS_CASE(A, B) hipLaunchKernelGGL((pda::wgrad_skinny_kernel<A, B>), dim3(S), dim3(256), 0, st, x, grad_out, pw, pb, tokens, M, N, KS)
         if (nt == 1 && mt == 1) PDA_WS_CASE(1, 1);
@@ -623,10 +642,7 @@ int pda::linear_wgrad(const float* x, const float* grad_out, float* grad_weight,
         else if (mt == 1) PDA_WS_CASE(2, 1);
         else PDA_WS_CASE(2, 2);
 #undef PDA_WS_CASE
-        const int64_t nm = (int64_t)N * M;
-        hipLaunchKernelGGL(pda::wgrad_reduce_kernel, dim3((unsigned)pda::divup64(nm, 64)), dim3(1024), 0, st, pw, pb, grad_weight,
-                           grad_bias, S, nm, N);
-        return pda::check_launch("pda_linear_wgrad");
+        return finish(pw, pb);
     }
     if (pda::wgrad_use_split(tokens, M, N)) {
         pda::wgrad_split_plan(tokens, M, N, tm, tn, S, KS);
@@ -640,25 +656,101 @@ int pda::linear_wgrad(const float* x, const float* grad_out, float* grad_weight,
         PDA_REQUIRE(ok, "pda_linear_wgrad: %d bytes of dynamic LDS refused", 2 * pda::WSP_TILE_U4 * 16);
         if (x_mi)
             hipLaunchKernelGGL(pda::wgrad_split_kernel<true>, dim3(pda::divup(nblocks, 8) * 8), dim3(512), 2 * pda::WSP_TILE_U4 * 16, st,
-                               x, grad_out, part_w, grad_bias ? part_b : (float*)nullptr, tokens, M, N, tm, tn, S, KS, nblocks, x_mi, x_g, x_b);
+                               x, grad_out, part_w, bias ? part_b : (float*)nullptr, tokens, M, N, tm, tn, S, KS, nblocks, x_mi, x_g, x_b);
         else
             hipLaunchKernelGGL(pda::wgrad_split_kernel<false>, dim3(pda::divup(nblocks, 8) * 8), dim3(512), 2 * pda::WSP_TILE_U4 * 16, st,
-                               x, grad_out, part_w, grad_bias ? part_b : (float*)nullptr, tokens, M, N, tm, tn, S, KS, nblocks, x_mi, x_g, x_b);
-        const int64_t nm = (int64_t)N * M;
-        hipLaunchKernelGGL(pda::wgrad_reduce_kernel, dim3((unsigned)pda::divup64(nm, 64)), dim3(1024), 0, st, part_w, part_b,
-                           grad_weight, grad_bias, S, nm, N);
-        return pda::check_launch("pda_linear_wgrad");
+                               x, grad_out, part_w, bias ? part_b : (float*)nullptr, tokens, M, N, tm, tn, S, KS, nblocks, x_mi, x_g, x_b);
+        return finish(part_w, part_b);
     }
     pda::wgrad_plan(tokens, M, N, tm, tn, S, KS);
     const int nblocks = S * tm * tn;
     float* part_w = (float*)scratch;
     float* part_b = part_w + (size_t)S * N * M;
     hipLaunchKernelGGL(pda::wgrad_kernel, dim3(pda::divup(nblocks, 8) * 8), dim3(256), 0, st, x, grad_out, part_w,
-                       grad_bias ? part_b : (float*)nullptr, tokens, M, N, tm, tn, S, KS, nblocks);
-    const int64_t nm = (int64_t)N * M;
-    hipLaunchKernelGGL(pda::wgrad_reduce_kernel, dim3((unsigned)pda::divup64(nm, 64)), dim3(1024), 0, st, part_w, part_b, grad_weight,
-                       grad_bias, S, nm, N);
-    return pda::check_launch("pda_linear_wgrad");
+                       bias ? part_b : (float*)nullptr, tokens, M, N, tm, tn, S, KS, nblocks);
+    return finish(part_w, part_b);
+}
+
+// ---- the grouped second stage: the gradients of many parameters finished by one launch -----------------------------
+// Every second stage above (and LayerNorm's, csrc/layer_norm.hip) is a handful of workgroups that wait on load latency:
+// 4-37 us each, 57 per training step, one behind the other on the stream.  Nothing on the backward chain reads what they
+// write, so a caller may run the first stages alone and finish all their gradients here: the entries travel as kernel
+// arguments (no allocation, no copy: capturable), a workgroup finds its entry in a prefix of block counts (a uniform binary
+// search over kernel arguments) and runs that entry's per-problem body unchanged -- the same bits as the per-problem kernels.
+namespace pda {
+
+constexpr int PG_MAX_ENTRIES = 48;          // 48 x 64 bytes of entries + the prefix: 3.3 KB of the 4 KB argument space
+
+struct ParamGradArgs {
+    pda_param_grad_entry_t e[PG_MAX_ENTRIES];
+    int first[PG_MAX_ENTRIES + 1];          // entry i owns blocks first[i] .. first[i + 1] - 1
+    int n;
+    int vec;                                // weight gradients that allow it (wgrad_reduce_vec_ok) take the 16-byte-load body
+};
+
+static int param_grad_blocks(const pda_param_grad_entry_t& en, bool vec) {
+    if (en.kind != PARAM_GRAD_WEIGHT) return divup(en.n, 64);
+    return (int)divup64(en.nm, vec && wgrad_reduce_vec_ok(en.part, en.part_bias, en.nm, en.n) ? 256 : 64);
+}
+
+__global__ __launch_bounds__(1024) void param_grad_reduce_grouped_kernel(const ParamGradArgs a) {
+    __shared__ __attribute__((aligned(16))) float red[16 * 256];       // [16][256], [16][64] or [2][16][64] by the entry's body
+    const int b = (int)blockIdx.x;
+    int lo = 0, hi = a.n;                   // first[lo] <= b < first[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (a.first[mid] <= b) lo = mid; else hi = mid;
+    }
+    const pda_param_grad_entry_t& en = a.e[lo];
+    const int blk = b - a.first[lo];
+    if (en.kind != PARAM_GRAD_WEIGHT)
+        layer_norm_finalize_block(en.part, en.count, en.n, en.dst, en.dst_bias, blk, reinterpret_cast<float (*)[16][64]>(red));
+    else if (a.vec && wgrad_reduce_vec_ok(en.part, en.part_bias, en.nm, en.n))
+        wgrad_reduce_block4(en.part, en.part_bias, en.dst, en.dst_bias, en.count, en.nm, en.n, en.cols, en.ld, blk,
+                            reinterpret_cast<float (*)[256]>(red));
+    else
+        wgrad_reduce_block(en.part, en.part_bias, en.dst, en.dst_bias, en.count, en.nm, en.n, en.cols, en.ld, blk,
+                           reinterpret_cast<float (*)[64]>(red));
+}
+
+}  // namespace pda
+
+PDA_API int pda_param_grad_reduce_grouped(const pda_param_grad_entry_t* entries, int n, pda_stream_t stream) {
+    PDA_REQUIRE(n >= 1, "pda_param_grad_reduce_grouped: bad size: n=%d", n);
+    PDA_REQUIRE(entries, "pda_param_grad_reduce_grouped: null pointer");
+    for (int i = 0; i < n; ++i) {           // every size of every entry before any launch
+        const pda_param_grad_entry_t& en = entries[i];
+        PDA_REQUIRE(en.kind == pda::PARAM_GRAD_WEIGHT || en.kind == pda::PARAM_GRAD_LAYER_NORM,
+                    "pda_param_grad_reduce_grouped: bad size: entry %d: kind=%d", i, en.kind);
+        PDA_REQUIRE(en.count >= 1 && en.n >= 1, "pda_param_grad_reduce_grouped: bad size: entry %d: count=%d n=%d", i, en.count, en.n);
+        if (en.kind == pda::PARAM_GRAD_WEIGHT)
+            PDA_REQUIRE(en.cols >= 1 && en.nm >= en.n && en.nm == (int64_t)en.n * en.cols && en.nm <= ((int64_t)1 << 30) && en.ld >= en.cols,
+                        "pda_param_grad_reduce_grouped: bad size: entry %d: nm=%lld n=%d cols=%d ld=%lld", i, (long long)en.nm, en.n, en.cols,
+                        (long long)en.ld);
+        else
+            PDA_REQUIRE(en.n <= 4096, "pda_param_grad_reduce_grouped: bad size: entry %d: d=%d", i, en.n);
+        PDA_REQUIRE(en.part && en.dst && (en.kind == pda::PARAM_GRAD_WEIGHT ? (en.dst_bias == nullptr || en.part_bias != nullptr) : en.dst_bias != nullptr),
+                    "pda_param_grad_reduce_grouped: entry %d: null pointer", i);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    for (int i0 = 0; i0 < n; i0 += pda::PG_MAX_ENTRIES) {
+        pda::ParamGradArgs a;
+        a.n = n - i0 < pda::PG_MAX_ENTRIES ? n - i0 : pda::PG_MAX_ENTRIES;
+        a.vec = pda::wgrad_reduce_vec(nullptr, nullptr, 0, 0) ? 1 : 0;
+        int blocks = 0;
+        for (int i = 0; i < pda::PG_MAX_ENTRIES; ++i) {
+            a.first[i] = blocks;
+            if (i < a.n) {
+                a.e[i] = entries[i0 + i];
+                blocks += pda::param_grad_blocks(a.e[i], a.vec != 0);
+            } else {
+                a.e[i] = pda_param_grad_entry_t{};
+            }
+        }
+        a.first[pda::PG_MAX_ENTRIES] = blocks;
+        hipLaunchKernelGGL(pda::param_grad_reduce_grouped_kernel, dim3((unsigned)blocks), dim3(1024), 0, st, a);
+    }
+    return pda::check_launch("pda_param_grad_reduce_grouped");
 }
 
 // ---- column sums of a bf16 (rows, cols) matrix: the bias gradient in dense-bf16 mode ---------------------------

@@ -14,6 +14,8 @@ reference's and every name has a kernel.
 import ctypes
 
 import functools
+import os
+import threading
 
 import torch
 
@@ -392,13 +394,101 @@ def layer_norm_fwd(x, residual, gamma, beta, sum_out, y, mean_rstd, rows, d, eps
     return 1
 
 
+# ---- parameter gradients finished by one grouped launch (include/pda_train.h, csrc/wgrad.hip) ----------------------------
+# Inside `with param_grad_group():` linear_wgrad, linear_wgrad_bn and layer_norm_bwd run their first stage only; the group
+# collects one entry per gradient and finishes all of them with one pda_param_grad_reduce_grouped launch when the block
+# ends.  The gradients are complete (in stream order) once the block has been left; the bits are those of the immediate
+# calls.  PDA_WGRAD_GROUPED=0: the block does nothing and every call finishes its own gradient as before.
+WGRAD_GROUPED = os.environ.get("PDA_WGRAD_GROUPED", "1") != "0"
+_TLS = threading.local()  # .group: the open group of this thread (autograd runs a backward on a thread of its own per device)
+GROUP_STATS = {"grouped_calls": 0, "entries": 0, "partial_bytes": 0}      # what the grouped launches finished so far
+
+
+class param_grad_group:
+    def __init__(self):
+        self.entries, self.keep = [], []
+
+    def __enter__(self):
+        if WGRAD_GROUPED and _open_group() is None:  # a group inside a group joins the outer one
+            _TLS.group = self
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if _open_group() is self:
+            _TLS.group = None
+            if exc_type is None:
+                self.flush()
+            self.entries, self.keep = [], []         # after an exception the partials are dropped unfinished
+        return False
+
+    def add(self, entry, *tensors):
+        """`tensors`: the partials and the destinations, kept alive until the grouped launch has been enqueued."""
+        self.entries.append(entry)
+        self.keep.extend(tensors)
+
+    def flush(self):
+        if not self.entries:
+            return
+        arr = (_lib.ParamGradEntry * len(self.entries))(*self.entries)
+        _call("pda_param_grad_reduce_grouped", self.keep[0], arr, len(self.entries))
+        GROUP_STATS["grouped_calls"] += 1
+        GROUP_STATS["entries"] += len(self.entries)
+        GROUP_STATS["partial_bytes"] += sum(4 * e.count * (e.nm + e.n if e.part_bias else e.nm) if e.kind == 0 else 8 * e.count * e.n
+                                            for e in self.entries)
+        self.entries, self.keep = [], []
+
+
+def _open_group():
+    return getattr(_TLS, "group", None)
+
+
+def param_grad_group_open():
+    return _open_group() is not None
+
+
+def _grad_dst(t, name, rows, cols):
+    """Destination of a grouped weight gradient: (rows, cols) fp32 with unit column stride; -> (pointer, row stride)."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == F32):
+        raise RuntimeError("%s must be a float32 CUDA(HIP) tensor" % name)
+    if t.is_contiguous():
+        _numel_ok(t, rows * cols, name)
+        return t.data_ptr(), cols
+    if t.dim() != 2 or t.shape[0] != rows or t.shape[1] != cols or t.stride(1) != 1 or t.stride(0) < cols:
+        raise RuntimeError("%s must be contiguous or a (%d, %d) column block of a row-major matrix" % (name, rows, cols))
+    return t.data_ptr(), t.stride(0)
+
+
+def _wgrad_entry(scratch, slices, grad_weight, grad_bias, in_features, out_features):
+    nm = in_features * out_features
+    dst, ld = _grad_dst(grad_weight, "grad_weight", out_features, in_features)
+    part = scratch.data_ptr()
+    gb = None if grad_bias is None else _chk(grad_bias, "grad_bias", F32)
+    return _lib.ParamGradEntry(0, slices, part, part + 4 * slices * nm if gb is not None else None, dst, gb, nm, out_features,
+                               in_features, ld)
+
+
 def layer_norm_bwd(x, grad_y, gamma, mean_rstd, grad_x, grad_gamma, grad_beta, scratch, rows, d, grad_y2=None, grad_x_bf16=None):
-    """grad_y2: optional second incoming gradient (fp32, or bf16 in dense-bf16 mode); grad_x_bf16: optional bf16 copy of grad_x."""
+    """grad_y2: optional second incoming gradient (fp32, or bf16 in dense-bf16 mode); grad_x_bf16: optional bf16 copy of grad_x.
+    Inside a param_grad_group grad_gamma / grad_beta are finished by the group, and `scratch` must be this call's own."""
     _numel_ok(x, rows * d, "x"); _numel_ok(grad_y, rows * d, "grad_y"); _numel_ok(grad_x, rows * d, "grad_x")
     g2 = None
     if grad_y2 is not None:
         _numel_ok(grad_y2, rows * d, "grad_y2")
         g2 = _chk(grad_y2, "grad_y2", BF16 if grad_y2.dtype == BF16 else F32)
+    group = _open_group()
+    if group is not None:
+        gxb = None
+        if grad_x_bf16 is not None:
+            _numel_ok(grad_x_bf16, rows * d, "grad_x_bf16"); gxb = _chk(grad_x_bf16, "grad_x_bf16", BF16)
+        _numel_ok(scratch, layer_norm_scratch_bytes(d), "scratch")
+        nblocks = ctypes.c_int(0)
+        _call("pda_layer_norm_bwd_partials", x, _chk(x, "x", F32), _chk(grad_y, "grad_y", F32), g2,
+              int(grad_y2 is not None and grad_y2.dtype == BF16), _chk(gamma, "gamma", F32), _chk(mean_rstd, "mean_rstd", F32),
+              _chk(grad_x, "grad_x", F32), gxb, _chk(scratch, "scratch", torch.uint8), rows, d, ctypes.byref(nblocks))
+        _numel_ok(grad_gamma, d, "grad_gamma"); _numel_ok(grad_beta, d, "grad_beta")
+        group.add(_lib.ParamGradEntry(1, nblocks.value, scratch.data_ptr(), None, _chk(grad_gamma, "grad_gamma", F32),
+                                       _chk(grad_beta, "grad_beta", F32), 0, d, 0, 0), scratch, grad_gamma, grad_beta)
+        return 1
     if grad_x_bf16 is not None or (grad_y2 is not None and grad_y2.dtype == BF16):
         gxb = None
         if grad_x_bf16 is not None:
@@ -441,11 +531,22 @@ def _cols_packed_size(n_out, k):
 
 
 def linear_wgrad(x, grad_out, grad_weight, grad_bias, tokens, in_features, out_features):
-    """MI355X extension: grad_weight (out, in) = grad_out^T x and grad_bias = column sums (csrc/wgrad.hip)."""
+    """MI355X extension: grad_weight (out, in) = grad_out^T x and grad_bias = column sums (csrc/wgrad.hip).  Inside a
+    param_grad_group the sums over the split-K partials are left to the group, and grad_weight may be a column block of a
+    wider row-major matrix."""
     _numel_ok(x, tokens * in_features, "x"); _numel_ok(grad_out, tokens * out_features, "grad_out")
-    _numel_ok(grad_weight, in_features * out_features, "grad_weight")
     nbytes = _wgrad_scratch_bytes(tokens, in_features, out_features)
     scratch = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    group = _open_group()
+    if group is not None:
+        if grad_bias is not None:
+            _numel_ok(grad_bias, out_features, "grad_bias")
+        slices = ctypes.c_int(0)
+        _call("pda_linear_wgrad_partials", x, _chk(x, "x", F32), _chk(grad_out, "grad_out", F32), scratch.data_ptr(),
+              int(grad_bias is not None), tokens, in_features, out_features, ctypes.byref(slices))
+        group.add(_wgrad_entry(scratch, slices.value, grad_weight, grad_bias, in_features, out_features), scratch, grad_weight, grad_bias)
+        return 1
+    _numel_ok(grad_weight, in_features * out_features, "grad_weight")
     gb = None if grad_bias is None else _chk(grad_bias, "grad_bias", F32)
     _call("pda_linear_wgrad", x, _chk(x, "x", F32), _chk(grad_out, "grad_out", F32), _chk(grad_weight, "grad_weight", F32),
           gb, _chk(scratch, "scratch", torch.uint8), tokens, in_features, out_features)
@@ -460,6 +561,14 @@ def linear_wgrad_bn(x, grad_out, grad_weight, tokens, in_features, out_features,
     _numel_ok(x_gamma, in_features, "x_gamma"); _numel_ok(x_beta, in_features, "x_beta")
     nbytes = _wgrad_scratch_bytes(tokens, in_features, out_features)
     scratch = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    group = _open_group()
+    if group is not None:
+        slices = ctypes.c_int(0)
+        _call("pda_linear_wgrad_bn_partials", x, _chk(x, "x", F32), _chk(grad_out, "grad_out", F32), scratch.data_ptr(), tokens,
+              in_features, out_features, _chk(x_mean_invstd, "x_mean_invstd", F32), _chk(x_gamma, "x_gamma", F32),
+              _chk(x_beta, "x_beta", F32), ctypes.byref(slices))
+        group.add(_wgrad_entry(scratch, slices.value, grad_weight, None, in_features, out_features), scratch, grad_weight)
+        return 1
     _call("pda_linear_wgrad_bn", x, _chk(x, "x", F32), _chk(grad_out, "grad_out", F32), _chk(grad_weight, "grad_weight", F32), None,
           _chk(scratch, "scratch", torch.uint8), tokens, in_features, out_features, _chk(x_mean_invstd, "x_mean_invstd", F32),
           _chk(x_gamma, "x_gamma", F32), _chk(x_beta, "x_beta", F32))

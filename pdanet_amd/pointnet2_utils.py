@@ -11,6 +11,7 @@ the kernels underneath are the hand-written gfx950 ones reached through the C AB
 """
 from typing import List, Tuple
 
+import functools
 import os
 
 import torch
@@ -543,6 +544,18 @@ def densitynet_multi(dns, xs, parts):
     return list(DensityNetFusedMulti.apply(metas, *xs, *params))
 
 
+def _grouped_param_grads(backward):
+    """For the backward of a Function that forms several parameter gradients: their second stages (the sums over the
+    weight gradients' split-K partials, LayerNorm's dgamma / dbeta) are collected and run as ONE launch when the backward
+    returns (pointnet2.param_grad_group) instead of one launch each behind its first stage -- nothing inside the backward
+    reads them.  The tensors returned to autograd are complete in stream order.  PDA_WGRAD_GROUPED=0: as before."""
+    @functools.wraps(backward)
+    def grouped(ctx, *grads):
+        with pointnet2.param_grad_group():
+            return backward(ctx, *grads)
+    return grouped
+
+
 class LinearLongTokens(Function):
     """y = x W^T + b over the last dim of x (..., in).  Forward and the input gradient are _gemm_nt / _gemm_nn (the
     split-bf16 kernels, or the library where those do not apply); the weight and bias gradients -- GEMMs with a tiny
@@ -913,6 +926,7 @@ class TransformerBlock(Function):
         return y
 
     @staticmethod
+    @_grouped_param_grads
     def backward(ctx, dy):
         x, st1, src1_s, qkv, lse, a_s, ssum, st2, src2_s, h, h_s, n1w, in_w, out_w, n2w, w1, w2, arg = ctx.saved_tensors
         G, S, D = x.shape
@@ -962,7 +976,8 @@ class TransformerBlock(Function):
         del dqkv, dqkv2
         d_x = torch.empty_like(x)
         gn1w, gn1b = torch.empty_like(n1w), torch.empty_like(n1w)
-        pointnet2.layer_norm_bwd(x, d_src1, n1w, st1, d_x, gn1w, gn1b, scratch, T, D)
+        scratch1 = torch.empty_like(scratch)      # partials of its own: those of both LayerNorms wait for the grouped launch
+        pointnet2.layer_norm_bwd(x, d_src1, n1w, st1, d_x, gn1w, gn1b, scratch1, T, D)
         return d_x, gn1w, gn1b, gwi, gbi, gwo, gbo, gn2w, gn2b, gw1, gb1, gw2, gb2, None, None, None, None
 
 
@@ -1382,6 +1397,7 @@ class SaWideChainTrain(Function):
         return out
 
     @staticmethod
+    @_grouped_param_grads
     def backward(ctx, grad_out):
         xyz, new_xyz, feats_pm, idx, w1, w2, w3, g1, b1, g2, b2, g3, b3, z1, z2, z3, mi1, mi2, mi3, arg = ctx.saved_tensors
         B, M, ns = idx.shape
@@ -1434,7 +1450,11 @@ class SaWideChainTrain(Function):
                 g_pts = torch.zeros((B, N, c1), dtype=torch.float32, device=dev)
                 pointnet2.group_rows_grad(B, N, c1, M * ns, gz1, idx, g_pts)
             g_pts = g_pts.view(B * N, c1)
-            dw1[:, 3:] = _wgrad(feats_pm.view(B * N, C), g_pts, torch.empty((c1, C), dtype=torch.float32, device=dev), False)[0]
+            x_pts = feats_pm.view(B * N, C)
+            if pointnet2.param_grad_group_open() and LINEAR_WGRAD_KERNEL and LinearLongTokens.kernel_wins(x_pts, dw1[:, 3:]):
+                pointnet2.linear_wgrad(x_pts, g_pts, dw1[:, 3:], None, B * N, C, c1)     # the group writes the column block in place
+            else:
+                dw1[:, 3:] = _wgrad(x_pts, g_pts, torch.empty((c1, C), dtype=torch.float32, device=dev), False)[0]
             g_feats = _gemm_nn(g_pts, w1c[:, 3:].contiguous()).view(B, N, C) if ctx.needs_input_grad[2] else None
         return None, g_new, g_feats, None, dw1, dw2, dw3, dg1, db1, dg2, db2, dg3, db3, None
 
@@ -1646,6 +1666,7 @@ class RaggedTransformerBlock(Function):
         return y
 
     @staticmethod
+    @_grouped_param_grads
     def backward(ctx, dy):
         x, st1, src1, qkv, lse, a, ssum, st2, src2, h, n1w, in_w, out_w, n2w, w1, w2, arg, cnt, off, rowmap = ctx.saved_tensors
         U, D = x.shape
@@ -1677,7 +1698,8 @@ class RaggedTransformerBlock(Function):
         del dqkv
         d_x = torch.empty_like(x)
         gn1w, gn1b = torch.empty_like(n1w), torch.empty_like(n1w)
-        pointnet2.layer_norm_bwd(x, d_src1, n1w, st1, d_x, gn1w, gn1b, scratch, U, D)
+        scratch1 = torch.empty_like(scratch)      # partials of its own: those of both LayerNorms wait for the grouped launch
+        pointnet2.layer_norm_bwd(x, d_src1, n1w, st1, d_x, gn1w, gn1b, scratch1, U, D)
         return d_x, None, gn1w, gn1b, gwi, gbi, gwo, gbo, gn2w, gn2b, gw1, gb1, gw2, gb2, None, None, None
 
 
