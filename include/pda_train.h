@@ -56,6 +56,20 @@ int pda_bn_relu_fwd_counted(const float *x, const float *gamma, const float *bet
 int pda_bn_relu_bwd_counted(const float *x, const float *grad_y, const float *gamma, const float *beta,
                             const float *mean_invstd, float *grad_x, float *grad_gamma, float *grad_beta, void *scratch,
                             int64_t rows, int c, const int32_t *count, int relu, int training, pda_stream_t stream);
+/* The residual tail of a sparse basic block in the counted form: y = max((xhat * gamma + beta) + identity, 0) over the live
+ * rows [0, *count) of x, identity (cap, C).  Statistics, running buffers, *status and the C contract are those of
+ * pda_bn_relu_fwd_counted; the BatchNorm value, the sum and the maximum round one after the other, so y has the bits of
+ * pda_bn_relu_fwd_counted(relu = 0) followed by an addition and a ReLU.  Backward: y is the saved output and the ReLU mask is
+ * y > 0; grad_identity (cap, C) is the masked gradient, grad_x its BatchNorm gradient, both written in one pass.  Dead rows of
+ * x, identity, y and grad_y are never read; dead rows of y, grad_x and grad_identity are exact zeros.  cap == 0 is PDA_OK. */
+int pda_bn_add_relu_fwd_counted(const float *x, const float *identity, const float *gamma, const float *beta,
+                                float *running_mean, float *running_var, float *y, float *mean_invstd, void *scratch,
+                                int64_t cap, int c, float eps, float momentum, const int32_t *count, int32_t *status,
+                                int training, pda_stream_t stream);
+int pda_bn_add_relu_bwd_counted(const float *x, const float *y, const float *grad_y, const float *gamma, const float *beta,
+                                const float *mean_invstd, float *grad_x, float *grad_identity, float *grad_gamma,
+                                float *grad_beta, void *scratch, int64_t cap, int c, const int32_t *count, int training,
+                                pda_stream_t stream);
 /* The reduction half of pda_bn_relu_bwd alone: grad_gamma, grad_beta and sums (2, C) = the per-channel means of the masked
  * gradient and of its product with the normalised input, for a consumer that forms grad_x itself (pda_sa_point_grad_bn). */
 int pda_bn_relu_bwd_reduce(const float *x, const float *grad_y, const float *gamma, const float *beta,

@@ -269,6 +269,8 @@ SIGNATURES = {
     "pda_spconv_index_strided_counted": [_vp, ctypes.c_int64, _vp] + [_i] * 13 + [ctypes.c_int64] + [_vp] * 7,
     "pda_bn_relu_fwd_counted": [_vp] * 8 + [ctypes.c_int64, _i, _f, _f, _vp, _vp, _i, _i, _vp],
     "pda_bn_relu_bwd_counted": [_vp] * 9 + [ctypes.c_int64, _i, _vp, _i, _i, _vp],
+    "pda_bn_add_relu_fwd_counted": [_vp] * 9 + [ctypes.c_int64, _i, _f, _f, _vp, _vp, _i, _vp],
+    "pda_bn_add_relu_bwd_counted": [_vp] * 11 + [ctypes.c_int64, _i, _vp, _i, _vp],
     "pda_spconv_gemm": [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, _i, _i, _i, _vp],
     "pda_spconv_wgrad_workspace_bytes": [ctypes.c_int64, _i, _i, _i],
     "pda_spconv_wgrad": [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, _i, _vp, _vp, _vp, _vp],

@@ -382,12 +382,16 @@ __device__ __forceinline__ int64_t bn_live_rows(const int32_t* __restrict__ coun
     return v < 0 ? 0 : (v > rows ? rows : (int64_t)v);
 }
 
-template <bool BWD>
+// ADD (backward only; the residual tail y = relu(bn(x) + identity)): the ReLU mask is yout > 0, taken from the saved output
+// `yout`, in place of the sign of the recomputed BatchNorm value.
+template <bool BWD, bool ADD = false>
 __global__ __launch_bounds__(256) void bn_reduce_counted_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                                 const float* __restrict__ mean_invstd,
                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                 double* __restrict__ partial, BnShape s,
-                                                                const int32_t* __restrict__ count, int relu) {
+                                                                const int32_t* __restrict__ count, int relu,
+                                                                const float* __restrict__ yout = nullptr) {
+    static_assert(BWD || !ADD, "the forward statistics of the residual tail are those of the plain form");
     __shared__ double lds[2 * 256 * 4];
     const int tid = threadIdx.x;
     const int64_t n = bn_live_rows(count, s.rows);
@@ -401,34 +405,41 @@ __global__ __launch_bounds__(256) void bn_reduce_counted_kernel(const float* __r
         be = reinterpret_cast<const float4*>(beta)[col];
     }
     const int64_t stride = (int64_t)gridDim.x * s.rpb;
-    auto row = [&](const float4& v, const float4& d) {
+    auto row = [&](const float4& v, const float4& d, const float4& yo) {
         if (!BWD) {
             a[0] += v.x; a[1] += v.y; a[2] += v.z; a[3] += v.w;
             b[0] += (double)v.x * v.x; b[1] += (double)v.y * v.y; b[2] += (double)v.z * v.z; b[3] += (double)v.w * v.w;
         } else {
             const float xh[4] = {(v.x - mu.x) * is.x, (v.y - mu.y) * is.y, (v.z - mu.z) * is.z, (v.w - mu.w) * is.w};
             const float gg[4] = {g.x, g.y, g.z, g.w}, bb[4] = {be.x, be.y, be.z, be.w}, dd[4] = {d.x, d.y, d.z, d.w};
+            const float yy[4] = {yo.x, yo.y, yo.z, yo.w};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const float dyh = (!relu || xh[k] * gg[k] + bb[k] > 0.f) ? dd[k] : 0.f;
+                const float dyh = (ADD ? yy[k] > 0.f : (!relu || xh[k] * gg[k] + bb[k] > 0.f)) ? dd[k] : 0.f;
                 a[k] += dyh;
                 b[k] += (double)dyh * xh[k];
             }
         }
     };
+    auto saved = [&](int64_t r) -> float4 {
+        if constexpr (ADD) return load4(yout + r * s.c + 4 * col);
+        else return make_float4(0, 0, 0, 0);
+    };
     constexpr int U = BWD ? 1 : 4;          // independent 16-byte loads in flight per thread: see bn_reduce_kernel
     int64_t r = (int64_t)blockIdx.x * s.rpb + r0;
     for (; r + (U - 1) * stride < n; r += U * stride) {
-        float4 v[U], d[U];
+        float4 v[U], d[U], yo[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             v[u] = load4(x + (r + u * stride) * s.c + 4 * col);
             d[u] = BWD ? load4(dy + (r + u * stride) * s.c + 4 * col) : make_float4(0, 0, 0, 0);
+            yo[u] = saved(r + u * stride);
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) row(v[u], d[u]);
+        for (int u = 0; u < U; ++u) row(v[u], d[u], yo[u]);
     }
-    for (; r < n; r += stride) row(load4(x + r * s.c + 4 * col), BWD ? load4(dy + r * s.c + 4 * col) : make_float4(0, 0, 0, 0));
+    for (; r < n; r += stride)
+        row(load4(x + r * s.c + 4 * col), BWD ? load4(dy + r * s.c + 4 * col) : make_float4(0, 0, 0, 0), saved(r));
     double* pa = partial + (size_t)blockIdx.x * 2 * s.c;
     block_reduce_cols(a, b, lds, s.cg, s.rpb, pa, pa + s.c);
 }
@@ -489,12 +500,19 @@ __global__ __launch_bounds__(512) void bn_finalize_bwd_counted_kernel(const doub
     sums[c + ch] = means ? (float)(s2 / (double)rows) : 0.f;
 }
 
-template <bool BWD>
+// ADD, the residual tail of a SparseBasicBlock in one sweep (`res` and `out2` are used by this form alone):
+// forward : y = max((xhat * gamma + beta) + res, 0) with res = the identity features -- the BatchNorm value is rounded, then
+//           the sum, then the maximum, as BatchNorm, `+` and ReLU one after the other round (the library is built with
+//           -ffp-contract=off), so the result has the bits of that sequence;
+// backward: res = the saved output y, the mask is y > 0; out = grad_x, out2 = grad_identity = the masked gradient.
+template <bool BWD, bool ADD = false>
 __global__ __launch_bounds__(256) void bn_apply_counted_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                                const float* __restrict__ mean_invstd,
                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                const float* __restrict__ sums, float* __restrict__ out, BnShape s,
-                                                               const int32_t* __restrict__ count, int relu) {
+                                                               const int32_t* __restrict__ count, int relu,
+                                                               const float* __restrict__ res = nullptr,
+                                                               float* __restrict__ out2 = nullptr) {
     const int tid = threadIdx.x;
     const int col = tid % s.cg, r0 = tid / s.cg;
     const int64_t n = bn_live_rows(count, s.rows);
@@ -510,22 +528,28 @@ __global__ __launch_bounds__(256) void bn_apply_counted_kernel(const float* __re
         const bool live = r < n;
         const float4 v = live ? load4(x + r * s.c + 4 * col) : zero;          // a dead row is not read
         const float4 d = (BWD && live) ? load4(dy + r * s.c + 4 * col) : zero;
-        const float xv[4] = {v.x, v.y, v.z, v.w}, dv[4] = {d.x, d.y, d.z, d.w};
-        float o[4];
+        float4 e = zero;
+        if constexpr (ADD) e = live ? load4(res + r * s.c + 4 * col) : zero;
+        const float xv[4] = {v.x, v.y, v.z, v.w}, dv[4] = {d.x, d.y, d.z, d.w}, ev[4] = {e.x, e.y, e.z, e.w};
+        float o[4], o2[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float xh = (xv[k] - muv[k]) * isv[k];
             const float y = xh * gv[k] + bv[k];
-            float val;
+            float val, val2 = 0.f;
             if (!BWD) {
-                val = relu ? fmaxf(y, 0.f) : y;
+                if constexpr (ADD) val = fmaxf(y + ev[k], 0.f);
+                else val = relu ? fmaxf(y, 0.f) : y;
             } else {
-                const float dyh = (!relu || y > 0.f) ? dv[k] : 0.f;
+                const float dyh = (ADD ? ev[k] > 0.f : (!relu || y > 0.f)) ? dv[k] : 0.f;
                 val = gv[k] * isv[k] * (dyh - (m1v[k] + xh * m2v[k]));
+                val2 = dyh;
             }
             o[k] = live ? val : 0.f;                                          // a select, not a product: exact zeros
+            o2[k] = live ? val2 : 0.f;
         }
         store4(out + r * s.c + 4 * col, make_float4(o[0], o[1], o[2], o[3]));
+        if constexpr (BWD && ADD) store4(out2 + r * s.c + 4 * col, make_float4(o2[0], o2[1], o2[2], o2[3]));
     }
 }
 
@@ -732,5 +756,67 @@ PDA_API int pda_bn_relu_bwd_counted(const float* x, const float* grad_y, const f
                        count, training, grad_gamma, grad_beta, sums);
     hipLaunchKernelGGL(pda::bn_apply_counted_kernel<true>, dim3(grid), dim3(256), 0, st, x, grad_y, mean_invstd, gamma, beta,
                        (const float*)sums, grad_x, s, count, relu);
+    return pda::check_launch(what);
+}
+
+// ---- the residual tail of a SparseBasicBlock: y = relu(bn(x) + identity) over the live rows, one apply pass in place of three ----
+// Statistics, running buffers and FLAG_FEW_ROWS: the kernels of pda_bn_relu_fwd_counted; only the apply pass differs.
+PDA_API int pda_bn_add_relu_fwd_counted(const float* x, const float* identity, const float* gamma, const float* beta,
+                                        float* running_mean, float* running_var, float* y, float* mean_invstd, void* scratch,
+                                        int64_t cap, int c, float eps, float momentum, const int32_t* count, int32_t* status,
+                                        int training, pda_stream_t stream) {
+    const char* what = "pda_bn_add_relu_fwd_counted";
+    pda::BnShape s;
+    if (int rc = pda::bn_counted_shape(cap, c, s, what)) return rc;
+    PDA_REQUIRE(x && identity && gamma && beta && y && mean_invstd && scratch && count && status, "%s: null pointer", what);
+    PDA_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "%s: running_mean/var must come together", what);
+    PDA_REQUIRE(training || running_mean, "%s: eval mode normalises with the running statistics", what);
+    PDA_REQUIRE((((uintptr_t)x | (uintptr_t)identity | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)mean_invstd) & 15) == 0,
+                "%s: pointers must be 16-byte aligned", what);
+    if (cap == 0) return PDA_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = pda::bn_grid(s);
+    if (training) {
+        hipLaunchKernelGGL(pda::bn_reduce_counted_kernel<false>, dim3(grid), dim3(256), 0, st, x, (const float*)nullptr,
+                           (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (double*)scratch, s, count, 0,
+                           (const float*)nullptr);
+        hipLaunchKernelGGL(pda::bn_finalize_fwd_counted_kernel, dim3(pda::divup(c, 32)), dim3(512), 0, st, (const double*)scratch, grid, c,
+                           cap, count, eps, momentum, mean_invstd, running_mean, running_var, status);
+    } else {
+        hipLaunchKernelGGL(pda::bn_eval_stats_kernel, dim3(pda::divup(c, 256)), dim3(256), 0, st, (const float*)running_mean,
+                           (const float*)running_var, c, eps, mean_invstd);
+    }
+    hipLaunchKernelGGL((pda::bn_apply_counted_kernel<false, true>), dim3(grid), dim3(256), 0, st, x, (const float*)nullptr,
+                       (const float*)mean_invstd, gamma, beta, (const float*)nullptr, y, s, count, 1, identity, (float*)nullptr);
+    return pda::check_launch(what);
+}
+
+PDA_API int pda_bn_add_relu_bwd_counted(const float* x, const float* y, const float* grad_y, const float* gamma, const float* beta,
+                                        const float* mean_invstd, float* grad_x, float* grad_identity, float* grad_gamma,
+                                        float* grad_beta, void* scratch, int64_t cap, int c, const int32_t* count, int training,
+                                        pda_stream_t stream) {
+    const char* what = "pda_bn_add_relu_bwd_counted";
+    pda::BnShape s;
+    if (int rc = pda::bn_counted_shape(cap, c, s, what)) return rc;
+    PDA_REQUIRE(x && y && grad_y && gamma && beta && mean_invstd && grad_x && grad_identity && grad_gamma && grad_beta && scratch && count,
+                "%s: null pointer", what);
+    PDA_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)grad_y | (uintptr_t)grad_x | (uintptr_t)grad_identity | (uintptr_t)gamma |
+                  (uintptr_t)beta | (uintptr_t)mean_invstd) & 15) == 0,
+                "%s: pointers must be 16-byte aligned", what);
+    if (cap == 0) {
+        if (hipMemsetAsync(grad_gamma, 0, (size_t)c * 4, (hipStream_t)stream) != hipSuccess ||
+            hipMemsetAsync(grad_beta, 0, (size_t)c * 4, (hipStream_t)stream) != hipSuccess)
+            return pda::check_launch(what);
+        return PDA_OK;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = pda::bn_grid(s);
+    float* sums = reinterpret_cast<float*>(reinterpret_cast<double*>(scratch) + (size_t)pda::BN_BLOCKS * 2 * c);
+    hipLaunchKernelGGL((pda::bn_reduce_counted_kernel<true, true>), dim3(grid), dim3(256), 0, st, x, grad_y, mean_invstd, gamma, beta,
+                       (double*)scratch, s, count, 1, y);
+    hipLaunchKernelGGL(pda::bn_finalize_bwd_counted_kernel, dim3(pda::divup(c, 32)), dim3(512), 0, st, (const double*)scratch, grid, c, cap,
+                       count, training, grad_gamma, grad_beta, sums);
+    hipLaunchKernelGGL((pda::bn_apply_counted_kernel<true, true>), dim3(grid), dim3(256), 0, st, x, grad_y, mean_invstd, gamma, beta,
+                       (const float*)sums, grad_x, s, count, 1, y, grad_identity);
     return pda::check_launch(what);
 }

@@ -95,12 +95,18 @@ def post_processing(batch_dict, post_process_cfg, num_class):
     if not batch_dict['cls_preds_normalized']:
         cls_preds = torch.sigmoid(cls_preds)
     scores, labels = torch.max(cls_preds, dim=-1)
+    valid = None
     if batch_dict.get('has_class_labels', False):
         # a two-stage head scores class-agnostically: the labels are the first stage's (detector3d_template.py:238-240)
         labels = batch_dict['roi_labels' if 'roi_labels' in batch_dict else 'batch_pred_labels'].view(B, -1)
+        if 'roi_labels' in batch_dict:
+            # CenterHead pads its RoIs with zero boxes of label 0 (proposal_layer's padding carries label 1): such a row is no
+            # proposal and does not become a prediction, whatever the second stage scores it (the reference lets it through)
+            valid = labels > 0
     else:
         labels = labels + 1
-    nms = class_agnostic_nms_batched(scores, box_preds, post_process_cfg["NMS_CONFIG"], score_thresh=post_process_cfg["SCORE_THRESH"])
+    nms = class_agnostic_nms_batched(scores, box_preds, post_process_cfg["NMS_CONFIG"], score_thresh=post_process_cfg["SCORE_THRESH"],
+                                     valid=valid)
     rows = {'pred_labels': labels}
     if post_process_cfg.get("OUTPUT_RAW_SCORE", False):
         rows['pred_scores'] = torch.max(src_cls_preds, dim=-1)[0]

@@ -6,13 +6,16 @@ BatchNorm1d(eps=1e-3, momentum=0.01) stays a plain module over the active rows. 
 per indice_key -- subm1, spconv2, subm2, spconv3, subm3, spconv4, subm4, spconv_down2; the Res form res1..res4 in place of
 subm2..subm4 and next to subm1 -- and makes four host reads, one per strided convolution.  A padded batch
 (voxel_num_active) makes none: the rulebooks keep their counts on the device, the BatchNorm1d modules run
-through the counted kernels, and model_cfg PADDED_CAPS says how many rows each strided convolution reserves."""
+through the counted kernels, the tail of a SparseBasicBlock -- relu(bn2(x) + identity) -- is one counted kernel pair
+(spconv_utils.counted_batch_norm_add_relu; PDA_RES_BN=composed keeps BatchNorm, `+` and ReLU apart, with the same bits), and
+model_cfg PADDED_CAPS says how many rows each strided convolution reserves."""
 from functools import partial
 
 import torch.nn as nn
 
 from . import spconv_utils as spconv
-from .spconv_utils import counted_batch_norm, replace_feature
+from .config import fused_or_composed
+from .spconv_utils import counted_batch_norm, counted_batch_norm_add_relu, replace_feature
 
 
 def post_act_block(in_channels, out_channels, kernel_size, indice_key=None, stride=1, padding=0, conv_type='subm', norm_fn=None):
@@ -49,6 +52,10 @@ class SparseBasicBlock(spconv.SparseModule):
         if x.num_active is not None:          # padded: counted BatchNorm, bn1's ReLU folded in; dead rows stay exact zeros
             out = replace_feature(out, counted_batch_norm(self.bn1, out.features, out.num_active, out.status, relu=True))
             out = self.conv2(out)
+            # PDA_RES_BN=composed: bn2, `+` and ReLU as three steps; the fused tail gives the same bits in one pass
+            if fused_or_composed("PDA_RES_BN") == "fused" and self.downsample is None:
+                return replace_feature(out, counted_batch_norm_add_relu(self.bn2, out.features, identity.features.contiguous(),
+                                                                        out.num_active, out.status))
             out = replace_feature(out, counted_batch_norm(self.bn2, out.features, out.num_active, out.status, relu=False))
         else:
             out = replace_feature(out, self.bn1(out.features))

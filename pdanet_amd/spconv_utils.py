@@ -342,11 +342,42 @@ class _CountedBatchNorm(torch.autograd.Function):
         return (g_x, g_w, g_b) + (None,) * 8
 
 
-def counted_batch_norm(bn, x, count, status, relu=False):
-    """nn.BatchNorm1d `bn` (+ ReLU) over the live rows [0, *count) of x (cap, C) through pda_bn_relu_*_counted, with the
-    module's own parameters and buffers: batch statistics in training mode (running statistics and num_batches_tracked
-    updated on the device), running statistics in eval mode.  Dead rows of the result and of the gradient are exact zeros.
-    Fewer than two live rows in training mode set FLAG_FEW_ROWS in *status where torch would have raised."""
+class _CountedBatchNormAddReLU(torch.autograd.Function):
+    """relu(bn(x) + identity): _CountedBatchNorm's statistics, one apply pass forward and one backward
+    (pda_bn_add_relu_*_counted).  The backward takes its ReLU mask from the saved output."""
+
+    @staticmethod
+    def forward(ctx, x, identity, weight, bias, running_mean, running_var, count, status, eps, momentum, training):
+        cap, c = x.shape
+        y = torch.empty_like(x)
+        stats = torch.empty((2, c), dtype=F32, device=x.device)
+        scratch = torch.empty((bn_relu_scratch_bytes(c),), dtype=torch.uint8, device=x.device)
+        if training and running_mean is not None:
+            _buffers_written(running_mean)
+        _call("pda_bn_add_relu_fwd_counted", x, x.data_ptr(), identity.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+              None if running_mean is None else running_mean.data_ptr(),
+              None if running_var is None else running_var.data_ptr(), y.data_ptr(), stats.data_ptr(), scratch.data_ptr(), cap, c,
+              float(eps), float(momentum), count.data_ptr(), status.data_ptr(), int(training))
+        ctx.save_for_backward(x, y, weight, bias, stats, count)
+        ctx.training = int(training)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, y, weight, bias, stats, count = ctx.saved_tensors
+        cap, c = x.shape
+        grad = grad.contiguous()
+        g_x, g_id = torch.empty_like(x), torch.empty_like(x)
+        g_w, g_b = torch.empty_like(weight), torch.empty_like(bias)
+        scratch = torch.empty((bn_relu_scratch_bytes(c),), dtype=torch.uint8, device=x.device)
+        _call("pda_bn_add_relu_bwd_counted", x, x.data_ptr(), y.data_ptr(), grad.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+              stats.data_ptr(), g_x.data_ptr(), g_id.data_ptr(), g_w.data_ptr(), g_b.data_ptr(), scratch.data_ptr(), cap, c,
+              count.data_ptr(), ctx.training)
+        return (g_x, g_id, g_w, g_b) + (None,) * 7
+
+
+def _counted_bn_mode(bn, x, count, status):
+    """The checks of a counted BatchNorm call and the module's mode; in training mode num_batches_tracked moves here."""
     _chk(x, "features", F32)
     _counted_args(count, status)
     if x.dim() != 2 or x.shape[1] != bn.num_features:
@@ -356,8 +387,30 @@ def counted_batch_norm(bn, x, count, status, relu=False):
     training = bn.training or bn.running_mean is None
     if training and bn.training and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
+    return bool(training)
+
+
+def counted_batch_norm(bn, x, count, status, relu=False):
+    """nn.BatchNorm1d `bn` (+ ReLU) over the live rows [0, *count) of x (cap, C) through pda_bn_relu_*_counted, with the
+    module's own parameters and buffers: batch statistics in training mode (running statistics and num_batches_tracked
+    updated on the device), running statistics in eval mode.  Dead rows of the result and of the gradient are exact zeros.
+    Fewer than two live rows in training mode set FLAG_FEW_ROWS in *status where torch would have raised."""
+    training = _counted_bn_mode(bn, x, count, status)
     return _CountedBatchNorm.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, count, status, bn.eps, bn.momentum,
-                                   bool(relu), bool(training))
+                                   bool(relu), training)
+
+
+def counted_batch_norm_add_relu(bn, x, identity, count, status):
+    """relu(bn(x) + identity) over the live rows [0, *count) of x and identity (cap, C), the tail of a residual block, through
+    pda_bn_add_relu_*_counted: the bits of counted_batch_norm(relu=False), `+` and ReLU one after the other, forward and
+    backward, in one apply pass each.  Mode, buffers, dead rows and FLAG_FEW_ROWS as in counted_batch_norm; dead rows of
+    identity are not read."""
+    training = _counted_bn_mode(bn, x, count, status)
+    _chk(identity, "identity", F32)
+    if identity.shape != x.shape:
+        raise ValueError("identity %s does not fit the features %s" % (tuple(identity.shape), tuple(x.shape)))
+    return _CountedBatchNormAddReLU.apply(x, identity, bn.weight, bn.bias, bn.running_mean, bn.running_var, count, status,
+                                          bn.eps, bn.momentum, training)
 
 
 def padded_report(batch_dict_or_tensor):
