@@ -456,6 +456,13 @@ int pda_nms_bev(const float *boxes, const int32_t *num_valid, int64_t *keep, int
 int pda_multi_nms_compact(const float *boxes, const float *scores, const int64_t *keep, const int32_t *num_keep,
                           const int32_t *label_map, int b, int c, int k, int post_max, float *pred_boxes, float *pred_scores,
                           int64_t *pred_labels, int32_t *num_pred, pda_stream_t stream);
+/* pda_multi_nms_compact for boxes (b * c, k, box_cols) and pred_boxes (b, c * cap, box_cols), box_cols in 7..9 (7 + custom
+ * columns): the same launch, every column of a kept row copied.  pda_nms_bev keeps reading 7-column rows, so the caller hands
+ * it a contiguous copy of columns 0..6 of the same rows and this entry the full rows; keep indexes both alike. */
+int pda_multi_nms_compact_wide(int box_cols, const float *boxes, const float *scores, const int64_t *keep,
+                               const int32_t *num_keep, const int32_t *label_map, int b, int c, int k, int post_max,
+                               float *pred_boxes, float *pred_scores, int64_t *pred_labels, int32_t *num_pred,
+                               pda_stream_t stream);
 
 /* ---- loss terms of the IA-SSD head, one launch each: the term AND its gradient (csrc/head_loss.hip) --------------------------
  * Replace the elementwise torch chains of IASSD_head.py:525-735, :1239-1321 and loss_utils.py:75-194, :340-363.  All tensors
@@ -1128,6 +1135,54 @@ int pda_anchor_multi_loss(const float *const *cls_preds, const float *const *box
                           double cls_weight, double loc_weight, double dir_weight, double dir_offset, double pos_cls_weight,
                           double neg_cls_weight, float *const *grad_cls, float *const *grad_box, float *const *grad_dir,
                           double *partials, float *out, pda_stream_t stream);
+/* The same five entries for ResidualCoder's wider codes (nuscenes_models/cbgs_*_multihead.yaml: code_size 9,
+ * encode_angle_by_sincos).  extra = gt_cols - 8 in 0..2 custom columns (velocities) stand behind the heading, sincos is 0 or 1,
+ * and a code row holds code = 6 + (sincos ? 2 : 1) + extra columns, 7..10: [x, y, z, log sizes, heading | cos, sin, custom].
+ * The anchors stay (n_anchors, 7): the reference pads them with zero columns, so a custom target is the gt's own value and a
+ * decoded custom column the code's own.  Every argument not named here, every check and every launch is that of the entry
+ * without the suffix, which runs the (code 7, sincos 0, smooth L1) instantiation of the same kernels.
+ *  - pda_anchor_assign_targets_coded, pda_anchor_multi_assign_targets_coded: gt_boxes (b, m, gt_cols), the label last; matching
+ *    reads columns 0..6 only.  box_reg_targets (b, n_anchors, code): columns 0..5 as before; with sincos columns 6, 7 are
+ *    cos(rg) - cos(ra) and sin(rg) - sin(ra), each cosine and sine evaluated in double and rounded once, the difference
+ *    float32; without, column 6 is rg - ra; the custom columns carry the gt's bits (a NaN velocity stays NaN).
+ *  - pda_anchor_loss_coded, pda_anchor_multi_loss_coded: box_preds, box_reg_targets and grad_box rows are code wide,
+ *    code_weights HOST (code).  reg_loss: PDA_REG_SMOOTH_L1 (WeightedSmoothL1Loss, beta 1/9) or PDA_REG_L1 (WeightedL1Loss:
+ *    |diff * code_weight| * weight, gradient sign(diff) * code_weight, 0 at diff == 0).  A NaN target contributes 0 to the
+ *    loss and the gradient under both.  The sine difference and the direction term read column 6 of a scalar heading only:
+ *    sincos with dir_cls_preds != NULL returns 1, and with sincos there is no sine difference.
+ *  - pda_anchor_decode_coded: batch_box_preds (b, n_anchors, 7 + extra).  With sincos the heading is
+ *    atan2(sin_t + sin(ra), cos_t + cos(ra)): sin(ra), cos(ra) in double and rounded once, the sums float32, the atan2 in
+ *    double and rounded once; no direction bins.  Custom columns are t + 0.
+ * Out-of-range gt_cols / code, a sincos or reg_loss that is no such value, sincos with dir_cls_preds and null pointers return
+ * 1 with pda_last_error() naming the argument, before any pointer is used. */
+#define PDA_REG_SMOOTH_L1 0
+#define PDA_REG_L1 1
+int pda_anchor_assign_targets_coded(const float *gt_boxes, int gt_cols, int sincos, int b, int m, const float *anchors,
+                                    int n_anchors, int n_cls, const int32_t *class_label, const float *matched,
+                                    const float *unmatched, const int32_t *class_count, uint32_t *col_max,
+                                    int32_t *box_cls_labels, float *box_reg_targets, float *reg_weights, int32_t *num_pos,
+                                    pda_stream_t stream);
+int pda_anchor_multi_assign_targets_coded(const float *gt_boxes, int gt_cols, int sincos, int b, int m, const float *anchors,
+                                          int n_anchors, int n_cls, const int32_t *class_label, const float *matched,
+                                          const float *unmatched, const int32_t *class_rows, uint32_t *col_max,
+                                          int32_t *box_cls_labels, float *box_reg_targets, float *reg_weights, int32_t *num_pos,
+                                          pda_stream_t stream);
+int pda_anchor_loss_coded(int code, int sincos, int reg_loss, const float *cls_preds, const float *box_preds,
+                          const float *dir_cls_preds, const int32_t *box_cls_labels, const float *box_reg_targets,
+                          const int32_t *num_pos, const float *anchors, int b, int n_anchors, int num_class, int bins,
+                          const float *code_weights, double cls_weight, double loc_weight, double dir_weight, double dir_offset,
+                          float *grad_cls, float *grad_box, float *grad_dir, double *partials, float *out, pda_stream_t stream);
+int pda_anchor_multi_loss_coded(int code, int sincos, int reg_loss, const float *const *cls_preds, const float *const *box_preds,
+                                const float *const *dir_cls_preds, int n_heads, const int32_t *head_rows,
+                                const int32_t *head_cols, const int32_t *head_col_base, const int32_t *box_cls_labels,
+                                const float *box_reg_targets, const int32_t *num_pos, const float *anchors, int b, int n_anchors,
+                                int num_class, int bins, const float *code_weights, double cls_weight, double loc_weight,
+                                double dir_weight, double dir_offset, double pos_cls_weight, double neg_cls_weight,
+                                float *const *grad_cls, float *const *grad_box, float *const *grad_dir, double *partials,
+                                float *out, pda_stream_t stream);
+int pda_anchor_decode_coded(int code, int sincos, const float *box_preds, const float *dir_cls_preds, const float *anchors, int b,
+                            int n_anchors, int bins, double dir_offset, double dir_limit_offset, float *batch_box_preds,
+                            pda_stream_t stream);
 /* PillarVFE's PFN input rows: voxels (v, p, c) float32 (c >= 3, padded rows zero), voxel_num_points (v) int32, voxel_coords
  * (v, 4) int32 (b, z, y, x) -> out (v, p, c' ) with c' = (absolute_xyz ? c : c - 3) + 6 + (with_distance ? 1 : 0): [the raw
  * columns (from column 3 on without absolute_xyz), xyz - mean, xyz - cell centre, |xyz|]; rows from num_points on are exactly

@@ -261,6 +261,16 @@ SIGNATURES = {
     "pda_anchor_multi_loss": [ctypes.POINTER(_vp)] * 3 + [_i] + [ctypes.POINTER(ctypes.c_int32)] * 3 + [_vp] * 4 + [_i] * 4
                              + [ctypes.POINTER(_f)] + [ctypes.c_double] * 6 + [ctypes.POINTER(_vp)] * 3 + [_vp] * 3,
     "pda_multi_nms_compact": [_vp] * 5 + [_i] * 4 + [_vp] * 5,
+    "pda_anchor_assign_targets_coded": [_vp, _i, _i, _i, _i, _vp, _i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_f),
+                                        ctypes.POINTER(_f), ctypes.POINTER(ctypes.c_int32), _vp, _vp, _vp, _vp, _vp, _vp],
+    "pda_anchor_multi_assign_targets_coded": [_vp, _i, _i, _i, _i, _vp, _i, _i, ctypes.POINTER(ctypes.c_int32),
+                                              ctypes.POINTER(_f), ctypes.POINTER(_f), ctypes.POINTER(ctypes.c_int32), _vp, _vp, _vp,
+                                              _vp, _vp, _vp],
+    "pda_anchor_loss_coded": [_i] * 3 + [_vp] * 7 + [_i] * 4 + [ctypes.POINTER(_f)] + [ctypes.c_double] * 4 + [_vp] * 6,
+    "pda_anchor_decode_coded": [_i, _i, _vp, _vp, _vp, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp, _vp],
+    "pda_anchor_multi_loss_coded": [_i] * 3 + [ctypes.POINTER(_vp)] * 3 + [_i] + [ctypes.POINTER(ctypes.c_int32)] * 3 + [_vp] * 4
+                                   + [_i] * 4 + [ctypes.POINTER(_f)] + [ctypes.c_double] * 6 + [ctypes.POINTER(_vp)] * 3 + [_vp] * 3,
+    "pda_multi_nms_compact_wide": [_i] + [_vp] * 5 + [_i] * 4 + [_vp] * 5,
     "pda_pillar_features": [_vp, _vp, _vp, ctypes.c_int64, _i, _i, ctypes.POINTER(_f), ctypes.POINTER(_f), _i, _i, _vp, _vp],
     "pda_spconv_index_workspace_bytes": [ctypes.c_int64, ctypes.c_int64, _i],
     "pda_spconv_index_subm": [_vp, ctypes.c_int64] + [_i] * 7 + [_vp, _vp, _vp, _vp],

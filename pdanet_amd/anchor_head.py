@@ -89,6 +89,7 @@ def anchor_table(anchors):
 
 class AxisAlignedTargetAssigner(object):
     CLASS_MAJOR = False       # anchor_head_multi.ClassMajorTargetAssigner: the table of USE_MULTIHEAD
+    CODED = False             # anchor_head_coded: sin-cos headings and custom columns
     ENTRY = "pda_anchor_assign_targets"
 
     def __init__(self, model_cfg, class_names, box_coder, match_height=False):
@@ -108,8 +109,8 @@ class AxisAlignedTargetAssigner(object):
         if bool(field(model_cfg, 'USE_MULTIHEAD', False)) != self.CLASS_MAJOR:
             raise NotImplementedError("USE_MULTIHEAD: %s (anchor_head_multi.AnchorHeadMulti has the class-major assigner)"
                                       % field(model_cfg, 'USE_MULTIHEAD', False))
-        if getattr(box_coder, 'encode_angle_by_sincos', False) or box_coder.code_size != 7:
-            raise NotImplementedError("encode_angle_by_sincos / a code size other than 7")
+        if not self.CODED and (getattr(box_coder, 'encode_angle_by_sincos', False) or box_coder.code_size != 7):
+            raise NotImplementedError("encode_angle_by_sincos / a code size other than 7 (anchor_head_coded has them)")
         self.pos_fraction = None
         self.sample_size = target_cfg['SAMPLE_SIZE']
         self.norm_by_num_examples = False
@@ -181,14 +182,14 @@ def _one(dev):
 class _AnchorLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cls_preds, box_preds, dir_preds, labels, targets, num_pos, table, host):
-        code_w, cls_w, loc_w, dir_w, dir_offset, num_class, bins = host
+        code_w, cls_w, loc_w, dir_w, dir_offset, num_class, bins, *coded = host      # coded: (code, sincos, reg_loss)
         B, N = labels.shape
         dev = cls_preds.device
         out = torch.empty((4,), dtype=F32, device=dev)
         g_cls, g_box = torch.empty_like(cls_preds), torch.empty_like(box_preds)
         g_dir = torch.empty_like(dir_preds) if dir_preds is not None else None
         partials = _partials("pda_anchor_loss_blocks", B * N, dev)
-        _call("pda_anchor_loss", cls_preds, cls_preds.data_ptr(), box_preds.data_ptr(),
+        _call("pda_anchor_loss_coded" if coded else "pda_anchor_loss", cls_preds, *coded, cls_preds.data_ptr(), box_preds.data_ptr(),
               None if dir_preds is None else dir_preds.data_ptr(), labels.data_ptr(), targets.data_ptr(), num_pos.data_ptr(),
               table.data_ptr(), B, N, num_class, bins, code_w, cls_w, loc_w, dir_w, dir_offset, g_cls.data_ptr(),
               g_box.data_ptr(), None if g_dir is None else g_dir.data_ptr(), partials.data_ptr(), out.data_ptr())
@@ -264,6 +265,7 @@ def anchor_decode(box_preds, dir_cls_preds, table, dir_offset=0.0, dir_limit_off
 
 class AnchorHeadTemplate(nn.Module):
     MULTIHEAD = False         # anchor_head_multi.AnchorHeadMulti: USE_MULTIHEAD, the class-major table
+    CODED = False             # anchor_head_coded: sin-cos headings, custom columns, WeightedL1Loss
 
     def __init__(self, model_cfg, num_class, class_names, grid_size, point_cloud_range, predict_boxes_when_training):
         super().__init__()
@@ -281,13 +283,14 @@ class AnchorHeadTemplate(nn.Module):
             raise NotImplementedError("BOX_CODER %r" % (coder,))
         self.box_coder = box_coder_utils.ResidualCoder(num_dir_bins=field(target_cfg, 'NUM_DIR_BINS', 6),
                                                        **(field(target_cfg, 'BOX_CODER_CONFIG', None) or {}))
-        if self.box_coder.encode_angle_by_sincos or self.box_coder.code_size != 7:
-            raise NotImplementedError("encode_angle_by_sincos / boxes with more than 7 columns")
+        if not self.CODED and (self.box_coder.encode_angle_by_sincos or self.box_coder.code_size != 7):
+            raise NotImplementedError("encode_angle_by_sincos / boxes with more than 7 columns (anchor_head_coded has them)")
         generator_cfg = model_cfg['ANCHOR_GENERATOR_CONFIG']
         if not self.MULTIHEAD and len({c['feature_map_stride'] for c in generator_cfg}) != 1:
             raise NotImplementedError("anchor classes with different feature_map_stride (the reference's torch.cat fails there)")
         anchors, self.num_anchors_per_location = self.generate_anchors(
-            generator_cfg, grid_size=grid_size, point_cloud_range=point_cloud_range, anchor_ndim=self.box_coder.code_size)
+            generator_cfg, grid_size=grid_size, point_cloud_range=point_cloud_range,
+            anchor_ndim=7 if self.CODED else self.box_coder.code_size)      # coded: the table stays 7 wide, the zero columns implied
         self.anchors = anchors                     # host tensors, the reference's bits; the device table is made once
         self.target_assigner = self.get_target_assigner(target_cfg)
         self.forward_ret_dict = {}

@@ -47,7 +47,7 @@ class ClassMajorTargetAssigner(AxisAlignedTargetAssigner):
 class _AnchorMultiLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, host, labels, targets, num_pos, table, *preds):
-        rows, cols, bases, num_class, bins, code_w, weights = host
+        rows, cols, bases, num_class, bins, code_w, weights, *coded = host      # coded: (code, sincos, reg_loss)
         H = len(rows)
         cls, box, dirs = preds[:H], preds[H:2 * H], preds[2 * H:]
         B, N = labels.shape
@@ -56,7 +56,7 @@ class _AnchorMultiLoss(torch.autograd.Function):
         grads = [torch.empty_like(p) for p in preds]
         partials = _partials("pda_anchor_multi_loss_blocks", B * N, dev)
         i32 = lambda v: (ctypes.c_int32 * H)(*v)
-        _call("pda_anchor_multi_loss", labels, _ptr_array(cls), _ptr_array(box), _ptr_array(dirs) if dirs else None, H, i32(rows),
+        _call("pda_anchor_multi_loss_coded" if coded else "pda_anchor_multi_loss", labels, *coded, _ptr_array(cls), _ptr_array(box), _ptr_array(dirs) if dirs else None, H, i32(rows),
               i32(cols), i32(bases), labels.data_ptr(), targets.data_ptr(), num_pos.data_ptr(), table.data_ptr(), B, N, num_class,
               bins, code_w, *weights, _ptr_array(grads[:H]), _ptr_array(grads[H:2 * H]),
               _ptr_array(grads[2 * H:]) if dirs else None, partials.data_ptr(), out.data_ptr())

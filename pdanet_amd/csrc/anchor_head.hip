@@ -28,6 +28,7 @@ constexpr int AH_TILE = 64;           // gt rows staged in LDS at a time
 constexpr int AH_MAX_SLOTS = 64;      // anchors per location, all classes
 constexpr int AH_MAX_CLASSES = 32;    // anchor classes; also num_class of the loss and the heads of a multihead
 constexpr int AH_MAX_BINS = 8;        // NUM_DIR_BINS
+constexpr int AH_MAX_CODE = 10;       // columns of a box code: 6 + cos, sin + two custom columns
 
 struct AnchorAssignCfg {
     int b, m, cols, n_anchors, slots, n_cls;
@@ -76,7 +77,9 @@ __global__ __launch_bounds__(AH_THREADS) void anchor_clear_kernel(int32_t* __res
 // SECOND == true: the same IoUs again; labels, targets, weights and the scene's positives.
 // grid (ceil(n_anchors / 256), b); anchor n of a scene is row n of `anchors`, its class the owner of slot n % slots, or with
 // SEGMENTED the owner of row n; `slot` then is the class itself.
-template <bool SECOND, bool SEGMENTED>
+// CODE, SINCOS (SECOND only): the width of a target row, 6 + (SINCOS ? 2 : 1) + extra, and encode_angle_by_sincos; the gt rows
+// then hold 7 + extra + 1 columns, the label last.  <.., 7, false> is ResidualCoder's plain code.
+template <bool SECOND, bool SEGMENTED, int CODE = 7, bool SINCOS = false>
 __global__ __launch_bounds__(AH_THREADS) void anchor_assign_kernel(const float* __restrict__ anchors,
                                                                    const float* __restrict__ gt, AnchorAssignCfg g,
                                                                    uint32_t* __restrict__ col_max,
@@ -172,7 +175,10 @@ __global__ __launch_bounds__(AH_THREADS) void anchor_assign_kernel(const float* 
         else label = -1;
     }
     if (live) {
-        float t[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        constexpr int ANGLE = SINCOS ? 2 : 1, EXTRA = CODE - 6 - ANGLE;
+        float t[CODE];
+#pragma unroll
+        for (int c = 0; c < CODE; ++c) t[c] = 0.f;
         if (pos) {
             label = my_label;
             const float* row = sgt + (size_t)row_arg * g.cols;
@@ -186,13 +192,21 @@ __global__ __launch_bounds__(AH_THREADS) void anchor_assign_kernel(const float* 
             t[3] = (float)log((double)(dxg / dxa));
             t[4] = (float)log((double)(dyg / dya));
             t[5] = (float)log((double)(dzg / dza));
-            t[6] = row[6] - a[6];
+            if (SINCOS) {      // each cosine and sine in double, rounded once; the differences in float32
+                t[6] = (float)cos((double)row[6]) - (float)cos((double)a[6]);
+                t[7] = (float)sin((double)row[6]) - (float)sin((double)a[6]);
+            } else {
+                t[6] = row[6] - a[6];
+            }
+            // the custom columns against the zero columns the reference pads its anchors with: the gt's own bits
+#pragma unroll
+            for (int c = 0; c < EXTRA; ++c) t[6 + ANGLE + c] = row[7 + c];
         }
         const size_t e = (size_t)s * g.n_anchors + n;
         labels[e] = label;
         weights[e] = pos ? 1.f : 0.f;
 #pragma unroll
-        for (int c = 0; c < 7; ++c) targets[e * 7 + c] = t[c];
+        for (int c = 0; c < CODE; ++c) targets[e * CODE + c] = t[c];
     }
     const uint64_t mask = __ballot(pos);
     if (lane == 0 && mask) atomicAdd(num_pos + s, (int)__popcll(mask));
@@ -205,7 +219,7 @@ constexpr int AL_MAX_BLOCKS = 2048;
 
 struct AnchorLossCfg {
     int b, n_anchors, num_class, bins;
-    float code_weight[7];
+    float code_weight[AH_MAX_CODE];
     float dir_offset, two_pi, bin_width;      // float32 roundings of DIR_OFFSET, 2 pi, 2 pi / bins
     double cls_scale, loc_scale, dir_scale;   // weight / b
 };
@@ -213,11 +227,14 @@ struct AnchorLossCfg {
 // The terms of one anchor, with w = 1 / max(num_pos[scene], 1):
 //   cls: SigmoidFocalClassificationLoss(alpha 0.25, gamma 2) over the row's n_cols logits, the one-hot at column hot_col
 //        (-1: none), weight w_cls (0 for an ignored anchor);
-//   loc: WeightedSmoothL1Loss(beta 1/9), after add_sin_difference on column 6 when sin_diff, weight (label > 0) * w, a NaN
-//        target 0;
-//   dir: softmax cross-entropy against the direction bin, weight (label > 0) * w; dp == nullptr: no direction classifier.
+//   loc: WeightedSmoothL1Loss(beta 1/9), or with L1 WeightedL1Loss, over the row's CODE columns, after add_sin_difference
+//        on column 6 when sin_diff (never with SINCOS, whose columns 6 and 7 are a cosine and a sine difference), weight
+//        (label > 0) * w, a NaN target 0;
+//   dir: softmax cross-entropy against the direction bin, weight (label > 0) * w; dp == nullptr: no direction classifier
+//        (always with SINCOS).
 // Every pointer is the anchor's own row.  The gradients hold d(rpn_loss) / d(prediction) for an incoming gradient of 1 and
 // are written whole; s_cls, s_loc, s_dir gather the unscaled sums.
+template <int CODE, bool SINCOS, bool L1>
 __device__ __forceinline__ void anchor_loss_row(const AnchorLossCfg& g, int label, double w_cls, double w, int hot_col, int n_cols,
                                                 bool sin_diff, const float* __restrict__ cls, const float* __restrict__ pr,
                                                 const float* __restrict__ tg, const float* __restrict__ anchor,
@@ -242,17 +259,19 @@ __device__ __forceinline__ void anchor_loss_row(const AnchorLossCfg& g, int labe
         grad_cls[k] = gr;
     }
     // regression and direction: positives only
-    float gb[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float gb[CODE];
+#pragma unroll
+    for (int c = 0; c < CODE; ++c) gb[c] = 0.f;
     float gd[AH_MAX_BINS];
 #pragma unroll
     for (int k = 0; k < AH_MAX_BINS; ++k) gd[k] = 0.f;
     if (label > 0) {
 #pragma unroll
-        for (int c = 0; c < 7; ++c) {
+        for (int c = 0; c < CODE; ++c) {
             const float tf = tg[c];
             if (is_nan_bits(tf)) continue;
             double p = (double)pr[c], t = (double)tf, chain = 1.0;
-            if (c == 6 && sin_diff) {      // sin(a - b) = sin a cos b - cos a sin b, both halves differentiated in the prediction
+            if (!SINCOS && c == 6 && sin_diff) {      // sin(a - b) = sin a cos b - cos a sin b, both halves differentiated in the prediction
                 const double a0 = p, b0 = t;
                 p = sin(a0) * cos(b0);
                 t = cos(a0) * sin(b0);
@@ -260,11 +279,12 @@ __device__ __forceinline__ void anchor_loss_row(const AnchorLossCfg& g, int labe
             }
             const double diff = (p - t) * (double)g.code_weight[c];
             const double ad = fabs(diff);
-            s_loc += (ad < beta ? 0.5 * ad * ad / beta : ad - 0.5 * beta) * w;
-            const double dl = ad < beta ? diff / beta : (diff > 0.0 ? 1.0 : (diff < 0.0 ? -1.0 : 0.0));
+            const double sign = diff > 0.0 ? 1.0 : (diff < 0.0 ? -1.0 : 0.0);
+            s_loc += (L1 ? ad : (ad < beta ? 0.5 * ad * ad / beta : ad - 0.5 * beta)) * w;
+            const double dl = L1 ? sign : (ad < beta ? diff / beta : sign);
             gb[c] = (float)(dl * (double)g.code_weight[c] * chain * w * g.loc_scale);
         }
-        if (dp) {
+        if (!SINCOS && dp) {
             // get_direction_target in float32, as the reference evaluates it
             const float rot_gt = tg[6] + anchor[6];
             const float val = rot_gt - g.dir_offset;
@@ -283,8 +303,8 @@ __device__ __forceinline__ void anchor_loss_row(const AnchorLossCfg& g, int labe
         }
     }
 #pragma unroll
-    for (int c = 0; c < 7; ++c) grad_box[c] = gb[c];
-    if (dp) {
+    for (int c = 0; c < CODE; ++c) grad_box[c] = gb[c];
+    if (!SINCOS && dp) {
 #pragma unroll
         for (int k = 0; k < AH_MAX_BINS; ++k)
             if (k < g.bins) grad_dir[k] = gd[k];
@@ -292,6 +312,7 @@ __device__ __forceinline__ void anchor_loss_row(const AnchorLossCfg& g, int labe
 }
 
 // One anchor per thread and step over (b, n_anchors), every prediction one tensor; partials (3, blocks) the unscaled sums.
+template <int CODE, bool SINCOS, bool L1>
 __global__ __launch_bounds__(AL_THREADS) void anchor_loss_kernel(
         const float* __restrict__ cls_preds, const float* __restrict__ box_preds, const float* __restrict__ dir_preds,
         const int32_t* __restrict__ labels, const float* __restrict__ targets, const int32_t* __restrict__ num_pos,
@@ -306,17 +327,18 @@ __global__ __launch_bounds__(AL_THREADS) void anchor_loss_kernel(
         const int label = labels[e];
         const double w = 1.0 / (double)max(num_pos[s], 1);
         const int hot_col = label > 0 ? (g.num_class == 1 ? 0 : label - 1) : -1;      // class-agnostic: every positive is class 1
-        anchor_loss_row(g, label, w, w, hot_col, g.num_class, true, cls_preds + (size_t)e * g.num_class, box_preds + (size_t)e * 7,
-                        targets + (size_t)e * 7, anchors + (size_t)n * 7,
+        anchor_loss_row<CODE, SINCOS, L1>(
+                        g, label, w, w, hot_col, g.num_class, true, cls_preds + (size_t)e * g.num_class, box_preds + (size_t)e * CODE,
+                        targets + (size_t)e * CODE, anchors + (size_t)n * 7,
                         dir_preds ? dir_preds + (size_t)e * g.bins : nullptr, grad_cls + (size_t)e * g.num_class,
-                        grad_box + (size_t)e * 7, dir_preds ? grad_dir + (size_t)e * g.bins : nullptr, s_cls, s_loc, s_dir);
+                        grad_box + (size_t)e * CODE, dir_preds ? grad_dir + (size_t)e * g.bins : nullptr, s_cls, s_loc, s_dir);
     }
     const double sums[3] = {s_cls, s_loc, s_dir};
     block_sums_to_partials<3, AL_THREADS>(sums, partials);
 }
 
 // AnchorHeadMulti: head h owns the rows [row0[h], row0[h + 1]) of the class-major table and predicts them in tensors of its own,
-// cls (b, rows_h, cols[h]), box (b, rows_h, 7), dir (b, rows_h, bins); labels, targets and anchors stay (b, n_anchors, ..).
+// cls (b, rows_h, cols[h]), box (b, rows_h, CODE), dir (b, rows_h, bins); labels, targets and anchors stay (b, n_anchors, ..) and (n_anchors, 7).
 struct AnchorMultiLossCfg {
     AnchorLossCfg t;                    // t.num_class: the detector's (1 = class-agnostic)
     int n_heads, sin_diff;
@@ -334,6 +356,7 @@ struct AnchorMultiLossCfg {
 
 // The elements run head after head, (scene, row) inside a head, so that neighbouring threads read neighbouring rows of one
 // head's tensors; the per-head descriptors are staged in LDS, where a per-thread head index costs nothing.
+template <int CODE, bool SINCOS, bool L1>
 __global__ __launch_bounds__(AL_THREADS) void anchor_multi_loss_kernel(const int32_t* __restrict__ labels,
                                                                         const float* __restrict__ targets,
                                                                         const int32_t* __restrict__ num_pos,
@@ -378,9 +401,10 @@ __global__ __launch_bounds__(AL_THREADS) void anchor_multi_loss_kernel(const int
         const int c = h_cols[h];
         const int hot_col = label > 0 ? (g.t.num_class == 1 ? 0 : label - 1 - h_base[h]) : -1;
         const float* dir = h_dir[h];
-        anchor_loss_row(g.t, label, w_cls, w, hot_col, c, g.sin_diff != 0, h_cls[h] + hr * c, h_box[h] + hr * 7, targets + at * 7,
+        anchor_loss_row<CODE, SINCOS, L1>(
+                        g.t, label, w_cls, w, hot_col, c, g.sin_diff != 0, h_cls[h] + hr * c, h_box[h] + hr * CODE, targets + at * CODE,
                         anchors + (size_t)n * 7, dir ? dir + hr * g.t.bins : nullptr, h_gcls[h] + hr * c,
-                        h_gbox[h] + hr * 7, dir ? h_gdir[h] + hr * g.t.bins : nullptr, s_cls, s_loc, s_dir);
+                        h_gbox[h] + hr * CODE, dir ? h_gdir[h] + hr * g.t.bins : nullptr, s_cls, s_loc, s_dir);
     }
     const double sums[3] = {s_cls, s_loc, s_dir};
     block_sums_to_partials<3, AL_THREADS>(sums, partials);
@@ -406,7 +430,11 @@ struct AnchorDecodeCfg {
     float dir_offset, dir_limit_offset, period;
 };
 
-// generate_predicted_boxes: ResidualCoder.decode_torch against the anchors, then the direction classifier's bin.
+// generate_predicted_boxes: ResidualCoder.decode_torch against the anchors, then the direction classifier's bin.  A code of
+// CODE columns gives a box of 7 + extra, the custom columns the code's own (the anchors' are zero); with SINCOS the heading is
+// atan2(sin + sin(ra), cos + cos(ra)): sin(ra) and cos(ra) in double and rounded once, the sums float32, the atan2 in double
+// and rounded once, and there is no direction bin.
+template <int CODE, bool SINCOS>
 __global__ __launch_bounds__(256) void anchor_decode_kernel(const float* __restrict__ box_preds,
                                                             const float* __restrict__ dir_preds,
                                                             const float* __restrict__ anchors, AnchorDecodeCfg g,
@@ -415,8 +443,9 @@ __global__ __launch_bounds__(256) void anchor_decode_kernel(const float* __restr
     if (e >= (long long)g.b * g.n_anchors) return;
     const int n = (int)(e % g.n_anchors);
     const float* a = anchors + (size_t)n * 7;
-    const float* t = box_preds + (size_t)e * 7;
-    float* o = out + (size_t)e * 7;
+    constexpr int ANGLE = SINCOS ? 2 : 1, EXTRA = CODE - 6 - ANGLE;
+    const float* t = box_preds + (size_t)e * CODE;
+    float* o = out + (size_t)e * (7 + EXTRA);
     const float dxa = a[3], dya = a[4], dza = a[5];
     const float diagonal = sqrtf(dxa * dxa + dya * dya);
     o[0] = t[0] * diagonal + a[0];
@@ -425,8 +454,15 @@ __global__ __launch_bounds__(256) void anchor_decode_kernel(const float* __restr
     o[3] = (float)exp((double)t[3]) * dxa;
     o[4] = (float)exp((double)t[4]) * dya;
     o[5] = (float)exp((double)t[5]) * dza;
-    float rg = t[6] + a[6];
-    if (dir_preds) {
+    float rg;
+    if (SINCOS) {
+        const float sn = t[7] + (float)sin((double)a[6]);
+        const float cs = t[6] + (float)cos((double)a[6]);
+        rg = (float)atan2((double)sn, (double)cs);
+    } else {
+        rg = t[6] + a[6];
+    }
+    if (!SINCOS && dir_preds) {
         const float* dp = dir_preds + (size_t)e * g.bins;
         int best = 0;
         float top = dp[0];
@@ -440,6 +476,8 @@ __global__ __launch_bounds__(256) void anchor_decode_kernel(const float* __restr
         rg = (dir_rot + g.dir_offset) + g.period * (float)best;
     }
     o[6] = rg;
+#pragma unroll
+    for (int c = 0; c < EXTRA; ++c) o[7 + c] = t[6 + ANGLE + c] + 0.f;      // decode_torch's t + a against a zero anchor column
 }
 
 }  // namespace
@@ -449,17 +487,38 @@ __global__ __launch_bounds__(256) void anchor_decode_kernel(const float* __restr
 namespace pda {
 namespace {
 
+// The instantiations of a (code, sincos) pair: code = 6 + (sincos ? 2 : 1) + extra with extra in 0..2.  CALL(CODE, SINCOS) is
+// expanded for the pair that holds; the callers have checked the range.
+#define PDA_ANCHOR_CODED(code, sincos, CALL)     \
+    switch ((code) * 2 + ((sincos) ? 1 : 0)) {   \
+        case 14: CALL(7, false); break;          \
+        case 16: CALL(8, false); break;          \
+        case 18: CALL(9, false); break;          \
+        case 17: CALL(8, true); break;           \
+        case 19: CALL(9, true); break;           \
+        case 21: CALL(10, true); break;          \
+        default: break;                          \
+    }
+
 // Both layouts of the anchor table.  class_count: the slots a class owns at every location (location-major), or with
-// `segmented` the contiguous rows it owns (class-major).
-int assign_targets(const char* what, bool segmented, const float* gt_boxes, int gt_cols, int b, int m, const float* anchors,
+// `segmented` the contiguous rows it owns (class-major).  coded: the entry takes gt rows of 7 + extra + 1 columns and `sincos`.
+int assign_targets(const char* what, bool segmented, bool coded, int sincos, const float* gt_boxes, int gt_cols, int b, int m, const float* anchors,
                    int n_anchors, int n_cls, const int32_t* class_label, const float* matched, const float* unmatched,
                    const int32_t* class_count, uint32_t* col_max, int32_t* box_cls_labels, float* box_reg_targets,
                    float* reg_weights, int32_t* num_pos, pda_stream_t stream) {
     PDA_REQUIRE(b >= 0 && m >= 0 && n_anchors >= 0, "%s: b=%d m=%d n_anchors=%d", what, b, m, n_anchors);
-    PDA_REQUIRE(gt_cols == 8, "%s: gt_cols=%d, boxes must have 7 + 1 columns", what, gt_cols);
+    if (coded) {
+        PDA_REQUIRE(gt_cols >= 8 && gt_cols <= 10, "%s: gt_cols=%d, boxes must have 7 + extra + 1 columns with extra in 0..2", what,
+                    gt_cols);
+        PDA_REQUIRE(sincos == 0 || sincos == 1, "%s: sincos=%d is no flag", what, sincos);
+    } else {
+        PDA_REQUIRE(gt_cols == 8, "%s: gt_cols=%d, boxes must have 7 + 1 columns", what, gt_cols);
+    }
+    const int code = 6 + (sincos ? 2 : 1) + (gt_cols - 8);
     PDA_REQUIRE(n_cls >= 1 && n_cls <= AH_MAX_CLASSES, "%s: n_cls=%d outside 1..%d", what, n_cls, AH_MAX_CLASSES);
     PDA_REQUIRE(b <= 65535, "%s: batch %d > 65535", what, b);
-    PDA_REQUIRE((int64_t)b * n_anchors < ((int64_t)1 << 31) / 8, "%s: b=%d n_anchors=%d too large", what, b, n_anchors);
+    PDA_REQUIRE((int64_t)b * n_anchors < ((int64_t)1 << 31) / (code > 8 ? 16 : 8), "%s: b=%d n_anchors=%d too large", what, b,
+                n_anchors);
     PDA_REQUIRE((int64_t)b * m < ((int64_t)1 << 28), "%s: b=%d m=%d too large", what, b, m);
     if (b == 0 || n_anchors == 0) return PDA_OK;
     PDA_REQUIRE(class_label && matched && unmatched && class_count, "%s: null class array", what);
@@ -504,7 +563,11 @@ int assign_targets(const char* what, bool segmented, const float* gt_boxes, int 
                            m > 0 ? col_max : (uint32_t*)nullptr, (int64_t)b * m);
     const dim3 grid(divup(n_anchors, AH_THREADS), b);
     auto first = segmented ? anchor_assign_kernel<false, true> : anchor_assign_kernel<false, false>;
-    auto second = segmented ? anchor_assign_kernel<true, true> : anchor_assign_kernel<true, false>;
+    auto second = first;
+#define PDA_SECOND(CODE, SINCOS) \
+    second = segmented ? anchor_assign_kernel<true, true, CODE, SINCOS> : anchor_assign_kernel<true, false, CODE, SINCOS>
+    PDA_ANCHOR_CODED(code, sincos, PDA_SECOND)
+#undef PDA_SECOND
     if (m > 0)
         hipLaunchKernelGGL(first, grid, dim3(AH_THREADS), 0, st, anchors, gt_boxes, g, col_max, (int32_t*)nullptr,
                            (float*)nullptr, (float*)nullptr, (int32_t*)nullptr);
@@ -520,7 +583,7 @@ PDA_API int pda_anchor_assign_targets(const float* gt_boxes, int gt_cols, int b,
                                       int n_cls, const int32_t* class_label, const float* matched, const float* unmatched,
                                       const int32_t* class_count, uint32_t* col_max, int32_t* box_cls_labels,
                                       float* box_reg_targets, float* reg_weights, int32_t* num_pos, pda_stream_t stream) {
-    return pda::assign_targets("pda_anchor_assign_targets", false, gt_boxes, gt_cols, b, m, anchors, n_anchors, n_cls, class_label,
+    return pda::assign_targets("pda_anchor_assign_targets", false, false, 0, gt_boxes, gt_cols, b, m, anchors, n_anchors, n_cls, class_label,
                                matched, unmatched, class_count, col_max, box_cls_labels, box_reg_targets, reg_weights, num_pos,
                                stream);
 }
@@ -529,7 +592,7 @@ PDA_API int pda_anchor_multi_assign_targets(const float* gt_boxes, int gt_cols, 
                                             int n_cls, const int32_t* class_label, const float* matched, const float* unmatched,
                                             const int32_t* class_rows, uint32_t* col_max, int32_t* box_cls_labels,
                                             float* box_reg_targets, float* reg_weights, int32_t* num_pos, pda_stream_t stream) {
-    return pda::assign_targets("pda_anchor_multi_assign_targets", true, gt_boxes, gt_cols, b, m, anchors, n_anchors, n_cls,
+    return pda::assign_targets("pda_anchor_multi_assign_targets", true, false, 0, gt_boxes, gt_cols, b, m, anchors, n_anchors, n_cls,
                                class_label, matched, unmatched, class_rows, col_max, box_cls_labels, box_reg_targets, reg_weights,
                                num_pos, stream);
 }
@@ -538,27 +601,41 @@ PDA_API int64_t pda_anchor_loss_blocks(int64_t n) {
     return pda::partial_blocks(n, (int64_t)pda::AL_THREADS * pda::AL_PER_THREAD, pda::AL_MAX_BLOCKS);
 }
 
-PDA_API int pda_anchor_loss(const float* cls_preds, const float* box_preds, const float* dir_cls_preds,
-                            const int32_t* box_cls_labels, const float* box_reg_targets, const int32_t* num_pos,
-                            const float* anchors, int b, int n_anchors, int num_class, int bins, const float* code_weights,
-                            double cls_weight, double loc_weight, double dir_weight, double dir_offset, float* grad_cls,
-                            float* grad_box, float* grad_dir, double* partials, float* out, pda_stream_t stream) {
-    PDA_REQUIRE(b >= 1 && n_anchors >= 1, "pda_anchor_loss: b=%d n_anchors=%d", b, n_anchors);
-    PDA_REQUIRE((int64_t)b * n_anchors < ((int64_t)1 << 31) / 32, "pda_anchor_loss: b=%d n_anchors=%d too large", b, n_anchors);
-    PDA_REQUIRE(num_class >= 1 && num_class <= pda::AH_MAX_CLASSES, "pda_anchor_loss: num_class=%d outside 1..%d", num_class,
-                pda::AH_MAX_CLASSES);
-    PDA_REQUIRE(!dir_cls_preds || (bins >= 1 && bins <= pda::AH_MAX_BINS), "pda_anchor_loss: bins=%d outside 1..%d", bins,
-                pda::AH_MAX_BINS);
+namespace pda {
+namespace {
+
+// The checks every coded entry makes on (code, sincos, reg_loss) and on sincos next to a direction classifier.
+int check_code(const char* what, int code, int sincos, int reg_loss, bool has_dir) {
+    PDA_REQUIRE(sincos == 0 || sincos == 1, "%s: sincos=%d is no flag", what, sincos);
+    PDA_REQUIRE(code >= 7 + sincos && code <= 9 + sincos,
+                "%s: code=%d outside %d..%d (6 + %d heading columns + extra, extra in 0..2)", what, code, 7 + sincos, 9 + sincos,
+                1 + sincos);
+    PDA_REQUIRE(reg_loss == PDA_REG_SMOOTH_L1 || reg_loss == PDA_REG_L1, "%s: reg_loss=%d is neither smooth L1 (%d) nor L1 (%d)",
+                what, reg_loss, PDA_REG_SMOOTH_L1, PDA_REG_L1);
+    PDA_REQUIRE(!(sincos && has_dir), "%s: sincos with dir_cls_preds (the sine difference and the direction bins need a scalar "
+                "heading)", what);
+    return PDA_OK;
+}
+
+int anchor_loss(const char* what, int code, int sincos, int reg_loss, const float* cls_preds, const float* box_preds,
+                const float* dir_cls_preds, const int32_t* box_cls_labels, const float* box_reg_targets, const int32_t* num_pos,
+                const float* anchors, int b, int n_anchors, int num_class, int bins, const float* code_weights, double cls_weight,
+                double loc_weight, double dir_weight, double dir_offset, float* grad_cls, float* grad_box, float* grad_dir,
+                double* partials, float* out, pda_stream_t stream) {
+    PDA_REQUIRE(b >= 1 && n_anchors >= 1, "%s: b=%d n_anchors=%d", what, b, n_anchors);
+    PDA_REQUIRE((int64_t)b * n_anchors < ((int64_t)1 << 31) / 32, "%s: b=%d n_anchors=%d too large", what, b, n_anchors);
+    PDA_REQUIRE(num_class >= 1 && num_class <= AH_MAX_CLASSES, "%s: num_class=%d outside 1..%d", what, num_class, AH_MAX_CLASSES);
+    PDA_REQUIRE(!dir_cls_preds || (bins >= 1 && bins <= AH_MAX_BINS), "%s: bins=%d outside 1..%d", what, bins, AH_MAX_BINS);
     PDA_REQUIRE(cls_preds && box_preds && box_cls_labels && box_reg_targets && num_pos && anchors && code_weights && grad_cls &&
                     grad_box && partials && out,
-                "pda_anchor_loss: null pointer");
-    PDA_REQUIRE(!dir_cls_preds || grad_dir, "pda_anchor_loss: null grad_dir");
-    pda::AnchorLossCfg g{};
+                "%s: null pointer", what);
+    PDA_REQUIRE(!dir_cls_preds || grad_dir, "%s: null grad_dir", what);
+    AnchorLossCfg g{};
     g.b = b;
     g.n_anchors = n_anchors;
     g.num_class = num_class;
     g.bins = dir_cls_preds ? bins : 0;
-    for (int c = 0; c < 7; ++c) g.code_weight[c] = code_weights[c];
+    for (int c = 0; c < code; ++c) g.code_weight[c] = code_weights[c];
     g.dir_offset = (float)dir_offset;
     g.two_pi = (float)(2.0 * M_PI);
     g.bin_width = (float)(2.0 * M_PI / (dir_cls_preds ? bins : 1));
@@ -566,50 +643,102 @@ PDA_API int pda_anchor_loss(const float* cls_preds, const float* box_preds, cons
     g.loc_scale = loc_weight / b;
     g.dir_scale = dir_cls_preds ? dir_weight / b : 0.0;
     const int blocks = (int)pda_anchor_loss_blocks((int64_t)b * n_anchors);
-    hipLaunchKernelGGL(pda::anchor_loss_kernel, dim3(blocks), dim3(pda::AL_THREADS), 0, (hipStream_t)stream, cls_preds, box_preds,
-                       dir_cls_preds, box_cls_labels, box_reg_targets, num_pos, anchors, g, grad_cls, grad_box, grad_dir,
-                       partials);
-    hipLaunchKernelGGL(pda::anchor_loss_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partials, blocks, g.cls_scale,
+    auto kernel = anchor_loss_kernel<7, false, false>;
+#define PDA_LOSS(CODE, SINCOS) \
+    kernel = reg_loss == PDA_REG_L1 ? anchor_loss_kernel<CODE, SINCOS, true> : anchor_loss_kernel<CODE, SINCOS, false>
+    PDA_ANCHOR_CODED(code, sincos, PDA_LOSS)
+#undef PDA_LOSS
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(AL_THREADS), 0, (hipStream_t)stream, cls_preds, box_preds, dir_cls_preds,
+                       box_cls_labels, box_reg_targets, num_pos, anchors, g, grad_cls, grad_box, grad_dir, partials);
+    hipLaunchKernelGGL(anchor_loss_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partials, blocks, g.cls_scale,
                        g.loc_scale, g.dir_scale, out);
-    return pda::check_launch("pda_anchor_loss");
+    return check_launch(what);
+}
+
+}  // namespace
+}  // namespace pda
+
+PDA_API int pda_anchor_loss(const float* cls_preds, const float* box_preds, const float* dir_cls_preds,
+                            const int32_t* box_cls_labels, const float* box_reg_targets, const int32_t* num_pos,
+                            const float* anchors, int b, int n_anchors, int num_class, int bins, const float* code_weights,
+                            double cls_weight, double loc_weight, double dir_weight, double dir_offset, float* grad_cls,
+                            float* grad_box, float* grad_dir, double* partials, float* out, pda_stream_t stream) {
+    return pda::anchor_loss("pda_anchor_loss", 7, 0, PDA_REG_SMOOTH_L1, cls_preds, box_preds, dir_cls_preds, box_cls_labels,
+                            box_reg_targets, num_pos, anchors, b, n_anchors, num_class, bins, code_weights, cls_weight, loc_weight,
+                            dir_weight, dir_offset, grad_cls, grad_box, grad_dir, partials, out, stream);
+}
+
+PDA_API int pda_anchor_loss_coded(int code, int sincos, int reg_loss, const float* cls_preds, const float* box_preds,
+                                  const float* dir_cls_preds, const int32_t* box_cls_labels, const float* box_reg_targets,
+                                  const int32_t* num_pos, const float* anchors, int b, int n_anchors, int num_class, int bins,
+                                  const float* code_weights, double cls_weight, double loc_weight, double dir_weight,
+                                  double dir_offset, float* grad_cls, float* grad_box, float* grad_dir, double* partials,
+                                  float* out, pda_stream_t stream) {
+    if (int rc = pda::check_code("pda_anchor_loss_coded", code, sincos, reg_loss, dir_cls_preds != nullptr)) return rc;
+    return pda::anchor_loss("pda_anchor_loss_coded", code, sincos, reg_loss, cls_preds, box_preds, dir_cls_preds, box_cls_labels,
+                            box_reg_targets, num_pos, anchors, b, n_anchors, num_class, bins, code_weights, cls_weight, loc_weight,
+                            dir_weight, dir_offset, grad_cls, grad_box, grad_dir, partials, out, stream);
+}
+
+PDA_API int pda_anchor_assign_targets_coded(const float* gt_boxes, int gt_cols, int sincos, int b, int m, const float* anchors,
+                                            int n_anchors, int n_cls, const int32_t* class_label, const float* matched,
+                                            const float* unmatched, const int32_t* class_count, uint32_t* col_max,
+                                            int32_t* box_cls_labels, float* box_reg_targets, float* reg_weights, int32_t* num_pos,
+                                            pda_stream_t stream) {
+    return pda::assign_targets("pda_anchor_assign_targets_coded", false, true, sincos, gt_boxes, gt_cols, b, m, anchors, n_anchors,
+                               n_cls, class_label, matched, unmatched, class_count, col_max, box_cls_labels, box_reg_targets,
+                               reg_weights, num_pos, stream);
+}
+
+PDA_API int pda_anchor_multi_assign_targets_coded(const float* gt_boxes, int gt_cols, int sincos, int b, int m, const float* anchors,
+                                                  int n_anchors, int n_cls, const int32_t* class_label, const float* matched,
+                                                  const float* unmatched, const int32_t* class_rows, uint32_t* col_max,
+                                                  int32_t* box_cls_labels, float* box_reg_targets, float* reg_weights,
+                                                  int32_t* num_pos, pda_stream_t stream) {
+    return pda::assign_targets("pda_anchor_multi_assign_targets_coded", true, true, sincos, gt_boxes, gt_cols, b, m, anchors,
+                               n_anchors, n_cls, class_label, matched, unmatched, class_rows, col_max, box_cls_labels,
+                               box_reg_targets, reg_weights, num_pos, stream);
 }
 
 PDA_API int64_t pda_anchor_multi_loss_blocks(int64_t n) {
     return pda::partial_blocks(n, (int64_t)pda::AL_THREADS * pda::AL_PER_THREAD, pda::AL_MAX_BLOCKS);
 }
 
-PDA_API int pda_anchor_multi_loss(const float* const* cls_preds, const float* const* box_preds, const float* const* dir_cls_preds,
+namespace pda {
+namespace {
+
+int anchor_multi_loss(const char* what, int code, int sincos, int reg_loss, const float* const* cls_preds, const float* const* box_preds, const float* const* dir_cls_preds,
                                   int n_heads, const int32_t* head_rows, const int32_t* head_cols, const int32_t* head_col_base,
                                   const int32_t* box_cls_labels, const float* box_reg_targets, const int32_t* num_pos,
                                   const float* anchors, int b, int n_anchors, int num_class, int bins, const float* code_weights,
                                   double cls_weight, double loc_weight, double dir_weight, double dir_offset, double pos_cls_weight,
                                   double neg_cls_weight, float* const* grad_cls, float* const* grad_box, float* const* grad_dir,
                                   double* partials, float* out, pda_stream_t stream) {
-    PDA_REQUIRE(b >= 1 && n_anchors >= 1, "pda_anchor_multi_loss: b=%d n_anchors=%d", b, n_anchors);
-    PDA_REQUIRE((int64_t)b * n_anchors < ((int64_t)1 << 31) / 32, "pda_anchor_multi_loss: b=%d n_anchors=%d too large", b, n_anchors);
-    PDA_REQUIRE(n_heads >= 1 && n_heads <= pda::AH_MAX_CLASSES, "pda_anchor_multi_loss: n_heads=%d outside 1..%d", n_heads,
-                pda::AH_MAX_CLASSES);
-    PDA_REQUIRE(num_class >= 1 && num_class <= pda::AH_MAX_CLASSES, "pda_anchor_multi_loss: num_class=%d outside 1..%d", num_class,
-                pda::AH_MAX_CLASSES);
-    PDA_REQUIRE(!dir_cls_preds || (bins >= 1 && bins <= pda::AH_MAX_BINS), "pda_anchor_multi_loss: bins=%d outside 1..%d", bins,
-                pda::AH_MAX_BINS);
+    PDA_REQUIRE(b >= 1 && n_anchors >= 1, "%s: b=%d n_anchors=%d", what, b, n_anchors);
+    PDA_REQUIRE((int64_t)b * n_anchors < ((int64_t)1 << 31) / 32, "%s: b=%d n_anchors=%d too large", what, b, n_anchors);
+    PDA_REQUIRE(n_heads >= 1 && n_heads <= AH_MAX_CLASSES, "%s: n_heads=%d outside 1..%d", what, n_heads,
+                AH_MAX_CLASSES);
+    PDA_REQUIRE(num_class >= 1 && num_class <= AH_MAX_CLASSES, "%s: num_class=%d outside 1..%d", what, num_class,
+                AH_MAX_CLASSES);
+    PDA_REQUIRE(!dir_cls_preds || (bins >= 1 && bins <= AH_MAX_BINS), "%s: bins=%d outside 1..%d", what, bins,
+                AH_MAX_BINS);
     PDA_REQUIRE(cls_preds && box_preds && head_rows && head_cols && head_col_base && grad_cls && grad_box,
-                "pda_anchor_multi_loss: null head array");
-    PDA_REQUIRE(!dir_cls_preds || grad_dir, "pda_anchor_multi_loss: null grad_dir");
-    pda::AnchorMultiLossCfg g{};
+                "%s: null head array", what);
+    PDA_REQUIRE(!dir_cls_preds || grad_dir, "%s: null grad_dir", what);
+    AnchorMultiLossCfg g{};
     int64_t rows = 0;
     for (int h = 0; h < n_heads; ++h) {
-        PDA_REQUIRE(head_rows[h] >= 1, "pda_anchor_multi_loss: head_rows[%d]=%d", h, head_rows[h]);
+        PDA_REQUIRE(head_rows[h] >= 1, "%s: head_rows[%d]=%d", what, h, head_rows[h]);
         PDA_REQUIRE(head_cols[h] >= 1 && head_col_base[h] >= 0 && head_cols[h] + head_col_base[h] <= num_class,
-                    "pda_anchor_multi_loss: head %d has columns %d..%d of num_class=%d", h, head_col_base[h],
+                    "%s: head %d has columns %d..%d of num_class=%d", what, h, head_col_base[h],
                     head_col_base[h] + head_cols[h], num_class);
         g.row0[h] = (int)rows;
         rows += head_rows[h];
-        PDA_REQUIRE(rows <= n_anchors, "pda_anchor_multi_loss: the heads own more than the n_anchors=%d rows", n_anchors);
+        PDA_REQUIRE(rows <= n_anchors, "%s: the heads own more than the n_anchors=%d rows", what, n_anchors);
         g.cols[h] = head_cols[h];
         g.col_base[h] = head_col_base[h];
         PDA_REQUIRE(cls_preds[h] && box_preds[h] && grad_cls[h] && grad_box[h] && (!dir_cls_preds || (dir_cls_preds[h] && grad_dir[h])),
-                    "pda_anchor_multi_loss: null pointer of head %d", h);
+                    "%s: null pointer of head %d", what, h);
         g.cls[h] = cls_preds[h];
         g.box[h] = box_preds[h];
         g.dir[h] = dir_cls_preds ? dir_cls_preds[h] : nullptr;
@@ -618,9 +747,9 @@ PDA_API int pda_anchor_multi_loss(const float* const* cls_preds, const float* co
         g.grad_dir[h] = dir_cls_preds ? grad_dir[h] : nullptr;
     }
     g.row0[n_heads] = (int)rows;
-    PDA_REQUIRE(rows == n_anchors, "pda_anchor_multi_loss: the heads own %d rows of n_anchors=%d", (int)rows, n_anchors);
+    PDA_REQUIRE(rows == n_anchors, "%s: the heads own %d rows of n_anchors=%d", what, (int)rows, n_anchors);
     PDA_REQUIRE(box_cls_labels && box_reg_targets && num_pos && anchors && code_weights && partials && out,
-                "pda_anchor_multi_loss: null pointer");
+                "%s: null pointer", what);
     g.n_heads = n_heads;
     g.sin_diff = dir_cls_preds ? 1 : 0;      // anchor_head_multi.py adds the sin difference only behind a direction classifier
     g.pos_w = pos_cls_weight;
@@ -629,7 +758,7 @@ PDA_API int pda_anchor_multi_loss(const float* const* cls_preds, const float* co
     g.t.n_anchors = n_anchors;
     g.t.num_class = num_class;
     g.t.bins = dir_cls_preds ? bins : 0;
-    for (int c = 0; c < 7; ++c) g.t.code_weight[c] = code_weights[c];
+    for (int c = 0; c < code; ++c) g.t.code_weight[c] = code_weights[c];
     g.t.dir_offset = (float)dir_offset;
     g.t.two_pi = (float)(2.0 * M_PI);
     g.t.bin_width = (float)(2.0 * M_PI / (dir_cls_preds ? bins : 1));
@@ -637,30 +766,91 @@ PDA_API int pda_anchor_multi_loss(const float* const* cls_preds, const float* co
     g.t.loc_scale = loc_weight / b;
     g.t.dir_scale = dir_cls_preds ? dir_weight / b : 0.0;
     const int blocks = (int)pda_anchor_multi_loss_blocks((int64_t)b * n_anchors);
-    hipLaunchKernelGGL(pda::anchor_multi_loss_kernel, dim3(blocks), dim3(pda::AL_THREADS), 0, (hipStream_t)stream, box_cls_labels,
-                       box_reg_targets, num_pos, anchors, g, partials);
-    hipLaunchKernelGGL(pda::anchor_loss_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partials, blocks, g.t.cls_scale,
+    auto kernel = anchor_multi_loss_kernel<7, false, false>;
+#define PDA_LOSS(CODE, SINCOS) \
+    kernel = reg_loss == PDA_REG_L1 ? anchor_multi_loss_kernel<CODE, SINCOS, true> : anchor_multi_loss_kernel<CODE, SINCOS, false>
+    PDA_ANCHOR_CODED(code, sincos, PDA_LOSS)
+#undef PDA_LOSS
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(AL_THREADS), 0, (hipStream_t)stream, box_cls_labels, box_reg_targets, num_pos,
+                       anchors, g, partials);
+    hipLaunchKernelGGL(anchor_loss_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partials, blocks, g.t.cls_scale,
                        g.t.loc_scale, g.t.dir_scale, out);
-    return pda::check_launch("pda_anchor_multi_loss");
+    return check_launch(what);
 }
 
-PDA_API int pda_anchor_decode(const float* box_preds, const float* dir_cls_preds, const float* anchors, int b, int n_anchors,
-                              int bins, double dir_offset, double dir_limit_offset, float* batch_box_preds,
-                              pda_stream_t stream) {
-    PDA_REQUIRE(b >= 0 && n_anchors >= 0 && (int64_t)b * n_anchors < ((int64_t)1 << 31) / 8, "pda_anchor_decode: b=%d n_anchors=%d",
-                b, n_anchors);
-    PDA_REQUIRE(!dir_cls_preds || (bins >= 1 && bins <= pda::AH_MAX_BINS), "pda_anchor_decode: bins=%d outside 1..%d", bins,
-                pda::AH_MAX_BINS);
+}  // namespace
+}  // namespace pda
+
+#define PDA_MULTI_LOSS_ARGS                                                                                                       \
+    cls_preds, box_preds, dir_cls_preds, n_heads, head_rows, head_cols, head_col_base, box_cls_labels, box_reg_targets, num_pos,  \
+            anchors, b, n_anchors, num_class, bins, code_weights, cls_weight, loc_weight, dir_weight, dir_offset, pos_cls_weight, \
+            neg_cls_weight, grad_cls, grad_box, grad_dir, partials, out, stream
+
+PDA_API int pda_anchor_multi_loss(const float* const* cls_preds, const float* const* box_preds, const float* const* dir_cls_preds,
+                                  int n_heads, const int32_t* head_rows, const int32_t* head_cols, const int32_t* head_col_base,
+                                  const int32_t* box_cls_labels, const float* box_reg_targets, const int32_t* num_pos,
+                                  const float* anchors, int b, int n_anchors, int num_class, int bins, const float* code_weights,
+                                  double cls_weight, double loc_weight, double dir_weight, double dir_offset, double pos_cls_weight,
+                                  double neg_cls_weight, float* const* grad_cls, float* const* grad_box, float* const* grad_dir,
+                                  double* partials, float* out, pda_stream_t stream) {
+    return pda::anchor_multi_loss("pda_anchor_multi_loss", 7, 0, PDA_REG_SMOOTH_L1, PDA_MULTI_LOSS_ARGS);
+}
+
+PDA_API int pda_anchor_multi_loss_coded(int code, int sincos, int reg_loss, const float* const* cls_preds,
+                                        const float* const* box_preds, const float* const* dir_cls_preds, int n_heads,
+                                        const int32_t* head_rows, const int32_t* head_cols, const int32_t* head_col_base,
+                                        const int32_t* box_cls_labels, const float* box_reg_targets, const int32_t* num_pos,
+                                        const float* anchors, int b, int n_anchors, int num_class, int bins,
+                                        const float* code_weights, double cls_weight, double loc_weight, double dir_weight,
+                                        double dir_offset, double pos_cls_weight, double neg_cls_weight, float* const* grad_cls,
+                                        float* const* grad_box, float* const* grad_dir, double* partials, float* out,
+                                        pda_stream_t stream) {
+    if (int rc = pda::check_code("pda_anchor_multi_loss_coded", code, sincos, reg_loss, dir_cls_preds != nullptr)) return rc;
+    return pda::anchor_multi_loss("pda_anchor_multi_loss_coded", code, sincos, reg_loss, PDA_MULTI_LOSS_ARGS);
+}
+#undef PDA_MULTI_LOSS_ARGS
+
+namespace pda {
+namespace {
+
+int anchor_decode(const char* what, int code, int sincos, const float* box_preds, const float* dir_cls_preds, const float* anchors,
+                  int b, int n_anchors, int bins, double dir_offset, double dir_limit_offset, float* batch_box_preds,
+                  pda_stream_t stream) {
+    PDA_REQUIRE(b >= 0 && n_anchors >= 0 && (int64_t)b * n_anchors < ((int64_t)1 << 31) / (code > 8 ? 16 : 8), "%s: b=%d n_anchors=%d",
+                what, b, n_anchors);
+    PDA_REQUIRE(!dir_cls_preds || (bins >= 1 && bins <= AH_MAX_BINS), "%s: bins=%d outside 1..%d", what, bins, AH_MAX_BINS);
     if (b == 0 || n_anchors == 0) return PDA_OK;
-    PDA_REQUIRE(box_preds && anchors && batch_box_preds, "pda_anchor_decode: null pointer");
-    pda::AnchorDecodeCfg g{};
+    PDA_REQUIRE(box_preds && anchors && batch_box_preds, "%s: null pointer", what);
+    AnchorDecodeCfg g{};
     g.b = b;
     g.n_anchors = n_anchors;
     g.bins = dir_cls_preds ? bins : 0;
     g.dir_offset = (float)dir_offset;
     g.dir_limit_offset = (float)dir_limit_offset;
     g.period = (float)(2.0 * M_PI / (dir_cls_preds ? bins : 1));
-    hipLaunchKernelGGL(pda::anchor_decode_kernel, dim3((unsigned)pda::divup64((int64_t)b * n_anchors, 256)), dim3(256), 0,
-                       (hipStream_t)stream, box_preds, dir_cls_preds, anchors, g, batch_box_preds);
-    return pda::check_launch("pda_anchor_decode");
+    auto kernel = anchor_decode_kernel<7, false>;
+#define PDA_DECODE(CODE, SINCOS) kernel = anchor_decode_kernel<CODE, SINCOS>
+    PDA_ANCHOR_CODED(code, sincos, PDA_DECODE)
+#undef PDA_DECODE
+    hipLaunchKernelGGL(kernel, dim3((unsigned)divup64((int64_t)b * n_anchors, 256)), dim3(256), 0, (hipStream_t)stream, box_preds,
+                       dir_cls_preds, anchors, g, batch_box_preds);
+    return check_launch(what);
+}
+
+}  // namespace
+}  // namespace pda
+
+PDA_API int pda_anchor_decode(const float* box_preds, const float* dir_cls_preds, const float* anchors, int b, int n_anchors,
+                              int bins, double dir_offset, double dir_limit_offset, float* batch_box_preds,
+                              pda_stream_t stream) {
+    return pda::anchor_decode("pda_anchor_decode", 7, 0, box_preds, dir_cls_preds, anchors, b, n_anchors, bins, dir_offset,
+                              dir_limit_offset, batch_box_preds, stream);
+}
+
+PDA_API int pda_anchor_decode_coded(int code, int sincos, const float* box_preds, const float* dir_cls_preds, const float* anchors,
+                                    int b, int n_anchors, int bins, double dir_offset, double dir_limit_offset,
+                                    float* batch_box_preds, pda_stream_t stream) {
+    if (int rc = pda::check_code("pda_anchor_decode_coded", code, sincos, PDA_REG_SMOOTH_L1, dir_cls_preds != nullptr)) return rc;
+    return pda::anchor_decode("pda_anchor_decode_coded", code, sincos, box_preds, dir_cls_preds, anchors, b, n_anchors, bins,
+                              dir_offset, dir_limit_offset, batch_box_preds, stream);
 }

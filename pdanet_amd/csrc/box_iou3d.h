@@ -9,7 +9,9 @@ namespace pda {
 
 // The reference keeps rows 0..k: k starts at t - 1 and steps down while k > 0 and row k's float32 sum == 0.  Returns
 // that k (0 when t == 0), the same on every lane.  The row is summed left to right; a row whose values cancel to zero only
-// under some summation orders is outside the contract (torch's reduction order is not specified).
+// under some summation orders is outside the contract (torch's reduction order is not specified).  A row that holds a NaN (an
+// unknown velocity) sums to NaN, which is not 0, so the row is kept: the NaN is found in the bits of the loaded values,
+// because the file is built with -fno-honor-nans, under which no comparison of the sum can be relied on.
 __device__ inline int trimmed_last_row(const float* __restrict__ gt, int t, int cols, int lane) {
     for (int base = t - 64; base + 63 >= 1; base -= 64) {
         const int r = base + lane;  // < t
@@ -17,8 +19,13 @@ __device__ inline int trimmed_last_row(const float* __restrict__ gt, int t, int 
         if (r >= 1) {
             const float* row = gt + (size_t)r * cols;
             float s = 0.f;
-            for (int c = 0; c < cols; ++c) s += row[c];
-            nz = s != 0.f;
+            bool nan = false;
+            for (int c = 0; c < cols; ++c) {
+                const float v = row[c];
+                nan = nan || is_nan_bits(v);
+                s += nan ? 0.f : v;
+            }
+            nz = nan || s != 0.f;
         }
         const uint64_t m = __ballot(nz);
         if (m) return base + 63 - __clzll((long long)m);

@@ -118,6 +118,8 @@ __global__ __launch_bounds__(64) void nms_scan_kernel(const unsigned long long* 
 constexpr int MN_THREADS = 256;
 constexpr int MN_MAX_PROBLEMS = 256;
 
+// W: the columns of a box row, 7 + extra; pda_nms_bev itself saw a 7-column copy of the same rows.
+template <int W>
 __global__ __launch_bounds__(MN_THREADS) void multi_nms_compact_kernel(
         const float* __restrict__ boxes, const float* __restrict__ scores, const long long* __restrict__ keep,
         const int* __restrict__ num_keep, const int* __restrict__ label_map, int c, int k, int cap,
@@ -136,7 +138,7 @@ __global__ __launch_bounds__(MN_THREADS) void multi_nms_compact_kernel(
     }
     __syncthreads();
     const int total = first[c], rows = c * cap;
-    float* ob = pred_boxes + (size_t)scene * rows * 7;
+    float* ob = pred_boxes + (size_t)scene * rows * W;
     float* os = pred_scores + (size_t)scene * rows;
     long long* ol = pred_labels + (size_t)scene * rows;
     for (int j = threadIdx.x; j < rows; j += MN_THREADS) {
@@ -146,16 +148,16 @@ __global__ __launch_bounds__(MN_THREADS) void multi_nms_compact_kernel(
             const long long i = keep[problem * k + r];
             if (i >= 0 && i < k) {      // what pda_nms_bev wrote for r < num_keep
                 const int o = first[p] + r;
-                const float* src = boxes + (problem * k + (size_t)i) * 7;
+                const float* src = boxes + (problem * k + (size_t)i) * W;
 #pragma unroll
-                for (int q = 0; q < 7; ++q) ob[(size_t)o * 7 + q] = src[q];
+                for (int q = 0; q < W; ++q) ob[(size_t)o * W + q] = src[q];
                 os[o] = scores[problem * k + (size_t)i];
                 ol[o] = label_map[p];
             }
         }
         if (j >= total) {
 #pragma unroll
-            for (int q = 0; q < 7; ++q) ob[(size_t)j * 7 + q] = 0.f;
+            for (int q = 0; q < W; ++q) ob[(size_t)j * W + q] = 0.f;
             os[j] = 0.f;
             ol[j] = 0;
         }
@@ -209,20 +211,40 @@ PDA_API int pda_nms_bev(const float* boxes, const int32_t* num_valid, int64_t* k
     return pda::check_launch("pda_nms_bev");
 }
 
+namespace pda {
+
+static int multi_nms_compact(const char* what, int width, const float* boxes, const float* scores, const int64_t* keep,
+                             const int32_t* num_keep, const int32_t* label_map, int b, int c, int k, int post_max,
+                             float* pred_boxes, float* pred_scores, int64_t* pred_labels, int32_t* num_pred, pda_stream_t stream) {
+    PDA_REQUIRE(width >= 7 && width <= 9, "%s: box_cols=%d outside 7..9", what, width);
+    PDA_REQUIRE(b >= 0 && k >= 0 && post_max >= 0, "%s: b=%d k=%d post_max=%d", what, b, k, post_max);
+    PDA_REQUIRE(c >= 1 && c <= MN_MAX_PROBLEMS, "%s: c=%d problems a scene outside 1..%d", what, c, MN_MAX_PROBLEMS);
+    PDA_REQUIRE(b <= 65535 && (int64_t)b * c * k < ((int64_t)1 << 31) / (width > 8 ? 16 : 8), "%s: b=%d c=%d k=%d too large", what, b,
+                c, k);
+    if (b == 0) return PDA_OK;
+    PDA_REQUIRE(num_keep && num_pred, "%s: null counts", what);
+    const int cap = post_max < k ? post_max : k;      // the rows a problem can contribute
+    PDA_REQUIRE(cap == 0 || (boxes && scores && keep && label_map && pred_boxes && pred_scores && pred_labels), "%s: null pointer",
+                what);
+    auto kernel = width == 7 ? multi_nms_compact_kernel<7> : (width == 8 ? multi_nms_compact_kernel<8> : multi_nms_compact_kernel<9>);
+    hipLaunchKernelGGL(kernel, dim3(b), dim3(MN_THREADS), 0, (hipStream_t)stream, boxes, scores, (const long long*)keep, num_keep,
+                       label_map, c, k, cap, pred_boxes, pred_scores, (long long*)pred_labels, num_pred);
+    return check_launch(what);
+}
+
+}  // namespace pda
+
 PDA_API int pda_multi_nms_compact(const float* boxes, const float* scores, const int64_t* keep, const int32_t* num_keep,
                                   const int32_t* label_map, int b, int c, int k, int post_max, float* pred_boxes,
                                   float* pred_scores, int64_t* pred_labels, int32_t* num_pred, pda_stream_t stream) {
-    PDA_REQUIRE(b >= 0 && k >= 0 && post_max >= 0, "pda_multi_nms_compact: b=%d k=%d post_max=%d", b, k, post_max);
-    PDA_REQUIRE(c >= 1 && c <= pda::MN_MAX_PROBLEMS, "pda_multi_nms_compact: c=%d problems a scene outside 1..%d", c,
-                pda::MN_MAX_PROBLEMS);
-    PDA_REQUIRE(b <= 65535 && (int64_t)b * c * k < ((int64_t)1 << 31) / 8, "pda_multi_nms_compact: b=%d c=%d k=%d too large", b, c, k);
-    if (b == 0) return PDA_OK;
-    PDA_REQUIRE(num_keep && num_pred, "pda_multi_nms_compact: null counts");
-    const int cap = post_max < k ? post_max : k;      // the rows a problem can contribute
-    PDA_REQUIRE(cap == 0 || (boxes && scores && keep && label_map && pred_boxes && pred_scores && pred_labels),
-                "pda_multi_nms_compact: null pointer");
-    hipLaunchKernelGGL(pda::multi_nms_compact_kernel, dim3(b), dim3(pda::MN_THREADS), 0, (hipStream_t)stream, boxes, scores,
-                       (const long long*)keep, num_keep, label_map, c, k, cap, pred_boxes, pred_scores, (long long*)pred_labels,
-                       num_pred);
-    return pda::check_launch("pda_multi_nms_compact");
+    return pda::multi_nms_compact("pda_multi_nms_compact", 7, boxes, scores, keep, num_keep, label_map, b, c, k, post_max,
+                                  pred_boxes, pred_scores, pred_labels, num_pred, stream);
+}
+
+PDA_API int pda_multi_nms_compact_wide(int box_cols, const float* boxes, const float* scores, const int64_t* keep,
+                                       const int32_t* num_keep, const int32_t* label_map, int b, int c, int k, int post_max,
+                                       float* pred_boxes, float* pred_scores, int64_t* pred_labels, int32_t* num_pred,
+                                       pda_stream_t stream) {
+    return pda::multi_nms_compact("pda_multi_nms_compact_wide", box_cols, boxes, scores, keep, num_keep, label_map, b, c, k,
+                                  post_max, pred_boxes, pred_scores, pred_labels, num_pred, stream);
 }

@@ -90,6 +90,26 @@ class WeightedSmoothL1Loss(nn.Module):
         return loss
 
 
+class WeightedL1Loss(nn.Module):
+    """pcdet/utils/loss_utils.py WeightedL1Loss, the REG_LOSS_TYPE of the nuScenes anchor heads: |diff * code_weights| * weights."""
+
+    def __init__(self, code_weights=None):
+        super().__init__()
+        self.register_buffer("code_weights", None if code_weights is None else torch.tensor(code_weights, dtype=torch.float32),
+                             persistent=False)
+
+    def forward(self, input, target, weights=None):
+        """(B, N, C) codes.  A NaN target contributes neither loss nor gradient."""
+        diff = input - torch.where(torch.isnan(target), input, target)
+        if self.code_weights is not None:
+            diff = diff * self.code_weights.view(1, 1, -1)
+        loss = torch.abs(diff)
+        if weights is not None:
+            assert weights.shape[:2] == loss.shape[:2]
+            loss = loss * weights.unsqueeze(-1)
+        return loss
+
+
 def get_corner_loss_lidar(pred_bbox3d, gt_bbox3d):
     """(N, 7), (N, 7) -> (N): Huber(1) of the eight corner distances, per corner the smaller of the distances to the box
     and to its heading-flipped twin, averaged over the corners (:340-363)."""

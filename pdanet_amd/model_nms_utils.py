@@ -119,7 +119,9 @@ def multi_classes_nms_batched(cls_preds, box_preds, label_mapping, nms_config, s
     the N_h rows behind those of the heads before it; label_mapping: per head the (C_h) 1-based labels of its columns.
     Every (scene, head, class column) is one NMS problem: its scores >= score_thresh, sorted, the first
     min(N_h, NMS_PRE_MAXSIZE) of them gathered -- only those rows, so a head may have more rows than pda_nms_bev takes --
-    and all problems go through one pda_nms_bev and one pda_multi_nms_compact.  Returns pred_boxes (B, K, 7), pred_scores
+    and all problems go through one pda_nms_bev and one pda_multi_nms_compact.  box_preds of 8 or 9 columns (velocities)
+    keep their columns: pda_nms_bev reads a contiguous copy of columns 0..6, pda_multi_nms_compact_wide copies whole rows, and
+    pred_boxes is (B, K, 7 + extra).  Returns pred_boxes (B, K, 7), pred_scores
     (B, K), pred_labels (B, K) int64 (0 = padding) and num_pred (B) int32, K = sum C_h * min(NMS_POST_MAXSIZE, max_h
     min(N_h, NMS_PRE_MAXSIZE)); a scene's rows run head after head, class column after class column, by descending score, as
     the reference concatenates them.  No host read.  Equal scores within a column are outside the parity claim: the
@@ -132,6 +134,9 @@ def multi_classes_nms_batched(cls_preds, box_preds, label_mapping, nms_config, s
     pre, post = int(nms_config["NMS_PRE_MAXSIZE"]), int(nms_config["NMS_POST_MAXSIZE"])
     if sum(x.shape[1] for x in cls_preds) != box_preds.shape[1]:
         raise ValueError("the heads score %d rows, box_preds has %d" % (sum(x.shape[1] for x in cls_preds), box_preds.shape[1]))
+    W = box_preds.shape[2]
+    if not 7 <= W <= 9:
+        raise NotImplementedError("box_preds with %d columns (7 + at most two custom columns)" % W)
     K = max(min(x.shape[1], pre) for x in cls_preds)
     boxes, scores, num_valid = [], [], []
     start = 0
@@ -143,27 +148,28 @@ def multi_classes_nms_batched(cls_preds, box_preds, label_mapping, nms_config, s
         ok = s >= score_thresh if score_thresh is not None else torch.ones_like(s, dtype=torch.bool)
         sorted_scores, order = torch.where(ok, s, torch.full_like(s, float("-inf"))).sort(dim=2, descending=True)
         sorted_scores, order = sorted_scores[..., :k], order[..., :k]          # before the gather: k rows a problem, not n
-        rows = box_preds[:, start:start + n, 0:7].unsqueeze(1).expand(B, c, n, 7)
-        picked = torch.gather(rows, 2, order.unsqueeze(-1).expand(B, c, k, 7))
+        rows = box_preds[:, start:start + n].unsqueeze(1).expand(B, c, n, W)
+        picked = torch.gather(rows, 2, order.unsqueeze(-1).expand(B, c, k, W))
         boxes.append(torch.nn.functional.pad(picked, (0, 0, 0, K - k)))
         scores.append(torch.nn.functional.pad(sorted_scores, (0, K - k)))
         num_valid.append(ok.sum(dim=2).clamp(max=k).to(torch.int32))
         start += n
-    boxes = torch.cat(boxes, dim=1).to(F32).contiguous()                                             # (B, C, K, 7)
+    boxes = torch.cat(boxes, dim=1).to(F32).contiguous()                                             # (B, C, K, W)
     scores = torch.cat(scores, dim=1).to(F32).contiguous()
     num_valid = torch.cat(num_valid, dim=1).contiguous()
     C = boxes.shape[1]
     labels = torch.cat([m.reshape(-1) for m in label_mapping]).to(device=boxes.device, dtype=torch.int32).contiguous()
-    keep, num_keep = iou3d_nms_utils.nms_batched(boxes.view(B * C, K, 7), nms_config["NMS_THRESH"], num_valid=num_valid.view(-1),
+    bev = boxes if W == 7 else boxes[..., :7].contiguous()
+    keep, num_keep = iou3d_nms_utils.nms_batched(bev.view(B * C, K, 7), nms_config["NMS_THRESH"], num_valid=num_valid.view(-1),
                                                  normal=nms_config["NMS_TYPE"] == "nms_normal_gpu")
     rows = C * min(post, K)
     dev = boxes.device
-    pred_boxes = torch.empty((B, rows, 7), dtype=F32, device=dev)
+    pred_boxes = torch.empty((B, rows, W), dtype=F32, device=dev)
     pred_scores = torch.empty((B, rows), dtype=F32, device=dev)
     pred_labels = torch.empty((B, rows), dtype=torch.int64, device=dev)
     num_pred = torch.empty((B,), dtype=torch.int32, device=dev)
     if B:
-        _call("pda_multi_nms_compact", boxes, _chk(boxes, "boxes", F32), _chk(scores, "scores", F32), _chk(keep, "keep", torch.int64),
+        _call(*(("pda_multi_nms_compact", boxes) if W == 7 else ("pda_multi_nms_compact_wide", boxes, W)), _chk(boxes, "boxes", F32), _chk(scores, "scores", F32), _chk(keep, "keep", torch.int64),
               _chk(num_keep, "num_keep", I32), _chk(labels, "label_mapping", I32), B, C, K, post, pred_boxes.data_ptr(),
               pred_scores.data_ptr(), pred_labels.data_ptr(), num_pred.data_ptr())
     return pred_boxes, pred_scores, pred_labels, num_pred
