@@ -1409,6 +1409,31 @@ int pda_parta2_pool_bwd(const int32_t *table, const int32_t *live_vox, const int
                         const float *grad_part_rows, const float *grad_feat_rows, float *grad_offset, float *grad_features,
                         int64_t n_live, int64_t n_points, int channels, int k_slots, pda_stream_t stream);
 
+/* ---- PV-RCNN++ (csrc/spc_sample.hip).
+ * pda_roi_point_filter: sample_points_with_roi (voxel_set_abstraction.py:45-75) for a stacked point set and, with
+ *   num_sectors > 0, the sector index of sector_fps (:88-90), in one launch and without an n x m tensor.  points (n, 3) ordered by
+ *   scene, point_cnt (b) int32 on the device, rois (b, m, roi_channels >= 6) [x, y, z, dx, dy, dz, ...]; ALL m rows of a scene take
+ *   part, zero rows included.  float32, no FMA: d = sqrtf((dx dx + dy dy) + dz dz) to every centre, the nearest RoI is the one of
+ *   the lowest index among equal distances, half = sqrtf of the same sum over (dims / 2), and mask[p] = d < half + radius.
+ *   keys[p] = scene * (num_sectors + 1) + sector with sector = clamp(floorf((atan2f(y, x) + (float)pi) / (float)(2 pi /
+ *   num_sectors)), 0, num_sectors) for a kept point and num_sectors for one that is not; keys may be NULL when num_sectors is 0.
+ *   Rows past the sum of the counts are not written (the caller fills mask and keys).  b <= 1024; n == 0 or m == 0 returns PDA_OK with nothing written.
+ * pda_vector_interp_fwd: the rows of VectorPoolLocalInterpolateModule.forward (pointnet2_modules.py:220-238) without an MLP.
+ *   dist, idx (m, g, 3) as pda_stack_three_nn_by_local_idxs leaves them after the caller's sqrt (idx GLOBAL rows of the support
+ *   set, idx[.][.][0] == -1 for a cell without neighbour), support_xyz (n, 3), support_features (n, c), grid_centers (m, g, 3) ->
+ *   out (m, g * (c + 9)), every element written once: per cell [sum_k w_k features[idx_k] (c) | grid centre - support_xyz[idx_k]
+ *   for k = 0, 1, 2 (9)] with r_k = 1 / (dist_k + 1e-8), w_k = r_k / max((r_0 + r_1) + r_2, 1e-8) and the blend evaluated as
+ *   pda_stack_three_interpolate evaluates it; zeros for a cell whose idx holds a value outside [0, n).
+ * pda_vector_interp_bwd: grad_out (m, g * (c + 9)) is read in place (the nine coordinate columns of a cell are skipped);
+ *   grad_support_features[idx_k][ch] += grad_out[cell][ch] * w_k with float atomics into the (n, c) buffer the caller zero-filled,
+ *   as pda_stack_three_interpolate_grad does.  Coordinates and grid centres get no gradient. */
+int pda_roi_point_filter(const float *points, const int32_t *point_cnt, const float *rois, float radius, uint8_t *mask,
+                         int32_t *keys, int64_t n, int b, int m, int roi_channels, int num_sectors, pda_stream_t stream);
+int pda_vector_interp_fwd(const float *dist, const int32_t *idx, const float *support_xyz, const float *support_features,
+                          const float *grid_centers, float *out, int m, int g, int n, int c, pda_stream_t stream);
+int pda_vector_interp_bwd(const float *grad_out, const float *dist, const int32_t *idx, float *grad_support_features, int m,
+                          int g, int n, int c, pda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -307,6 +307,9 @@ SIGNATURES = {
     "pda_parta2_pool_sparsify": [_vp, _vp, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, _vp],
     "pda_parta2_pool_features": [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, _i, _vp],
     "pda_parta2_pool_bwd": [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _i, _i, _vp],
+    "pda_roi_point_filter": [_vp, _vp, _vp, _f, _vp, _vp, ctypes.c_int64, _i, _i, _i, _i, _vp],
+    "pda_vector_interp_fwd": [_vp] * 6 + [_i] * 4 + [_vp],
+    "pda_vector_interp_bwd": [_vp] * 4 + [_i] * 4 + [_vp],
     # include/pda_pointnet2_stack.h
     "pda_stack_ball_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     "pda_stack_group_points": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],

@@ -21,10 +21,12 @@ from .voxel_set_abstraction import scene_counts
 
 
 class PVRCNNHead(RoIHeadTemplate):
+    build_local_aggregation_module = staticmethod(build_local_aggregation_module)     # pv_rcnn_plusplus.py names another
+
     def __init__(self, input_channels, model_cfg, num_class=1, **kwargs):
         super().__init__(num_class=num_class, model_cfg=model_cfg)
         self.pool_cfg = model_cfg['ROI_GRID_POOL']
-        self.roi_grid_pool_layer, num_c_out = build_local_aggregation_module(input_channels=input_channels, config=self.pool_cfg)
+        self.roi_grid_pool_layer, num_c_out = self.build_local_aggregation_module(input_channels=input_channels, config=self.pool_cfg)
 
         grid = self.pool_cfg['GRID_SIZE']
         self.shared_fc_layer, pre_channel = self.make_shared_fc_layers(grid * grid * grid * num_c_out, model_cfg['SHARED_FC'])

@@ -2,8 +2,8 @@
 reference's constructor, config keys, module names (SA_layers, SA_rawpoints, vsa_point_feature_fusion) and state-dict keys.
 
 Built: POINT_SOURCE raw_points | voxel_centers, SAMPLE_METHOD FPS, FEATURES_SOURCE any of bev, raw_points, x_conv1..4.
-Refused at construction (PV-RCNN++ only): SAMPLE_METHOD SPC (sample_points_with_roi / sector_fps) and
-FILTER_NEIGHBOR_WITH_ROI.
+Refused at construction by this class: SAMPLE_METHOD SPC (sample_points_with_roi / sector_fps) and
+FILTER_NEIGHBOR_WITH_ROI; voxel_set_abstraction_spc.py builds both on the hooks named at the top of the class.
 
 Keypoints.  The reference cuts the batch into scenes with boolean masks and samples each in a Python loop.  Here the counts
 per scene come from a bincount of the batch column, one stacked FPS launch samples min(N_b, NUM_KEYPOINTS) points of every
@@ -77,12 +77,18 @@ def sample_keypoints(src_points, batch_indices, batch_size, num_keypoints):
 
 
 class VoxelSetAbstraction(nn.Module):
+    # what voxel_set_abstraction_spc.py (PV-RCNN++) widens: the sampling methods taken, whether a source may ask for
+    # FILTER_NEIGHBOR_WITH_ROI, the builder of the layers; and the two methods keypoints_and_counts / source_rows below
+    SAMPLE_METHODS = ('FPS',)
+    NEIGHBOR_FILTER = False
+    build_local_aggregation_module = staticmethod(pointnet2_stack_modules.build_local_aggregation_module)
+
     def __init__(self, model_cfg, voxel_size, point_cloud_range, num_bev_features=None, num_rawpoint_features=None, **kwargs):
         super().__init__()
         self.model_cfg = model_cfg
         self.voxel_size = [float(v) for v in voxel_size]
         self.point_cloud_range = [float(v) for v in point_cloud_range]
-        if model_cfg['SAMPLE_METHOD'] != 'FPS':
+        if model_cfg['SAMPLE_METHOD'] not in self.SAMPLE_METHODS:
             raise NotImplementedError("SAMPLE_METHOD %r (SPC is PV-RCNN++)" % (model_cfg['SAMPLE_METHOD'],))
         if model_cfg['POINT_SOURCE'] not in ('raw_points', 'voxel_centers'):
             raise NotImplementedError("POINT_SOURCE %r" % (model_cfg['POINT_SOURCE'],))
@@ -90,7 +96,7 @@ class VoxelSetAbstraction(nn.Module):
         for src_name in model_cfg['FEATURES_SOURCE']:
             if src_name not in ('bev', 'raw_points', 'x_conv1', 'x_conv2', 'x_conv3', 'x_conv4'):
                 raise NotImplementedError("FEATURES_SOURCE %r" % (src_name,))
-            if src_name != 'bev' and SA_cfg[src_name].get('FILTER_NEIGHBOR_WITH_ROI', False):
+            if src_name != 'bev' and SA_cfg[src_name].get('FILTER_NEIGHBOR_WITH_ROI', False) and not self.NEIGHBOR_FILTER:
                 raise NotImplementedError("FILTER_NEIGHBOR_WITH_ROI (PV-RCNN++)")
 
         self.SA_layers = nn.ModuleList()
@@ -106,7 +112,7 @@ class VoxelSetAbstraction(nn.Module):
                 input_channels = first[0] if isinstance(first, (list, tuple)) else first
             else:
                 input_channels = SA_cfg[src_name]['INPUT_CHANNELS']
-            cur_layer, cur_num_c_out = pointnet2_stack_modules.build_local_aggregation_module(
+            cur_layer, cur_num_c_out = self.build_local_aggregation_module(
                 input_channels=input_channels, config=SA_cfg[src_name])
             self.SA_layers.append(cur_layer)
             self.SA_layer_names.append(src_name)
@@ -114,7 +120,7 @@ class VoxelSetAbstraction(nn.Module):
         if 'bev' in model_cfg['FEATURES_SOURCE']:
             c_in += num_bev_features
         if 'raw_points' in model_cfg['FEATURES_SOURCE']:
-            self.SA_rawpoints, cur_num_c_out = pointnet2_stack_modules.build_local_aggregation_module(
+            self.SA_rawpoints, cur_num_c_out = self.build_local_aggregation_module(
                 input_channels=num_rawpoint_features - 3, config=SA_cfg['raw_points'])
             c_in += cur_num_c_out
         self.vsa_point_feature_fusion = nn.Sequential(
@@ -149,6 +155,16 @@ class VoxelSetAbstraction(nn.Module):
         keypoints = torch.cat((batch_idx.float(), src_points[rows.view(-1)].float()), dim=1)
         return (keypoints, rows) if return_indices else keypoints
 
+    def keypoints_and_counts(self, batch_dict):
+        """-> keypoints (M1 + M2 + ..., 4) and their int32 counts per scene: here NUM_KEYPOINTS of every scene."""
+        keypoints = self.get_sampled_points(batch_dict)
+        return keypoints, torch.full((batch_dict['batch_size'],), self.model_cfg['NUM_KEYPOINTS'], dtype=torch.int32,
+                                     device=keypoints.device)
+
+    def source_rows(self, src_name, xyz, xyz_features, xyz_bs_idxs, batch_dict):
+        """The rows of one feature source that reach its layer: here all of them."""
+        return xyz, xyz_features, xyz_bs_idxs
+
     @staticmethod
     def aggregate_keypoint_features_from_one_source(batch_size, aggregate_func, xyz, xyz_features, xyz_bs_idxs, new_xyz,
                                                     new_xyz_batch_cnt):
@@ -160,7 +176,7 @@ class VoxelSetAbstraction(nn.Module):
     def forward(self, batch_dict):
         """batch_size, points (N, 1 + 3 + C) and / or voxel_coords, multi_scale_3d_features, spatial_features and its stride
         -> point_features_before_fusion, point_features (B * K, C), point_coords (B * K, 4)."""
-        keypoints = self.get_sampled_points(batch_dict)
+        keypoints, new_xyz_batch_cnt = self.keypoints_and_counts(batch_dict)
         batch_size = batch_dict['batch_size']
         point_features_list = []
         if 'bev' in self.model_cfg['FEATURES_SOURCE']:
@@ -168,25 +184,26 @@ class VoxelSetAbstraction(nn.Module):
                 keypoints, batch_dict['spatial_features'], batch_size, bev_stride=batch_dict['spatial_features_stride']))
 
         new_xyz = keypoints[:, 1:4].contiguous()
-        new_xyz_batch_cnt = torch.full((batch_size,), self.model_cfg['NUM_KEYPOINTS'], dtype=torch.int32, device=new_xyz.device)
 
         if 'raw_points' in self.model_cfg['FEATURES_SOURCE']:
             raw_points = batch_dict['points']
             if raw_points.shape[1] <= 4:
                 raise ValueError("FEATURES_SOURCE raw_points needs point features next to the coordinates")
+            xyz, xyz_features, xyz_bs_idxs = self.source_rows('raw_points', raw_points[:, 1:4], raw_points[:, 4:], raw_points[:, 0],
+                                                              batch_dict)
             point_features_list.append(self.aggregate_keypoint_features_from_one_source(
-                batch_size=batch_size, aggregate_func=self.SA_rawpoints, xyz=raw_points[:, 1:4],
-                xyz_features=raw_points[:, 4:], xyz_bs_idxs=raw_points[:, 0], new_xyz=new_xyz,
-                new_xyz_batch_cnt=new_xyz_batch_cnt))
+                batch_size=batch_size, aggregate_func=self.SA_rawpoints, xyz=xyz, xyz_features=xyz_features,
+                xyz_bs_idxs=xyz_bs_idxs, new_xyz=new_xyz, new_xyz_batch_cnt=new_xyz_batch_cnt))
 
         for k, src_name in enumerate(self.SA_layer_names):
             cur = batch_dict['multi_scale_3d_features'][src_name]
             cur_coords = cur.indices
             xyz = get_voxel_centers(cur_coords[:, 1:4], downsample_times=self.downsample_times_map[src_name],
                                     voxel_size=self.voxel_size, point_cloud_range=self.point_cloud_range)
+            xyz, xyz_features, xyz_bs_idxs = self.source_rows(src_name, xyz, cur.features, cur_coords[:, 0], batch_dict)
             point_features_list.append(self.aggregate_keypoint_features_from_one_source(
-                batch_size=batch_size, aggregate_func=self.SA_layers[k], xyz=xyz, xyz_features=cur.features,
-                xyz_bs_idxs=cur_coords[:, 0], new_xyz=new_xyz, new_xyz_batch_cnt=new_xyz_batch_cnt))
+                batch_size=batch_size, aggregate_func=self.SA_layers[k], xyz=xyz, xyz_features=xyz_features,
+                xyz_bs_idxs=xyz_bs_idxs, new_xyz=new_xyz, new_xyz_batch_cnt=new_xyz_batch_cnt))
 
         point_features = torch.cat(point_features_list, dim=-1)
         batch_dict['point_features_before_fusion'] = point_features.view(-1, point_features.shape[-1])
