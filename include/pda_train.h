@@ -1434,6 +1434,46 @@ int pda_vector_interp_fwd(const float *dist, const int32_t *idx, const float *su
 int pda_vector_interp_bwd(const float *grad_out, const float *dist, const int32_t *idx, float *grad_support_features, int m,
                           int g, int n, int c, pda_stream_t stream);
 
+/* ---- CaDDN: FrustumToVoxel over the factors of the frustum tensor, and DDNLoss (csrc/frustum_sample.hip) ----------------
+ * The reference multiplies softmax(depth_logits)[:, :-1] (B,D,Hf,Wf) into the image features (B,C,Hf,Wf), builds a
+ * (B,X,Y,Z,3) grid and calls a 5-D grid_sample.  The trilinear sample of an outer product factorises, so neither the
+ * (B,C,D,Hf,Wf) tensor nor the grid exists here:
+ *   out[b,c,k,j,i] = sum over the 4 pixel corners (v',u') of  w_uv(v',u') * (sum over the 2 depth corners d' of
+ *                    w_d(d') * prob[b,d',v',u']) * feat[b,c,v',u'],          a corner outside the volume contributes 0.
+ * Per voxel (i,j,k) of the (gx,gy,gz) grid, in float32:
+ *   T = lidar_to_cam[b] @ [[sx,0,0,minx],[0,sy,0,miny],[0,0,sz,minz],[0,0,0,1]]   (voxel_size s, pc_min; multiplied first)
+ *   cam = T[:3] @ [i+.5, j+.5, k+.5, 1];  t = cam_to_img[b] @ [cam, 1];  s = |t2| > 1e-8 ? 1/t2 : 1;  (u,v) = (t0,t1) * s
+ *   depth = t2 - cam_to_img[b][2][3];  d = the continuous bin index of depth:
+ *     mode 0 UD (depth - depth_min) / ((depth_max - depth_min) / D);  mode 1 LID -0.5 + 0.5 sqrt(1 + 8 (depth - depth_min) / bs),
+ *     bs = 2 (depth_max - depth_min) / (D (1 + D));  mode 2 SID D (log(1 + depth) - log(1 + depth_min)) / (log(1 + depth_max) -
+ *     log(1 + depth_min))
+ *   (u,v,d) / (W_img - 1, H_img - 1, D - 1) * 2 - 1 with image_hw = [H_img, W_img] read on the device (the ORIGINAL image
+ *   size); a coordinate that is not finite becomes -2; then ((x + 1) * size - 1) / 2 against (wf, hf, d), floor, the two
+ *   corners and weights per axis (grid_sample, align_corners=False, zero padding).
+ * feat (B,C,Hf,Wf), prob (B,D,Hf,Wf), lidar_to_cam (B,4,4), cam_to_img (B,3,4), image_hw (2) on the device; pc_min and
+ * voxel_size: 3 host floats each.  out (B,C,gz,gy,gx) is written in full.  Any c >= 1.
+ * pda_frustum_sample_bwd recomputes the corners: grad_feat and grad_prob, both zero-filled by the caller, are accumulated
+ * with float atomics after the lanes of a 16-lane row that hit the same cell have been added up. */
+int pda_frustum_sample_fwd(const float *feat, const float *prob, const float *lidar_to_cam, const float *cam_to_img,
+                           const float *image_hw, float *out, int b, int c, int d, int hf, int wf, int gx, int gy, int gz,
+                           const float *pc_min, const float *voxel_size, int mode, float depth_min, float depth_max,
+                           pda_stream_t stream);
+int pda_frustum_sample_bwd(const float *grad_out, const float *feat, const float *prob, const float *lidar_to_cam,
+                           const float *cam_to_img, const float *image_hw, float *grad_feat, float *grad_prob, int b, int c,
+                           int d, int hf, int wf, int gx, int gy, int gz, const float *pc_min, const float *voxel_size,
+                           int mode, float depth_min, float depth_max, pda_stream_t stream);
+/* DDNLoss in one pass over logits (B, num_bins + 1, H, W): per pixel the target bin of depth_maps (B,H,W) (the index above,
+ * truncated; below 0, above num_bins or not finite -> num_bins), the focal term -alpha (1 - p_t)^gamma log_softmax(x)_t, and
+ * the weight fg_weight if the pixel (v,u) lies in any [floor(u1/f), ceil(u2/f)) x [floor(v1/f), ceil(v2/f)) of boxes2d
+ * (B,N,4) [u1,v1,u2,v2] (read only; f = downsample), else bg_weight.  out3 = [loss, fg_loss, bg_loss] float32 with
+ * fg/bg_loss = the float64 sum of the weighted terms / (B H W), loss = weight (fg_loss + bg_loss); grad_logits = d loss /
+ * d logits.  partials: 2 * pda_ddn_loss_blocks(B H W) doubles of scratch. */
+int64_t pda_ddn_loss_blocks(int64_t pixels);
+int pda_ddn_loss_fwd_bwd(const float *logits, const float *depth_maps, const float *boxes2d, float *grad_logits,
+                         double *partials, float *out3, int b, int num_bins, int h, int w, int n_boxes, int mode,
+                         float depth_min, float depth_max, float downsample, double alpha, double gamma, double fg_weight,
+                         double bg_weight, double weight, pda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -310,6 +310,10 @@ SIGNATURES = {
     "pda_roi_point_filter": [_vp, _vp, _vp, _f, _vp, _vp, ctypes.c_int64, _i, _i, _i, _i, _vp],
     "pda_vector_interp_fwd": [_vp] * 6 + [_i] * 4 + [_vp],
     "pda_vector_interp_bwd": [_vp] * 4 + [_i] * 4 + [_vp],
+    "pda_frustum_sample_fwd": [_vp] * 6 + [_i] * 8 + [ctypes.POINTER(_f)] * 2 + [_i, _f, _f, _vp],
+    "pda_frustum_sample_bwd": [_vp] * 8 + [_i] * 8 + [ctypes.POINTER(_f)] * 2 + [_i, _f, _f, _vp],
+    "pda_ddn_loss_blocks": [ctypes.c_int64],
+    "pda_ddn_loss_fwd_bwd": [_vp] * 6 + [_i] * 6 + [_f] * 3 + [ctypes.c_double] * 5 + [_vp],
     # include/pda_pointnet2_stack.h
     "pda_stack_ball_query": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     "pda_stack_group_points": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -338,7 +342,7 @@ SIZE_QUERIES = [
     "pda_voxel_workspace_bytes", "pda_dyn_voxel_workspace_bytes", "pda_center_focal_blocks", "pda_anchor_loss_blocks",
     "pda_anchor_multi_loss_blocks",
     "pda_spconv_index_workspace_bytes", "pda_spconv_wgrad_workspace_bytes", "pda_voxel_pool_scratch_doubles",
-    "pda_stack_sa_scratch_doubles", "pda_part_loss_blocks", "pda_parta2_pool_workspace_bytes"]
+    "pda_stack_sa_scratch_doubles", "pda_part_loss_blocks", "pda_parta2_pool_workspace_bytes", "pda_ddn_loss_blocks"]
 INFO_SYMBOLS = ["pda_abi_version", "pda_last_error", "pda_fp_contract_mode", "pda_opt_n_threads",
                 "pda_fps_coop_timeouts", "pda_debug_fps_spin_limit", "pda_debug_fps_exchange_nonzero"]
 
